@@ -91,7 +91,14 @@ def parse():
                          "cfg2 = the headline 640x480 4-level workload; cfg3 = BASELINE.json configs[2]'s configuration "
                          "(640x480, config_5_level); cfg5 = configs[4]'s shape (1280x960, config_6_level; combine with "
                          "--storage f16 --huber 0.05)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller (every pair's state "
+                         "vector and report) as DIR/<name>.npy in float64, for output-for-output comparison of two builds "
+                         "(the inputs are seeded: the same arguments give the same pairs)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def algorithmic_bytes(level_sizes, iterations):
@@ -271,6 +278,32 @@ def step_wall_summary():
     return dict(min=float(a.min()), median=float(np.median(a)), max=float(a.max()), steps=int(a.size))
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, states, reports, nl, rank, world):
+    """--dump-outputs: the arrays the last timed step handed its caller (phovo_engine_fetch_results: the 6-vector state and
+    the report of every pair), float64, one .npy per field; pair_index.npy names the pair of every row.  Above 64 MB in
+    all (about 500 000 pairs) a fixed, seeded sample of the pairs is written instead.  With several ranks every rank
+    writes its own shard, suffixed _rank<r>."""
+    n = len(states)
+    fields = dict(states=np.asarray(states, dtype=np.float64).reshape(n, 6),
+                  iterations=np.array([list(r.iterations[:nl]) for r in reports], dtype=np.float64).reshape(n, nl),
+                  gradient_norm=np.array([r.gradient_norm for r in reports], dtype=np.float64),
+                  flags=np.array([r.flags for r in reports], dtype=np.float64),
+                  valid_pixels=np.array([list(r.valid_pixels[:nl]) for r in reports], dtype=np.float64).reshape(n, nl))
+    row_bytes = 8 * (1 + sum(a.shape[1] if a.ndim == 2 else 1 for a in fields.values()))     # 1: pair_index
+    rows = np.arange(n)
+    if n * row_bytes > DUMP_LIMIT_BYTES:
+        rows = np.sort(np.random.RandomState(0).choice(n, DUMP_LIMIT_BYTES // row_bytes, replace=False))
+    fields = dict(pair_index=rows.astype(np.float64), **{k: a[rows] for k, a in fields.items()})
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for name, a in fields.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a)
+    print(f"bench.py: wrote {len(rows)} of {n} pairs' outputs to {out_dir}", file=sys.stderr, flush=True)
+
+
 def launch_ranks(args):
     """`python bench.py --gpus N` with N > 1 and no launcher around it: start the N ranks ourselves.
 
@@ -441,6 +474,8 @@ def main():
     states, reports = eng.fetch_results(n_local, want_reports=True)
     timed_launches = eng.last_launches()         # what one timed step launched, as the engine recorded it
     iters = np.array([list(r.iterations[:nl]) for r in reports])
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, states, reports, nl, rank, world)
     nonfinite = int(sum(1 for r in reports if r.flags & native.PAIR_NONFINITE))
     window_fallback = int(sum(1 for r in reports if r.flags & native.PAIR_WINDOW_FALLBACK))
     value = n_global * args.steps / wall

@@ -90,3 +90,73 @@ def test_two_gloo_ranks_share_the_gpu_and_print_one_contract_line():
     assert d["value"] > 0 and d["nonfinite_pairs"] == 0 and d["cpu_baseline"] is None
     assert abs(d["value"] - 512 * 2 / (d["ms_per_step"] * 2e-3)) < 1e-6 * d["value"]
     assert "rank 0/2 joined the gloo group" in r.stderr and "rank 1/2 joined the gloo group" in r.stderr
+
+
+def test_dump_outputs_writes_float64_fields_and_a_fixed_sample_above_the_cap(tmp_path, monkeypatch):
+    """--dump-outputs on made-up results: one float64 .npy per field with a row per pair; above the size cap the same
+    seeded subset of pairs in every run and every field, named by pair_index.npy, and the files stay under the cap."""
+    import numpy as np
+    import bench
+    import phovo_amd  # noqa: F401
+    from phovo_amd import native
+    n, nl = 300, 4
+    rs = np.random.RandomState(5)
+    states = rs.standard_normal((n, 6))
+    reports = [native.PairReport() for _ in range(n)]
+    for i, r in enumerate(reports):
+        r.iterations[:nl] = [i % 7, 3, 20, 50]
+        r.gradient_norm, r.flags = 0.25 * i, i % 3
+        r.valid_pixels[:nl] = [i, 2 * i, 3 * i, 4 * i]
+    bench.dump_outputs(str(tmp_path / "all"), states, reports, nl, 0, 1)
+    names = ["flags", "gradient_norm", "iterations", "pair_index", "states", "valid_pixels"]
+    assert sorted(f[:-4] for f in os.listdir(tmp_path / "all")) == names
+    load = {k: np.load(tmp_path / "all" / f"{k}.npy") for k in names}
+    assert all(a.dtype == np.float64 and a.shape[0] == n for a in load.values())
+    np.testing.assert_array_equal(load["states"], states)
+    np.testing.assert_array_equal(load["iterations"][:, 0], np.arange(n) % 7)
+    np.testing.assert_array_equal(load["valid_pixels"][:, 3], 4 * np.arange(n))
+    np.testing.assert_array_equal(load["pair_index"], np.arange(n))
+
+    cap = 8 * (1 + 6 + nl + 1 + 1 + nl) * 50                      # room for 50 pairs
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", cap)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), states, reports, nl, 1, 2)
+    for k in names:
+        a, b = np.load(tmp_path / "s1" / f"{k}_rank1.npy"), np.load(tmp_path / "s2" / f"{k}_rank1.npy")
+        assert a.shape[0] == 50 and np.array_equal(a, b), k
+    idx = np.load(tmp_path / "s1" / "pair_index_rank1.npy").astype(int)
+    assert len(set(idx)) == 50 and np.all(np.diff(idx) > 0)
+    np.testing.assert_array_equal(np.load(tmp_path / "s1" / "states_rank1.npy"), states[idx])
+    np.testing.assert_array_equal(np.load(tmp_path / "s1" / "gradient_norm_rank1.npy"), 0.25 * idx)
+    assert sum(a.nbytes for a in (np.load(tmp_path / "s1" / f"{k}_rank1.npy") for k in names)) <= cap
+
+
+def test_steps_below_one_are_refused():
+    r = _run(["--steps", "0"])
+    assert r.returncode != 0 and "--steps must be at least 1" in r.stderr
+
+
+@pytest.mark.gpu
+def test_dump_outputs_hold_the_last_timed_step_and_repeat_exactly(tmp_path):
+    """Two runs with the same arguments: `--steps` timed steps each, and the dumped results of the last one are bit for bit
+    the same (seeded inputs, one arithmetic per pair), finite, one row per pair, with the iteration counts the line reports."""
+    import json
+    import numpy as np
+    args = ["--steps", "3", "--warmup", "1", "--pairs", "256", "--distinct", "8", "--no-cpu-baseline",
+            "--no-reference-termination"]
+    lines = []
+    for d in ("a", "b"):
+        r = _run(args + ["--dump-outputs", str(tmp_path / d)])
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append(json.loads(r.stdout.strip().splitlines()[-1]))
+    for d in lines:
+        assert d["steps"] == 3 and d["roofline"]["step_wall_ms"]["steps"] == 3
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and "states.npy" in names
+    for f in names:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float64 and a.shape[0] == 256 and np.array_equal(a, b), f
+    states = np.load(tmp_path / "a" / "states.npy")
+    assert states.shape == (256, 6) and np.all(np.isfinite(states)) and np.any(states != 0)
+    its = np.load(tmp_path / "a" / "iterations.npy")
+    np.testing.assert_array_equal(its.mean(axis=0), lines[0]["iterations_per_pair"])
