@@ -203,6 +203,16 @@ def make_pair(seed, width=640, height=480, holes=0.0, trans=0.03, rot=0.015, sce
     return dict(gray0=g0, depth0=d0, gray1=g1, depth1=d1, K=K, motion=m)
 
 
+def render_pair_with_motion(seed, width, height, motion, holes=0.02):
+    """One frame pair of the plane scene under a GIVEN motion (state vector x, y, z, yaw, pitch, roll of T_10) instead of
+    a random one: large in-plane rotations, rolls, motions that leave a kernel's window.  Returns what make_pair does."""
+    scene = Scene(seed)
+    K = intrinsics(width, height)
+    g0, d0 = render(scene, np.eye(4), width, height, K, holes, hole_seed=2 * seed)
+    g1, d1 = render(scene, eigen_pose(motion), width, height, K, holes, hole_seed=2 * seed + 1)
+    return dict(gray0=g0, depth0=d0, gray1=g1, depth1=d1, K=K, motion=np.array(motion, dtype=np.float64))
+
+
 def make_sequence(seed, n_frames, width=640, height=480, holes=0.0, trans=0.02, rot=0.01, scene="plane", invalid=0.2,
                   workers=1):
     """A sequence of n_frames of one scene under cumulative small motions.

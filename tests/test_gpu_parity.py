@@ -315,14 +315,6 @@ def test_hbm_owner_map_tags_survive_wraparound_and_form_changes():
     assert all(np.array_equal(d[0], d[i]) for i in range(40))
 
 
-def _render_pair_with_motion(seed, w, h, motion, holes=0.02):
-    scene = synthetic.Scene(seed)
-    K = synthetic.intrinsics(w, h)
-    g0, d0 = synthetic.render(scene, np.eye(4), w, h, K, holes, hole_seed=2 * seed)
-    g1, d1 = synthetic.render(scene, se3.eigen_pose(motion), w, h, K, holes, hole_seed=2 * seed + 1)
-    return dict(gray0=g0, depth0=d0, gray1=g1, depth1=d1, K=K, motion=np.array(motion))
-
-
 @pytest.mark.parametrize("size,iters", [((320, 240), 9), ((640, 480), 4), ((330, 250), 5)])
 def test_sliding_window_kernel_matches_exact_kernel_and_oracle(size, iters):
     """Levels whose owner map exceeds LDS: the sliding-window kernel (owner ring in LDS, gn_slide_kernel.hip) against the
@@ -396,7 +388,7 @@ def test_sliding_window_hands_large_motions_to_the_exact_kernel():
     the first iteration, (b) drifting out of it after a few iterations, (c) a well-behaved pair in the same launch
     that must not be touched.  48 pairs, mixed."""
     w, h = 320, 240
-    big = _render_pair_with_motion(91, w, h, [0.01, -0.005, 0.004, 0.30, 0.002, -0.003])
+    big = synthetic.render_pair_with_motion(91, w, h, [0.01, -0.005, 0.004, 0.30, 0.002, -0.003])
     small = synthetic.make_pair(92, w, h, holes=0.02, trans=0.01, rot=0.004)
     ncfg, ocfg = _cfgs(1, [8], [0.0])
     init_a = big["motion"] + np.array([0.004, 0.002, -0.003, 0.004, -0.002, 0.001])      # near the truth: yaw 0.3 at once

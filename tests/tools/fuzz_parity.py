@@ -13,7 +13,12 @@ scaling starts: there the bar is the flat 1e-9 the GPU tests hold.  It matters f
 dozen rows barely constrain the rotation about the image's long axis (cond 1e6 ... 1e8): round 3's sweeps met two such
 cases at 1.2e-9 and 1.3e-9 (282x15, 309x15), round 4's strips sweep cases up to 5e-9 at cond 2e6.
 
-    python tests/tools/fuzz_parity.py [cases=150] [seed=0] [ext] [big] [strips]
+    python tests/tools/fuzz_parity.py [cases=150] [seed=0] [ext] [big] [strips] [angles]
+
+With `angles` the true motion is an in-plane rotation (yaw) of up to 0.9 rad, rendered, and the initial state draws each
+Euler angle from a mix with mass in every branch of the device's sin / cos (write_pose_constants, gn_device.hpp: the
+polynomials below 0.3 and up to fl(pi/4), the library's sincos beyond), near both thresholds to the ulp, and -- for pitch
+and roll -- beyond pi/2, i.e. points behind the camera.
 
 With `strips` every case is a one-level strip of 250-330 x 12-20 pixels (that shape class, on purpose).
 
@@ -42,6 +47,7 @@ rs = np.random.RandomState(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
 with_ext = "ext" in sys.argv[3:]
 big = "big" in sys.argv[3:]
 strips = "strips" in sys.argv[3:]
+angles = "angles" in sys.argv[3:]
 bad, worst, variants, fallbacks = 0, 0.0, {}, 0
 worst_ratio, worst_cond, ill = 0.0, 0.0, 0
 worst_ill, ill_only_by_scaling = 0.0, 0
@@ -55,6 +61,30 @@ def worst_condition(trace):
         if np.all(np.isfinite(h)) and np.any(h != 0.0):
             c = max(c, float(np.linalg.cond(h)))
     return c
+
+
+P4 = 0.78539816339744828          # fl(pi/4): beyond it the device takes the library's sincos
+
+
+def draw_angle(rs, axis, truth):
+    """One Euler angle of an initial state (axis 0 = yaw): every branch of the device's sin / cos and both thresholds."""
+    kind, sign, u = int(rs.randint(0, 7)), float(rs.choice([-1.0, 1.0])), rs.rand()
+    if kind == 0:
+        return truth + 0.05 * (u - 0.5)                                   # near the truth (for yaw: up to 0.9 rad)
+    if kind == 1:
+        return sign * 0.3 * u                                             # branch 1
+    if kind == 2:
+        return sign * (0.3 + (P4 - 0.3) * u)                              # branch 2
+    if kind == 3:                                                         # within 3 ulp of 0.3, 0.78125, fl(pi/4)
+        a, steps = float(rs.choice([0.3, 0.78125, P4])), int(rs.randint(-3, 4))
+        for _ in range(abs(steps)):
+            a = float(np.nextafter(a, np.inf if steps > 0 else -np.inf))
+        return sign * a
+    if kind == 4:
+        return sign * (P4 + 0.5 * u)                                      # branch 3, just beyond
+    if kind == 5 and axis > 0:
+        return sign * (np.pi - 0.2 - 0.3 * u)                             # pitch / roll beyond pi/2: behind the camera
+    return sign * 0.01 * u
 
 
 # FUZZ_ONLY=12,345: replay the random draws of every case but run only these (to look at a failure again)
@@ -71,7 +101,12 @@ for case in range(cases):
         w, h = int(rs.randint(250, 331)), int(rs.randint(12, 21))
     kw = dict(holes=float(rs.choice([0.0, 0.02, 0.2])), trans=float(rs.choice([0.002, 0.02, 0.08])),
               rot=float(rs.choice([0.001, 0.01, 0.05, 0.25] if big else [0.001, 0.01, 0.05])))
-    p = synthetic.make_pair(1000 + case, w, h, **kw) if active else dict(K=synthetic.intrinsics(w, h), depth0=np.zeros((h, w)))
+    if angles:
+        motion = np.concatenate([rs.uniform(-1, 1, 3) * kw["trans"], [rs.uniform(-0.9, 0.9)], rs.uniform(-0.01, 0.01, 2)])
+    if active and angles:
+        p = synthetic.render_pair_with_motion(1000 + case, w, h, motion, kw["holes"])
+    else:
+        p = synthetic.make_pair(1000 + case, w, h, **kw) if active else dict(K=synthetic.intrinsics(w, h), depth0=np.zeros((h, w)))
     K = p["K"].copy()
     if rs.rand() < 0.6:                     # principal point / focal lengths that are not exactly representable
         K[0, 2] += rs.uniform(-3, 3)
@@ -92,6 +127,9 @@ for case in range(cases):
     ncfg = native.make_config(num_levels=nl, max_iter=max_iter, min_grad=min_grad, lam=lam)
     ocfg = oracle.make_config(num_levels=nl, max_iter=max_iter, min_grad=min_grad, lam=lam)
     init = None if rs.rand() < 0.5 else rs.uniform(-1, 1, 6) * np.array([0.02, 0.02, 0.02, 0.01, 0.01, 0.01])
+    if angles:
+        init = rs.uniform(-1, 1, 6) * np.array([0.02, 0.02, 0.02, 0.01, 0.01, 0.01])
+        init[3:] = [draw_angle(rs, axis, motion[3 + axis]) for axis in range(3)]
     storage, huber, bilinear, corrected = native.STORAGE_F64, None, False, False
     if not active:                          # the remaining draws of this case, in order, and on to the next one
         if with_ext:
