@@ -3,6 +3,9 @@
 // Same command line, hard-coded intrinsics, depth scale and console output as the reference's app
 // (apps/PhotoconsistencyFrameAlignment/PhotoconsistencyFrameAlignment.cpp:49-115):
 //   ./PhotoconsistencyFrameAlignment <config_file.yml> <imgRGB0.png> <imgDepth0.png> <imgRGB1.png> <imgDepth1.png> [diff.png]
+//                                    [--method analytic|biobjective]
+// --method picks the aligner as the reference's USE_PHOTOCONSISTENCY_ODOMETRY_METHOD does: analytic (0, the default) or
+// biobjective (2, CPhotoconsistencyOdometryBiObjective: photometric and depth error together).
 // Differences: the reference tests `argc<5` but reads argv[5] (:56,79) -- five arguments are required
 // here; the final |I1 - warp(I0)| image goes to the optional sixth argument as a PNG instead of an
 // imshow window (:107-112), because the target machines are headless.
@@ -10,9 +13,11 @@
 #include <cstdlib>
 #include <iostream>
 #include <string>
+#include <vector>
 
 #include "io/png_io.h"
 #include "phovo/CPhotoconsistencyOdometryAnalytic.h"
+#include "phovo/CPhotoconsistencyOdometryBiObjective.h"
 
 typedef double CoordinateType;
 typedef unsigned char PixelType;
@@ -25,7 +30,7 @@ typedef phovo::compat::Mat_<CoordinateType> DepthImageType;
 static void printHelp()
 {
   std::cout << "./PhotoconsistencyFrameAlignment <config_file.yml> <imgRGB0.png> <imgDepth0.png> "
-               "<imgRGB1.png> <imgDepth1.png> [imgDiff.png]" << std::endl;
+               "<imgRGB1.png> <imgDepth1.png> [imgDiff.png] [--method analytic|biobjective]" << std::endl;
 }
 
 static bool loadGray(const char *path, IntensityImageType &img)
@@ -48,7 +53,37 @@ static bool loadDepthMetres(const char *path, DepthImageType &img)
   return true;
 }
 
+static int alignPair(int argc, char **argv, bool biobjective);
+
 int main(int argc, char **argv)
+{
+  // --method may stand anywhere after the program name; the remaining arguments keep their positions
+  bool biobjective = false;
+  std::vector<char *> args;
+  for (int i = 0; i < argc; i++) {
+    if (i > 0 && std::string(argv[i]) == "--method") {
+      if (i + 1 >= argc) { printHelp(); return -1; }
+      const std::string m(argv[++i]);
+      if (m == "biobjective") biobjective = true;
+      else if (m != "analytic") { printHelp(); return -1; }
+      continue;
+    }
+    args.push_back(argv[i]);
+  }
+  return alignPair((int)args.size(), args.data(), biobjective);
+}
+
+template <class Odometry>
+static int alignWith(int argc, char **argv);
+
+static int alignPair(int argc, char **argv, bool biobjective)
+{
+  if (biobjective) return alignWith<phovo::Analytic::CPhotoconsistencyOdometryBiObjective<PixelType, CoordinateType>>(argc, argv);
+  return alignWith<phovo::Analytic::CPhotoconsistencyOdometryAnalytic<PixelType, CoordinateType>>(argc, argv);
+}
+
+template <class Odometry>
+static int alignWith(int argc, char **argv)
 {
   if (argc < 6) { printHelp(); return -1; }
 
@@ -64,7 +99,7 @@ int main(int argc, char **argv)
     return EXIT_FAILURE;
 
   try {
-    phovo::Analytic::CPhotoconsistencyOdometryAnalytic<PixelType, CoordinateType> photoconsistencyOdometry;
+    Odometry photoconsistencyOdometry;
     Vector6Type stateVector;                          // x,y,z,yaw,pitch,roll = 0
     photoconsistencyOdometry.ReadConfigurationFile(std::string(argv[1]));       // :92
     photoconsistencyOdometry.SetIntrinsicMatrix(intrinsicMatrix);

@@ -2,6 +2,9 @@
 // directory, writing a TUM trajectory file.
 //
 //   ./PhotoconsistencyVisualOdometry <config_file.yml> <rgbd_dataset_directory> <output_trajectory_file> [--batch [--gpus N] [--rccl]]
+//                                    [--method analytic|biobjective]
+// --method picks the aligner as the reference's USE_PHOTOCONSISTENCY_ODOMETRY_METHOD does (0 = analytic, the default;
+// 2 = bi-objective: photometric and depth error together, CPhotoconsistencyOdometryBiObjective), in every mode.
 //
 // Behaviour kept from the reference's app (apps/PhotoconsistencyVisualOdometry/PhotoconsistencyVisualOdometry.cpp):
 //   * <dir>/rgb.txt and <dir>/depth.txt are read in lock step -- line n of one is paired with line n of the
@@ -37,6 +40,7 @@
 #include "rccl/rccl_gather.h"
 #include "rccl/shard_vote.h"
 #include "phovo/CPhotoconsistencyOdometryAnalytic.h"
+#include "phovo/CPhotoconsistencyOdometryBiObjective.h"
 
 typedef double CoordinateType;
 typedef unsigned char PixelType;
@@ -103,7 +107,7 @@ static bool writePose(std::ofstream &f, double timestamp, const Matrix44Type &po
 static void printHelp()
 {
   std::cout << "./PhotoconsistencyVisualOdometry <config_file.yml> <rgbd_dataset_directory> "
-               "<output_trajectory_file> [--batch [--gpus N] [--rccl]]" << std::endl;
+               "<output_trajectory_file> [--batch [--gpus N] [--rccl]] [--method analytic|biobjective]" << std::endl;
 }
 
 #define PHOVO_OK_OR_FAIL(call)                                                              \
@@ -116,9 +120,16 @@ int main(int argc, char *argv[])
   bool batch = false;
   int nGpus = 1;                                      // --batch --gpus N: the pairs of the sequence sharded over N devices
   bool rccl = false;                                  // ... --rccl: the shards' states meet through ONE RCCL all_gather
+  int objective = PHOVO_OBJECTIVE_PHOTOMETRIC;        // --method analytic (default) | biobjective
   for (int i = 4; i < argc; i++) {
     const std::string a(argv[i]);
     if (a == "--batch") batch = true;
+    else if (a == "--method" && i + 1 < argc) {
+      const std::string m(argv[++i]);
+      if (m == "analytic") objective = PHOVO_OBJECTIVE_PHOTOMETRIC;
+      else if (m == "biobjective") objective = PHOVO_OBJECTIVE_BIOBJECTIVE;
+      else { printHelp(); return EXIT_FAILURE; }
+    }
     else if (a == "--rccl") rccl = true;
     else if (a == "--gpus" && i + 1 < argc) nGpus = std::atoi(argv[++i]);
     else { printHelp(); return EXIT_FAILURE; }
@@ -154,8 +165,8 @@ int main(int argc, char *argv[])
 
   Matrix44Type pose = Matrix44Type::Identity();
   try {
-    if (!batch) {
-      phovo::Analytic::CPhotoconsistencyOdometryAnalytic<PixelType, CoordinateType> odometry;
+    // the pair-by-pair loop through the class surface, with the class --method names
+    auto runLoop = [&](auto &odometry) -> int {
       odometry.ReadConfigurationFile(configFile);
       odometry.SetIntrinsicMatrix(intrinsicMatrix);
       IntensityImageType prevGray, curGray;
@@ -184,6 +195,16 @@ int main(int argc, char *argv[])
         std::cout << "Rt:" << std::endl << Rt << std::endl;
         prevGray = curGray.clone();
         prevDepth = curDepth.clone();
+      }
+      return EXIT_SUCCESS;
+    };
+    if (!batch) {
+      if (objective == PHOVO_OBJECTIVE_BIOBJECTIVE) {
+        phovo::Analytic::CPhotoconsistencyOdometryBiObjective<PixelType, CoordinateType> odometry;
+        if (runLoop(odometry) != EXIT_SUCCESS) return EXIT_FAILURE;
+      } else {
+        phovo::Analytic::CPhotoconsistencyOdometryAnalytic<PixelType, CoordinateType> odometry;
+        if (runLoop(odometry) != EXIT_SUCCESS) return EXIT_FAILURE;
       }
     } else {
       phovo_config cfg;
@@ -280,6 +301,7 @@ int main(int argc, char *argv[])
           if (injectFailure == g) { shardError[g] = "shard " + std::to_string(g) + ": failure injected (PHOVO_VO_INJECT_SHARD_FAILURE)"; return false; }
           if (phovo_engine_create(g % nDevices, &engine) != PHOVO_OK) return fail("phovo_engine_create");
           if (phovo_engine_set_config(engine, &cfg) != PHOVO_OK) return fail("phovo_engine_set_config");
+          if (phovo_engine_set_objective(engine, objective) != PHOVO_OK) return fail("phovo_engine_set_objective");
           // a pair's pose must not depend on the size of the shard it falls into (same trajectory file for every N)
           if (phovo_engine_set_batch_invariant(engine, 1) != PHOVO_OK) return fail("phovo_engine_set_batch_invariant");
           if (phovo_engine_set_intrinsic_matrix(engine, intrinsicMatrix.data()) != PHOVO_OK) return fail("phovo_engine_set_intrinsic_matrix");

@@ -138,12 +138,15 @@ class CPhotoconsistencyOdometryAnalytic : public CPhotoconsistencyOdometry<TPixe
     return ms;
   }
 
- private:
+ protected:
+  phovo_odometry *Handle() const { return m_Handle; }
   static void Check(int status, const char *where)
   {
     if (status != PHOVO_OK)
       throw std::runtime_error(std::string(where) + ": " + phovo_status_string(status) + " -- " + phovo_last_error());
   }
+
+ private:
   phovo_odometry *m_Handle;
 };
 

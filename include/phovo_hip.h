@@ -118,6 +118,22 @@ typedef struct phovo_extensions {
   double huber_delta[PHOVO_MAX_LEVELS];     /* optional yml key "huber_delta (at each level)"             */
 } phovo_extensions;
 
+/* Objective (phovo_engine_set_objective):
+ *   PHOVO_OBJECTIVE_PHOTOMETRIC  the reference's method 0, CPhotoconsistencyOdometryAnalytic (default)
+ *   PHOVO_OBJECTIVE_BIOBJECTIVE  the reference's method 2, CPhotoconsistencyOdometryBiObjective: photometric and depth
+ *                                error together over 2N rows, reproduced with the reference's row collisions (last
+ *                                writer wins).  Target frames keep their depth: their uploads need it and
+ *                                build the target depth pyramid, the depth-gradient planes (Scharr of
+ *                                depth * (1.0/max_depth), with the max depth in force at upload) and the per-level gain
+ *                                mean(intensity) / mean(depth).  Reference-exact only: fp64 planes, nearest / scatter
+ *                                sampling, no Huber weights -- anything else is PHOVO_E_UNSUPPORTED, from
+ *                                phovo_engine_set_objective or phovo_engine_set_extensions, whichever comes second.
+ *                                Fusion, sliding-window, wide and latency-form settings are accepted and have no
+ *                                effect.  phovo_pair_report: valid_pixels counts contributing source pixels,
+ *                                PHOVO_PAIR_RANK_DEFICIENT means fewer than 6 of them. */
+#define PHOVO_OBJECTIVE_PHOTOMETRIC 0
+#define PHOVO_OBJECTIVE_BIOBJECTIVE 1
+
 typedef struct phovo_engine phovo_engine;
 typedef struct phovo_odometry phovo_odometry;
 
@@ -176,6 +192,9 @@ int phovo_odometry_set_extensions(phovo_odometry *o, const phovo_extensions *ext
 /* not in the reference: 1 = Optimize() may take the forms that finish soonest for ONE pair (phovo_engine_set_latency_forms:
  * last bits may then differ from the same pair aligned in a batch); default 0 */
 int phovo_odometry_set_latency_forms(phovo_odometry *o, int on);
+/* not in the reference's class (its apps pick the class): PHOVO_OBJECTIVE_*, default photometric.  A change drops the
+ * frames set so far.  Under the bi-objective phovo_odometry_set_target_frame needs depth (NULL: PHOVO_E_INVALID_ARGUMENT). */
+int phovo_odometry_set_objective(phovo_odometry *o, int objective);
 int phovo_odometry_set_min_depth(phovo_odometry *o, double min_depth);     /* :448 */
 int phovo_odometry_set_max_depth(phovo_odometry *o, double max_depth);     /* :454 */
 int phovo_odometry_set_intrinsic_matrix(phovo_odometry *o, const double k[9]);     /* :460, row-major 3x3 */
@@ -259,6 +278,11 @@ int phovo_engine_set_latency_forms(phovo_engine *e, int on);
 int phovo_engine_set_batch_invariant(phovo_engine *e, int on);
 /* 1 if `level` would run in the wide form for a batch of n_pairs under the current settings. */
 int phovo_engine_level_uses_wide(const phovo_engine *e, int level, int n_pairs);
+/* PHOVO_OBJECTIVE_*.  A change of objective drops the frame pool (as a change of plane_storage does): reserve_frames
+ * and upload again.  PHOVO_E_UNSUPPORTED for the bi-objective under anything but fp64 planes, nearest / scatter
+ * sampling and no Huber weights. */
+int phovo_engine_set_objective(phovo_engine *e, int objective);
+int phovo_engine_get_objective(const phovo_engine *e, int *objective);
 
 /* Page-locks (and releases) a host buffer the caller will hand to the upload entry points repeatedly: uploads from
  * registered memory are direct DMA at the link rate instead of going through the runtime's bounce buffers.  Optional;
@@ -303,6 +327,11 @@ int phovo_engine_set_level_planes(phovo_engine *e, int frame, int level,
 int phovo_engine_get_level_planes(const phovo_engine *e, int frame, int level,
                                   double *intensity, double *depth,
                                   double *grad_x, double *grad_y);
+/* Bi-objective only (else PHOVO_E_UNSUPPORTED): the depth-gradient planes (w*h doubles each, NULL = skip) and the depth
+ * gain of one level of one target frame.  phovo_engine_set_level_planes recomputes the gain of the level it writes and,
+ * when it writes depth, the depth gradients with the max depth in force. */
+int phovo_engine_get_level_depth_gradients(const phovo_engine *e, int frame, int level, double *grad_x, double *grad_y);
+int phovo_engine_get_level_depth_gain(const phovo_engine *e, int frame, int level, double *gain);
 
 /* Optimize() for n_pairs independent (source, target) frame pairs.
  *   init_states  n_pairs x 6 (SetInitialStateVector) or NULL for all-zero
@@ -364,7 +393,8 @@ enum { PHOVO_LAUNCH_PERSISTENT = 0,       /* gn_level_kernel: one level, one wor
        PHOVO_LAUNCH_SLIDE = 2,            /* gn_level_kernel_slide: owner ring in LDS */
        PHOVO_LAUNCH_SLIDE_FALLBACK = 3,   /* gn_level_kernel on the pairs the sliding-window launch handed over */
        PHOVO_LAUNCH_WIDE = 4,             /* k_wide_pass1 / k_wide_pass2 per iteration, many workgroups per pair */
-       PHOVO_LAUNCH_BILINEAR = 5 };       /* gn_level_kernel_bilinear (extension) */
+       PHOVO_LAUNCH_BILINEAR = 5,         /* gn_level_kernel_bilinear (extension) */
+       PHOVO_LAUNCH_BIOBJECTIVE = 6 };    /* gn_level_kernel_biobjective (PHOVO_OBJECTIVE_BIOBJECTIVE) */
 typedef struct phovo_launch_record {
   int level_first, level_last;            /* pyramid levels the launch covers (level_first >= level_last) */
   int kind;                               /* PHOVO_LAUNCH_* */

@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <algorithm>
 #include <map>
 #include <mutex>
 #include <new>
@@ -44,6 +45,10 @@ struct LevelPool {
   size_t frame_bytes = 0;
   size_t plane_off[PLANES_PER_FRAME] = {0, 0, 0, 0};
   size_t rec_off = 0;                  // bilinear sampling: the frame's tap records {I, GX, GY, pad} behind its planes (0: none)
+  // bi-objective: the target's depth-gradient planes and its depth gain behind the four planes (0: none)
+  size_t dgx_off = 0, dgy_off = 0, gain_off = 0;
+  GNLaunchPlan plan_bi{};
+  bool plan_bi_ok = false;
   GNLaunchPlan plan{};
   bool plan_ok = false;
   GNLaunchPlan plan_few{};             // geometry for a handful of pairs (LATENCY_PAIRS or fewer)
@@ -123,6 +128,7 @@ struct phovo_engine {
   int cu_count = 256;
   int wide_policy = 0;                         // 0 auto, 1 always (where possible), -1 never
   bool batch_invariant = false;                // every batch takes the same kernels and geometries (phovo_engine_set_batch_invariant)
+  int objective = PHOVO_OBJECTIVE_PHOTOMETRIC;  // phovo_engine_set_objective
   bool latency_forms = false;                  // a handful of pairs may take the forms that finish soonest also where a level has a one-workgroup form with its owner map in LDS (phovo_engine_set_latency_forms)
 };
 
@@ -211,13 +217,38 @@ void level_dims(int w, int h, int level, int *lw, int *lh)
 // there a handful of pairs takes the wide form unless the caller pins the batch forms (phovo_engine_set_batch_invariant).
 bool use_wide_level(const phovo_engine *e, int n_pairs, const LevelPool &lv)
 {
-  if (e->wide_policy < 0) return false;
+  if (e->wide_policy < 0 || e->objective == PHOVO_OBJECTIVE_BIOBJECTIVE) return false;
   if (e->ext.plane_storage != PHOVO_STORAGE_F64 || e->ext.sampling != PHOVO_SAMPLING_NEAREST_SCATTER) return false;
   if (e->wide_policy > 0) return true;
   if (e->batch_invariant) return false;        // the automatic choice looks at the batch size
   if (n_pairs * 8 > 256) return false;
   if (lv.plan_ok && lv.plan.owner_in_lds) return e->latency_forms && lv.n >= 16384;
   return true;
+}
+
+// The bi-objective runs reference-exact only: fp64 planes, nearest / scatter sampling, no Huber weights.
+bool biobjective_supports(const phovo_extensions &x)
+{
+  if (x.plane_storage != PHOVO_STORAGE_F64 || x.sampling != PHOVO_SAMPLING_NEAREST_SCATTER || x.jacobian_corrected != 0)
+    return false;
+  for (int l = 0; l < PHOVO_MAX_LEVELS; l++)
+    if (x.huber_delta[l] > 0.0) return false;
+  return true;
+}
+
+// Depth gradients (with the max depth in force) and gain of `count` consecutive target frames of level l, from the
+// intensity and depth planes already in the pool (fp64, packed: the frame is frame_bytes / 8 doubles).
+int build_biobjective_target(phovo_engine *e, int l, int first_frame, int count)
+{
+  const LevelPool &lv = e->levels[l];
+  const double *base = reinterpret_cast<const double *>(lv.planes + (size_t)first_frame * lv.frame_bytes);
+  const size_t fstride = lv.frame_bytes / sizeof(double);
+  PHOVO_HIP_CHECK(pyr_scharr_scaled(base, fstride, lv.plane_off[PLANE_D] / sizeof(double), lv.dgx_off / sizeof(double),
+                                    lv.dgy_off / sizeof(double), count, lv.w, lv.h, 1. / e->max_depth,
+                                    e->cfg.image_gradients_scaling_factor[l], e->stream));
+  PHOVO_HIP_CHECK(pyr_depth_gain(base, fstride, lv.plane_off[PLANE_I] / sizeof(double), lv.plane_off[PLANE_D] / sizeof(double),
+                                 lv.gain_off / sizeof(double), count, lv.n, e->stream));
+  return PHOVO_OK;
 }
 
 constexpr int HEAD_SETS = 2;
@@ -314,8 +345,9 @@ int build_pyramids(phovo_engine *e, int first_frame, int count, int roles, Depth
     if (!lv.stored) continue;
     // fp64 storage: the producers write straight into the pool.  Narrow storage: they write fp64 planes into
     // the scratch chunk (same [frame][4][n] layout) and a convert pass rounds them into the pool once.
-    const size_t fstride = (size_t)PLANES_PER_FRAME * (size_t)lv.n;
     const bool direct = storage == PHOVO_STORAGE_F64 && lv.rec_off == 0;
+    // (fp64, packed: the frame as the pool holds it -- four planes, and under the bi-objective the target planes behind them)
+    const size_t fstride = direct ? lv.frame_bytes / sizeof(double) : (size_t)PLANES_PER_FRAME * (size_t)lv.n;
     double *base = direct ? reinterpret_cast<double *>(lv.planes + (size_t)first_frame * lv.frame_bytes) : e->d_scratch;
     // BuildPyramid(intensity, applyBlur = true)  :474,487
     const int ks = e->cfg.blur_filter_size[l];
@@ -337,7 +369,8 @@ int build_pyramids(phovo_engine *e, int first_frame, int count, int roles, Depth
         PHOVO_HIP_CHECK(pyr_gaussian_blur(pi, e->d_tmp, lv.w, lv.h, ks, kern, e->stream));
       }
     }
-    if (roles & PHOVO_ROLE_SOURCE) {                                    // BuildPyramid(depth, false)  :475
+    const bool bi_target = e->objective == PHOVO_OBJECTIVE_BIOBJECTIVE && (roles & PHOVO_ROLE_TARGET);
+    if ((roles & PHOVO_ROLE_SOURCE) || bi_target) {                     // BuildPyramid(depth, false)  :475 (...BiObjective.h:573)
       double *pd = base + (size_t)PLANE_D * lv.n;
       if (kind == DEPTH_U16)
         PHOVO_HIP_CHECK(pyr_depth_level_u16(s_depth16, px, depth_scale, count, w, h, l, lv.w, lv.h, pd, fstride, e->stream));
@@ -361,6 +394,10 @@ int build_pyramids(phovo_engine *e, int first_frame, int count, int roles, Depth
     if (lv.rec_off && (roles & PHOVO_ROLE_TARGET))                      // bilinear sampling: the target's tap records
       PHOVO_HIP_CHECK(pyr_build_tap_records(lv.planes + (size_t)first_frame * lv.frame_bytes, lv.frame_bytes, lv.plane_off,
                                             lv.rec_off, count, lv.n, storage, e->stream));
+    if (bi_target) {                                                    // BuildDepthDerivativesPyramids  :577, gain  :300
+      const int st = build_biobjective_target(e, l, first_frame, count);
+      if (st != PHOVO_OK) return st;
+    }
   }
   return PHOVO_OK;
 }
@@ -483,6 +520,7 @@ int phovo_engine_create(int device, phovo_engine **out)
   }
   if (he == hipSuccess) he = gn_prepare_kernels();
   if (he == hipSuccess) he = gn_prepare_slide_kernels();
+  if (he == hipSuccess) he = gn_prepare_biobjective_kernels();
   if (he == hipSuccess) {
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) e->cu_count = cus;
@@ -568,6 +606,9 @@ int phovo_engine_set_extensions(phovo_engine *e, const phovo_extensions *ext)
                                      "(the scatter path is kept reference-exact)");
   for (int l = 0; l < PHOVO_MAX_LEVELS; l++)
     if (!(ext->huber_delta[l] == ext->huber_delta[l])) return fail(PHOVO_E_INVALID_ARGUMENT, "set_extensions: huber_delta is NaN");
+  if (e->objective == PHOVO_OBJECTIVE_BIOBJECTIVE && !biobjective_supports(*ext))
+    return fail(PHOVO_E_UNSUPPORTED, "set_extensions: the bi-objective runs on fp64 planes with nearest / scatter sampling "
+                                     "and no Huber weights only");
   // the pool layout changes with the storage type, and -- fp16 planes under bilinear sampling carry tap records -- with the
   // sampling where that adds or removes the records
   auto has_records = [](const phovo_extensions &x) { return x.sampling == PHOVO_SAMPLING_BILINEAR && x.plane_storage == PHOVO_STORAGE_F16; };
@@ -578,6 +619,31 @@ int phovo_engine_set_extensions(phovo_engine *e, const phovo_extensions *ext)
     free_pool(e);
   }
   e->ext = *ext;
+  return PHOVO_OK;
+}
+
+int phovo_engine_set_objective(phovo_engine *e, int objective)
+{
+  if (!e) return fail(PHOVO_E_INVALID_ARGUMENT, "set_objective: null");
+  if (objective != PHOVO_OBJECTIVE_PHOTOMETRIC && objective != PHOVO_OBJECTIVE_BIOBJECTIVE)
+    return fail(PHOVO_E_INVALID_ARGUMENT, "set_objective: unknown objective");
+  if (objective == PHOVO_OBJECTIVE_BIOBJECTIVE && !biobjective_supports(e->ext))
+    return fail(PHOVO_E_UNSUPPORTED, "set_objective: the bi-objective runs on fp64 planes with nearest / scatter sampling "
+                                     "and no Huber weights only");
+  if (objective != e->objective) {             // the pool layout changes (the bi-objective's target planes): dropped
+    (void)hipSetDevice(e->device);
+    (void)hipStreamSynchronize(e->stream);
+    (void)quiesce(e);
+    free_pool(e);
+  }
+  e->objective = objective;
+  return PHOVO_OK;
+}
+
+int phovo_engine_get_objective(const phovo_engine *e, int *objective)
+{
+  if (!e || !objective) return fail(PHOVO_E_INVALID_ARGUMENT, "get_objective: null");
+  *objective = e->objective;
   return PHOVO_OK;
 }
 
@@ -653,6 +719,7 @@ int phovo_engine_set_batch_invariant(phovo_engine *e, int on)
 int phovo_engine_level_uses_wide(const phovo_engine *e, int level, int n_pairs)
 {
   if (!e || level < 0 || level >= e->cfg.num_levels || e->n_frames == 0) return 0;
+  if (e->objective == PHOVO_OBJECTIVE_BIOBJECTIVE) return 0;
   return use_wide_level(e, n_pairs, e->levels[level]) && !(e->ext.huber_delta[level] > 0.0) ? 1 : 0;
 }
 
@@ -744,6 +811,17 @@ int phovo_engine_reserve_frames(phovo_engine *e, int n_frames, int width, int he
         lv.rec_off = off;
         off += 4 * storage_elem_size(e->ext.plane_storage, false) * (size_t)lv.n;
         off = (off + 31) & ~(size_t)31;
+      }
+      lv.dgx_off = lv.dgy_off = lv.gain_off = 0;
+      lv.plan_bi_ok = false;
+      if (e->objective == PHOVO_OBJECTIVE_BIOBJECTIVE) {     // (fp64 packed planes only: biobjective_supports)
+        lv.dgx_off = off;
+        lv.dgy_off = off + sizeof(double) * (size_t)lv.n;
+        lv.gain_off = off + 2 * sizeof(double) * (size_t)lv.n;
+        // (frames start on a 128-byte line, as the packed fp64 layout's 32n bytes do for every level of 4+ pixels: a wave's
+        // 512-byte plane load then touches 4 lines, not 5)
+        off = (lv.gain_off + sizeof(double) + 127) & ~(size_t)127;
+        lv.plan_bi_ok = gn_plan_level_biobjective(lv.n, &lv.plan_bi);
       }
       lv.frame_bytes = off;
     }
@@ -839,7 +917,10 @@ static int upload_batch(phovo_engine *e, int first_frame, int count, int roles,
     return fail(PHOVO_E_INVALID_ARGUMENT, "upload_frames: frame range out of the reserved pool");
   if ((roles & PHOVO_ROLE_BOTH) == 0) return fail(PHOVO_E_INVALID_ARGUMENT, "upload_frames: roles empty");
   if ((roles & PHOVO_ROLE_SOURCE) && !depth) return fail(PHOVO_E_INVALID_ARGUMENT, "upload_frames: a source frame needs depth");
-  if (!(roles & PHOVO_ROLE_SOURCE)) kind = DEPTH_NONE;
+  const bool bi_target = e->objective == PHOVO_OBJECTIVE_BIOBJECTIVE && (roles & PHOVO_ROLE_TARGET);
+  if (bi_target && !depth)
+    return fail(PHOVO_E_INVALID_ARGUMENT, "upload_frames: under the bi-objective a target frame needs depth");
+  if (!(roles & PHOVO_ROLE_SOURCE) && !bi_target) kind = DEPTH_NONE;
   if (count == 0) return PHOVO_OK;
   PHOVO_HIP_CHECK(hipSetDevice(e->device));
   PHOVO_HIP_CHECK(quiesce(e));                 // (an alignment in flight may be reading the frames about to be replaced)
@@ -960,7 +1041,45 @@ int phovo_engine_set_level_planes(phovo_engine *e, int frame, int level,
   if (lv.rec_off && (intensity || grad_x || grad_y))                    // bilinear sampling: this frame's tap records follow its planes
     PHOVO_HIP_CHECK(pyr_build_tap_records(lv.planes + (size_t)frame * lv.frame_bytes, lv.frame_bytes, lv.plane_off, lv.rec_off,
                                           1, lv.n, e->ext.plane_storage, e->stream));
+  if (lv.gain_off) {               // bi-objective: the gain always, the depth gradients when the depth changed (max depth in force)
+    const double *fb = reinterpret_cast<const double *>(base);
+    const size_t fstride = lv.frame_bytes / sizeof(double);
+    if (depth) {
+      const int bst = build_biobjective_target(e, level, frame, 1);
+      if (bst != PHOVO_OK) return bst;
+    } else {
+      PHOVO_HIP_CHECK(pyr_depth_gain(fb, fstride, lv.plane_off[PLANE_I] / sizeof(double), lv.plane_off[PLANE_D] / sizeof(double),
+                                     lv.gain_off / sizeof(double), 1, lv.n, e->stream));
+    }
+  }
   PHOVO_HIP_CHECK(hipStreamSynchronize(e->stream));
+  return PHOVO_OK;
+}
+
+int phovo_engine_get_level_depth_gradients(const phovo_engine *e, int frame, int level, double *grad_x, double *grad_y)
+{
+  const int st = plane_access_check(e, frame, level);
+  if (st != PHOVO_OK) return st;
+  const LevelPool &lv = e->levels[level];
+  if (!lv.gain_off) return fail(PHOVO_E_UNSUPPORTED, "level depth gradients: the objective is not PHOVO_OBJECTIVE_BIOBJECTIVE");
+  PHOVO_HIP_CHECK(hipSetDevice(e->device));
+  PHOVO_HIP_CHECK(hipStreamSynchronize(e->stream));
+  const unsigned char *base = lv.planes + (size_t)frame * lv.frame_bytes;
+  if (grad_x) PHOVO_HIP_CHECK(hipMemcpy(grad_x, base + lv.dgx_off, sizeof(double) * (size_t)lv.n, hipMemcpyDeviceToHost));
+  if (grad_y) PHOVO_HIP_CHECK(hipMemcpy(grad_y, base + lv.dgy_off, sizeof(double) * (size_t)lv.n, hipMemcpyDeviceToHost));
+  return PHOVO_OK;
+}
+
+int phovo_engine_get_level_depth_gain(const phovo_engine *e, int frame, int level, double *gain)
+{
+  const int st = plane_access_check(e, frame, level);
+  if (st != PHOVO_OK) return st;
+  if (!gain) return fail(PHOVO_E_INVALID_ARGUMENT, "level depth gain: null");
+  const LevelPool &lv = e->levels[level];
+  if (!lv.gain_off) return fail(PHOVO_E_UNSUPPORTED, "level depth gain: the objective is not PHOVO_OBJECTIVE_BIOBJECTIVE");
+  PHOVO_HIP_CHECK(hipSetDevice(e->device));
+  PHOVO_HIP_CHECK(hipStreamSynchronize(e->stream));
+  PHOVO_HIP_CHECK(hipMemcpy(gain, lv.planes + (size_t)frame * lv.frame_bytes + lv.gain_off, sizeof(double), hipMemcpyDeviceToHost));
   return PHOVO_OK;
 }
 
@@ -1006,6 +1125,12 @@ int phovo_engine_enqueue_align(phovo_engine *e, int n_pairs, const int *source_f
     if (e->cfg.max_num_iterations[l] <= 0) continue;
     const LevelPool &lv = e->levels[l];
     if (!lv.stored) return fail(PHOVO_E_NOT_READY, "align: an active level is not resident");
+    if (e->objective == PHOVO_OBJECTIVE_BIOBJECTIVE) {
+      if (!lv.plan_bi_ok)
+        return fail(PHOVO_E_SHAPE, "align: pyramid level too large for the bi-objective (more than 2 097 151 pixels)");
+      if (!lv.plan_bi.owner_in_lds) owner_need = std::max(owner_need, (size_t)n_pairs * (size_t)lv.n);
+      continue;
+    }
     if (e->ext.sampling == PHOVO_SAMPLING_BILINEAR) continue;       // no owner map, no LDS limit
     const bool wide = use_wide_level(e, n_pairs, lv) && !(e->ext.huber_delta[l] > 0.0);
     if (wide) {
@@ -1147,6 +1272,7 @@ int phovo_engine_enqueue_align(phovo_engine *e, int n_pairs, const int *source_f
   auto fusable = [&](int l) {
     const LevelPool &lv = e->levels[l];
     if (e->fusion == PHOVO_FUSION_OFF || e->ext.sampling == PHOVO_SAMPLING_BILINEAR || few_batch) return false;
+    if (e->objective == PHOVO_OBJECTIVE_BIOBJECTIVE) return false;
     if (use_wide_level(e, n_pairs, lv) && !(e->ext.huber_delta[l] > 0.0)) return false;
     return gn_level_fusable(lv.n);
   };
@@ -1201,7 +1327,14 @@ int phovo_engine_enqueue_align(phovo_engine *e, int n_pairs, const int *source_f
       }
     }
 
-    if (e->ext.sampling == PHOVO_SAMPLING_BILINEAR) {
+    if (e->objective == PHOVO_OBJECTIVE_BIOBJECTIVE) {
+      GNBiObjectiveArgs b{};
+      b.lv = a;
+      b.dgx_off = lv.dgx_off; b.dgy_off = lv.dgy_off; b.gain_off = lv.gain_off;
+      PHOVO_HIP_CHECK(gn_launch_level_biobjective(b, lv.plan_bi, e->cu_count, s.stream));
+      record(l, l, PHOVO_LAUNCH_BIOBJECTIVE, lv.plan_bi.threads, lv.plan_bi.lds_bytes, persistent_grid(lv.plan_bi.wgs_per_cu));
+      if (!lv.plan_bi.owner_in_lds) s.owner_tagged = true;    // tagged entries stay behind (the kernel wipes per pair)
+    } else if (e->ext.sampling == PHOVO_SAMPLING_BILINEAR) {
       PHOVO_HIP_CHECK(gn_launch_level_bilinear(a, e->ext.plane_storage, e->ext.jacobian_corrected != 0, e->cu_count, s.stream));
       record(l, l, PHOVO_LAUNCH_BILINEAR, 256, 0, persistent_grid(gn_bilinear_wgs_per_cu(e->ext.plane_storage)));
     } else if (use_wide_level(e, n_pairs, lv) && !(e->ext.huber_delta[l] > 0.0)) {
@@ -1475,6 +1608,15 @@ int phovo_odometry_set_extensions(phovo_odometry *o, const phovo_extensions *ext
   return st;
 }
 
+int phovo_odometry_set_objective(phovo_odometry *o, int objective)
+{
+  if (!o) return fail(PHOVO_E_INVALID_ARGUMENT, "set_objective: null");
+  const int before = o->engine->objective;
+  const int st = phovo_engine_set_objective(o->engine, objective);
+  if (st == PHOVO_OK && objective != before) o->have_source = o->have_target = o->optimized = false;
+  return st;
+}
+
 int phovo_odometry_set_latency_forms(phovo_odometry *o, int on)
 {
   if (!o) return fail(PHOVO_E_INVALID_ARGUMENT, "set_latency_forms: null");
@@ -1525,6 +1667,10 @@ int phovo_odometry_set_source_frame(phovo_odometry *o, const uint8_t *intensity,
 int phovo_odometry_set_target_frame(phovo_odometry *o, const uint8_t *intensity, size_t istride,
                                     const double *depth, size_t dstride, int width, int height)
 {
+  if (o && o->engine->objective == PHOVO_OBJECTIVE_BIOBJECTIVE) {       // the target keeps its depth  (...BiObjective.h:573)
+    if (!depth) return fail(PHOVO_E_INVALID_ARGUMENT, "SetTargetFrame: the bi-objective needs the target's depth");
+    return odometry_set_frame(o, 1, PHOVO_ROLE_TARGET, intensity, istride, depth, dstride, width, height);
+  }
   (void)depth; (void)dstride;                      // "Depth image is ignored"  :478
   return odometry_set_frame(o, 1, PHOVO_ROLE_TARGET, intensity, istride, nullptr, 0, width, height);
 }

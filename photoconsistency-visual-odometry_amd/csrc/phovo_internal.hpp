@@ -108,6 +108,19 @@ size_t gn_wide_workspace_bytes(int n, int n_pairs);
 hipError_t gn_run_level_wide(const GNLevelArgs &args, int n_pairs, void *workspace, int *h_done_scratch,
                              hipStream_t stream);
 hipError_t gn_prepare_kernels();   // raises the dynamic-LDS limit of every instantiation
+// Bi-objective (intensity + depth) form (gn_biobjective_kernel.hip, PHOVO_OBJECTIVE_BIOBJECTIVE): fp64 planes, nearest /
+// scatter sampling.  Every frame of the level carries, beside the four planes, the target's depth gradients (fp64 planes at
+// dgx_off / dgy_off) and its depth gain mean(I) / mean(D) (one double at gain_off).
+struct GNBiObjectiveArgs {
+  GNLevelArgs lv;
+  size_t dgx_off, dgy_off, gain_off;
+};
+// Geometry for a level of n pixels: owner map in LDS where it fits (256 threads, two per CU; else 512 threads, one per
+// CU), else in HBM (lv.g_owner: [pairs][n]).  False: the level is too large (more than 2 097 151 pixels).
+bool gn_plan_level_biobjective(int n, GNLaunchPlan *plan);
+hipError_t gn_prepare_biobjective_kernels();
+hipError_t gn_launch_level_biobjective(const GNBiObjectiveArgs &args, const GNLaunchPlan &plan, int cu_count,
+                                       hipStream_t stream);
 // Sliding-window form for levels whose owner map exceeds LDS (gn_slide_kernel.hip): owner ring in LDS; pairs whose
 // motion leaves the window are appended to args.handover_out for a follow-up gn_launch_level that takes that list.
 hipError_t gn_prepare_slide_kernels();
@@ -138,6 +151,14 @@ hipError_t pyr_load_plane(const unsigned char *src, int n, double *dst, int stor
 // gathers: frames consecutive frames of a level pool, planes at plane_off[] and the records at rec_off in every frame.
 hipError_t pyr_build_tap_records(unsigned char *pool, size_t frame_bytes, const size_t plane_off[PLANES_PER_FRAME],
                                  size_t rec_off, int frames, int n, int storage, hipStream_t stream);
+// Bi-objective target planes (BuildDepthDerivativesPyramids, ...BiObjective.h:214-240): Scharr of depth * (1.0/max_depth),
+// where inv_max_depth is that quotient, with the frame layout of pyr_scharr.
+hipError_t pyr_scharr_scaled(const double *base, size_t frame_stride, size_t img_off, size_t gx_off, size_t gy_off,
+                             int frames, int w, int h, double inv_max_depth, double scale, hipStream_t stream);
+// Per frame: mean(intensity) / mean(depth) over all n pixels (:300), each mean summed in a fixed order, written to
+// base + f*frame_stride + gain_off (elements).
+hipError_t pyr_depth_gain(const double *base, size_t frame_stride, size_t img_off, size_t depth_off, size_t gain_off,
+                          int frames, int n, hipStream_t stream);
 hipError_t pyr_gaussian_blur(double *img, double *tmp, int w, int h, int ksize,
                              const double *d_kernel, hipStream_t stream);
 hipError_t fill_i32(int *dst, size_t n, int value, hipStream_t stream);

@@ -121,6 +121,63 @@ __global__ __launch_bounds__(256) void k_scharr(const double *base, size_t frame
   gy[(size_t)y * w + x] = 0.0 + 1.0 * (ty[2] - ty[0]);
 }
 
+// The depth-gradient planes of the bi-objective target (BuildDepthDerivativesPyramids, ...BiObjective.h:214-240): every
+// level is first scaled, convertTo(..., 1./m_MaxDepth) -- d * (1.0/max_depth) per pixel, inv_max_depth being that
+// quotient -- and then run through the Scharr stencil of k_scharr.  The scaled value is formed at every tap the same way,
+// so the planes equal scharr(depth * (1.0/max_depth)) bit for bit.
+__global__ __launch_bounds__(256) void k_scharr_scaled(const double *base, size_t frame_stride, size_t img_off,
+                                                       size_t gx_off, size_t gy_off, int w, int h, double inv_max_depth,
+                                                       double scale)
+{
+  const int x = blockIdx.x * blockDim.x + threadIdx.x;
+  const int y = blockIdx.y;
+  if (x >= w || y >= h) return;
+  const double *img = base + (size_t)blockIdx.z * frame_stride + img_off;
+  double *gx = const_cast<double *>(base) + (size_t)blockIdx.z * frame_stride + gx_off;
+  double *gy = const_cast<double *>(base) + (size_t)blockIdx.z * frame_stride + gy_off;
+  const double k3 = 3.0 * scale, k10 = 10.0 * scale;
+  const int xl = reflect101(x - 1, w), xr = reflect101(x + 1, w);
+  const int yu = reflect101(y - 1, h), yd = reflect101(y + 1, h);
+  const int rows[3] = {yu, y, yd};
+  double tx[3], ty[3];
+#pragma unroll
+  for (int j = 0; j < 3; j++) {
+    const double *row = img + (size_t)rows[j] * w;
+    const double a = row[xl] * inv_max_depth, b = row[x] * inv_max_depth, c = row[xr] * inv_max_depth;
+    tx[j] = ((-1.0 * a) + (0.0 * b)) + (1.0 * c);
+    ty[j] = ((k3 * a) + (k10 * b)) + (k3 * c);
+  }
+  gx[(size_t)y * w + x] = (k10 * tx[1]) + (k3 * (tx[2] + tx[0]));
+  gy[(size_t)y * w + x] = 0.0 + 1.0 * (ty[2] - ty[0]);
+}
+
+// Depth gain of the bi-objective target (:300): cv::mean(gray) / cv::mean(depth) over every pixel of the level, invalid
+// depth included (a NaN makes the gain NaN, as in the reference).  One workgroup per frame; thread t sums the pixels
+// t, t + 256, ... in order, then a fixed tree over the 256 partial sums: the same bits on every run.
+__global__ __launch_bounds__(256) void k_depth_gain(const double *base, size_t frame_stride, size_t img_off,
+                                                    size_t depth_off, size_t gain_off, int n)
+{
+  __shared__ double s_i[256], s_d[256];
+  const double *frame = base + (size_t)blockIdx.x * frame_stride;
+  const int t = threadIdx.x;
+  double si = 0.0, sd = 0.0;
+  for (int k = t; k < n; k += 256) {
+    si += frame[img_off + (size_t)k];
+    sd += frame[depth_off + (size_t)k];
+  }
+  s_i[t] = si;
+  s_d[t] = sd;
+  __syncthreads();
+  for (int half = 128; half > 0; half >>= 1) {
+    if (t < half) {
+      s_i[t] += s_i[t + half];
+      s_d[t] += s_d[t + half];
+    }
+    __syncthreads();
+  }
+  if (t == 0) const_cast<double *>(frame)[gain_off] = (s_i[0] / (double)n) / (s_d[0] / (double)n);
+}
+
 // One separable Gaussian pass (rows, then columns) -- cv::GaussianBlur(k x k, sigma 3)  (:146-147).
 __global__ __launch_bounds__(256) void k_blur_rows(const double *img, int w, int h, int ksize,
                                                    const double *kern, double *tmp)
@@ -234,6 +291,22 @@ hipError_t pyr_scharr(const double *base, size_t frame_stride, size_t img_off, s
 {
   hipLaunchKernelGGL(k_scharr, grid3d(w, h, frames), dim3(256), 0, stream, base, frame_stride, img_off, gx_off,
                      gy_off, w, h, scale);
+  return hipGetLastError();
+}
+
+hipError_t pyr_scharr_scaled(const double *base, size_t frame_stride, size_t img_off, size_t gx_off, size_t gy_off,
+                             int frames, int w, int h, double inv_max_depth, double scale, hipStream_t stream)
+{
+  hipLaunchKernelGGL(k_scharr_scaled, grid3d(w, h, frames), dim3(256), 0, stream, base, frame_stride, img_off, gx_off,
+                     gy_off, w, h, inv_max_depth, scale);
+  return hipGetLastError();
+}
+
+hipError_t pyr_depth_gain(const double *base, size_t frame_stride, size_t img_off, size_t depth_off, size_t gain_off,
+                          int frames, int n, hipStream_t stream)
+{
+  hipLaunchKernelGGL(k_depth_gain, dim3((unsigned)frames), dim3(256), 0, stream, base, frame_stride, img_off, depth_off,
+                     gain_off, n);
   return hipGetLastError();
 }
 

@@ -68,7 +68,8 @@ class PairReport(C.Structure):
 
 
 FUSION_AUTO, FUSION_OFF, FUSION_SPLIT = 0, -1, -2
-LAUNCH_KINDS = ("persistent", "fused", "slide", "slide_fallback", "wide", "bilinear")
+OBJECTIVE_PHOTOMETRIC, OBJECTIVE_BIOBJECTIVE = 0, 1
+LAUNCH_KINDS = ("persistent", "fused", "slide", "slide_fallback", "wide", "bilinear", "biobjective")
 
 
 class LaunchRecord(C.Structure):
@@ -102,6 +103,7 @@ SYMBOLS = {
     "phovo_odometry_set_config": (C.c_int, [_vp, C.POINTER(Config)]),
     "phovo_odometry_set_extensions": (C.c_int, [_vp, C.POINTER(Extensions)]),
     "phovo_odometry_set_latency_forms": (C.c_int, [_vp, C.c_int]),
+    "phovo_odometry_set_objective": (C.c_int, [_vp, C.c_int]),
     "phovo_odometry_set_min_depth": (C.c_int, [_vp, C.c_double]),
     "phovo_odometry_set_max_depth": (C.c_int, [_vp, C.c_double]),
     "phovo_odometry_set_intrinsic_matrix": (C.c_int, [_vp, _dp]),
@@ -128,6 +130,8 @@ SYMBOLS = {
     "phovo_engine_set_latency_forms": (C.c_int, [_vp, C.c_int]),
     "phovo_engine_set_slide_policy": (C.c_int, [_vp, C.c_int]),
     "phovo_engine_level_uses_wide": (C.c_int, [_vp, C.c_int, C.c_int]),
+    "phovo_engine_set_objective": (C.c_int, [_vp, C.c_int]),
+    "phovo_engine_get_objective": (C.c_int, [_vp, _vp]),
     "phovo_host_register": (C.c_int, [_vp, C.c_size_t]),
     "phovo_host_unregister": (C.c_int, [_vp]),
     "phovo_engine_reserve_frames": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int]),
@@ -139,6 +143,8 @@ SYMBOLS = {
     "phovo_engine_upload_frames_u16": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_size_t, C.c_size_t, _vp, C.c_size_t, C.c_size_t, C.c_double]),
     "phovo_engine_set_level_planes": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "phovo_engine_get_level_planes": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "phovo_engine_get_level_depth_gradients": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),
+    "phovo_engine_get_level_depth_gain": (C.c_int, [_vp, C.c_int, C.c_int, _vp]),
     "phovo_engine_align_pairs": (C.c_int, [_vp, C.c_int, _ip, _ip, _vp, _vp, _vp]),
     "phovo_engine_enqueue_align": (C.c_int, [_vp, C.c_int, _ip, _ip, _vp]),
     "phovo_engine_synchronize": (C.c_int, [_vp]),

@@ -149,6 +149,20 @@ class CPhotoconsistencyOdometryAnalytic:
         return ms.value
 
 
+class CPhotoconsistencyOdometryBiObjective(CPhotoconsistencyOdometryAnalytic):
+    """One frame pair at a time; 1:1 with the reference's CPhotoconsistencyOdometryBiObjective (photometric and depth
+    error together).  The target frame keeps its depth: SetTargetFrame requires it."""
+
+    def __init__(self, device=0):
+        super().__init__(device)
+        check(self._lib.phovo_odometry_set_objective(self._h, native.OBJECTIVE_BIOBJECTIVE), "SetObjective")
+
+    def SetTargetFrame(self, intensityImage, depthImage):
+        if depthImage is None:
+            raise ValueError("the bi-objective needs the target's depth")
+        super().SetTargetFrame(intensityImage, depthImage)
+
+
 class AlignmentEngine:
     """Batched alignment: a pool of frames resident in HBM, pairs aligned one launch per level."""
 
@@ -281,6 +295,30 @@ class AlignmentEngine:
             check(self._lib.phovo_engine_upload_frames_u16(self._h, int(first_frame), g.shape[0], int(roles), g.ctypes.data,
                                                            g.strides[1], g.strides[0], d.ctypes.data, d.strides[1], d.strides[0],
                                                            float(depth_scale)), "phovo_engine_upload_frames_u16")
+
+    def set_objective(self, objective):
+        """native.OBJECTIVE_PHOTOMETRIC (default) or native.OBJECTIVE_BIOBJECTIVE; a change drops the frame pool."""
+        check(self._lib.phovo_engine_set_objective(self._h, int(objective)), "phovo_engine_set_objective")
+
+    def get_objective(self):
+        v = C.c_int()
+        check(self._lib.phovo_engine_get_objective(self._h, C.byref(v)), "phovo_engine_get_objective")
+        return v.value
+
+    def get_level_depth_gradients(self, frame, level):
+        """Bi-objective: the target's depth-gradient planes (grad_x, grad_y) of one level."""
+        w, h = self.level_size(level)
+        gx, gy = np.empty((h, w), dtype=np.float64), np.empty((h, w), dtype=np.float64)
+        check(self._lib.phovo_engine_get_level_depth_gradients(self._h, int(frame), int(level), gx.ctypes.data,
+                                                               gy.ctypes.data), "phovo_engine_get_level_depth_gradients")
+        return gx, gy
+
+    def get_level_depth_gain(self, frame, level):
+        """Bi-objective: mean(intensity) / mean(depth) of one level of a target frame."""
+        g = C.c_double()
+        check(self._lib.phovo_engine_get_level_depth_gain(self._h, int(frame), int(level), C.byref(g)),
+              "phovo_engine_get_level_depth_gain")
+        return g.value
 
     def set_level_planes(self, frame, level, intensity=None, depth=None, grad_x=None, grad_y=None):
         arrs = [None if a is None else np.ascontiguousarray(a, dtype=np.float64)

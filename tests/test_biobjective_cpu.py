@@ -1,0 +1,188 @@
+"""CPU checks of the bi-objective checker (tests/biobjective_ref.py) and of the library surface it is compared with.
+
+* The vectorised normal equations (owner map + row-resolution rule) equal J^T J and J^T r of the literal per-pixel loop
+  of the reference (dense r[2N], J[2N x 6], last writer wins) on seeded tiny images, and the sweep reaches every
+  resolution branch.
+* The per-pixel Jacobians equal the true chain rule of the reference's own forward model
+  (phovo/Maxima/derivatives_photoconsistency_separated_jacobians.wxm), restated in sympy.
+* libphovo_hip.so exports every symbol of the bi-objective surface.
+"""
+import ctypes
+
+import numpy as np
+import pytest
+
+import biobjective_ref as ref
+
+import phovo_amd  # noqa: F401
+from phovo_amd import native
+
+
+def _tiny_case(seed):
+    rs = np.random.RandomState(seed)
+    w, h = rs.randint(1, 10), rs.randint(1, 8)
+    gray = rs.uniform(0, 1, (h, w))
+    d0 = rs.uniform(0.5, 4.0, (h, w))
+    d0[rs.uniform(size=(h, w)) < 0.15] = 0.0                                # holes
+    d0[rs.uniform(size=(h, w)) < 0.05] = 7.0                                # beyond max depth
+    i1 = rs.uniform(0, 1, (h, w))
+    d1 = rs.uniform(0.5, 4.0, (h, w))
+    planes = [rs.normal(0, 1, (h, w)) for _ in range(4)]
+    f = rs.uniform(1.0, 6.0)
+    K = np.array([[f, 0, (w - 1) / 2.0], [0, f, (h - 1) / 2.0], [0, 0, 1.0]])
+    kind = seed % 4
+    if kind == 0:
+        state = np.zeros(6)
+    elif kind == 1:                                                         # zoom: z translation
+        state = np.array([0, 0, rs.uniform(-1.5, -0.2), 0, 0, 0])
+    elif kind == 2:                                                         # large motion
+        state = rs.uniform(-0.6, 0.6, 6)
+    else:
+        state = rs.normal(0, 0.05, 6)
+    gain = rs.uniform(0.1, 2.0)
+    return gray, d0, i1, d1, planes, gain, K, state
+
+
+def test_vectorised_normal_equations_equal_the_literal_loop():
+    totals = dict(intensity_won=0, depth_won_below_n=0, row0_tie=0, jdep_below_n=0, depth_rows_at_n=0)
+    for seed in range(240):
+        gray, d0, i1, d1, (gx, gy, dgx, dgy), gain, K, state = _tiny_case(seed)
+        r, J, nc = ref.literal_system(gray, d0, i1, d1, gx, gy, dgx, dgy, gain, 0, K, state)
+        H0, g0 = J.T @ J, J.T @ r
+        H, g, st = ref.normal_equations(gray, d0, i1, d1, gx, gy, dgx, dgy, gain, 0, K, state)
+        assert st["contributing"] == nc
+        scale_h = max(np.abs(H0).max(), 1e-300)
+        scale_g = max(np.abs(g0).max(), 1e-300)
+        assert np.abs(H - H0).max() <= 1e-12 * scale_h, seed
+        assert np.abs(g - g0).max() <= 1e-12 * scale_g, seed
+        for k in totals:
+            totals[k] += st[k]
+    assert all(v > 0 for v in totals.values()), totals
+
+
+def _chain_rule_model():
+    sympy = pytest.importorskip("sympy")
+    x, y, z, yaw, pitch, roll, px, py, pz, fx, fy, ox, oy = sympy.symbols(
+        "x y z yaw pitch roll px py pz fx fy ox oy", real=True)
+    c, s = sympy.cos, sympy.sin
+    Rt = sympy.Matrix([
+        [c(yaw) * c(pitch), c(yaw) * s(pitch) * s(roll) - s(yaw) * c(roll), c(yaw) * s(pitch) * c(roll) + s(yaw) * s(roll), x],
+        [s(yaw) * c(pitch), s(yaw) * s(pitch) * s(roll) + c(yaw) * c(roll), s(yaw) * s(pitch) * c(roll) - c(yaw) * s(roll), y],
+        [-s(pitch), c(pitch) * s(roll), c(pitch) * c(roll), z],
+        [0, 0, 0, 1]])
+    P = Rt * sympy.Matrix([px, py, pz, 1])
+    u = P[0] * fx / P[2] + ox
+    v = P[1] * fy / P[2] + oy
+    params = (x, y, z, yaw, pitch, roll)
+    out = [sympy.diff(u, p) for p in params] + [sympy.diff(v, p) for p in params] + [sympy.diff(P[2], p) for p in params]
+    return sympy.lambdify(params + (px, py, pz, fx, fy, ox, oy), out, "math")
+
+
+def test_jacobians_are_the_true_chain_rule():
+    """Jint = dI/du du/dp + dI/dv dv/dp and Jdep = gain (dD/du du/dp + dD/dv dv/dp - dZ/dp), per pixel."""
+    f = _chain_rule_model()
+    rs = np.random.RandomState(5)
+    for case in range(20):
+        h, w = 5, 7
+        K = np.array([[rs.uniform(3, 8), 0, 3.0], [0, rs.uniform(3, 8), 2.0], [0, 0, 1.0]])
+        state = rs.uniform(-0.4, 0.4, 6)
+        d0 = rs.uniform(1.0, 3.0, (h, w))
+        gx, gy, dgx, dgy = [rs.normal(0, 1, (h, w)) for _ in range(4)]
+        gain = rs.uniform(0.2, 2.0)
+        wp = ref.warp(d0, 0, K, state, 0.3, 5.0)
+        Jint, Jdep = ref.jacobians(wp, gx, gy, dgx, dgy, gain, state)
+        fx, fy, ox, oy = K[0, 0], K[1, 1], K[0, 2], K[1, 2]
+        for i in range(h * w):
+            vals = f(*state, wp["px"][i], wp["py"][i], wp["pz"][i], fx, fy, ox, oy)
+            du, dv, dz = np.array(vals[0:6]), np.array(vals[6:12]), np.array(vals[12:18])
+            ji = gx.ravel()[i] * du + gy.ravel()[i] * dv
+            jd = gain * (dgx.ravel()[i] * du + dgy.ravel()[i] * dv - dz)
+            np.testing.assert_allclose(Jint[i], ji, rtol=1e-10, atol=1e-10 * max(1.0, np.abs(ji).max()))
+            np.testing.assert_allclose(Jdep[i], jd, rtol=1e-10, atol=1e-10 * max(1.0, np.abs(jd).max()))
+
+
+def test_row_zero_tie_goes_to_depth():
+    """Pixel 0 lands on target 0: row 0 carries Jdep(0) and the depth residual (it writes them after its intensity
+    row, :422-443)."""
+    gray = np.array([[0.2, 0.7]])
+    d0 = np.array([[1.0, 0.0]])
+    i1 = np.array([[0.5, 0.1]])
+    d1 = np.array([[1.5, 2.0]])
+    planes = [np.array([[0.3, 0.1]]), np.array([[0.2, 0.4]]), np.array([[0.6, 0.5]]), np.array([[0.1, 0.9]])]
+    K = np.array([[2.0, 0, 0.0], [0, 2.0, 0.0], [0, 0, 1.0]])
+    r, J, nc = ref.literal_system(gray, d0, i1, d1, *planes, 0.8, 0, K, np.zeros(6))
+    assert nc == 1
+    assert r[0] == pytest.approx(0.8 * (1.5 - 1.0))
+    H, g, st = ref.normal_equations(gray, d0, i1, d1, *planes, 0.8, 0, K, np.zeros(6))
+    assert st["row0_tie"] == 1
+    np.testing.assert_allclose(g, J.T @ r, rtol=1e-14)
+
+
+def test_library_exports_the_biobjective_surface():
+    lib = ctypes.CDLL(native.library_path())
+    for name in ("phovo_engine_set_objective", "phovo_engine_get_objective", "phovo_odometry_set_objective",
+                 "phovo_engine_get_level_depth_gradients", "phovo_engine_get_level_depth_gain"):
+        assert hasattr(lib, name), name
+    assert native.OBJECTIVE_PHOTOMETRIC == 0 and native.OBJECTIVE_BIOBJECTIVE == 1
+    assert native.LAUNCH_KINDS[6] == "biobjective"
+
+
+def test_literal_loop_write_order_on_a_collision():
+    """One row of 4 pixels at depth 2 moved by z = +2 (f = 1, cx = 0): the warped columns 0, 0.5, 1, 1.5 round (half away
+    from zero) to targets 0, 1, 1, 2.  Pixels 1 and 2 collide on target 1 and the later one, 2, owns its residual; row 2
+    gets the depth residual of pixel 1 and of pixel 2 and then the intensity residual of pixel 3, which is written last."""
+    gray = np.array([[0.1, 0.2, 0.3, 0.4]])
+    d0 = np.full((1, 4), 2.0)
+    i1 = np.array([[0.9, 0.8, 0.7, 0.6]])
+    d1 = np.array([[2.5, 2.25, 2.75, 3.0]])
+    planes = [np.ones((1, 4)) * v for v in (0.1, 0.2, 0.3, 0.4)]
+    K = np.array([[1.0, 0, 0.0], [0, 1.0, 0.0], [0, 0, 1.0]])
+    state = np.array([0.0, 0.0, 2.0, 0.0, 0.0, 0.0])
+    gain = 0.5
+    r, J, nc = ref.literal_system(gray, d0, i1, d1, *planes, gain, 0, K, state)
+    assert nc == 4
+    assert list(ref.warp(d0, 0, K, state, 0.3, 5.0)["tgt"]) == [0, 1, 1, 2]
+    assert r[0] == gain * (d1[0, 0] - d0[0, 0])              # pixel 0: depth row 0 after its intensity row 0
+    assert r[1] == i1[0, 1] - gray[0, 2]                     # target 1: pixel 2 wrote last
+    assert r[2] == i1[0, 2] - gray[0, 3]                     # pixel 3's intensity write follows pixel 2's depth write
+    assert r[4] == gain * (d1[0, 2] - d0[0, 3])              # pixel 3's depth row
+    assert r[3] == 0.0 and r[5] == r[6] == r[7] == 0.0
+    H, g, st = ref.normal_equations(gray, d0, i1, d1, *planes, gain, 0, K, state)
+    assert st["row0_tie"] == 1 and st["intensity_won"] == 2
+    np.testing.assert_allclose(g, J.T @ r, rtol=1e-13, atol=1e-14)
+    np.testing.assert_allclose(H, J.T @ J, rtol=1e-13, atol=1e-14)
+
+
+CPP_CLIENT = r"""
+#include "phovo/CPhotoconsistencyOdometryBiObjective.h"
+int main(int argc, char **)
+{
+  if (argc > 5) {          // compiled and linked, never run here: constructing the class needs a GPU
+    phovo::Analytic::CPhotoconsistencyOdometryBiObjective<unsigned char, double> o;
+    o.ReadConfigurationFile("config.yml");
+    o.SetMinDepth(0.3);
+    o.SetMaxDepth(5.0);
+    o.Optimize();
+    return (int)o.GetOptimalStateVector()(0);
+  }
+  int objective = -1;
+  return (PHOVO_OBJECTIVE_BIOBJECTIVE == 1 && phovo_engine_get_objective(nullptr, &objective) != PHOVO_OK) ? 0 : 1;
+}
+"""
+
+
+def test_cpp_client_of_the_biobjective_class_compiles_and_links(tmp_path):
+    import os
+    import shutil
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cxx = shutil.which("g++") or shutil.which("c++")
+    if cxx is None:
+        pytest.skip("no C++ compiler")
+    src = tmp_path / "client.cpp"
+    src.write_text(CPP_CLIENT)
+    lib = native.library_path()
+    exe = tmp_path / "client"
+    subprocess.check_call([cxx, "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(root, "include"),
+                           str(src), lib, "-Wl,-rpath," + os.path.dirname(lib), "-o", str(exe)])
+    assert subprocess.run([str(exe)]).returncode == 0
