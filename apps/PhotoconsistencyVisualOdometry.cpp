@@ -2,9 +2,14 @@
 // directory, writing a TUM trajectory file.
 //
 //   ./PhotoconsistencyVisualOdometry <config_file.yml> <rgbd_dataset_directory> <output_trajectory_file> [--batch [--gpus N] [--rccl]]
-//                                    [--method analytic|biobjective]
+//                                    [--method analytic|biobjective] [--information <file>]
 // --method picks the aligner as the reference's USE_PHOTOCONSISTENCY_ODOMETRY_METHOD does (0 = analytic, the default;
 // 2 = bi-objective: photometric and depth error together, CPhotoconsistencyOdometryBiObjective), in every mode.
+// --information <file> (not in the reference; analytic method, one device): one line per pair, stamped like its trajectory
+// line, with the Gauss-Newton system at the pair's optimal state on the finest level the configuration optimises --
+// `timestamp rows cost` and the 21 upper-triangle entries of J^T J (phovo_pair_system_format).  The loop takes it from the
+// class surface (GetPairSystem), --batch from phovo_engine_evaluate_pairs; both write the same bytes, and the trajectory
+// file is the same with and without the flag.  The printed times do not include the evaluation.
 //
 // Behaviour kept from the reference's app (apps/PhotoconsistencyVisualOdometry/PhotoconsistencyVisualOdometry.cpp):
 //   * <dir>/rgb.txt and <dir>/depth.txt are read in lock step -- line n of one is paired with line n of the
@@ -104,10 +109,19 @@ static bool writePose(std::ofstream &f, double timestamp, const Matrix44Type &po
   return true;
 }
 
+static bool writeSystem(std::ofstream &f, double timestamp, const phovo_pair_system &s)
+{
+  char line[1024];
+  if (phovo_pair_system_format(timestamp, &s, line, sizeof(line)) != PHOVO_OK) return false;
+  f << line << std::endl;
+  return true;
+}
+
 static void printHelp()
 {
   std::cout << "./PhotoconsistencyVisualOdometry <config_file.yml> <rgbd_dataset_directory> "
-               "<output_trajectory_file> [--batch [--gpus N] [--rccl]] [--method analytic|biobjective]" << std::endl;
+               "<output_trajectory_file> [--batch [--gpus N] [--rccl]] [--method analytic|biobjective] "
+               "[--information <file>]" << std::endl;
 }
 
 #define PHOVO_OK_OR_FAIL(call)                                                              \
@@ -121,6 +135,7 @@ int main(int argc, char *argv[])
   int nGpus = 1;                                      // --batch --gpus N: the pairs of the sequence sharded over N devices
   bool rccl = false;                                  // ... --rccl: the shards' states meet through ONE RCCL all_gather
   int objective = PHOVO_OBJECTIVE_PHOTOMETRIC;        // --method analytic (default) | biobjective
+  std::string informationPath;                        // --information <file>: the pairs' systems at their optimal states
   for (int i = 4; i < argc; i++) {
     const std::string a(argv[i]);
     if (a == "--batch") batch = true;
@@ -132,10 +147,20 @@ int main(int argc, char *argv[])
     }
     else if (a == "--rccl") rccl = true;
     else if (a == "--gpus" && i + 1 < argc) nGpus = std::atoi(argv[++i]);
+    else if (a == "--information" && i + 1 < argc) informationPath = argv[++i];
     else { printHelp(); return EXIT_FAILURE; }
   }
   if (nGpus < 1 || (nGpus > 1 && !batch)) { std::cerr << "--gpus N needs --batch and N >= 1" << std::endl; return EXIT_FAILURE; }
   if (rccl && !batch) { std::cerr << "--rccl needs --batch" << std::endl; return EXIT_FAILURE; }
+  const bool information = !informationPath.empty();
+  if (information && (nGpus > 1 || rccl)) {
+    std::cerr << "--information runs on one device: it cannot be combined with --gpus N > 1 or --rccl" << std::endl;
+    return EXIT_FAILURE;
+  }
+  if (information && objective != PHOVO_OBJECTIVE_PHOTOMETRIC) {
+    std::cerr << "--information needs --method analytic (the bi-objective has no pair system)" << std::endl;
+    return EXIT_FAILURE;
+  }
   if (!fileExists(configFile)) { std::cerr << "Input config file " << configFile << " does not exist" << std::endl; return EXIT_FAILURE; }
   if (!fileExists(datasetDir)) { std::cerr << "Input RGBD dataset directory " << datasetDir << " does not exist" << std::endl; return EXIT_FAILURE; }
   const std::string rgbList = datasetDir + "/rgb.txt", depthList = datasetDir + "/depth.txt";
@@ -161,6 +186,11 @@ int main(int argc, char *argv[])
   if (!trajectoryFile.is_open()) { std::cerr << "Cannot open output trajectory file " << trajectoryPath << std::endl; return EXIT_FAILURE; }
   trajectoryFile << "# estimated trajectory" << std::endl;                    // :187-188
   trajectoryFile << "# timestamp tx ty tz qx qy qz qw" << std::endl;
+  std::ofstream informationFile;
+  if (information) {
+    informationFile.open(informationPath.c_str());
+    if (!informationFile.is_open()) { std::cerr << "Cannot open output information file " << informationPath << std::endl; return EXIT_FAILURE; }
+  }
   if (nFrames < 2) return EXIT_SUCCESS;
 
   Matrix44Type pose = Matrix44Type::Identity();
@@ -192,6 +222,7 @@ int main(int argc, char *argv[])
         const Vector6Type state = odometry.GetOptimalStateVector();
         PHOVO_OK_OR_FAIL(phovo_trajectory_chain(1, state.data(), pose.data(), nullptr));   // pose *= Rt^-1  :233-234
         if (!writePose(trajectoryFile, rgb[t].timestamp, pose)) return EXIT_FAILURE;
+        if (information && !writeSystem(informationFile, rgb[t].timestamp, odometry.GetPairSystem())) return EXIT_FAILURE;
         std::cout << "Rt:" << std::endl << Rt << std::endl;
         prevGray = curGray.clone();
         prevDepth = curDepth.clone();
@@ -270,6 +301,11 @@ int main(int argc, char *argv[])
       // RCCL all_gather is).  With phovo_engine_set_batch_invariant a pair's result does not depend on its batch, so the file is the same for every N.
       const int nPairs = (int)nFrames - 1;
       std::vector<double> states((size_t)nPairs * 6);
+      std::vector<phovo_pair_system> systems(information ? (size_t)nPairs : 0);
+      int finestLevel = -1;                             // --information: the lowest level the configuration optimises
+      for (int l = cfg.num_levels - 1; l >= 0; l--)
+        if (cfg.max_num_iterations[l] > 0) finestLevel = l;
+      if (information && finestLevel < 0) { std::cerr << "--information: the configuration optimises no level" << std::endl; return EXIT_FAILURE; }
       std::vector<std::string> shardError(nGpus);
       // --rccl: instead of every shard copying its states to the host itself, the shards' device buffers meet in ONE RCCL
       // all_gather (one communicator and one host thread per device in this one process) and rank 0 copies the lot out --
@@ -283,6 +319,7 @@ int main(int argc, char *argv[])
         if (!group.create(devices, &err)) { std::cerr << err << std::endl; return EXIT_FAILURE; }
       }
       const auto t0 = std::chrono::steady_clock::now();
+      std::chrono::steady_clock::time_point tAligned{};     // --information (one shard): when the alignment had ended
       // Every shard thread arrives at the vote exactly once -- also one that failed on its way there, and one whose range
       // is empty -- and the collective is entered only if all of them are ready for it: a rank that stays away from an
       // all_gather leaves the others waiting in it for ever.
@@ -315,6 +352,10 @@ int main(int argc, char *argv[])
           if (!rccl) {
             if (phovo_engine_align_pairs(engine, b - a, src.data(), tgt.data(), nullptr, states.data() + (size_t)a * 6, nullptr) != PHOVO_OK)
               return fail("phovo_engine_align_pairs");
+            if (information) tAligned = std::chrono::steady_clock::now();      // (the evaluation is not part of the timed run)
+            if (information && phovo_engine_evaluate_pairs(engine, b - a, src.data(), tgt.data(), states.data() + (size_t)a * 6,
+                                                           finestLevel, systems.data() + a) != PHOVO_OK)
+              return fail("phovo_engine_evaluate_pairs");
             return true;
           }
           if (phovo_engine_enqueue_align(engine, b - a, src.data(), tgt.data(), nullptr) != PHOVO_OK) return fail("phovo_engine_enqueue_align");
@@ -348,7 +389,7 @@ int main(int argc, char *argv[])
           std::copy(group.gathered(g), group.gathered(g) + (size_t)(b - a) * 6, states.begin() + (size_t)a * 6);
         }
       }
-      const auto t1 = std::chrono::steady_clock::now();
+      const auto t1 = information ? tAligned : std::chrono::steady_clock::now();
       std::cout << "Time = " << std::chrono::duration<double>(t1 - t0).count() << " sec. (" << nPairs << " pairs on " << nGpus
                 << " device(s), upload and pyramids included)" << std::endl;
       std::vector<double> poses((size_t)nPairs * 16);
@@ -357,6 +398,7 @@ int main(int argc, char *argv[])
         Matrix44Type P;
         for (int i = 0; i < 16; i++) P(i) = poses[(size_t)p * 16 + i];
         if (!writePose(trajectoryFile, rgb[(size_t)p + 1].timestamp, P)) return EXIT_FAILURE;
+        if (information && !writeSystem(informationFile, rgb[(size_t)p + 1].timestamp, systems[(size_t)p])) return EXIT_FAILURE;
       }
     }
   } catch (const std::exception &e) {
@@ -364,5 +406,6 @@ int main(int argc, char *argv[])
     return EXIT_FAILURE;
   }
   trajectoryFile.close();
+  if (information) informationFile.close();
   return EXIT_SUCCESS;
 }

@@ -131,6 +131,15 @@ class CPhotoconsistencyOdometryAnalytic : public CPhotoconsistencyOdometry<TPixe
     Check(phovo_odometry_get_report(m_Handle, &r), "GetReport");
     return r;
   }
+  // Not in the reference: the Gauss-Newton system (J^T W J, J^T W r, r^T W r, rows) at the optimal state on the finest
+  // level the configuration optimises, for a pose graph or an outlier test (phovo_hip.h, phovo_pair_system).  Throws
+  // before Optimize() and, PHOVO_E_UNSUPPORTED, for the bi-objective and bilinear sampling.
+  phovo_pair_system GetPairSystem() const
+  {
+    phovo_pair_system s;
+    Check(phovo_odometry_get_pair_system(m_Handle, &s), "GetPairSystem");
+    return s;
+  }
   double GetLastOptimizeMilliseconds() const
   {
     double ms = 0;

@@ -8,7 +8,7 @@
 // The types come from the same place as CPhotoconsistencyOdometryAnalytic.h's (PHOVO_HIP_USE_REFERENCE_TYPES or
 // phovo/compat/).  It differs from that class in one method only: SetTargetFrame keeps the target's depth (reference
 // :566-578), so the depth image must be valid.  Plane storage, sampling and Huber extensions other than the reference's
-// are refused (std::runtime_error, PHOVO_E_UNSUPPORTED).
+// are refused (std::runtime_error, PHOVO_E_UNSUPPORTED), and so is the inherited GetPairSystem().
 #ifndef PHOVO_HIP_CPHOTOCONSISTENCY_ODOMETRY_BIOBJECTIVE_H
 #define PHOVO_HIP_CPHOTOCONSISTENCY_ODOMETRY_BIOBJECTIVE_H
 

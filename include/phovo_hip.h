@@ -88,6 +88,31 @@ typedef struct phovo_pair_report {
                                             them (a rank-deficient J^T J) is what precedes PHOVO_PAIR_NONFINITE.   */
 } phovo_pair_report;
 
+/* The Gauss-Newton system of one frame pair at a given state on one level (phovo_engine_evaluate_pairs,
+ * phovo_odometry_get_pair_system) -- not in the reference, which forms it in every iteration and discards it.
+ * Its rows are exactly those ComputeResidualsAndJacobians (...Analytic.h:191-367) fills at that state on that level:
+ * the depth gate (:280) and the round() bounds test (:297-303), the residual scattered to the rounded target index
+ * with the last source pixel in raster order winning (:358), the target gradients read at the SOURCE index
+ * (:346-347), and the reference's Jacobian INCLUDING its transcription slip `temp11 = cos(pitch)*cos(yaw) + x` (:253):
+ * this is the matrix the aligner inverts (:538-540), not the normal matrix of the true warp Jacobian.  With
+ * huber_delta[level] > 0 the rows carry the aligner's IRLS weights at that state (w = 1 if |r| <= delta, delta/|r|
+ * otherwise); else W = I.  The parameterisation is the state's: (x, y, z, yaw, pitch, roll).  A caller that turns
+ * `information` into a covariance (its inverse, scaled by cost / (rows - 6) for example) gets the covariance of that
+ * parameterisation under that Jacobian.
+ * Relation to the aligner: the system the aligner solves in iteration k of a level is this system at the state the
+ * iteration starts from; after its last system the aligner always takes one more step, so the system AT the returned
+ * state is a pass of its own.  Arithmetic: fp64 on the device; the sums are taken in an order that depends on the
+ * level size only, so a pair's result is the same bit for bit whatever the batch, its position in it, or the engine's
+ * fusion, latency-form and batch-invariant settings. */
+typedef struct phovo_pair_system {
+  double   information[36]; /* J^T W J, row-major, exactly symmetric (filled from the upper triangle)            */
+  double   gradient[6];     /* J^T W r                                                                          */
+  double   cost;            /* r^T W r over the reference's residual vector, which is indexed by TARGET pixel:
+                               every target pixel with an owner counts, filled Jacobian row or not             */
+  int32_t  rows;            /* rows of J filled: the count phovo_pair_report.valid_pixels uses                  */
+  uint32_t flags;           /* PHOVO_PAIR_RANK_DEFICIENT if rows < 6, PHOVO_PAIR_NONFINITE if any sum is inf/NaN */
+} phovo_pair_system;
+
 /* ---- extensions that are NOT in the reference (BASELINE.json configs[4]); all off by default -------------
  * plane_storage: how the pyramid planes are kept in HBM.  Arithmetic is fp64 in every mode; pyramids are built
  * in fp64 and rounded once when stored (fp64 -> fp32 by round-to-nearest-even, fp16 via fp32).
@@ -173,6 +198,10 @@ int phovo_trajectory_chain(int n_pairs, const double *states /* [n_pairs][6] */,
  * rotation block as Eigen::Quaternion(Matrix3) builds it (:237); no newline.  Returns PHOVO_E_INVALID_ARGUMENT if
  * `capacity` is too small (256 always suffices). */
 int phovo_trajectory_format_pose(double timestamp, const double pose[16], char *line, size_t capacity);
+/* One line of the VisualOdometry app's --information file: `timestamp rows cost` and the 21 upper-triangle entries of
+ * s->information in row-major order (H00 H01 .. H05 H11 .. H55), every double as "%.17g" (round-trips exactly), no
+ * newline.  Host only.  PHOVO_E_INVALID_ARGUMENT for NULL pointers or if `capacity` is too small (640 always suffices). */
+int phovo_pair_system_format(double timestamp, const phovo_pair_system *s, char *line, size_t capacity);
 
 /* warpImage, CPhotoconsistencyOdometry.h:73-134 -- the forward warp both reference apps call after Optimize()
  * (...FrameAlignment.cpp:108, ...VisualOdometry.cpp:248-250) to show |I1 - warp(I0)|.  Host buffers in and out,
@@ -213,6 +242,11 @@ int phovo_odometry_optimize(phovo_odometry *o);                                 
 int phovo_odometry_get_optimal_state_vector(const phovo_odometry *o, double state[6]);     /* :566 */
 int phovo_odometry_get_optimal_rigid_transformation_matrix(const phovo_odometry *o, double rt[16]); /* :572 */
 int phovo_odometry_get_report(const phovo_odometry *o, phovo_pair_report *report);
+/* not in the reference: the system (phovo_pair_system) at the optimal state on the finest level the configuration
+ * optimises (the lowest L with max_num_iterations[L] > 0), evaluated on demand (Optimize() and its timing are unchanged).
+ * PHOVO_E_NOT_READY before a successful Optimize() and after a Set*Frame since; PHOVO_E_UNSUPPORTED as for
+ * phovo_engine_evaluate_pairs (bilinear sampling, bi-objective). */
+int phovo_odometry_get_pair_system(const phovo_odometry *o, phovo_pair_system *out);
 /* Device time of the last Optimize() in milliseconds (HIP events; the reference wraps the same
  * call in cv::TickMeter, apps/PhotoconsistencyFrameAlignment/PhotoconsistencyFrameAlignment.cpp:99-102). */
 int phovo_odometry_last_optimize_ms(const phovo_odometry *o, double *ms);
@@ -354,6 +388,24 @@ int phovo_engine_fetch_results(phovo_engine *e, int n_pairs, double *out_states,
                                phovo_pair_report *reports);
 /* Device pointer to the n_pairs x 6 fp64 result of the last enqueue (for an RCCL gather). */
 int phovo_engine_results_device_ptr(phovo_engine *e, void **states);
+
+/* The Gauss-Newton system (phovo_pair_system) of n_pairs (source, target) frame pairs at the states [n_pairs][6] on one
+ * level -- e.g. at the optimal states of an alignment, on the finest level it optimised, as information matrices for a
+ * pose graph and costs to reject bad alignments.  Synchronous, like phovo_engine_align_pairs; ordered behind every
+ * enqueue in flight, and it changes nothing that phovo_engine_fetch / fetch_results return.  Photometric objective with
+ * nearest / scatter sampling, any plane storage, with or without Huber weights.
+ *   PHOVO_E_UNSUPPORTED       bilinear sampling or the bi-objective
+ *   PHOVO_E_INVALID_ARGUMENT  NULL pointers (with n_pairs > 0), n_pairs < 0, a frame index or level out of range
+ *   PHOVO_E_NOT_READY         no intrinsics, the level is not stored (phovo_engine_level_is_stored), or a source frame
+ *                             was not given its depth / a target frame its gradients (uploaded without that role)
+ *                             on that level.  Roles are kept per frame AND level: an upload gives its roles on every
+ *                             level, phovo_engine_set_level_planes on the level it writes (a depth plane: source, a
+ *                             gradient plane: target).
+ * n_pairs == 0 is OK.  Device memory: a workspace kept until the engine is destroyed -- per pair of a group 4 bytes of
+ * owner map per pixel, 1 bit of ballots per pixel and 256 bytes of tile sums per 1024 pixels; large batches run in
+ * groups whose owner maps take at most 256 MB (218 pairs at 640x480). */
+int phovo_engine_evaluate_pairs(phovo_engine *e, int n_pairs, const int *src, const int *tgt,
+                                const double *states /* [n_pairs][6] */, int level, phovo_pair_system *out);
 
 /* Pipelining.  Pairs are independent, and with data-dependent termination a batch ends with a few long pairs on an
  * otherwise idle chip.  The engine therefore keeps PHOVO_ENQUEUE_DEPTH enqueues in flight, each with its own stream, pair

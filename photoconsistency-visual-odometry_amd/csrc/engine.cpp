@@ -130,6 +130,13 @@ struct phovo_engine {
   bool batch_invariant = false;                // every batch takes the same kernels and geometries (phovo_engine_set_batch_invariant)
   int objective = PHOVO_OBJECTIVE_PHOTOMETRIC;  // phovo_engine_set_objective
   bool latency_forms = false;                  // a handful of pairs may take the forms that finish soonest also where a level has a one-workgroup form with its owner map in LDS (phovo_engine_set_latency_forms)
+  std::vector<unsigned char> frame_roles;      // [frame][PHOVO_MAX_LEVELS]: PHOVO_ROLE_* each level of each frame has been given since the
+                                               // pool was reserved (an upload: every level; a plane write: its level)
+  // phovo_engine_evaluate_pairs: its own workspace (owner maps, ballots, tile sums, pair data), allocated on first use and
+  // kept until the engine is destroyed; between calls the owner maps hold -1 everywhere
+  unsigned char *d_eval_ws = nullptr;
+  size_t eval_ws_capacity = 0;
+  size_t eval_owner_clean = 0;                 // leading ints of d_eval_ws known to hold -1
 };
 
 namespace {
@@ -152,6 +159,7 @@ void free_pool(phovo_engine *e)
   e->d_blur_kernel = nullptr;
   e->stage_frames = 0; e->stage_has_f64 = e->stage_has_u16 = false;
   e->n_frames = 0; e->width = 0; e->height = 0;
+  e->frame_roles.clear();
 }
 
 void free_pairs(AlignSlot &s)
@@ -541,6 +549,7 @@ int phovo_engine_destroy(phovo_engine *e)
   if (e->stream) (void)hipStreamSynchronize(e->stream);
     (void)quiesce(e);
   free_pool(e);
+  if (e->d_eval_ws) (void)hipFree(e->d_eval_ws);
   for (AlignSlot &s : e->slots) {
     free_slot(s);
     for (int l = 0; l < PHOVO_MAX_LEVELS; l++) {
@@ -868,6 +877,7 @@ int phovo_engine_reserve_frames(phovo_engine *e, int n_frames, int width, int he
   }
   if (he != hipSuccess) { free_pool(e); return fail(PHOVO_E_HIP, std::string("hipMalloc(staging): ") + hipGetErrorString(he)); }
   e->n_frames = n_frames; e->width = width; e->height = height;
+  e->frame_roles.assign((size_t)n_frames * PHOVO_MAX_LEVELS, 0);
   PHOVO_HIP_CHECK(hipStreamSynchronize(e->stream));
   return PHOVO_OK;
 }
@@ -971,6 +981,8 @@ static int upload_batch(phovo_engine *e, int first_frame, int count, int roles,
   // the caller's buffers may be reused on return, and the staging buffers by the next upload
   PHOVO_HIP_CHECK(hipStreamSynchronize(e->copy_stream));
   PHOVO_HIP_CHECK(hipStreamSynchronize(e->stream));
+  for (size_t i = (size_t)first_frame * PHOVO_MAX_LEVELS; i < (size_t)(first_frame + count) * PHOVO_MAX_LEVELS; i++)
+    e->frame_roles[i] |= (unsigned char)(roles & PHOVO_ROLE_BOTH);
   return PHOVO_OK;
 }
 
@@ -1053,6 +1065,9 @@ int phovo_engine_set_level_planes(phovo_engine *e, int frame, int level,
     }
   }
   PHOVO_HIP_CHECK(hipStreamSynchronize(e->stream));
+  unsigned char &roles = e->frame_roles[(size_t)frame * PHOVO_MAX_LEVELS + (size_t)level];     // (this level only)
+  if (depth) roles |= PHOVO_ROLE_SOURCE;
+  if (grad_x || grad_y) roles |= PHOVO_ROLE_TARGET;
   return PHOVO_OK;
 }
 
@@ -1480,6 +1495,99 @@ int phovo_engine_align_pairs(phovo_engine *e, int n_pairs, const int *source_fra
   return phovo_engine_fetch_results(e, n_pairs, out_states, reports);
 }
 
+// Owner maps of one evaluation group take at most this much: 218 pairs at 640x480.
+static constexpr size_t EVAL_OWNER_CAP_BYTES = (size_t)256 << 20;
+
+int phovo_engine_evaluate_pairs(phovo_engine *e, int n_pairs, const int *src, const int *tgt, const double *states,
+                                int level, phovo_pair_system *out)
+{
+  if (!e) return fail(PHOVO_E_INVALID_ARGUMENT, "evaluate_pairs: null engine");
+  if (e->objective != PHOVO_OBJECTIVE_PHOTOMETRIC)
+    return fail(PHOVO_E_UNSUPPORTED, "evaluate_pairs: the bi-objective has no pair system here (photometric objective only)");
+  if (e->ext.sampling != PHOVO_SAMPLING_NEAREST_SCATTER)
+    return fail(PHOVO_E_UNSUPPORTED, "evaluate_pairs: bilinear sampling has no pair system here (nearest / scatter only)");
+  if (n_pairs < 0) return fail(PHOVO_E_INVALID_ARGUMENT, "evaluate_pairs: n_pairs < 0");
+  if (n_pairs > 0 && (!src || !tgt || !states || !out)) return fail(PHOVO_E_INVALID_ARGUMENT, "evaluate_pairs: null");
+  if (level < 0 || level >= e->cfg.num_levels) return fail(PHOVO_E_INVALID_ARGUMENT, "evaluate_pairs: level out of range");
+  if (n_pairs == 0) return PHOVO_OK;
+  if (e->n_frames == 0) return fail(PHOVO_E_NOT_READY, "evaluate_pairs: no frames uploaded");
+  for (int i = 0; i < n_pairs; i++) {
+    if (src[i] < 0 || src[i] >= e->n_frames || tgt[i] < 0 || tgt[i] >= e->n_frames)
+      return fail(PHOVO_E_INVALID_ARGUMENT, "evaluate_pairs: frame index out of range");
+  }
+  if (!e->have_K) return fail(PHOVO_E_NOT_READY, "evaluate_pairs: SetIntrinsicMatrix has not been called");
+  const LevelPool &lv = e->levels[level];
+  if (!lv.stored) return fail(PHOVO_E_NOT_READY, "evaluate_pairs: the level is not resident (phovo_engine_level_is_stored)");
+  for (int i = 0; i < n_pairs; i++) {
+    if (!(e->frame_roles[(size_t)src[i] * PHOVO_MAX_LEVELS + (size_t)level] & PHOVO_ROLE_SOURCE))
+      return fail(PHOVO_E_NOT_READY, "evaluate_pairs: a source frame has no depth (upload it with PHOVO_ROLE_SOURCE)");
+    if (!(e->frame_roles[(size_t)tgt[i] * PHOVO_MAX_LEVELS + (size_t)level] & PHOVO_ROLE_TARGET))
+      return fail(PHOVO_E_NOT_READY, "evaluate_pairs: a target frame has no gradients (upload it with PHOVO_ROLE_TARGET)");
+  }
+  PHOVO_HIP_CHECK(hipSetDevice(e->device));
+  PHOVO_HIP_CHECK(quiesce(e));                 // behind every enqueue in flight; their slots are not touched
+
+  // Workspace for a group of G pairs, every region 256-byte aligned: owner maps first (kept at -1 between calls), then
+  // ballots, tile sums, states, pair indices and the results.
+  const size_t n = (size_t)lv.n, n_chunks = (n + 63) / 64;
+  const int group = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_pairs, EVAL_OWNER_CAP_BYTES / (n * sizeof(int))));
+  auto align256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t G = (size_t)group;
+  const size_t owner_bytes = align256(G * n * sizeof(int));
+  const size_t mask_off = owner_bytes;
+  const size_t part_off = mask_off + align256(G * n_chunks * sizeof(unsigned long long));
+  const size_t st_off = part_off + align256(G * gn_eval_slab_doubles_per_pair(lv.n) * sizeof(double));
+  const size_t src_off = st_off + align256(G * 6 * sizeof(double));
+  const size_t tgt_off = src_off + align256(G * sizeof(int));
+  const size_t out_off = tgt_off + align256(G * sizeof(int));
+  const size_t need = out_off + align256(G * sizeof(phovo_pair_system));
+  if (need > e->eval_ws_capacity) {
+    if (e->d_eval_ws) { (void)hipFree(e->d_eval_ws); e->d_eval_ws = nullptr; e->eval_ws_capacity = 0; }
+    PHOVO_HIP_CHECK(hipMalloc(&e->d_eval_ws, need));
+    e->eval_ws_capacity = need;
+    e->eval_owner_clean = 0;
+  }
+  unsigned char *ws = e->d_eval_ws;
+  int *d_owner = reinterpret_cast<int *>(ws);
+  // the owner maps of this call must start at -1: pass 2 restores what it covers, but the regions behind an earlier, smaller
+  // owner area may hold ballots or sums of that call
+  const size_t owner_ints = G * n;
+  if (owner_ints > e->eval_owner_clean) {
+    e->eval_owner_clean = 0;
+    PHOVO_HIP_CHECK(fill_i32(d_owner, owner_ints, -1, e->stream));
+  }
+  e->eval_owner_clean = 0;                     // (until this call has ended without an error)
+
+  GNEvalArgs a{};
+  a.w = lv.w; a.h = lv.h; a.n = lv.n; a.n_chunks = (int)n_chunks;
+  const double scaleFactor = 1.0 / std::pow(2, level);                               // :203
+  a.fx = e->K[0] * scaleFactor; a.fy = e->K[4] * scaleFactor;                        // :204-207
+  a.ox = e->K[2] * scaleFactor; a.oy = e->K[5] * scaleFactor;
+  a.ifx = 1.f / a.fx; a.ify = 1.f / a.fy;                                            // :208-209
+  a.min_depth = e->min_depth; a.max_depth = e->max_depth;
+  a.huber_delta = e->ext.huber_delta[level];
+  a.planes = lv.planes;
+  a.frame_bytes = lv.frame_bytes;
+  for (int p = 0; p < PLANES_PER_FRAME; p++) a.plane_off[p] = lv.plane_off[p];
+  a.states = reinterpret_cast<const double *>(ws + st_off);
+  a.src = reinterpret_cast<const int *>(ws + src_off);
+  a.tgt = reinterpret_cast<const int *>(ws + tgt_off);
+  auto *d_mask = reinterpret_cast<unsigned long long *>(ws + mask_off);
+  auto *d_part = reinterpret_cast<double *>(ws + part_off);
+  auto *d_out = reinterpret_cast<phovo_pair_system *>(ws + out_off);
+  for (int g0 = 0; g0 < n_pairs; g0 += group) {
+    const int c = std::min(group, n_pairs - g0);
+    PHOVO_HIP_CHECK(hipMemcpyAsync(ws + st_off, states + (size_t)g0 * 6, sizeof(double) * 6 * (size_t)c, hipMemcpyHostToDevice, e->stream));
+    PHOVO_HIP_CHECK(hipMemcpyAsync(ws + src_off, src + g0, sizeof(int) * (size_t)c, hipMemcpyHostToDevice, e->stream));
+    PHOVO_HIP_CHECK(hipMemcpyAsync(ws + tgt_off, tgt + g0, sizeof(int) * (size_t)c, hipMemcpyHostToDevice, e->stream));
+    PHOVO_HIP_CHECK(gn_eval_pairs(a, c, e->ext.plane_storage, d_owner, d_mask, d_part, d_out, e->stream));
+    PHOVO_HIP_CHECK(hipMemcpyAsync(out + g0, d_out, sizeof(phovo_pair_system) * (size_t)c, hipMemcpyDeviceToHost, e->stream));
+    PHOVO_HIP_CHECK(hipStreamSynchronize(e->stream));      // (the next group's inputs overwrite this one's)
+  }
+  e->eval_owner_clean = owner_ints;
+  return PHOVO_OK;
+}
+
 int phovo_engine_align_ms(const phovo_engine *e, int ticket, double *total_ms, double level_ms[PHOVO_MAX_LEVELS])
 {
   if (!e) return fail(PHOVO_E_INVALID_ARGUMENT, "align_ms: null");
@@ -1808,6 +1916,19 @@ int phovo_odometry_get_report(const phovo_odometry *o, phovo_pair_report *report
   if (!o->optimized) return fail(PHOVO_E_NOT_READY, "get_report: Optimize has not run");
   *report = o->report;
   return PHOVO_OK;
+}
+
+int phovo_odometry_get_pair_system(const phovo_odometry *o, phovo_pair_system *out)
+{
+  if (!o || !out) return fail(PHOVO_E_INVALID_ARGUMENT, "get_pair_system: null");
+  if (!o->optimized) return fail(PHOVO_E_NOT_READY, "get_pair_system: Optimize has not run since the frames were set");
+  const phovo_engine *e = o->engine;
+  int finest = -1;                                        // the lowest level Optimize() iterates on
+  for (int l = e->cfg.num_levels - 1; l >= 0; l--)
+    if (e->cfg.max_num_iterations[l] > 0) finest = l;
+  if (finest < 0) return fail(PHOVO_E_NOT_READY, "get_pair_system: the configuration optimises no level");
+  const int src = 0, tgt = 1;
+  return phovo_engine_evaluate_pairs(o->engine, 1, &src, &tgt, o->state, finest, out);
 }
 
 int phovo_odometry_last_optimize_ms(const phovo_odometry *o, double *ms)

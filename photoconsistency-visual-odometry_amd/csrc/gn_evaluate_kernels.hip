@@ -1,0 +1,315 @@
+// Evaluation of the Gauss-Newton system at caller-supplied states (phovo_engine_evaluate_pairs): per pair
+//   information = J^T W J,  gradient = J^T W r,  cost = r^T W r,  rows = Jacobian rows filled
+// with exactly the rows ComputeResidualsAndJacobians (...Analytic.h:191-367) fills at that state on one level: the depth
+// gate (:280), the round() bounds test (:297-303), the scatter to the rounded target index with the last source pixel in
+// raster order winning (:358), the target gradients read at the SOURCE index (:346-347) and the reference's Jacobian
+// including its temp11 slip (:253) -- the matrix the aligner inverts (:538-540).  W is the identity, or with
+// huber_delta > 0 the IRLS weights the aligner uses (1 or delta/|r|, from r at the state).
+//
+// The wide form's shape (gn_wide_kernels.hip): a pair is cut into tiles of 16 64-pixel chunks, one 256-thread workgroup
+// per tile, and the kernel boundary is the only synchronisation (no grid barrier, nothing that can hang):
+//   k_eval_pass1   pose constants of the pair's state into LDS (write_pose_constants: every sin/cos branch is the
+//                  aligner's), warp, atomicMax into the owner map in HBM, per-chunk in-bounds ballots
+//   k_eval_pass2   residual and Jacobian rows, 21 + 6 + 1 sums and the row count per tile into a slab; the owner slots
+//                  are put back to -1.  No float atomics.
+//   k_eval_finish  fixed-order sum of the tile slabs into phovo_pair_system, one workgroup per pair
+// The tile count and every summation order depend on the level size only: a pair's result is the same bit for bit
+// whatever the batch, its position in it, or any setting of the engine.
+#include <hip/hip_runtime.h>
+#include <hip/hip_fp16.h>
+
+#include "gn_device.hpp"
+#include "phovo_internal.hpp"
+
+namespace phovo_hip {
+
+namespace {
+
+constexpr int ET = 256;                 // threads per tile workgroup
+constexpr int E_TILE_CHUNKS = 16;       // 64-pixel chunks per tile (1024 pixels), 4 per wave
+constexpr int ENW = ET / WAVE;
+constexpr int ECPW = E_TILE_CHUNKS / ENW;       // chunks per wave
+constexpr int RED_COST = 28;            // slot behind the row count: r^T W r
+
+struct EvalPose {
+  double cx, cyy, cz, r01, r02, r11, r12, t1, t2, t3, t4, t5, t6, t8, t11, t14, t15, t16, t17, t24, cosy, siny;
+};
+
+// Wave 0 writes the pose constants of the pair's state into s_cst; every thread reads them back behind the barrier.
+__device__ __forceinline__ EvalPose eval_pose(const double *st, double *s_cst)
+{
+  const int tid = threadIdx.x;
+  if (tid < WAVE) write_pose_constants(st[0], st[1], st[2], st[3], st[4], st[5], s_cst, tid);
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __syncthreads();
+  const double *c = s_cst;
+  EvalPose p;
+  p.cx = c[C_X]; p.cyy = c[C_Y]; p.cz = c[C_Z];
+  p.r01 = c[C_R01]; p.r02 = c[C_R02]; p.r11 = c[C_R11]; p.r12 = c[C_R12];
+  p.t1 = c[C_T1]; p.t2 = c[C_T2]; p.t3 = c[C_T3]; p.t4 = c[C_T4]; p.t5 = c[C_T5]; p.t6 = c[C_T6];
+  p.t8 = c[C_T8]; p.t11 = c[C_T11]; p.t14 = c[C_T14]; p.t15 = c[C_T15]; p.t16 = c[C_T16]; p.t17 = c[C_T17];
+  p.t24 = c[C_T24]; p.cosy = c[C_CY]; p.siny = c[C_SY];
+  return p;
+}
+
+// grid (tiles, pairs of the group).  TD: storage type of the depth plane.
+// TWIN: the warp / atomicMax / ballot body is k_wide_pass1's (gn_wide_kernels.hip) with the depth plane typed; the two
+// must select the same rows, so a change to the warp semantics (:279-303, :358) goes into both.  k_eval_pass2's row
+// arithmetic is k_wide_pass2's in the same way.
+template <typename TD>
+__global__ __launch_bounds__(ET) void k_eval_pass1(const GNEvalArgs A, int *g_owner, unsigned long long *g_mask)
+{
+  __shared__ double s_cst[32];
+  const int pair = blockIdx.y;
+  const int tid = threadIdx.x, lane = tid & (WAVE - 1);
+  const int wave = __builtin_amdgcn_readfirstlane(tid / WAVE);
+  const int n = A.n, W = A.w, H = A.h;
+  const EvalPose P = eval_pose(A.states + (size_t)pair * 6, s_cst);
+  const unsigned char *src_frame = A.planes + (size_t)A.src[pair] * A.frame_bytes;
+  const __amdgpu_buffer_rsrc_t rD0 = plane_rsrc<TD>(src_frame + A.plane_off[PLANE_D], n);
+  int *owner = g_owner + (size_t)pair * (size_t)n;
+  const double fx = A.fx, fy = A.fy, ox = A.ox, oy = A.oy, ifx = A.ifx, ify = A.ify;
+  const double min_d = A.min_depth, max_d = A.max_depth, dW = (double)W, dH = (double)H;
+  const RowColFromIndex rc_map = make_rowcol_from_index(W);
+  double pzs[ECPW];
+#pragma unroll
+  for (int j = 0; j < ECPW; j++)
+    pzs[j] = plane_load<TD>(rD0, (blockIdx.x * E_TILE_CHUNKS + j * ENW + wave) * WAVE + lane);    // past the plane: 0
+#pragma unroll
+  for (int j = 0; j < ECPW; j++) {
+    const int chunk = blockIdx.x * E_TILE_CHUNKS + j * ENW + wave;
+    if (chunk >= A.n_chunks) break;
+    const int k = chunk * WAVE + lane;
+    bool inb = false;
+    const double pz = pzs[j];                                             // :279
+    if (k < n && min_d < pz && pz < max_d) {                              // :280
+      double cd, rd;
+      rowcol_from_index((double)k, rc_map, cd, rd);
+      const double px = (cd - ox) * pz * ifx;                             // :282
+      const double py = (rd - oy) * pz * ify;                             // :283
+      const double X = ((P.t15 * px + P.r01 * py) + P.r02 * pz) + P.cx;   // :291
+      const double Y = ((P.t14 * px + P.r11 * py) + P.r12 * pz) + P.cyy;
+      const double Z = ((-P.t3 * px + P.t1 * py) + P.t2 * pz) + P.cz;
+      const double iz = fast_rcp(Z);                                      // :294
+      const double tc = (X * fx) * iz + ox;                               // :295
+      const double tr = (Y * fy) * iz + oy;                               // :296
+      const double rr = round(tr), rc = round(tc);                        // :297-298
+      if (rr >= 0.0 && rr < dH && rc >= 0.0 && rc < dW) {                 // :302-303
+        inb = true;
+        atomicMax(&owner[__mul24((int)rr, W) + (int)rc], k);              // last raster writer wins  :358
+      }
+    }
+    const unsigned long long m = __ballot(inb);
+    if (lane == 0) g_mask[(size_t)pair * A.n_chunks + chunk] = m;
+  }
+}
+
+// grid (tiles, pairs of the group).  TI / TD: storage type of the intensity and gradient planes / of the depth plane.
+template <typename TI, typename TD>
+__global__ __launch_bounds__(ET) void k_eval_pass2(const GNEvalArgs A, int *g_owner, const unsigned long long *g_mask,
+                                                   double *g_part, int tiles)
+{
+  __shared__ double s_cst[32];
+  __shared__ double s_red[ENW * NRED];
+  const int pair = blockIdx.y;
+  const int tid = threadIdx.x, lane = tid & (WAVE - 1);
+  const int wave = __builtin_amdgcn_readfirstlane(tid / WAVE);
+  const int n = A.n, W = A.w;
+  const EvalPose P = eval_pose(A.states + (size_t)pair * 6, s_cst);
+  const unsigned char *src_frame = A.planes + (size_t)A.src[pair] * A.frame_bytes;
+  const unsigned char *tgt_frame = A.planes + (size_t)A.tgt[pair] * A.frame_bytes;
+  const __amdgpu_buffer_rsrc_t rI0 = plane_rsrc<TI>(src_frame + A.plane_off[PLANE_I], n);
+  const __amdgpu_buffer_rsrc_t rD0 = plane_rsrc<TD>(src_frame + A.plane_off[PLANE_D], n);
+  const __amdgpu_buffer_rsrc_t rI1 = plane_rsrc<TI>(tgt_frame + A.plane_off[PLANE_I], n);
+  const __amdgpu_buffer_rsrc_t rGX = plane_rsrc<TI>(tgt_frame + A.plane_off[PLANE_GX], n);
+  const __amdgpu_buffer_rsrc_t rGY = plane_rsrc<TI>(tgt_frame + A.plane_off[PLANE_GY], n);
+  int *owner = g_owner + (size_t)pair * (size_t)n;
+  const double fx = A.fx, fy = A.fy, ox = A.ox, oy = A.oy, ifx = A.ifx, ify = A.ify;
+  const double t7 = -P.t6, t9 = -P.t8, t21 = -P.t5;
+  const double huber_delta = A.huber_delta;
+
+  double acc[NRED];
+#pragma unroll
+  for (int j = 0; j < NRED; j++) acc[j] = 0.0;
+  const RowColFromIndex rc_map = make_rowcol_from_index(W);
+  int n_rows = 0;
+  // every load of the wave's four chunks goes out first, the owner slots are reset behind the last one (as k_wide_pass2)
+  int os[ECPW];
+  unsigned long long ms[ECPW];
+  double pzs[ECPW], gxs[ECPW], gys[ECPW], i1s[ECPW], i0s[ECPW];
+#pragma unroll
+  for (int j = 0; j < ECPW; j++) {
+    const int chunk = blockIdx.x * E_TILE_CHUNKS + j * ENW + wave;
+    const int k = chunk * WAVE + lane;
+    os[j] = k < n ? owner[k] : -1;
+    ms[j] = chunk < A.n_chunks ? g_mask[(size_t)pair * A.n_chunks + chunk] : 0ull;
+  }
+#pragma unroll
+  for (int j = 0; j < ECPW; j++) {
+    const int k = (blockIdx.x * E_TILE_CHUNKS + j * ENW + wave) * WAVE + lane;
+    pzs[j] = plane_load<TD>(rD0, k);                                      // past the plane: 0
+    gxs[j] = plane_load<TI>(rGX, k);                                      // gradient at the SOURCE index  :346-347
+    gys[j] = plane_load<TI>(rGY, k);
+    i1s[j] = plane_load<TI>(rI1, k);                                      // :309
+  }
+#pragma unroll
+  for (int j = 0; j < ECPW; j++) i0s[j] = plane_load<TI>(rI0, os[j]);     // :308 (owner -1: past the plane -> 0)
+#pragma unroll
+  for (int j = 0; j < ECPW; j++) {                // every slot is read once and left at -1 for the next evaluation
+    const int k = (blockIdx.x * E_TILE_CHUNKS + j * ENW + wave) * WAVE + lane;
+    if (k < n) owner[k] = -1;
+  }
+  // Two compiled copies of the row loop behind a wave-uniform branch: without Huber weights none of the extension's
+  // instructions run.
+  auto rows = [&](auto huber_tag) {
+    constexpr bool HUBER = decltype(huber_tag)::value;
+#pragma unroll
+    for (int j = 0; j < ECPW; j++) {
+      const int chunk = blockIdx.x * E_TILE_CHUNKS + j * ENW + wave;
+      if (chunk >= A.n_chunks) break;
+      const int k = chunk * WAVE + lane;
+      const int o = os[j];
+      const unsigned long long m = ms[j];
+      n_rows += __builtin_popcountll(m);
+      // r[k] is the residual of TARGET pixel k (:358): it enters the cost whenever k has an owner, and the gradient through
+      // Jacobian row k, which belongs to SOURCE pixel k and is filled iff that pixel's warp passed (the ballot)
+      const double res = o >= 0 ? i1s[j] - i0s[j] : 0.0;                  // :308-309,358
+      double wgt = 1.0;
+      if (HUBER) {                                  // the aligner's IRLS weight (gn_level_kernel, extension)
+        const double ar = fabs(res);
+        wgt = ar <= huber_delta ? 1.0 : huber_delta / ar;
+      }
+      if (o >= 0) acc[RED_COST] = fma(HUBER ? res * wgt : res, res, acc[RED_COST]);          // r^T W r
+      if (!((m >> lane) & 1ull)) continue;
+      const double pz = pzs[j];
+      const double gxi = gxs[j], gyi = gys[j];
+      double cd, rd;
+      rowcol_from_index((double)k, rc_map, cd, rd);
+      const double px = (cd - ox) * pz * ifx;
+      const double py = (rd - oy) * pz * ify;
+      // the factored Jacobian of gn_level_kernel / k_wide_pass2 (derivation in gn_kernels.hip)
+      const double Zr = py * P.t1 + pz * P.t2 - px * P.t3;
+      const double t25 = fast_rcp(P.cz + Zr);                             // :313
+      const double Au = pz * P.t4 + py * P.t5 + px * P.t11;               // temp11 = temp15 + x: the reference's slip, kept
+      const double Bv = py * P.t6 + pz * t9 + px * P.t14 + P.cyy;
+      const double Cm = -py * P.t16 - pz * P.t17 - px * P.t24;
+      const double Dm = py * P.t2 - pz * P.t1;
+      double J[6];
+      J[0] = (gxi * fx) * t25;
+      J[1] = (gyi * fy) * t25;
+      J[2] = -(J[0] * Au + J[1] * Bv) * t25;
+      J[3] = J[0] * (P.cyy - Bv) + J[1] * (Au - px * P.cx);
+      J[4] = (J[0] * P.cosy + J[1] * P.siny) * Zr + Cm * J[2];
+      J[5] = J[0] * (py * P.t4 + pz * t21) + J[1] * (pz * t7 + py * t9) + Dm * J[2];
+      double Jw[6];
+#pragma unroll
+      for (int a = 0; a < 6; a++) Jw[a] = HUBER ? J[a] * wgt : J[a];
+      int q = 0;
+#pragma unroll
+      for (int a = 0; a < 6; a++) {
+#pragma unroll
+        for (int b = a; b < 6; b++) {
+          acc[q] = fma(Jw[a], J[b], acc[q]);                              // J^T W J  :540
+          q++;
+        }
+      }
+#pragma unroll
+      for (int a = 0; a < 6; a++) acc[21 + a] = fma(Jw[a], res, acc[21 + a]);      // J^T W r  :538
+    }
+  };
+  if (huber_delta > 0.0) rows(std::true_type{}); else rows(std::false_type{});
+  acc[RED_VALID] = lane == 0 ? (double)n_rows : 0.0;
+  // tile sums: wave butterfly, then the four waves in fixed order
+  reduce_wave_to_row(acc, lane, wave, s_red);
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (tid < NRED) {
+    double v = 0.0;
+#pragma unroll
+    for (int w2 = 0; w2 < ENW; w2++) v += s_red[w2 * NRED + tid];
+    g_part[((size_t)pair * tiles + blockIdx.x) * NRED + tid] = v;
+  }
+}
+
+// One workgroup per pair: thread (s, j) adds tiles s, s + 8, s + 16, ... of value j, then the 8 subset sums are added in
+// subset order; the system is written from the upper triangle.
+constexpr int FIN_SUBSETS = ET / NRED;
+__global__ __launch_bounds__(ET) void k_eval_finish(const double *g_part, int tiles, phovo_pair_system *out)
+{
+  __shared__ double s_part[FIN_SUBSETS * NRED];
+  const int pair = blockIdx.x, tid = threadIdx.x;
+  {
+    const int j = tid & (NRED - 1), sub = tid / NRED;
+    const double *base = g_part + (size_t)pair * tiles * NRED + j;
+    double v = 0.0;
+#pragma unroll 4
+    for (int t = sub; t < tiles; t += FIN_SUBSETS) v += base[(size_t)t * NRED];
+    s_part[sub * NRED + j] = v;
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (tid >= WAVE) return;
+  const int lane = tid;
+  double v = 0.0;
+  if (lane < NRED) {
+#pragma unroll
+    for (int sub = 0; sub < FIN_SUBSETS; sub++) v += s_part[sub * NRED + lane];
+  }
+  phovo_pair_system *o = out + pair;
+  // lane (a, b) of the 6x6 matrix, 36 lanes: the upper-triangle slot of (min, max)(a, b).  Every shuffle runs in the
+  // whole wave (its source lanes must be active).
+  const int a = lane / 6, b = lane % 6;
+  const int q = lane >= 36 ? 0 : (a <= b ? tri(a, b) : tri(b, a));
+  const double h = __shfl(v, q, WAVE);
+  if (lane < 36) o->information[lane] = h;
+  const double g = __shfl(v, lane < 6 ? 21 + lane : 0, WAVE);
+  if (lane < 6) o->gradient[lane] = g;
+  const double rows = __shfl(v, RED_VALID, WAVE);
+  const double cost = __shfl(v, RED_COST, WAVE);
+  const bool finite = lane >= RED_VALID || fabs(v) <= 1.79769313486231570815e308;
+  const bool all_finite = __ballot(!finite) == 0ull && fabs(cost) <= 1.79769313486231570815e308;
+  if (lane == 0) {
+    o->cost = cost;
+    o->rows = (int32_t)rows;
+    uint32_t flags = 0;
+    if (rows < 6.0) flags |= PHOVO_PAIR_RANK_DEFICIENT;
+    if (!all_finite) flags |= PHOVO_PAIR_NONFINITE;
+    o->flags = flags;
+  }
+}
+
+template <typename TI, typename TD>
+hipError_t eval_launch(const GNEvalArgs &a, int n_pairs, int tiles, int *g_owner, unsigned long long *g_mask,
+                       double *g_part, phovo_pair_system *out, hipStream_t stream)
+{
+  const dim3 grid((unsigned)tiles, (unsigned)n_pairs);
+  hipLaunchKernelGGL(k_eval_pass1<TD>, grid, dim3(ET), 0, stream, a, g_owner, g_mask);
+  hipLaunchKernelGGL((k_eval_pass2<TI, TD>), grid, dim3(ET), 0, stream, a, g_owner, g_mask, g_part, tiles);
+  hipLaunchKernelGGL(k_eval_finish, dim3((unsigned)n_pairs), dim3(ET), 0, stream, g_part, tiles, out);
+  return hipGetLastError();
+}
+
+}  // namespace
+
+int gn_eval_tiles(int n)
+{
+  const int n_chunks = (n + WAVE - 1) / WAVE;
+  return (n_chunks + E_TILE_CHUNKS - 1) / E_TILE_CHUNKS;
+}
+
+size_t gn_eval_slab_doubles_per_pair(int n) { return (size_t)gn_eval_tiles(n) * NRED; }
+
+hipError_t gn_eval_pairs(const GNEvalArgs &a, int n_pairs, int storage, int *g_owner, unsigned long long *g_mask,
+                         double *g_part, phovo_pair_system *out, hipStream_t stream)
+{
+  if (n_pairs <= 0) return hipSuccess;
+  const int tiles = gn_eval_tiles(a.n);
+  switch (storage) {
+    case PHOVO_STORAGE_F64: return eval_launch<double, double>(a, n_pairs, tiles, g_owner, g_mask, g_part, out, stream);
+    case PHOVO_STORAGE_F32: return eval_launch<float, float>(a, n_pairs, tiles, g_owner, g_mask, g_part, out, stream);
+    case PHOVO_STORAGE_F16: return eval_launch<__half, float>(a, n_pairs, tiles, g_owner, g_mask, g_part, out, stream);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+}  // namespace phovo_hip

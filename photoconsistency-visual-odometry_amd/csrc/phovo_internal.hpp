@@ -108,6 +108,25 @@ size_t gn_wide_workspace_bytes(int n, int n_pairs);
 hipError_t gn_run_level_wide(const GNLevelArgs &args, int n_pairs, void *workspace, int *h_done_scratch,
                              hipStream_t stream);
 hipError_t gn_prepare_kernels();   // raises the dynamic-LDS limit of every instantiation
+// Evaluation of the Gauss-Newton system at given states (gn_evaluate_kernels.hip, phovo_engine_evaluate_pairs): one level,
+// nearest / scatter sampling, any plane storage, optional Huber weights.
+struct GNEvalArgs {
+  int w, h, n, n_chunks;
+  double fx, fy, ox, oy, ifx, ify;   // level-scaled intrinsics, as GNLevelArgs
+  double min_depth, max_depth;
+  double huber_delta;                // > 0: Huber IRLS weights at the given state
+  const unsigned char *planes;       // pool of the level (GNLevelArgs)
+  size_t frame_bytes;
+  size_t plane_off[PLANES_PER_FRAME];
+  const int *src, *tgt;              // [pairs of the group]
+  const double *states;              // [pairs of the group][6]
+};
+int gn_eval_tiles(int n);                          // 1024-pixel tiles of a level of n pixels
+size_t gn_eval_slab_doubles_per_pair(int n);       // doubles of tile sums per pair
+// g_owner: [n_pairs][n] int32 holding -1 everywhere (and again on return); g_mask: [n_pairs][n_chunks];
+// g_part: [n_pairs][gn_eval_slab_doubles_per_pair(n)]; out: [n_pairs] on the device.
+hipError_t gn_eval_pairs(const GNEvalArgs &a, int n_pairs, int storage, int *g_owner, unsigned long long *g_mask,
+                         double *g_part, phovo_pair_system *out, hipStream_t stream);
 // Bi-objective (intensity + depth) form (gn_biobjective_kernel.hip, PHOVO_OBJECTIVE_BIOBJECTIVE): fp64 planes, nearest /
 // scatter sampling.  Every frame of the level carries, beside the four planes, the target's depth gradients (fp64 planes at
 // dgx_off / dgy_off) and its depth gain mean(I) / mean(D) (one double at gain_off).

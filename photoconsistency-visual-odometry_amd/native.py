@@ -67,6 +67,17 @@ class PairReport(C.Structure):
     ]
 
 
+class PairSystem(C.Structure):
+    """phovo_pair_system: the Gauss-Newton system of one pair at a given state on one level."""
+    _fields_ = [
+        ("information", C.c_double * 36),
+        ("gradient", C.c_double * 6),
+        ("cost", C.c_double),
+        ("rows", C.c_int32),
+        ("flags", C.c_uint32),
+    ]
+
+
 FUSION_AUTO, FUSION_OFF, FUSION_SPLIT = 0, -1, -2
 OBJECTIVE_PHOTOMETRIC, OBJECTIVE_BIOBJECTIVE = 0, 1
 LAUNCH_KINDS = ("persistent", "fused", "slide", "slide_fallback", "wide", "bilinear", "biobjective")
@@ -95,6 +106,7 @@ SYMBOLS = {
     "phovo_eigen_pose": (C.c_int, [_dp, _dp]),
     "phovo_trajectory_chain": (C.c_int, [C.c_int, _vp, _dp, _vp]),
     "phovo_trajectory_format_pose": (C.c_int, [C.c_double, _dp, C.c_char_p, C.c_size_t]),
+    "phovo_pair_system_format": (C.c_int, [C.c_double, C.POINTER(PairSystem), C.c_char_p, C.c_size_t]),
     "phovo_warp_image": (C.c_int, [C.c_int, _vp, C.c_size_t, _vp, C.c_size_t, C.c_int, C.c_int, _dp, _dp, C.c_int,
                                    _vp, C.c_size_t]),
     "phovo_odometry_create": (C.c_int, [C.c_int, C.POINTER(_vp)]),
@@ -115,6 +127,7 @@ SYMBOLS = {
     "phovo_odometry_get_optimal_rigid_transformation_matrix": (C.c_int, [_vp, _dp]),
     "phovo_odometry_get_report": (C.c_int, [_vp, C.POINTER(PairReport)]),
     "phovo_odometry_last_optimize_ms": (C.c_int, [_vp, _dp]),
+    "phovo_odometry_get_pair_system": (C.c_int, [_vp, C.POINTER(PairSystem)]),
     "phovo_engine_create": (C.c_int, [C.c_int, C.POINTER(_vp)]),
     "phovo_engine_destroy": (C.c_int, [_vp]),
     "phovo_engine_set_config": (C.c_int, [_vp, C.POINTER(Config)]),
@@ -158,6 +171,7 @@ SYMBOLS = {
     "phovo_engine_fetch": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),
     "phovo_engine_device_states": (C.c_int, [_vp, C.c_int, C.POINTER(_vp)]),
     "phovo_engine_align_ms": (C.c_int, [_vp, C.c_int, _dp, _dp]),
+    "phovo_engine_evaluate_pairs": (C.c_int, [_vp, C.c_int, _ip, _ip, _vp, C.c_int, _vp]),
 }
 
 
@@ -262,3 +276,10 @@ def read_config_file(path):
     cfg = Config()
     check(lib().phovo_config_read_file(os.fsencode(path), C.byref(cfg)), "phovo_config_read_file")
     return cfg
+
+
+def format_pair_system(timestamp, system):
+    """phovo_pair_system_format: the line the VisualOdometry app writes per pair with --information."""
+    buf = C.create_string_buffer(1024)
+    check(lib().phovo_pair_system_format(float(timestamp), C.byref(system), buf, len(buf)), "phovo_pair_system_format")
+    return buf.value.decode()

@@ -143,6 +143,13 @@ class CPhotoconsistencyOdometryAnalytic:
         check(self._lib.phovo_odometry_get_report(self._h, C.byref(rep)), "GetReport")
         return rep
 
+    def GetPairSystem(self):
+        """The Gauss-Newton system at the optimal state on the finest level the configuration optimises
+        (native.PairSystem: information, gradient, cost, rows, flags); evaluated on demand after Optimize()."""
+        ps = native.PairSystem()
+        check(self._lib.phovo_odometry_get_pair_system(self._h, C.byref(ps)), "GetPairSystem")
+        return ps
+
     def LastOptimizeMilliseconds(self):
         ms = C.c_double()
         check(self._lib.phovo_odometry_last_optimize_ms(self._h, C.byref(ms)), "LastOptimizeMilliseconds")
@@ -161,6 +168,13 @@ class CPhotoconsistencyOdometryBiObjective(CPhotoconsistencyOdometryAnalytic):
         if depthImage is None:
             raise ValueError("the bi-objective needs the target's depth")
         super().SetTargetFrame(intensityImage, depthImage)
+
+
+# phovo_pair_system as a numpy record (352 bytes, the layout of native.PairSystem): evaluate_pairs fills an array of
+# these in place and returns column views, with no per-record Python work
+PAIR_SYSTEM_DTYPE = np.dtype([("information", "<f8", (36,)), ("gradient", "<f8", (6,)), ("cost", "<f8"),
+                              ("rows", "<i4"), ("flags", "<u4")])
+assert PAIR_SYSTEM_DTYPE.itemsize == C.sizeof(native.PairSystem)
 
 
 class AlignmentEngine:
@@ -359,6 +373,24 @@ class AlignmentEngine:
             init.ctypes.data if init is not None else None, out.ctypes.data,
             C.cast(reps, C.c_void_p) if reps is not None else None), "phovo_engine_align_pairs")
         return (out, list(reps)[:n]) if want_reports else out
+
+    def evaluate_pairs(self, src, tgt, states, level, want_structs=False):
+        """The Gauss-Newton system of each (source, target) pair at states [n, 6] on `level` (phovo_engine_evaluate_pairs).
+        Returns a dict of numpy arrays: information [n, 6, 6], gradient [n, 6], cost [n], rows [n], flags [n]
+        (with want_structs, also the native.PairSystem records under "structs")."""
+        s, t = self._pairs(src, tgt)
+        n = s.size
+        st = np.ascontiguousarray(states, dtype=np.float64).reshape(n, 6)
+        out = np.zeros(max(n, 1), dtype=PAIR_SYSTEM_DTYPE)         # the C records, written in place
+        ip = C.POINTER(C.c_int)
+        check(self._lib.phovo_engine_evaluate_pairs(self._h, n, s.ctypes.data_as(ip), t.ctypes.data_as(ip), st.ctypes.data,
+                                                    int(level), out.ctypes.data), "phovo_engine_evaluate_pairs")
+        out = out[:n]
+        res = dict(information=out["information"].reshape(n, 6, 6).copy(), gradient=out["gradient"].copy(),
+                   cost=out["cost"].copy(), rows=out["rows"].astype(np.int64), flags=out["flags"].astype(np.int64))
+        if want_structs:
+            res["structs"] = list((native.PairSystem * n).from_buffer_copy(out.tobytes()))
+        return res
 
     def enqueue_align(self, src, tgt, init_states=None):
         s, t = self._pairs(src, tgt)

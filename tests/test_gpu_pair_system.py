@@ -1,0 +1,353 @@
+"""GPU tests of phovo_engine_evaluate_pairs / phovo_odometry_get_pair_system: the Gauss-Newton system (J^T W J, J^T W r,
+r^T W r, rows) of a pair at a given state on one level.  Checked against the oracle's per-iteration trace (trace entry k
+holds the system at the state of entry k - 1) and its residuals and Jacobians, fed the planes exactly as the device
+holds them; then batch independence, no interference with alignments, the odometry / class surface and the refusals."""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+
+import phovo_amd  # noqa: F401
+from phovo_amd import native, odometry, synthetic
+from oracle import oracle
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CFG4 = os.path.join(ROOT, "config_files", "config_4_level_optimization_analytic.yml")
+CFG5 = os.path.join(ROOT, "config_files", "config_5_level_optimization_analytic.yml")
+STORAGES = [native.STORAGE_F64, native.STORAGE_F32, native.STORAGE_F16]
+MAX_ITER4 = [2, 3, 4, 6]            # every level of a 640x480 pyramid iterates: 640x480, 320x240, 160x120, 80x60
+HUBER = [0.02, 0.03, 0.04, 0.05]
+
+
+def _engine(p, n_levels, max_iter, storage=native.STORAGE_F64, huber=None, build_all=False, w=None, h=None):
+    eng = odometry.AlignmentEngine()
+    eng.set_config(native.make_config(num_levels=n_levels, max_iter=max_iter, min_grad=[0.0] * n_levels))
+    eng.set_extensions(native.make_extensions(plane_storage=storage, huber_delta=huber))
+    eng.set_build_all_levels(build_all)
+    eng.set_intrinsic_matrix(p["K"])
+    hh, ww = p["gray0"].shape
+    eng.reserve_frames(2, ww if w is None else w, hh if h is None else h)
+    eng.upload_frame(0, p["gray0"], p["depth0"])
+    eng.upload_frame(1, p["gray1"], p["depth1"])
+    return eng
+
+
+def _planes(eng, nl, w, h, levels):
+    """Oracle inputs: what the device holds at `levels`, zeros elsewhere."""
+    out = [[], [], [], [], []]
+    for l in range(nl):
+        if l in levels:
+            i0, d0, _, _ = eng.get_level_planes(0, l)
+            i1, _, gx, gy = eng.get_level_planes(1, l)
+        else:
+            lw, lh = oracle.level_size(w, h, l)
+            i0 = d0 = i1 = gx = gy = np.zeros((lh, lw))
+        for lst, a in zip(out, (i0, d0, i1, gx, gy)):
+            lst.append(a)
+    return out
+
+
+def _numpy_system(planes, level, K, state, delta):
+    """H, g, cost from the oracle's residuals and Jacobians at `state`, weighted in numpy."""
+    i0p, d0p, i1p, gxp, gyp = planes
+    r, J = oracle.compute_residuals_and_jacobians(i0p[level], d0p[level], i1p[level], gxp[level], gyp[level], level, K, state)
+    w = np.ones_like(r)
+    if delta is not None and delta > 0:
+        ar = np.abs(r)
+        w = np.where(ar <= delta, 1.0, delta / np.where(ar > 0, ar, 1.0))
+    return (J * w) @ J.T, (J * w) @ r, float(np.sum(w * r * r))
+
+
+def _oracle_trace_system(planes, level, K, state, delta):
+    """rows, H, g of ONE oracle iteration on `level` from `state` (the aligner's system at that state)."""
+    nl = len(planes[0])
+    mi = [0] * nl
+    mi[level] = 1
+    cfg = oracle.make_config(num_levels=nl, max_iter=mi, min_grad=[0.0] * nl)
+    hd = None
+    if delta is not None:
+        hd = [0.0] * nl
+        hd[level] = delta
+    _, _, tr = oracle.optimize(cfg, K, *planes, init_state=state, want_trace=True, huber_delta=hd)
+    assert len(tr) == 1
+    return tr[0]["valid_pixels"], tr[0]["hessian"], tr[0]["gradient"]
+
+
+def _check_against(sys_h, sys_g, rows, cost, ref_h, ref_g, ref_rows, ref_cost):
+    assert rows == ref_rows
+    scale = np.max(np.abs(ref_h))
+    assert np.max(np.abs(sys_h - ref_h)) <= 1e-10 * scale, (np.max(np.abs(sys_h - ref_h)), scale)
+    bar = 1e-9 * np.sqrt(np.maximum(np.diag(ref_h) * ref_cost, 0.0))
+    assert np.all(np.abs(sys_g - ref_g) <= bar), (sys_g - ref_g, bar)
+    assert abs(cost - ref_cost) <= 1e-12 * abs(ref_cost)
+
+
+# ---- 1, 2: the oracle's trace and its residuals ---------------------------------------------------------------------
+@pytest.mark.parametrize("storage", STORAGES)
+@pytest.mark.parametrize("huber", [False, True])
+def test_matches_oracle_trace_every_iteration(storage, huber):
+    p = synthetic.make_pair(31, 640, 480, holes=0.02)
+    deltas = HUBER if huber else None
+    with _engine(p, 4, MAX_ITER4, storage, deltas) as eng:
+        planes = _planes(eng, 4, 640, 480, range(4))
+        _, _, trace = oracle.optimize(oracle.make_config(num_levels=4, max_iter=MAX_ITER4, min_grad=[0.0] * 4), p["K"],
+                                      *planes, want_trace=True, huber_delta=deltas)
+        assert len(trace) == sum(MAX_ITER4)
+        before = [np.zeros(6)] + [e["state"] for e in trace[:-1]]
+        for level in range(4):
+            ks = [k for k, e in enumerate(trace) if e["level"] == level]
+            states = np.array([before[k] for k in ks])
+            s = eng.evaluate_pairs([0] * len(ks), [1] * len(ks), states, level)
+            for i, k in enumerate(ks):
+                e = trace[k]
+                d = deltas[level] if huber else None
+                _, _, cost_ref = _numpy_system(planes, level, p["K"], states[i], d)
+                _check_against(s["information"][i], s["gradient"][i], s["rows"][i], s["cost"][i],
+                               e["hessian"], e["gradient"], e["valid_pixels"], cost_ref)
+                assert s["flags"][i] == 0
+                np.testing.assert_array_equal(s["information"][i], s["information"][i].T)
+
+
+@pytest.mark.parametrize("huber", [False, True])
+def test_cost_matches_oracle_residuals(huber):
+    p = synthetic.make_pair(32, 640, 480, holes=0.02, scene="layered")
+    deltas = HUBER if huber else None
+    with _engine(p, 4, MAX_ITER4, native.STORAGE_F64, deltas) as eng:
+        planes = _planes(eng, 4, 640, 480, range(4))
+        rs = np.random.RandomState(3)
+        states = [np.zeros(6), p["motion"], p["motion"] + rs.uniform(-0.01, 0.01, 6), rs.uniform(-0.03, 0.03, 6)]
+        for level in (0, 2):
+            s = eng.evaluate_pairs([0] * 4, [1] * 4, np.array(states), level)
+            for i, st in enumerate(states):
+                H, g, cost = _numpy_system(planes, level, p["K"], st, deltas[level] if huber else None)
+                assert abs(s["cost"][i] - cost) <= 1e-12 * cost
+                assert np.max(np.abs(s["information"][i] - H)) <= 1e-10 * np.max(np.abs(H))
+
+
+# ---- 3: level geometries and edges -------------------------------------------------------------------------------
+@pytest.mark.parametrize("w,h", [(640, 480), (200, 152), (75, 53), (1, 40), (2, 33), (3, 17), (4, 64), (5, 70)])
+def test_level_geometries(w, h):
+    p = synthetic.make_pair(33, w, h, holes=0.02) if w >= 8 else synthetic.make_pair(33, 64, h, holes=0.02)
+    if w < 8:                                     # a narrow strip of a wider render
+        for k in ("gray0", "depth0", "gray1", "depth1"):
+            p[k] = np.ascontiguousarray(p[k][:, 30:30 + w])
+    nl = 4 if w >= 80 else 1
+    with _engine(p, nl, [1] * nl, build_all=True) as eng:
+        planes = _planes(eng, nl, w, h, range(nl))
+        rs = np.random.RandomState(w * 1000 + h)
+        for level in range(nl):
+            states = np.array([np.zeros(6), p["motion"], rs.uniform(-0.02, 0.02, 6)])
+            s = eng.evaluate_pairs([0] * 3, [1] * 3, states, level)
+            for i in range(3):
+                rows, H, g = _oracle_trace_system(planes, level, p["K"], states[i], None)
+                _, _, cost = _numpy_system(planes, level, p["K"], states[i], None)
+                if rows == 0:
+                    assert s["rows"][i] == 0 and not s["information"][i].any()
+                    continue
+                _check_against(s["information"][i], s["gradient"][i], s["rows"][i], s["cost"][i], H, g, rows, cost)
+
+
+def test_large_motion_mostly_out_of_bounds():
+    p = synthetic.make_pair(34, 640, 480, holes=0.02)
+    with _engine(p, 4, MAX_ITER4) as eng:
+        planes = _planes(eng, 4, 640, 480, range(4))
+        st = np.array([1.5, 0.4, 0.0, 0.3, 0.1, 0.0])            # about a quarter of the pixels stay in the image
+        s = eng.evaluate_pairs([0], [1], st[None], 1)
+        rows, H, g = _oracle_trace_system(planes, 1, p["K"], st, None)
+        _, _, cost = _numpy_system(planes, 1, p["K"], st, None)
+        assert 6 <= rows < 0.5 * 320 * 240
+        _check_against(s["information"][0], s["gradient"][0], s["rows"][0], s["cost"][0], H, g, rows, cost)
+
+
+def test_all_depths_invalid_is_rank_deficient_and_zero():
+    p = synthetic.make_pair(35, 160, 120)
+    p["depth0"] = np.zeros_like(p["depth0"])
+    with _engine(p, 1, [1]) as eng:
+        s = eng.evaluate_pairs([0], [1], np.zeros((1, 6)), 0)
+    assert s["rows"][0] == 0
+    assert s["flags"][0] == native.PAIR_RANK_DEFICIENT
+    assert not s["information"].any() and not s["gradient"].any() and s["cost"][0] == 0.0
+
+
+@pytest.mark.parametrize("storage", STORAGES)
+def test_nan_in_target_intensity_is_flagged(storage):
+    p = synthetic.make_pair(36, 160, 120)
+    with _engine(p, 1, [1], storage) as eng:
+        i1, _, _, _ = eng.get_level_planes(1, 0)
+        i1[50:60, 70:90] = np.nan
+        eng.set_level_planes(1, 0, intensity=i1)
+        s = eng.evaluate_pairs([0], [1], np.zeros((1, 6)), 0)
+    assert s["flags"][0] & native.PAIR_NONFINITE
+    assert np.isnan(s["cost"][0])
+
+
+# ---- 4: bit identity ---------------------------------------------------------------------------------------------
+def _bytes(structs):
+    return [bytes(memoryview(r)) for r in structs]
+
+
+def test_bit_identical_across_batches_positions_and_settings():
+    seq = synthetic.make_sequence(37, 5, 640, 480, holes=0.01)
+    with odometry.AlignmentEngine() as eng:
+        eng.set_config(native.make_config(num_levels=4, max_iter=MAX_ITER4, min_grad=[300.0] * 4))
+        eng.set_intrinsic_matrix(seq["K"])
+        eng.reserve_frames(5, 640, 480)
+        eng.upload_frames(0, seq["gray"], seq["depth"])
+        st = np.array([0.01, -0.02, 0.015, 0.01, -0.005, 0.008])
+        for level in (0, 2):
+            alone = _bytes(eng.evaluate_pairs([1], [2], st[None], level, want_structs=True)["structs"])[0]
+            n = 300                                   # more than one group of 218 pairs at 640x480
+            rs = np.random.RandomState(level)
+            src = rs.randint(0, 4, n)
+            tgt = src + 1
+            states = rs.uniform(-0.02, 0.02, (n, 6))
+            pos = [0, 150, 217, 218, 299]
+            for q in pos:
+                src[q], tgt[q], states[q] = 1, 2, st
+            got = _bytes(eng.evaluate_pairs(src, tgt, states, level, want_structs=True)["structs"])
+            for q in pos:
+                assert got[q] == alone, (level, q)
+            for setter, values in ((eng.set_level_fusion, [native.FUSION_OFF, native.FUSION_SPLIT, native.FUSION_AUTO]),
+                                   (eng.set_latency_forms, [True, False]), (eng.set_batch_invariant, [True, False])):
+                for v in values:
+                    setter(v)
+                    again = _bytes(eng.evaluate_pairs([1], [2], st[None], level, want_structs=True)["structs"])[0]
+                    assert again == alone
+            assert _bytes(eng.evaluate_pairs([1], [2], st[None], level, want_structs=True)["structs"])[0] == alone
+
+
+# ---- 5: no interference ------------------------------------------------------------------------------------------
+def test_no_interference_with_alignments():
+    seq = synthetic.make_sequence(38, 9, 640, 480, holes=0.01)
+    with odometry.AlignmentEngine() as eng:
+        eng.read_configuration_file(CFG4)
+        eng.set_intrinsic_matrix(seq["K"])
+        eng.reserve_frames(9, 640, 480)
+        eng.upload_frames(0, seq["gray"], seq["depth"])
+        src, tgt = list(range(8)), list(range(1, 9))
+        a0, r0 = eng.align_pairs(src, tgt, want_reports=True)
+        eng.evaluate_pairs(src, tgt, a0, 2)
+        a1, r1 = eng.align_pairs(src, tgt, want_reports=True)
+        np.testing.assert_array_equal(a0, a1)
+        assert [bytes(memoryview(r)) for r in r0] == [bytes(memoryview(r)) for r in r1]
+        eng.enqueue_align(src, tgt)
+        sys_mid = eng.evaluate_pairs(src, tgt, a0, 2)
+        a2, r2 = eng.fetch_results(8, want_reports=True)
+        np.testing.assert_array_equal(a0, a2)
+        assert [bytes(memoryview(r)) for r in r0] == [bytes(memoryview(r)) for r in r2]
+        sys_after = eng.evaluate_pairs(src, tgt, a0, 2)
+        np.testing.assert_array_equal(sys_mid["information"], sys_after["information"])
+
+
+# ---- 6: odometry and class surface -------------------------------------------------------------------------------
+@pytest.mark.parametrize("max_iter,finest", [([3, 4, 5, 6], 0), ([0, 4, 5, 6], 1)])
+def test_class_surface_matches_engine(max_iter, finest):
+    p = synthetic.make_pair(39, 640, 480, holes=0.02)
+    cfg = native.make_config(num_levels=4, max_iter=max_iter, min_grad=[300.0] * 4)
+    with odometry.CPhotoconsistencyOdometryAnalytic() as od:
+        od.SetConfiguration(cfg)
+        od.SetIntrinsicMatrix(p["K"])
+        od.SetSourceFrame(p["gray0"], p["depth0"])
+        od.SetTargetFrame(p["gray1"], p["depth1"])
+        with pytest.raises(native.PhovoError) as ex:
+            od.GetPairSystem()
+        assert ex.value.status == native.E_NOT_READY
+        od.Optimize()
+        ps = od.GetPairSystem()
+        state = od.GetOptimalStateVector()
+        assert od.GetReport().valid_pixels[finest] > 0
+        with odometry.AlignmentEngine() as eng:
+            eng.set_config(cfg)
+            eng.set_intrinsic_matrix(p["K"])
+            eng.reserve_frames(2, 640, 480)
+            eng.upload_frame(0, p["gray0"], p["depth0"])
+            eng.upload_frame(1, p["gray1"], p["depth1"])
+            ref = eng.evaluate_pairs([0], [1], state[None], finest, want_structs=True)["structs"][0]
+        assert bytes(memoryview(ps)) == bytes(memoryview(ref))
+        od.SetSourceFrame(p["gray0"], p["depth0"])
+        with pytest.raises(native.PhovoError) as ex:
+            od.GetPairSystem()
+        assert ex.value.status == native.E_NOT_READY
+
+
+def test_class_surface_biobjective_is_unsupported():
+    p = synthetic.make_pair(40, 160, 120)
+    with odometry.CPhotoconsistencyOdometryBiObjective() as od:
+        od.SetConfiguration(native.make_config(num_levels=2, max_iter=[3, 3], min_grad=[0.0, 0.0]))
+        od.SetIntrinsicMatrix(p["K"])
+        od.SetSourceFrame(p["gray0"], p["depth0"])
+        od.SetTargetFrame(p["gray1"], p["depth1"])
+        od.Optimize()
+        with pytest.raises(native.PhovoError) as ex:
+            od.GetPairSystem()
+        assert ex.value.status == native.E_UNSUPPORTED
+
+
+# ---- 7: refusals -------------------------------------------------------------------------------------------------
+def _raw(eng, n, src, tgt, states, level, out):
+    return eng._lib.phovo_engine_evaluate_pairs(eng._h, n, src, tgt, states, level, out)
+
+
+def test_refusals():
+    p = synthetic.make_pair(41, 160, 120)
+    L = native.lib()
+    with _engine(p, 3, [0, 2, 2]) as eng:
+        s = (C.c_int * 1)(0)
+        t = (C.c_int * 1)(1)
+        st = (C.c_double * 6)()
+        out = (native.PairSystem * 1)()
+        ok = _raw(eng, 1, s, t, st, 1, out)
+        assert ok == native.OK
+        assert _raw(eng, 0, None, None, None, 1, None) == native.OK
+        for args in ((None, t, st, 1, out), (s, None, st, 1, out), (s, t, None, 1, out), (s, t, st, 1, None)):
+            assert _raw(eng, 1, *args) == native.E_INVALID_ARGUMENT
+        assert _raw(eng, -1, s, t, st, 1, out) == native.E_INVALID_ARGUMENT
+        assert _raw(eng, 1, s, t, st, 3, out) == native.E_INVALID_ARGUMENT
+        assert _raw(eng, 1, s, t, st, -1, out) == native.E_INVALID_ARGUMENT
+        bad = (C.c_int * 1)(2)
+        assert _raw(eng, 1, bad, t, st, 1, out) == native.E_INVALID_ARGUMENT
+        assert _raw(eng, 1, s, bad, st, 1, out) == native.E_INVALID_ARGUMENT
+        assert _raw(eng, 1, s, t, st, 0, out) == native.E_NOT_READY          # level 0 is not stored
+        assert L.phovo_engine_evaluate_pairs(None, 1, s, t, st, 1, out) == native.E_INVALID_ARGUMENT
+        eng.set_extensions(native.make_extensions(sampling=native.SAMPLING_BILINEAR))
+        assert _raw(eng, 1, s, t, st, 1, out) == native.E_UNSUPPORTED
+    with odometry.AlignmentEngine() as eng:                                  # roles
+        eng.set_config(native.make_config(num_levels=3, max_iter=[0, 2, 2], min_grad=[0.0] * 3))
+        eng.set_intrinsic_matrix(p["K"])
+        eng.reserve_frames(2, 160, 120)
+        eng.upload_frame(1, p["gray1"], None, roles=native.ROLE_TARGET)
+        eng.upload_frame(0, p["gray0"], p["depth0"], roles=native.ROLE_SOURCE)
+        with pytest.raises(native.PhovoError) as ex:
+            eng.evaluate_pairs([1], [0], np.zeros((1, 6)), 1)
+        assert ex.value.status == native.E_NOT_READY
+        eng.evaluate_pairs([0], [1], np.zeros((1, 6)), 1)
+    with odometry.AlignmentEngine() as eng:
+        eng.set_config(native.make_config(num_levels=2, max_iter=[2, 2], min_grad=[0.0, 0.0]))
+        eng.set_intrinsic_matrix(p["K"])
+        with pytest.raises(native.PhovoError) as ex:                       # no pool yet
+            eng.evaluate_pairs([0], [1], np.zeros((1, 6)), 0)
+        assert ex.value.status == native.E_NOT_READY
+        eng.set_objective(native.OBJECTIVE_BIOBJECTIVE)
+        with pytest.raises(native.PhovoError) as ex:
+            eng.evaluate_pairs([0], [1], np.zeros((1, 6)), 0)
+        assert ex.value.status == native.E_UNSUPPORTED
+
+
+def test_roles_are_kept_per_level():
+    """A plane write gives a role on the level it writes only."""
+    p = synthetic.make_pair(42, 160, 120)
+    with odometry.AlignmentEngine() as eng:
+        eng.set_config(native.make_config(num_levels=2, max_iter=[2, 2], min_grad=[0.0, 0.0]))
+        eng.set_intrinsic_matrix(p["K"])
+        eng.reserve_frames(2, 160, 120)
+        eng.upload_frame(0, p["gray1"], p["depth1"])                                 # both roles
+        eng.upload_frame(1, p["gray0"], None, roles=native.ROLE_TARGET)
+        _, d0, _, _ = eng.get_level_planes(0, 0)
+        eng.set_level_planes(1, 0, depth=d0)                                         # frame 1 is a source on level 0 only
+        eng.evaluate_pairs([1], [0], np.zeros((1, 6)), 0)
+        with pytest.raises(native.PhovoError) as ex:
+            eng.evaluate_pairs([1], [0], np.zeros((1, 6)), 1)
+        assert ex.value.status == native.E_NOT_READY
