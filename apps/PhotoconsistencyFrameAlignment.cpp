@@ -3,9 +3,11 @@
 // Same command line, hard-coded intrinsics, depth scale and console output as the reference's app
 // (apps/PhotoconsistencyFrameAlignment/PhotoconsistencyFrameAlignment.cpp:49-115):
 //   ./PhotoconsistencyFrameAlignment <config_file.yml> <imgRGB0.png> <imgDepth0.png> <imgRGB1.png> <imgDepth1.png> [diff.png]
-//                                    [--method analytic|biobjective]
-// --method picks the aligner as the reference's USE_PHOTOCONSISTENCY_ODOMETRY_METHOD does: analytic (0, the default) or
-// biobjective (2, CPhotoconsistencyOdometryBiObjective: photometric and depth error together).
+//                                    [--method analytic|ceres|biobjective]
+// --method picks the aligner as the reference's USE_PHOTOCONSISTENCY_ODOMETRY_METHOD does: analytic (0, the default),
+// ceres (1, CPhotoconsistencyOdometryCeres: Levenberg-Marquardt on bilinear samples; reads config_*_ceres.yml files) or
+// biobjective (2, CPhotoconsistencyOdometryBiObjective: photometric and depth error together).  A configuration file of
+// the other kind is refused with a message that says so.
 // Differences: the reference tests `argc<5` but reads argv[5] (:56,79) -- five arguments are required
 // here; the final |I1 - warp(I0)| image goes to the optional sixth argument as a PNG instead of an
 // imshow window (:107-112), because the target machines are headless.
@@ -18,6 +20,7 @@
 #include "io/png_io.h"
 #include "phovo/CPhotoconsistencyOdometryAnalytic.h"
 #include "phovo/CPhotoconsistencyOdometryBiObjective.h"
+#include "phovo/CPhotoconsistencyOdometryCeres.h"
 
 typedef double CoordinateType;
 typedef unsigned char PixelType;
@@ -30,7 +33,7 @@ typedef phovo::compat::Mat_<CoordinateType> DepthImageType;
 static void printHelp()
 {
   std::cout << "./PhotoconsistencyFrameAlignment <config_file.yml> <imgRGB0.png> <imgDepth0.png> "
-               "<imgRGB1.png> <imgDepth1.png> [imgDiff.png] [--method analytic|biobjective]" << std::endl;
+               "<imgRGB1.png> <imgDepth1.png> [imgDiff.png] [--method analytic|ceres|biobjective]" << std::endl;
 }
 
 static bool loadGray(const char *path, IntensityImageType &img)
@@ -53,32 +56,50 @@ static bool loadDepthMetres(const char *path, DepthImageType &img)
   return true;
 }
 
-static int alignPair(int argc, char **argv, bool biobjective);
+enum Method { METHOD_ANALYTIC, METHOD_CERES, METHOD_BIOBJECTIVE };
+static int alignPair(int argc, char **argv, Method method);
+
+// The Ceres method reads the config_*_ceres.yml keys, the other two the config_*_analytic.yml keys.
+static bool configFitsMethod(const char *path, Method method)
+{
+  phovo_config cfg;
+  phovo_trust_region_options opt;
+  const bool ceres = method == METHOD_CERES;
+  const int st = ceres ? phovo_trust_region_read_file(path, &cfg, &opt) : phovo_config_read_file(path, &cfg);
+  if (st == PHOVO_OK) return true;
+  std::cerr << path << " is not a configuration file for --method " << (ceres ? "ceres" : "analytic|biobjective") << " ("
+            << phovo_last_error() << "): --method ceres reads the config_*_ceres.yml files, the other methods the "
+            << "config_*_analytic.yml files" << std::endl;
+  return false;
+}
 
 int main(int argc, char **argv)
 {
   // --method may stand anywhere after the program name; the remaining arguments keep their positions
-  bool biobjective = false;
+  Method method = METHOD_ANALYTIC;
   std::vector<char *> args;
   for (int i = 0; i < argc; i++) {
     if (i > 0 && std::string(argv[i]) == "--method") {
       if (i + 1 >= argc) { printHelp(); return -1; }
       const std::string m(argv[++i]);
-      if (m == "biobjective") biobjective = true;
+      if (m == "biobjective") method = METHOD_BIOBJECTIVE;
+      else if (m == "ceres") method = METHOD_CERES;
       else if (m != "analytic") { printHelp(); return -1; }
       continue;
     }
     args.push_back(argv[i]);
   }
-  return alignPair((int)args.size(), args.data(), biobjective);
+  if (args.size() >= 6 && !configFitsMethod(args[1], method)) return EXIT_FAILURE;
+  return alignPair((int)args.size(), args.data(), method);
 }
 
 template <class Odometry>
 static int alignWith(int argc, char **argv);
 
-static int alignPair(int argc, char **argv, bool biobjective)
+static int alignPair(int argc, char **argv, Method method)
 {
-  if (biobjective) return alignWith<phovo::Analytic::CPhotoconsistencyOdometryBiObjective<PixelType, CoordinateType>>(argc, argv);
+  if (method == METHOD_CERES) return alignWith<phovo::Ceres::CPhotoconsistencyOdometryCeres<PixelType, CoordinateType>>(argc, argv);
+  if (method == METHOD_BIOBJECTIVE) return alignWith<phovo::Analytic::CPhotoconsistencyOdometryBiObjective<PixelType, CoordinateType>>(argc, argv);
   return alignWith<phovo::Analytic::CPhotoconsistencyOdometryAnalytic<PixelType, CoordinateType>>(argc, argv);
 }
 

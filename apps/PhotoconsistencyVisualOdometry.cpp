@@ -2,9 +2,11 @@
 // directory, writing a TUM trajectory file.
 //
 //   ./PhotoconsistencyVisualOdometry <config_file.yml> <rgbd_dataset_directory> <output_trajectory_file> [--batch [--gpus N] [--rccl]]
-//                                    [--method analytic|biobjective] [--information <file>]
+//                                    [--method analytic|ceres|biobjective] [--information <file>]
 // --method picks the aligner as the reference's USE_PHOTOCONSISTENCY_ODOMETRY_METHOD does (0 = analytic, the default;
-// 2 = bi-objective: photometric and depth error together, CPhotoconsistencyOdometryBiObjective), in every mode.
+// 1 = ceres: Levenberg-Marquardt on bilinear samples, CPhotoconsistencyOdometryCeres, which reads config_*_ceres.yml
+// files; 2 = bi-objective: photometric and depth error together, CPhotoconsistencyOdometryBiObjective), in every mode.
+// A configuration file of the other kind is refused with a message that says so.
 // --information <file> (not in the reference; analytic method, one device): one line per pair, stamped like its trajectory
 // line, with the Gauss-Newton system at the pair's optimal state on the finest level the configuration optimises --
 // `timestamp rows cost` and the 21 upper-triangle entries of J^T J (phovo_pair_system_format).  The loop takes it from the
@@ -46,6 +48,7 @@
 #include "rccl/shard_vote.h"
 #include "phovo/CPhotoconsistencyOdometryAnalytic.h"
 #include "phovo/CPhotoconsistencyOdometryBiObjective.h"
+#include "phovo/CPhotoconsistencyOdometryCeres.h"
 
 typedef double CoordinateType;
 typedef unsigned char PixelType;
@@ -120,7 +123,7 @@ static bool writeSystem(std::ofstream &f, double timestamp, const phovo_pair_sys
 static void printHelp()
 {
   std::cout << "./PhotoconsistencyVisualOdometry <config_file.yml> <rgbd_dataset_directory> "
-               "<output_trajectory_file> [--batch [--gpus N] [--rccl]] [--method analytic|biobjective] "
+               "<output_trajectory_file> [--batch [--gpus N] [--rccl]] [--method analytic|ceres|biobjective] "
                "[--information <file>]" << std::endl;
 }
 
@@ -134,7 +137,7 @@ int main(int argc, char *argv[])
   bool batch = false;
   int nGpus = 1;                                      // --batch --gpus N: the pairs of the sequence sharded over N devices
   bool rccl = false;                                  // ... --rccl: the shards' states meet through ONE RCCL all_gather
-  int objective = PHOVO_OBJECTIVE_PHOTOMETRIC;        // --method analytic (default) | biobjective
+  int objective = PHOVO_OBJECTIVE_PHOTOMETRIC;        // --method analytic (default) | ceres | biobjective
   std::string informationPath;                        // --information <file>: the pairs' systems at their optimal states
   for (int i = 4; i < argc; i++) {
     const std::string a(argv[i]);
@@ -143,6 +146,7 @@ int main(int argc, char *argv[])
       const std::string m(argv[++i]);
       if (m == "analytic") objective = PHOVO_OBJECTIVE_PHOTOMETRIC;
       else if (m == "biobjective") objective = PHOVO_OBJECTIVE_BIOBJECTIVE;
+      else if (m == "ceres") objective = PHOVO_OBJECTIVE_TRUST_REGION;
       else { printHelp(); return EXIT_FAILURE; }
     }
     else if (a == "--rccl") rccl = true;
@@ -158,10 +162,21 @@ int main(int argc, char *argv[])
     return EXIT_FAILURE;
   }
   if (information && objective != PHOVO_OBJECTIVE_PHOTOMETRIC) {
-    std::cerr << "--information needs --method analytic (the bi-objective has no pair system)" << std::endl;
+    std::cerr << "--information needs --method analytic (the bi-objective and the Ceres method have no pair system)" << std::endl;
     return EXIT_FAILURE;
   }
   if (!fileExists(configFile)) { std::cerr << "Input config file " << configFile << " does not exist" << std::endl; return EXIT_FAILURE; }
+  {   // the Ceres method reads the config_*_ceres.yml keys, the other two the config_*_analytic.yml keys
+    phovo_config c;
+    phovo_trust_region_options o;
+    const bool ceres = objective == PHOVO_OBJECTIVE_TRUST_REGION;
+    if ((ceres ? phovo_trust_region_read_file(configFile.c_str(), &c, &o) : phovo_config_read_file(configFile.c_str(), &c)) != PHOVO_OK) {
+      std::cerr << configFile << " is not a configuration file for --method " << (ceres ? "ceres" : "analytic|biobjective")
+                << " (" << phovo_last_error() << "): --method ceres reads the config_*_ceres.yml files, the other methods "
+                << "the config_*_analytic.yml files" << std::endl;
+      return EXIT_FAILURE;
+    }
+  }
   if (!fileExists(datasetDir)) { std::cerr << "Input RGBD dataset directory " << datasetDir << " does not exist" << std::endl; return EXIT_FAILURE; }
   const std::string rgbList = datasetDir + "/rgb.txt", depthList = datasetDir + "/depth.txt";
   if (!fileExists(rgbList)) { std::cerr << "Input RGB data file " << rgbList << " does not exist" << std::endl; return EXIT_FAILURE; }
@@ -233,13 +248,20 @@ int main(int argc, char *argv[])
       if (objective == PHOVO_OBJECTIVE_BIOBJECTIVE) {
         phovo::Analytic::CPhotoconsistencyOdometryBiObjective<PixelType, CoordinateType> odometry;
         if (runLoop(odometry) != EXIT_SUCCESS) return EXIT_FAILURE;
+      } else if (objective == PHOVO_OBJECTIVE_TRUST_REGION) {
+        phovo::Ceres::CPhotoconsistencyOdometryCeres<PixelType, CoordinateType> odometry;
+        if (runLoop(odometry) != EXIT_SUCCESS) return EXIT_FAILURE;
       } else {
         phovo::Analytic::CPhotoconsistencyOdometryAnalytic<PixelType, CoordinateType> odometry;
         if (runLoop(odometry) != EXIT_SUCCESS) return EXIT_FAILURE;
       }
     } else {
       phovo_config cfg;
-      PHOVO_OK_OR_FAIL(phovo_config_read_file(configFile.c_str(), &cfg));
+      phovo_trust_region_options trOptions;           // --method ceres: the solver options of the file
+      if (objective == PHOVO_OBJECTIVE_TRUST_REGION)
+        PHOVO_OK_OR_FAIL(phovo_trust_region_read_file(configFile.c_str(), &cfg, &trOptions));
+      else
+        PHOVO_OK_OR_FAIL(phovo_config_read_file(configFile.c_str(), &cfg));
       const int nDevices = phovo_device_count();
       if (nDevices < 1) { std::cerr << "phovo_engine_create: no HIP device available: this library has no CPU path" << std::endl; return EXIT_FAILURE; }
       // PHOVO_VO_SHARE_DEVICES=1 lets more shards than devices run (a rehearsal of --gpus N on a smaller machine)
@@ -339,6 +361,8 @@ int main(int argc, char *argv[])
           if (phovo_engine_create(g % nDevices, &engine) != PHOVO_OK) return fail("phovo_engine_create");
           if (phovo_engine_set_config(engine, &cfg) != PHOVO_OK) return fail("phovo_engine_set_config");
           if (phovo_engine_set_objective(engine, objective) != PHOVO_OK) return fail("phovo_engine_set_objective");
+          if (objective == PHOVO_OBJECTIVE_TRUST_REGION && phovo_engine_set_trust_region_options(engine, &trOptions) != PHOVO_OK)
+            return fail("phovo_engine_set_trust_region_options");
           // a pair's pose must not depend on the size of the shard it falls into (same trajectory file for every N)
           if (phovo_engine_set_batch_invariant(engine, 1) != PHOVO_OK) return fail("phovo_engine_set_batch_invariant");
           if (phovo_engine_set_intrinsic_matrix(engine, intrinsicMatrix.data()) != PHOVO_OK) return fail("phovo_engine_set_intrinsic_matrix");

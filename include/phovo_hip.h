@@ -158,6 +158,56 @@ typedef struct phovo_extensions {
  *                                PHOVO_PAIR_RANK_DEFICIENT means fewer than 6 of them. */
 #define PHOVO_OBJECTIVE_PHOTOMETRIC 0
 #define PHOVO_OBJECTIVE_BIOBJECTIVE 1
+/*   PHOVO_OBJECTIVE_TRUST_REGION the reference's method 1, CPhotoconsistencyOdometryCeres: the photometric residual with
+ *                                bilinear samples of the target at the real-valued warped position, the exact warp
+ *                                Jacobian (no temp11 slip) and a Levenberg-Marquardt trust-region solver per level with
+ *                                function, gradient and parameter tolerances (phovo_trust_region_options; DESIGN.md §12
+ *                                has the contract, a reading of Ceres 1.14's TrustRegionMinimizer).  Frames are the
+ *                                photometric objective's: switching between the two keeps the frame pool.
+ *                                Reference-exact only: fp64 planes, nearest / scatter sampling setting, no Huber
+ *                                weights, jacobian_corrected 0 -- anything else is PHOVO_E_UNSUPPORTED, whichever setter
+ *                                comes second; phovo_engine_evaluate_pairs is PHOVO_E_UNSUPPORTED too.  Fusion,
+ *                                sliding-window, wide and latency-form settings are accepted and have no effect.
+ *                                phovo_pair_report: iterations[L] = LM steps (iteration 0 not counted), valid_pixels[L] =
+ *                                owned targets at the final point, gradient_norm = ||J^T r||_2 there (of the last level
+ *                                run), PHOVO_PAIR_NONFINITE when an evaluation was not finite, PHOVO_PAIR_RANK_DEFICIENT
+ *                                when fewer than 6 rows remain.  The per-level solver record is phovo_trust_region_report. */
+#define PHOVO_OBJECTIVE_TRUST_REGION 2
+
+/* Solver options of the trust-region objective, per level (CPhotoconsistencyOdometryCeres.h:526-576).  num_levels, blur,
+ * gradient scale and max_num_iterations stay in phovo_config. */
+typedef struct phovo_trust_region_options {
+  double function_tolerance[PHOVO_MAX_LEVELS];          /* function_tolerance (at each level)           */
+  double gradient_tolerance[PHOVO_MAX_LEVELS];          /* gradient_tolerance (at each level)           */
+  double parameter_tolerance[PHOVO_MAX_LEVELS];         /* parameter_tolerance (at each level)          */
+  double initial_trust_region_radius[PHOVO_MAX_LEVELS]; /* initial_trust_region_radius (at each level)  */
+  double max_trust_region_radius[PHOVO_MAX_LEVELS];     /* max_trust_region_radius (at each level)      */
+  double min_trust_region_radius[PHOVO_MAX_LEVELS];     /* min_trust_region_radius (at each level)      */
+  double min_relative_decrease[PHOVO_MAX_LEVELS];       /* min_relative_decrease (at each level)        */
+} phovo_trust_region_options;
+
+/* Why a level of the trust-region solver stopped (phovo_trust_region_level.termination). */
+#define PHOVO_TR_SKIPPED           0   /* max_num_iterations[L] == 0: the level was not optimised             */
+#define PHOVO_TR_MAX_ITERATIONS    1   /* NO_CONVERGENCE: max_num_iterations steps taken                        */
+#define PHOVO_TR_GRADIENT          2   /* CONVERGENCE: max |x - (x - g)| <= gradient_tolerance                   */
+#define PHOVO_TR_FUNCTION          3   /* CONVERGENCE: |cost change| <= function_tolerance * cost               */
+#define PHOVO_TR_PARAMETER         4   /* CONVERGENCE: |step| <= parameter_tolerance * (|x| + parameter_tolerance) */
+#define PHOVO_TR_MIN_RADIUS        5   /* CONVERGENCE: radius <= min_trust_region_radius                        */
+#define PHOVO_TR_INVALID_STEP      6   /* FAILURE: the LM system could not be solved or did not promise a decrease */
+#define PHOVO_TR_EVALUATION_FAILED 7   /* FAILURE: the cost or the system at the point was not finite           */
+typedef struct phovo_trust_region_level {
+  int32_t steps;          /* LM steps (iteration 0, the first evaluation, not counted)      */
+  int32_t accepted;       /* steps whose candidate was accepted                              */
+  int32_t termination;    /* PHOVO_TR_*                                                      */
+  int32_t rows;           /* owned targets (filled rows) at the final point                 */
+  double  initial_cost;   /* 1/2 sum r^2 at the level's first point                          */
+  double  final_cost;     /* at the level's final point (the last accepted one)              */
+  double  final_radius;   /* the trust-region radius when the level stopped                  */
+  double  jacobi_scaling[6]; /* S_j = 1 / (1 + sqrt(H_jj)) from the level's first system (0 if it failed) */
+} phovo_trust_region_level;
+typedef struct phovo_trust_region_report {
+  phovo_trust_region_level level[PHOVO_MAX_LEVELS];
+} phovo_trust_region_report;
 
 typedef struct phovo_engine phovo_engine;
 typedef struct phovo_odometry phovo_odometry;
@@ -175,6 +225,18 @@ int phovo_config_default(phovo_config *cfg);
 /* Parses the reference's config_files/ *.yml unchanged (OpenCV FileStorage "%YAML:1.0" dialect,
  * keys with spaces and parentheses, per-level arrays that may be longer than num_levels). */
 int phovo_config_read_file(const char *path, phovo_config *cfg);
+
+/* The trust-region objective's keys (CPhotoconsistencyOdometryCeres.h:526-576): numOptimizationLevels, blurFilterSize,
+ * imageGradientsScalingFactor, max_num_iterations into cfg (lambda and min_gradient_norm keep their defaults) and the
+ * seven solver lists into opt; num_threads, num_linear_solver_threads, minimizer_progress_to_stdout and
+ * visualizeIterations are read and ignored (cfg->visualize_iterations is 0).  Lists may be longer than
+ * numOptimizationLevels.  A min_trust_region_radius list one entry short takes Ceres's default 1e-32 for the missing last
+ * (coarsest) level, as 4 of the reference's 8 files need; any other short list or missing key is PHOVO_E_CONFIG (so is an
+ * analytic file).  cfg or opt may be NULL. */
+int phovo_trust_region_read_file(const char *path, phovo_config *cfg, phovo_trust_region_options *opt);
+/* Ceres's defaults for every level: function 1e-6, gradient 1e-10, parameter 1e-8, radius 1e4 (max 1e16, min 1e-32),
+ * min_relative_decrease 1e-3. */
+int phovo_trust_region_options_default(phovo_trust_region_options *opt);
 
 int phovo_extensions_default(phovo_extensions *ext);
 /* Optional keys in the same yml file (the reference's cv::FileStorage lookups ignore keys they do not ask for,
@@ -224,6 +286,12 @@ int phovo_odometry_set_latency_forms(phovo_odometry *o, int on);
 /* not in the reference's class (its apps pick the class): PHOVO_OBJECTIVE_*, default photometric.  A change drops the
  * frames set so far.  Under the bi-objective phovo_odometry_set_target_frame needs depth (NULL: PHOVO_E_INVALID_ARGUMENT). */
 int phovo_odometry_set_objective(phovo_odometry *o, int objective);
+/* Trust-region objective: its solver options (defaults: phovo_trust_region_options_default) and the solver record of the
+ * last Optimize() (PHOVO_E_NOT_READY before one; PHOVO_E_UNSUPPORTED under another objective).  Under this objective
+ * phovo_odometry_read_configuration_file reads the Ceres keys (phovo_trust_region_read_file). */
+int phovo_odometry_set_trust_region_options(phovo_odometry *o, const phovo_trust_region_options *opt);
+int phovo_odometry_get_trust_region_options(const phovo_odometry *o, phovo_trust_region_options *opt);
+int phovo_odometry_get_trust_region_report(const phovo_odometry *o, phovo_trust_region_report *report);
 int phovo_odometry_set_min_depth(phovo_odometry *o, double min_depth);     /* :448 */
 int phovo_odometry_set_max_depth(phovo_odometry *o, double max_depth);     /* :454 */
 int phovo_odometry_set_intrinsic_matrix(phovo_odometry *o, const double k[9]);     /* :460, row-major 3x3 */
@@ -317,6 +385,11 @@ int phovo_engine_level_uses_wide(const phovo_engine *e, int level, int n_pairs);
  * sampling and no Huber weights. */
 int phovo_engine_set_objective(phovo_engine *e, int objective);
 int phovo_engine_get_objective(const phovo_engine *e, int *objective);
+/* Trust-region objective: solver options (kept under every objective, used by this one) and the per-pair solver records
+ * of the LAST enqueue (n_pairs must be that enqueue's; PHOVO_E_UNSUPPORTED if it ran under another objective). */
+int phovo_engine_set_trust_region_options(phovo_engine *e, const phovo_trust_region_options *opt);
+int phovo_engine_get_trust_region_options(const phovo_engine *e, phovo_trust_region_options *opt);
+int phovo_engine_fetch_trust_region_reports(phovo_engine *e, int n_pairs, phovo_trust_region_report *reports);
 
 /* Page-locks (and releases) a host buffer the caller will hand to the upload entry points repeatedly: uploads from
  * registered memory are direct DMA at the link rate instead of going through the runtime's bounce buffers.  Optional;
@@ -446,7 +519,8 @@ enum { PHOVO_LAUNCH_PERSISTENT = 0,       /* gn_level_kernel: one level, one wor
        PHOVO_LAUNCH_SLIDE_FALLBACK = 3,   /* gn_level_kernel on the pairs the sliding-window launch handed over */
        PHOVO_LAUNCH_WIDE = 4,             /* k_wide_pass1 / k_wide_pass2 per iteration, many workgroups per pair */
        PHOVO_LAUNCH_BILINEAR = 5,         /* gn_level_kernel_bilinear (extension) */
-       PHOVO_LAUNCH_BIOBJECTIVE = 6 };    /* gn_level_kernel_biobjective (PHOVO_OBJECTIVE_BIOBJECTIVE) */
+       PHOVO_LAUNCH_BIOBJECTIVE = 6,      /* gn_level_kernel_biobjective (PHOVO_OBJECTIVE_BIOBJECTIVE) */
+       PHOVO_LAUNCH_TRUST_REGION = 7 };   /* gn_level_kernel_trust_region (PHOVO_OBJECTIVE_TRUST_REGION) */
 typedef struct phovo_launch_record {
   int level_first, level_last;            /* pyramid levels the launch covers (level_first >= level_last) */
   int kind;                               /* PHOVO_LAUNCH_* */

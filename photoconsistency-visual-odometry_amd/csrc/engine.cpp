@@ -49,6 +49,8 @@ struct LevelPool {
   size_t dgx_off = 0, dgy_off = 0, gain_off = 0;
   GNLaunchPlan plan_bi{};
   bool plan_bi_ok = false;
+  GNLaunchPlan plan_tr{};              // trust-region objective
+  bool plan_tr_ok = false;
   GNLaunchPlan plan{};
   bool plan_ok = false;
   GNLaunchPlan plan_few{};             // geometry for a handful of pairs (LATENCY_PAIRS or fewer)
@@ -92,6 +94,9 @@ struct AlignSlot {
   size_t wide_ws_capacity = 0;
   std::vector<int> h_wide_done;
   std::vector<phovo_launch_record> launches;   // what the enqueue launched, in order (phovo_engine_last_launches)
+  phovo_trust_region_report *d_tr_reports = nullptr;   // trust-region objective: the solver records of the enqueue's pairs
+  int tr_capacity = 0;
+  bool tr_ran = false;                         // the enqueue ran under PHOVO_OBJECTIVE_TRUST_REGION
 };
 
 struct phovo_engine {
@@ -129,6 +134,7 @@ struct phovo_engine {
   int wide_policy = 0;                         // 0 auto, 1 always (where possible), -1 never
   bool batch_invariant = false;                // every batch takes the same kernels and geometries (phovo_engine_set_batch_invariant)
   int objective = PHOVO_OBJECTIVE_PHOTOMETRIC;  // phovo_engine_set_objective
+  phovo_trust_region_options tr_opt{};         // phovo_engine_set_trust_region_options (Ceres's defaults at creation)
   bool latency_forms = false;                  // a handful of pairs may take the forms that finish soonest also where a level has a one-workgroup form with its owner map in LDS (phovo_engine_set_latency_forms)
   std::vector<unsigned char> frame_roles;      // [frame][PHOVO_MAX_LEVELS]: PHOVO_ROLE_* each level of each frame has been given since the
                                                // pool was reserved (an upload: every level; a plane write: its level)
@@ -178,6 +184,8 @@ void free_slot(AlignSlot &s)
   if (s.d_owner) (void)hipFree(s.d_owner);
   if (s.d_mask) (void)hipFree(s.d_mask);
   if (s.d_wide_ws) (void)hipFree(s.d_wide_ws);
+  if (s.d_tr_reports) (void)hipFree(s.d_tr_reports);
+  s.d_tr_reports = nullptr; s.tr_capacity = 0;
   s.d_owner = nullptr; s.owner_capacity = 0; s.d_wide_ws = nullptr; s.wide_ws_capacity = 0;
   s.d_mask = nullptr; s.mask_capacity = 0;
 }
@@ -225,7 +233,7 @@ void level_dims(int w, int h, int level, int *lw, int *lh)
 // there a handful of pairs takes the wide form unless the caller pins the batch forms (phovo_engine_set_batch_invariant).
 bool use_wide_level(const phovo_engine *e, int n_pairs, const LevelPool &lv)
 {
-  if (e->wide_policy < 0 || e->objective == PHOVO_OBJECTIVE_BIOBJECTIVE) return false;
+  if (e->wide_policy < 0 || e->objective != PHOVO_OBJECTIVE_PHOTOMETRIC) return false;
   if (e->ext.plane_storage != PHOVO_STORAGE_F64 || e->ext.sampling != PHOVO_SAMPLING_NEAREST_SCATTER) return false;
   if (e->wide_policy > 0) return true;
   if (e->batch_invariant) return false;        // the automatic choice looks at the batch size
@@ -243,6 +251,9 @@ bool biobjective_supports(const phovo_extensions &x)
     if (x.huber_delta[l] > 0.0) return false;
   return true;
 }
+
+// The trust-region objective likewise (the same four conditions: jacobian_corrected 0 included).
+bool trust_region_supports(const phovo_extensions &x) { return biobjective_supports(x); }
 
 // Depth gradients (with the max depth in force) and gain of `count` consecutive target frames of level l, from the
 // intensity and depth planes already in the pool (fp64, packed: the frame is frame_bytes / 8 doubles).
@@ -511,6 +522,7 @@ int phovo_engine_create(int device, phovo_engine **out)
   e->device = device;
   phovo_config_default(&e->cfg);
   phovo_extensions_default(&e->ext);
+  phovo_trust_region_options_default(&e->tr_opt);
   hipError_t he = hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking);
   if (he == hipSuccess) he = hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking);
   for (int i = 0; i < 2 && he == hipSuccess; i++) {
@@ -529,6 +541,7 @@ int phovo_engine_create(int device, phovo_engine **out)
   if (he == hipSuccess) he = gn_prepare_kernels();
   if (he == hipSuccess) he = gn_prepare_slide_kernels();
   if (he == hipSuccess) he = gn_prepare_biobjective_kernels();
+  if (he == hipSuccess) he = gn_prepare_trust_region_kernels();
   if (he == hipSuccess) {
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) e->cu_count = cus;
@@ -618,6 +631,9 @@ int phovo_engine_set_extensions(phovo_engine *e, const phovo_extensions *ext)
   if (e->objective == PHOVO_OBJECTIVE_BIOBJECTIVE && !biobjective_supports(*ext))
     return fail(PHOVO_E_UNSUPPORTED, "set_extensions: the bi-objective runs on fp64 planes with nearest / scatter sampling "
                                      "and no Huber weights only");
+  if (e->objective == PHOVO_OBJECTIVE_TRUST_REGION && !trust_region_supports(*ext))
+    return fail(PHOVO_E_UNSUPPORTED, "set_extensions: the trust-region objective runs on fp64 planes with the default "
+                                     "sampling, no Huber weights and jacobian_corrected 0 only");
   // the pool layout changes with the storage type, and -- fp16 planes under bilinear sampling carry tap records -- with the
   // sampling where that adds or removes the records
   auto has_records = [](const phovo_extensions &x) { return x.sampling == PHOVO_SAMPLING_BILINEAR && x.plane_storage == PHOVO_STORAGE_F16; };
@@ -634,12 +650,18 @@ int phovo_engine_set_extensions(phovo_engine *e, const phovo_extensions *ext)
 int phovo_engine_set_objective(phovo_engine *e, int objective)
 {
   if (!e) return fail(PHOVO_E_INVALID_ARGUMENT, "set_objective: null");
-  if (objective != PHOVO_OBJECTIVE_PHOTOMETRIC && objective != PHOVO_OBJECTIVE_BIOBJECTIVE)
+  if (objective != PHOVO_OBJECTIVE_PHOTOMETRIC && objective != PHOVO_OBJECTIVE_BIOBJECTIVE &&
+      objective != PHOVO_OBJECTIVE_TRUST_REGION)
     return fail(PHOVO_E_INVALID_ARGUMENT, "set_objective: unknown objective");
   if (objective == PHOVO_OBJECTIVE_BIOBJECTIVE && !biobjective_supports(e->ext))
     return fail(PHOVO_E_UNSUPPORTED, "set_objective: the bi-objective runs on fp64 planes with nearest / scatter sampling "
                                      "and no Huber weights only");
-  if (objective != e->objective) {             // the pool layout changes (the bi-objective's target planes): dropped
+  if (objective == PHOVO_OBJECTIVE_TRUST_REGION && !trust_region_supports(e->ext))
+    return fail(PHOVO_E_UNSUPPORTED, "set_objective: the trust-region objective runs on fp64 planes with the default "
+                                     "sampling, no Huber weights and jacobian_corrected 0 only");
+  // The photometric and trust-region objectives share the frame layout: a switch between them keeps the pool.
+  auto bi = [](int o) { return o == PHOVO_OBJECTIVE_BIOBJECTIVE; };
+  if (objective != e->objective && (bi(objective) || bi(e->objective))) {   // the pool layout changes (the bi-objective's target planes): dropped
     (void)hipSetDevice(e->device);
     (void)hipStreamSynchronize(e->stream);
     (void)quiesce(e);
@@ -653,6 +675,34 @@ int phovo_engine_get_objective(const phovo_engine *e, int *objective)
 {
   if (!e || !objective) return fail(PHOVO_E_INVALID_ARGUMENT, "get_objective: null");
   *objective = e->objective;
+  return PHOVO_OK;
+}
+
+int phovo_trust_region_read_file(const char *path, phovo_config *cfg, phovo_trust_region_options *opt)
+{
+  return read_trust_region_file(path, cfg, opt);
+}
+
+int phovo_engine_set_trust_region_options(phovo_engine *e, const phovo_trust_region_options *opt)
+{
+  if (!e || !opt) return fail(PHOVO_E_INVALID_ARGUMENT, "set_trust_region_options: null");
+  for (int l = 0; l < PHOVO_MAX_LEVELS; l++) {
+    const double v[7] = {opt->function_tolerance[l], opt->gradient_tolerance[l], opt->parameter_tolerance[l],
+                         opt->initial_trust_region_radius[l], opt->max_trust_region_radius[l],
+                         opt->min_trust_region_radius[l], opt->min_relative_decrease[l]};
+    for (double x : v)
+      if (!(x == x)) return fail(PHOVO_E_INVALID_ARGUMENT, "set_trust_region_options: NaN");
+    if (!(opt->initial_trust_region_radius[l] > 0.0))
+      return fail(PHOVO_E_INVALID_ARGUMENT, "set_trust_region_options: initial_trust_region_radius must be positive");
+  }
+  e->tr_opt = *opt;
+  return PHOVO_OK;
+}
+
+int phovo_engine_get_trust_region_options(const phovo_engine *e, phovo_trust_region_options *opt)
+{
+  if (!e || !opt) return fail(PHOVO_E_INVALID_ARGUMENT, "get_trust_region_options: null");
+  *opt = e->tr_opt;
   return PHOVO_OK;
 }
 
@@ -728,7 +778,7 @@ int phovo_engine_set_batch_invariant(phovo_engine *e, int on)
 int phovo_engine_level_uses_wide(const phovo_engine *e, int level, int n_pairs)
 {
   if (!e || level < 0 || level >= e->cfg.num_levels || e->n_frames == 0) return 0;
-  if (e->objective == PHOVO_OBJECTIVE_BIOBJECTIVE) return 0;
+  if (e->objective != PHOVO_OBJECTIVE_PHOTOMETRIC) return 0;
   return use_wide_level(e, n_pairs, e->levels[level]) && !(e->ext.huber_delta[level] > 0.0) ? 1 : 0;
 }
 
@@ -833,6 +883,7 @@ int phovo_engine_reserve_frames(phovo_engine *e, int n_frames, int width, int he
         lv.plan_bi_ok = gn_plan_level_biobjective(lv.n, &lv.plan_bi);
       }
       lv.frame_bytes = off;
+      lv.plan_tr_ok = gn_plan_level_trust_region(lv.n, &lv.plan_tr);
     }
     if (lv.stored) {
       const size_t bytes = (size_t)n_frames * lv.frame_bytes;
@@ -1146,6 +1197,14 @@ int phovo_engine_enqueue_align(phovo_engine *e, int n_pairs, const int *source_f
       if (!lv.plan_bi.owner_in_lds) owner_need = std::max(owner_need, (size_t)n_pairs * (size_t)lv.n);
       continue;
     }
+    if (e->objective == PHOVO_OBJECTIVE_TRUST_REGION) {
+      if (!lv.plan_tr_ok)
+        return fail(PHOVO_E_SHAPE, "align: pyramid level too large for the trust-region objective (more than 2 097 151 pixels)");
+      // (one map per resident workgroup: the persistent grid, not the batch)
+      const size_t wgs = (size_t)std::min(n_pairs, e->cu_count * lv.plan_tr.wgs_per_cu);
+      if (!lv.plan_tr.owner_in_lds) owner_need = std::max(owner_need, wgs * (size_t)lv.n);
+      continue;
+    }
     if (e->ext.sampling == PHOVO_SAMPLING_BILINEAR) continue;       // no owner map, no LDS limit
     const bool wide = use_wide_level(e, n_pairs, lv) && !(e->ext.huber_delta[l] > 0.0);
     if (wide) {
@@ -1179,6 +1238,7 @@ int phovo_engine_enqueue_align(phovo_engine *e, int n_pairs, const int *source_f
   s.launches.clear();
   for (bool &b : s.level_launched) b = false;
   s.d_states = nullptr;
+  s.tr_ran = e->objective == PHOVO_OBJECTIVE_TRUST_REGION;
   if (n_pairs == 0) {                    // nothing to run: a valid, empty enqueue (fetch of 0 pairs succeeds, no device buffer)
     e->ticket = ticket;
     s.ticket = ticket;
@@ -1227,6 +1287,11 @@ int phovo_engine_enqueue_align(phovo_engine *e, int n_pairs, const int *source_f
     s.wide_ws_capacity = wide_need;
   }
   if (wide_need) s.h_wide_done.resize((size_t)n_pairs * 4);
+  if (s.tr_ran && n_pairs > s.tr_capacity) {
+    if (s.d_tr_reports) { (void)hipFree(s.d_tr_reports); s.d_tr_reports = nullptr; s.tr_capacity = 0; }
+    PHOVO_HIP_CHECK(hipMalloc(&s.d_tr_reports, sizeof(phovo_trust_region_report) * (size_t)n_pairs));
+    s.tr_capacity = n_pairs;
+  }
   // The caller may reuse its arrays as soon as this returns and the copies below are asynchronous: the slot's pinned
   // mirror keeps them alive until the slot is used again (synchronised above).
   const PairLayout pl = pair_layout(n_pairs);
@@ -1244,6 +1309,8 @@ int phovo_engine_enqueue_align(phovo_engine *e, int n_pairs, const int *source_f
   // one copy in (pair list + initial states, zeros without them), one memset (reports + the work-queue heads of all levels)
   PHOVO_HIP_CHECK(hipMemcpyAsync(s.d_pairs, s.h_up, pl.reports, hipMemcpyHostToDevice, s.stream));
   PHOVO_HIP_CHECK(hipMemsetAsync(s.d_pairs + pl.reports, 0, pl.total - pl.reports, s.stream));
+  if (s.tr_ran)          // (every level the configuration skips stays PHOVO_TR_SKIPPED = 0)
+    PHOVO_HIP_CHECK(hipMemsetAsync(s.d_tr_reports, 0, sizeof(phovo_trust_region_report) * (size_t)n_pairs, s.stream));
   PHOVO_HIP_CHECK(hipEventRecord(s.ev_total_start, s.stream));
 
   const PairLayout lay = pair_layout(n_pairs);
@@ -1287,7 +1354,7 @@ int phovo_engine_enqueue_align(phovo_engine *e, int n_pairs, const int *source_f
   auto fusable = [&](int l) {
     const LevelPool &lv = e->levels[l];
     if (e->fusion == PHOVO_FUSION_OFF || e->ext.sampling == PHOVO_SAMPLING_BILINEAR || few_batch) return false;
-    if (e->objective == PHOVO_OBJECTIVE_BIOBJECTIVE) return false;
+    if (e->objective != PHOVO_OBJECTIVE_PHOTOMETRIC) return false;
     if (use_wide_level(e, n_pairs, lv) && !(e->ext.huber_delta[l] > 0.0)) return false;
     return gn_level_fusable(lv.n);
   };
@@ -1349,6 +1416,22 @@ int phovo_engine_enqueue_align(phovo_engine *e, int n_pairs, const int *source_f
       PHOVO_HIP_CHECK(gn_launch_level_biobjective(b, lv.plan_bi, e->cu_count, s.stream));
       record(l, l, PHOVO_LAUNCH_BIOBJECTIVE, lv.plan_bi.threads, lv.plan_bi.lds_bytes, persistent_grid(lv.plan_bi.wgs_per_cu));
       if (!lv.plan_bi.owner_in_lds) s.owner_tagged = true;    // tagged entries stay behind (the kernel wipes per pair)
+    } else if (e->objective == PHOVO_OBJECTIVE_TRUST_REGION) {
+      GNTrustRegionArgs b{};
+      b.lv = a;
+      const phovo_trust_region_options &o = e->tr_opt;
+      b.lv.fx = e->K[0] / std::pow(2.0, l); b.lv.fy = e->K[4] / std::pow(2.0, l);      // Ceres.h:164-169: divisions
+      b.lv.ox = e->K[2] / std::pow(2.0, l); b.lv.oy = e->K[5] / std::pow(2.0, l);
+      b.lv.ifx = 1.0 / b.lv.fx; b.lv.ify = 1.0 / b.lv.fy;
+      b.max_iterations = e->cfg.max_num_iterations[l];
+      b.function_tolerance = o.function_tolerance[l]; b.gradient_tolerance = o.gradient_tolerance[l];
+      b.parameter_tolerance = o.parameter_tolerance[l];
+      b.initial_radius = o.initial_trust_region_radius[l]; b.max_radius = o.max_trust_region_radius[l];
+      b.min_radius = o.min_trust_region_radius[l]; b.min_relative_decrease = o.min_relative_decrease[l];
+      b.tr_reports = s.d_tr_reports;
+      PHOVO_HIP_CHECK(gn_launch_level_trust_region(b, lv.plan_tr, e->cu_count, s.stream));
+      record(l, l, PHOVO_LAUNCH_TRUST_REGION, lv.plan_tr.threads, lv.plan_tr.lds_bytes, persistent_grid(lv.plan_tr.wgs_per_cu));
+      if (!lv.plan_tr.owner_in_lds) s.owner_tagged = true;    // tagged entries stay behind (the kernel wipes per pair)
     } else if (e->ext.sampling == PHOVO_SAMPLING_BILINEAR) {
       PHOVO_HIP_CHECK(gn_launch_level_bilinear(a, e->ext.plane_storage, e->ext.jacobian_corrected != 0, e->cu_count, s.stream));
       record(l, l, PHOVO_LAUNCH_BILINEAR, 256, 0, persistent_grid(gn_bilinear_wgs_per_cu(e->ext.plane_storage)));
@@ -1454,11 +1537,27 @@ int phovo_engine_fetch(phovo_engine *e, int ticket, int n_pairs, double *out_sta
   if (out_states) std::memcpy(out_states, s->h_down, sizeof(double) * 6 * (size_t)n_pairs);
   if (reports) {
     std::memcpy(reports, s->h_down + (pl.reports - pl.states), sizeof(phovo_pair_report) * (size_t)n_pairs);
-    // Levels with max_num_iterations == 0 still run the loop body once in the reference (:510,547-549).
-    for (int i = 0; i < n_pairs; i++)
+    // Levels with max_num_iterations == 0 still run the loop body once in the reference (:510,547-549).  (The Ceres
+    // aligner skips them: 0 steps.)
+    for (int i = 0; i < n_pairs && !s->tr_ran; i++)
       for (int l = 0; l < e->cfg.num_levels; l++)
         if (e->cfg.max_num_iterations[l] <= 0) reports[i].iterations[l] = 1;
   }
+  return PHOVO_OK;
+}
+
+int phovo_engine_fetch_trust_region_reports(phovo_engine *e, int n_pairs, phovo_trust_region_report *reports)
+{
+  if (!e) return fail(PHOVO_E_INVALID_ARGUMENT, "fetch_trust_region_reports: null");
+  AlignSlot *s = slot_of(e, e->ticket);
+  if (!s) return fail(PHOVO_E_INVALID_ARGUMENT, "fetch_trust_region_reports: nothing has been enqueued");
+  if (!s->tr_ran) return fail(PHOVO_E_UNSUPPORTED, "fetch_trust_region_reports: the last enqueue ran under another objective");
+  if (n_pairs != s->last_pairs) return fail(PHOVO_E_INVALID_ARGUMENT, "fetch_trust_region_reports: n_pairs differs from that enqueue's");
+  if (n_pairs == 0) return PHOVO_OK;
+  if (!reports) return fail(PHOVO_E_INVALID_ARGUMENT, "fetch_trust_region_reports: null");
+  PHOVO_HIP_CHECK(hipSetDevice(e->device));
+  PHOVO_HIP_CHECK(hipStreamSynchronize(s->stream));
+  PHOVO_HIP_CHECK(hipMemcpy(reports, s->d_tr_reports, sizeof(phovo_trust_region_report) * (size_t)n_pairs, hipMemcpyDeviceToHost));
   return PHOVO_OK;
 }
 
@@ -1503,7 +1602,8 @@ int phovo_engine_evaluate_pairs(phovo_engine *e, int n_pairs, const int *src, co
 {
   if (!e) return fail(PHOVO_E_INVALID_ARGUMENT, "evaluate_pairs: null engine");
   if (e->objective != PHOVO_OBJECTIVE_PHOTOMETRIC)
-    return fail(PHOVO_E_UNSUPPORTED, "evaluate_pairs: the bi-objective has no pair system here (photometric objective only)");
+    return fail(PHOVO_E_UNSUPPORTED, "evaluate_pairs: the bi-objective and the trust-region objective have no pair system "
+                                     "here (photometric objective only)");
   if (e->ext.sampling != PHOVO_SAMPLING_NEAREST_SCATTER)
     return fail(PHOVO_E_UNSUPPORTED, "evaluate_pairs: bilinear sampling has no pair system here (nearest / scatter only)");
   if (n_pairs < 0) return fail(PHOVO_E_INVALID_ARGUMENT, "evaluate_pairs: n_pairs < 0");
@@ -1651,6 +1751,8 @@ struct phovo_odometry {
   double init_state[6] = {0, 0, 0, 0, 0, 0};
   double state[6] = {0, 0, 0, 0, 0, 0};          // m_StateVector.setZero()  :432
   phovo_pair_report report{};
+  phovo_trust_region_report tr_report{};         // trust-region objective: the solver record of the last Optimize()
+  bool have_tr_report = false;
 };
 
 namespace {
@@ -1725,6 +1827,18 @@ int phovo_odometry_set_objective(phovo_odometry *o, int objective)
   return st;
 }
 
+int phovo_odometry_set_trust_region_options(phovo_odometry *o, const phovo_trust_region_options *opt)
+{
+  if (!o) return fail(PHOVO_E_INVALID_ARGUMENT, "set_trust_region_options: null");
+  return phovo_engine_set_trust_region_options(o->engine, opt);
+}
+
+int phovo_odometry_get_trust_region_options(const phovo_odometry *o, phovo_trust_region_options *opt)
+{
+  if (!o) return fail(PHOVO_E_INVALID_ARGUMENT, "get_trust_region_options: null");
+  return phovo_engine_get_trust_region_options(o->engine, opt);
+}
+
 int phovo_odometry_set_latency_forms(phovo_odometry *o, int on)
 {
   if (!o) return fail(PHOVO_E_INVALID_ARGUMENT, "set_latency_forms: null");
@@ -1735,6 +1849,14 @@ int phovo_odometry_read_configuration_file(phovo_odometry *o, const char *path)
 {
   if (!o) return fail(PHOVO_E_INVALID_ARGUMENT, "ReadConfigurationFile: null");
   phovo_config c;
+  if (o->engine->objective == PHOVO_OBJECTIVE_TRUST_REGION) {    // CPhotoconsistencyOdometryCeres::ReadConfigurationFile
+    phovo_trust_region_options opt;
+    int st = read_trust_region_file(path, &c, &opt);
+    if (st != PHOVO_OK) return st;
+    st = phovo_engine_set_trust_region_options(o->engine, &opt);
+    if (st != PHOVO_OK) return st;
+    return phovo_odometry_set_config(o, &c);
+  }
   int st = read_config_file(path, &c);
   if (st != PHOVO_OK) return st;
   phovo_extensions x;                        // optional keys; a reference yml has none -> everything stays off
@@ -1891,8 +2013,13 @@ int phovo_odometry_optimize(phovo_odometry *o)
   }
   const int src = 0, tgt = 1;
   // Like the reference, Optimize() starts from the CURRENT state vector (:539 updates m_StateVector in place).
-  const int st = phovo_engine_align_pairs(o->engine, 1, &src, &tgt, o->state, o->state, &o->report);
+  int st = phovo_engine_align_pairs(o->engine, 1, &src, &tgt, o->state, o->state, &o->report);
   if (st != PHOVO_OK) return st;
+  o->have_tr_report = o->engine->objective == PHOVO_OBJECTIVE_TRUST_REGION;
+  if (o->have_tr_report) {
+    st = phovo_engine_fetch_trust_region_reports(o->engine, 1, &o->tr_report);
+    if (st != PHOVO_OK) return st;
+  }
   o->optimized = true;
   return PHOVO_OK;
 }
@@ -1915,6 +2042,15 @@ int phovo_odometry_get_report(const phovo_odometry *o, phovo_pair_report *report
   if (!o || !report) return fail(PHOVO_E_INVALID_ARGUMENT, "get_report: null");
   if (!o->optimized) return fail(PHOVO_E_NOT_READY, "get_report: Optimize has not run");
   *report = o->report;
+  return PHOVO_OK;
+}
+
+int phovo_odometry_get_trust_region_report(const phovo_odometry *o, phovo_trust_region_report *report)
+{
+  if (!o || !report) return fail(PHOVO_E_INVALID_ARGUMENT, "get_trust_region_report: null");
+  if (!o->optimized) return fail(PHOVO_E_NOT_READY, "get_trust_region_report: Optimize has not run");
+  if (!o->have_tr_report) return fail(PHOVO_E_UNSUPPORTED, "get_trust_region_report: the last Optimize ran under another objective");
+  *report = o->tr_report;
   return PHOVO_OK;
 }
 

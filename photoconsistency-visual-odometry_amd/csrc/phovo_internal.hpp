@@ -140,6 +140,22 @@ bool gn_plan_level_biobjective(int n, GNLaunchPlan *plan);
 hipError_t gn_prepare_biobjective_kernels();
 hipError_t gn_launch_level_biobjective(const GNBiObjectiveArgs &args, const GNLaunchPlan &plan, int cu_count,
                                        hipStream_t stream);
+// Trust-region (Levenberg-Marquardt) form (gn_trust_region_kernel.hip, PHOVO_OBJECTIVE_TRUST_REGION): fp64 planes, the
+// photometric objective's frames; bilinear samples of the target, the owner-map row rule, the LM loop inside the workgroup.
+struct GNTrustRegionArgs {
+  GNLevelArgs lv;                    // (lambda, min_grad_norm and huber_delta unused; max_iter = max_num_iterations[level])
+  int max_iterations;
+  double function_tolerance, gradient_tolerance, parameter_tolerance;
+  double initial_radius, max_radius, min_radius, min_relative_decrease;
+  phovo_trust_region_report *tr_reports;   // [pairs], zeroed before the first level
+};
+// Geometry for a level of n pixels: owner map in LDS where it fits (256 threads, two per CU; else 512 threads, one per
+// CU), else in HBM (lv.g_owner: [workgroups][n], the grid being min(pairs, CUs x wgs_per_cu)).  False: the level is too
+// large (more than 2 097 151 pixels).
+bool gn_plan_level_trust_region(int n, GNLaunchPlan *plan);
+hipError_t gn_prepare_trust_region_kernels();
+hipError_t gn_launch_level_trust_region(const GNTrustRegionArgs &args, const GNLaunchPlan &plan, int cu_count,
+                                        hipStream_t stream);
 // Sliding-window form for levels whose owner map exceeds LDS (gn_slide_kernel.hip): owner ring in LDS; pairs whose
 // motion leaves the window are appended to args.handover_out for a follow-up gn_launch_level that takes that list.
 hipError_t gn_prepare_slide_kernels();
@@ -197,5 +213,6 @@ int fail(int status, const std::string &msg);
 // OpenCV-FileStorage-dialect reader (yml_config.cpp)
 int read_config_file(const char *path, phovo_config *cfg);
 int read_extensions_file(const char *path, phovo_extensions *ext);
+int read_trust_region_file(const char *path, phovo_config *cfg, phovo_trust_region_options *opt);
 
 }  // namespace phovo_hip

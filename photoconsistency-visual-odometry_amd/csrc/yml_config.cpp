@@ -73,15 +73,12 @@ bool parse_values(const std::string &value, std::vector<double> *out)
 // cv::FileNode -> int conversion rounds reals (cvRound).
 int to_int(double v) { return (int)std::lrint(v); }
 
-}  // namespace
-
-int read_config_file(const char *path, phovo_config *cfg)
+// The `key: value` lines of a file, flow sequences joined.  PHOVO_OK or the failure.
+int read_key_values(const char *path, std::map<std::string, std::string> &kv)
 {
-  if (!path || !cfg) return fail(PHOVO_E_INVALID_ARGUMENT, "read_config_file: null argument");
   std::ifstream in(path);
   if (!in.is_open()) return fail(PHOVO_E_IO, std::string("cannot open configuration file ") + path);
 
-  std::map<std::string, std::string> kv;
   std::string line, pending_key, pending_val;
   bool open_seq = false;
   while (std::getline(in, line)) {
@@ -108,6 +105,17 @@ int read_config_file(const char *path, phovo_config *cfg)
     kv[key] = val;
   }
   if (open_seq) return fail(PHOVO_E_CONFIG, "unterminated sequence for key '" + pending_key + "'");
+  return PHOVO_OK;
+}
+
+}  // namespace
+
+int read_config_file(const char *path, phovo_config *cfg)
+{
+  if (!path || !cfg) return fail(PHOVO_E_INVALID_ARGUMENT, "read_config_file: null argument");
+  std::map<std::string, std::string> kv;
+  const int rst = read_key_values(path, kv);
+  if (rst != PHOVO_OK) return rst;
 
   auto get = [&](const char *key, std::vector<double> *out) -> bool {
     auto it = kv.find(key);
@@ -193,6 +201,89 @@ int read_extensions_file(const char *path, phovo_extensions *ext)
     }
   }
   *ext = e;
+  return PHOVO_OK;
+}
+
+}  // namespace phovo_hip
+
+extern "C" int phovo_trust_region_options_default(phovo_trust_region_options *opt)
+{
+  if (!opt) return phovo_hip::fail(PHOVO_E_INVALID_ARGUMENT, "trust_region_options_default: null");
+  for (int l = 0; l < PHOVO_MAX_LEVELS; l++) {          // ceres::Solver::Options (1.14)
+    opt->function_tolerance[l] = 1e-6;
+    opt->gradient_tolerance[l] = 1e-10;
+    opt->parameter_tolerance[l] = 1e-8;
+    opt->initial_trust_region_radius[l] = 1e4;
+    opt->max_trust_region_radius[l] = 1e16;
+    opt->min_trust_region_radius[l] = 1e-32;
+    opt->min_relative_decrease[l] = 1e-3;
+  }
+  return PHOVO_OK;
+}
+
+namespace phovo_hip {
+
+// The trust-region objective's keys (CPhotoconsistencyOdometryCeres.h:526-576).  Same line format as the analytic files.
+int read_trust_region_file(const char *path, phovo_config *cfg, phovo_trust_region_options *opt)
+{
+  if (!path) return fail(PHOVO_E_INVALID_ARGUMENT, "read_trust_region_file: null path");
+  std::map<std::string, std::string> kv;
+  const int rst = read_key_values(path, kv);
+  if (rst != PHOVO_OK) return rst;
+  auto get = [&](const char *key, std::vector<double> *out) -> bool {
+    auto it = kv.find(key);
+    if (it == kv.end()) { set_last_error(std::string("configuration key missing: '") + key + "'"); return false; }
+    if (!parse_values(it->second, out)) {
+      set_last_error(std::string("configuration key malformed: '") + key + "'");
+      return false;
+    }
+    return true;
+  };
+  phovo_config c;
+  phovo_config_default(&c);
+  phovo_trust_region_options o;
+  phovo_trust_region_options_default(&o);
+  std::vector<double> v;
+  if (!get("numOptimizationLevels", &v) || v.size() != 1) return PHOVO_E_CONFIG;
+  c.num_levels = to_int(v[0]);
+  if (c.num_levels < 1 || c.num_levels > PHOVO_MAX_LEVELS)
+    return fail(PHOVO_E_CONFIG, "numOptimizationLevels out of range [1, 16]");
+  struct IntKey { const char *key; int *dst; };
+  struct DblKey { const char *key; double *dst; };
+  const IntKey ints[] = {
+      {"blurFilterSize (at each level)", c.blur_filter_size},
+      {"max_num_iterations (at each level)", c.max_num_iterations},
+  };
+  const DblKey dbls[] = {
+      {"imageGradientsScalingFactor (at each level)", c.image_gradients_scaling_factor},
+      {"function_tolerance (at each level)", o.function_tolerance},
+      {"gradient_tolerance (at each level)", o.gradient_tolerance},
+      {"parameter_tolerance (at each level)", o.parameter_tolerance},
+      {"initial_trust_region_radius (at each level)", o.initial_trust_region_radius},
+      {"max_trust_region_radius (at each level)", o.max_trust_region_radius},
+      {"min_trust_region_radius (at each level)", o.min_trust_region_radius},
+      {"min_relative_decrease (at each level)", o.min_relative_decrease},
+  };
+  for (const IntKey &k : ints) {
+    if (!get(k.key, &v)) return PHOVO_E_CONFIG;
+    if ((int)v.size() < c.num_levels)
+      return fail(PHOVO_E_CONFIG, std::string("'") + k.key + "' has fewer entries than numOptimizationLevels");
+    for (int i = 0; i < PHOVO_MAX_LEVELS && i < (int)v.size(); i++) k.dst[i] = to_int(v[i]);
+  }
+  for (const DblKey &k : dbls) {
+    if (!get(k.key, &v)) return PHOVO_E_CONFIG;
+    // The reference reads min_trust_region_radius[numOptimizationLevels - 1] past the end of a list one entry short (4 of
+    // its 8 files): that level -- the coarsest, optimised first -- takes Ceres's default here (phovo_trust_region_options_default).
+    const bool short_ok = k.dst == o.min_trust_region_radius && (int)v.size() == c.num_levels - 1;
+    if ((int)v.size() < c.num_levels && !short_ok)
+      return fail(PHOVO_E_CONFIG, std::string("'") + k.key + "' has fewer entries than numOptimizationLevels");
+    for (int i = 0; i < PHOVO_MAX_LEVELS && i < (int)v.size(); i++) k.dst[i] = v[i];
+  }
+  for (const char *key : {"num_threads", "num_linear_solver_threads", "minimizer_progress_to_stdout", "visualizeIterations"})
+    if (!get(key, &v) || v.size() != 1) return PHOVO_E_CONFIG;                   // read and ignored
+  c.visualize_iterations = 0;
+  if (cfg) *cfg = c;
+  if (opt) *opt = o;
   return PHOVO_OK;
 }
 

@@ -7,6 +7,8 @@ import ctypes as C
 import os
 import subprocess
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # The product library, always -- unless a tools/ entry point has opted in to a diagnostic build (tools/_variant.py sets
 # PHOVO_TOOLS_LIBRARY_OPT_IN=tools before the package is imported and names the build in PHOVO_HIP_LIBRARY: csrc/Makefile
@@ -79,8 +81,31 @@ class PairSystem(C.Structure):
 
 
 FUSION_AUTO, FUSION_OFF, FUSION_SPLIT = 0, -1, -2
-OBJECTIVE_PHOTOMETRIC, OBJECTIVE_BIOBJECTIVE = 0, 1
-LAUNCH_KINDS = ("persistent", "fused", "slide", "slide_fallback", "wide", "bilinear", "biobjective")
+OBJECTIVE_PHOTOMETRIC, OBJECTIVE_BIOBJECTIVE, OBJECTIVE_TRUST_REGION = 0, 1, 2
+LAUNCH_KINDS = ("persistent", "fused", "slide", "slide_fallback", "wide", "bilinear", "biobjective", "trust_region")
+
+# phovo_trust_region_level.termination
+(TR_SKIPPED, TR_MAX_ITERATIONS, TR_GRADIENT, TR_FUNCTION, TR_PARAMETER, TR_MIN_RADIUS, TR_INVALID_STEP,
+ TR_EVALUATION_FAILED) = range(8)
+TR_TERMINATIONS = ("skipped", "max_iterations", "gradient", "function", "parameter", "min_radius", "invalid_step",
+                   "evaluation_failed")
+TR_OPTION_FIELDS = ("function_tolerance", "gradient_tolerance", "parameter_tolerance", "initial_trust_region_radius",
+                    "max_trust_region_radius", "min_trust_region_radius", "min_relative_decrease")
+
+
+class TrustRegionOptions(C.Structure):
+    """phovo_trust_region_options: the trust-region objective's per-level solver options."""
+    _fields_ = [(name, C.c_double * MAX_LEVELS) for name in TR_OPTION_FIELDS]
+
+
+class TrustRegionLevel(C.Structure):
+    _fields_ = [("steps", C.c_int32), ("accepted", C.c_int32), ("termination", C.c_int32), ("rows", C.c_int32),
+                ("initial_cost", C.c_double), ("final_cost", C.c_double), ("final_radius", C.c_double),
+                ("jacobi_scaling", C.c_double * 6)]
+
+
+class TrustRegionReport(C.Structure):
+    _fields_ = [("level", TrustRegionLevel * MAX_LEVELS)]
 
 
 class LaunchRecord(C.Structure):
@@ -145,6 +170,14 @@ SYMBOLS = {
     "phovo_engine_level_uses_wide": (C.c_int, [_vp, C.c_int, C.c_int]),
     "phovo_engine_set_objective": (C.c_int, [_vp, C.c_int]),
     "phovo_engine_get_objective": (C.c_int, [_vp, _vp]),
+    "phovo_trust_region_read_file": (C.c_int, [C.c_char_p, C.POINTER(Config), C.POINTER(TrustRegionOptions)]),
+    "phovo_trust_region_options_default": (C.c_int, [C.POINTER(TrustRegionOptions)]),
+    "phovo_engine_set_trust_region_options": (C.c_int, [_vp, C.POINTER(TrustRegionOptions)]),
+    "phovo_engine_get_trust_region_options": (C.c_int, [_vp, C.POINTER(TrustRegionOptions)]),
+    "phovo_engine_fetch_trust_region_reports": (C.c_int, [_vp, C.c_int, _vp]),
+    "phovo_odometry_set_trust_region_options": (C.c_int, [_vp, C.POINTER(TrustRegionOptions)]),
+    "phovo_odometry_get_trust_region_options": (C.c_int, [_vp, C.POINTER(TrustRegionOptions)]),
+    "phovo_odometry_get_trust_region_report": (C.c_int, [_vp, C.POINTER(TrustRegionReport)]),
     "phovo_host_register": (C.c_int, [_vp, C.c_size_t]),
     "phovo_host_unregister": (C.c_int, [_vp]),
     "phovo_engine_reserve_frames": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int]),
@@ -283,3 +316,30 @@ def format_pair_system(timestamp, system):
     buf = C.create_string_buffer(1024)
     check(lib().phovo_pair_system_format(float(timestamp), C.byref(system), buf, len(buf)), "phovo_pair_system_format")
     return buf.value.decode()
+
+
+def trust_region_options_default():
+    opt = TrustRegionOptions()
+    check(lib().phovo_trust_region_options_default(C.byref(opt)), "phovo_trust_region_options_default")
+    return opt
+
+
+def make_trust_region_options(**per_level):
+    """Ceres's defaults, with any of TR_OPTION_FIELDS given as a per-level list (or one value for every level)."""
+    opt = trust_region_options_default()
+    for name, vals in per_level.items():
+        if name not in TR_OPTION_FIELDS:
+            raise KeyError(name)
+        arr = getattr(opt, name)
+        vals = [vals] * MAX_LEVELS if np.isscalar(vals) else list(vals)
+        for i, v in enumerate(vals[:MAX_LEVELS]):
+            arr[i] = float(v)
+    return opt
+
+
+def read_trust_region_file(path):
+    """phovo_trust_region_read_file: (Config, TrustRegionOptions) from a Ceres-method yml."""
+    cfg, opt = Config(), TrustRegionOptions()
+    check(lib().phovo_trust_region_read_file(str(path).encode(), C.byref(cfg), C.byref(opt)),
+          "phovo_trust_region_read_file")
+    return cfg, opt

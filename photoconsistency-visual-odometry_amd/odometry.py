@@ -170,6 +170,43 @@ class CPhotoconsistencyOdometryBiObjective(CPhotoconsistencyOdometryAnalytic):
         super().SetTargetFrame(intensityImage, depthImage)
 
 
+class CPhotoconsistencyOdometryCeres(CPhotoconsistencyOdometryAnalytic):
+    """One frame pair at a time; 1:1 with the reference's phovo::Ceres::CPhotoconsistencyOdometryCeres (bilinear samples,
+    exact warp Jacobian, Levenberg-Marquardt trust region per level; hand-derived derivatives in HIP, no Ceres).
+    ReadConfigurationFile reads the Ceres keys.  Optimize() does not print; GetSolverReport() returns what it did."""
+
+    def __init__(self, device=0):
+        super().__init__(device)
+        check(self._lib.phovo_odometry_set_objective(self._h, native.OBJECTIVE_TRUST_REGION), "SetObjective")
+
+    def SetTrustRegionOptions(self, opt):
+        check(self._lib.phovo_odometry_set_trust_region_options(self._h, C.byref(opt)), "SetTrustRegionOptions")
+
+    def GetTrustRegionOptions(self):
+        opt = native.TrustRegionOptions()
+        check(self._lib.phovo_odometry_get_trust_region_options(self._h, C.byref(opt)), "GetTrustRegionOptions")
+        return opt
+
+    def GetSolverReport(self):
+        """native.TrustRegionReport of the last Optimize(): per level steps, accepted, termination, rows, costs, radius."""
+        rep = native.TrustRegionReport()
+        check(self._lib.phovo_odometry_get_trust_region_report(self._h, C.byref(rep)), "GetSolverReport")
+        return rep
+
+
+# phovo_trust_region_report as a numpy record: one row of per-level fields per pair
+TRUST_REGION_REPORT_DTYPE = np.dtype([("steps", "<i4", (native.MAX_LEVELS,)), ("accepted", "<i4", (native.MAX_LEVELS,)),
+                                      ("termination", "<i4", (native.MAX_LEVELS,)), ("rows", "<i4", (native.MAX_LEVELS,)),
+                                      ("initial_cost", "<f8", (native.MAX_LEVELS,)),
+                                      ("final_cost", "<f8", (native.MAX_LEVELS,)),
+                                      ("final_radius", "<f8", (native.MAX_LEVELS,)),
+                                      ("jacobi_scaling", "<f8", (native.MAX_LEVELS, 6))])
+_TR_LEVEL_DTYPE = np.dtype([("steps", "<i4"), ("accepted", "<i4"), ("termination", "<i4"), ("rows", "<i4"),
+                            ("initial_cost", "<f8"), ("final_cost", "<f8"), ("final_radius", "<f8"),
+                            ("jacobi_scaling", "<f8", (6,))])
+assert _TR_LEVEL_DTYPE.itemsize * native.MAX_LEVELS == C.sizeof(native.TrustRegionReport)
+
+
 # phovo_pair_system as a numpy record (352 bytes, the layout of native.PairSystem): evaluate_pairs fills an array of
 # these in place and returns column views, with no per-record Python work
 PAIR_SYSTEM_DTYPE = np.dtype([("information", "<f8", (36,)), ("gradient", "<f8", (6,)), ("cost", "<f8"),
@@ -318,6 +355,35 @@ class AlignmentEngine:
         v = C.c_int()
         check(self._lib.phovo_engine_get_objective(self._h, C.byref(v)), "phovo_engine_get_objective")
         return v.value
+
+    def set_trust_region_options(self, opt):
+        """native.TrustRegionOptions (native.make_trust_region_options / read_trust_region_file)."""
+        check(self._lib.phovo_engine_set_trust_region_options(self._h, C.byref(opt)),
+              "phovo_engine_set_trust_region_options")
+
+    def get_trust_region_options(self):
+        opt = native.TrustRegionOptions()
+        check(self._lib.phovo_engine_get_trust_region_options(self._h, C.byref(opt)),
+              "phovo_engine_get_trust_region_options")
+        return opt
+
+    def read_trust_region_file(self, path):
+        """A Ceres-method yml: its config and solver options."""
+        cfg, opt = native.read_trust_region_file(path)
+        self.set_trust_region_options(opt)
+        self.set_config(cfg)
+
+    def trust_region_reports(self, n):
+        """The solver records of the last enqueue's n pairs (trust-region objective) as one structured numpy array of
+        TRUST_REGION_REPORT_DTYPE: out["steps"][p, L], out["termination"][p, L] (native.TR_*), ..."""
+        raw = np.zeros(max(n, 1) * native.MAX_LEVELS, dtype=_TR_LEVEL_DTYPE)
+        check(self._lib.phovo_engine_fetch_trust_region_reports(self._h, int(n), raw.ctypes.data),
+              "phovo_engine_fetch_trust_region_reports")
+        raw = raw[:n * native.MAX_LEVELS].reshape(n, native.MAX_LEVELS)
+        out = np.zeros(n, dtype=TRUST_REGION_REPORT_DTYPE)
+        for name in _TR_LEVEL_DTYPE.names:
+            out[name] = raw[name]
+        return out
 
     def get_level_depth_gradients(self, frame, level):
         """Bi-objective: the target's depth-gradient planes (grad_x, grad_y) of one level."""

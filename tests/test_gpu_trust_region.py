@@ -1,0 +1,252 @@
+"""GPU tests of the trust-region aligner (PHOVO_OBJECTIVE_TRUST_REGION, gn_trust_region_kernel.hip) against the CPU
+checker tests/trust_region_ref.py: poses within 1e-9 with equal per-level steps, accepted steps and terminations and
+costs within 1e-9 relative, on the shipped Ceres fixtures and in fixed mode; every geometry; one arithmetic per pair; no
+change to the photometric objective; the refusals.  Every comparison first asserts that the checker's decisions on its
+seeds are not knife-edge (margins above 1e-6 relative)."""
+import os
+
+import numpy as np
+import pytest
+
+import trust_region_ref as ref
+
+import phovo_amd  # noqa: F401
+from phovo_amd import native, odometry, synthetic
+
+pytestmark = pytest.mark.gpu
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+CERES = os.path.join(HERE, "golden", "ceres")
+POSE_TOL = 1e-9
+COST_TOL = 1e-9
+MARGIN = 1e-6
+
+
+def _fixture(name):
+    return native.read_trust_region_file(os.path.join(CERES, name))
+
+
+def _fixed(opt, nl):
+    """Fixed mode: every tolerance and the minimum radius 0."""
+    o = native.TrustRegionOptions()
+    for f in native.TR_OPTION_FIELDS:
+        getattr(o, f)[:] = getattr(opt, f)[:]
+    for L in range(nl):
+        o.function_tolerance[L] = o.gradient_tolerance[L] = o.parameter_tolerance[L] = o.min_trust_region_radius[L] = 0.0
+    return o
+
+
+@pytest.fixture(scope="module")
+def pairs():
+    return [synthetic.make_pair(s, 640, 480, holes=0.05 if s % 2 else 0.0) for s in range(3)]
+
+
+def _engine(cfg, opt, K):
+    e = odometry.AlignmentEngine(0)
+    e.set_config(cfg)
+    e.set_intrinsic_matrix(K)
+    e.set_objective(native.OBJECTIVE_TRUST_REGION)
+    e.set_trust_region_options(opt)
+    e.set_batch_invariant(True)
+    return e
+
+
+def _upload(e, ps):
+    h, w = ps[0]["gray0"].shape
+    e.reserve_frames(2 * len(ps), w, h)
+    for k, p in enumerate(ps):
+        e.upload_frame(2 * k, p["gray0"], p["depth0"], native.ROLE_SOURCE)
+        e.upload_frame(2 * k + 1, p["gray1"], None, native.ROLE_TARGET)
+
+
+def _check(cfg, opt, ps, init=None):
+    """Align ps on the device and through the checker; compare.  Returns the device reports."""
+    n = len(ps)
+    NOISE_LEVELS.clear()
+    with _engine(cfg, opt, ps[0]["K"]) as e:
+        _upload(e, ps)
+        states, reps = e.align_pairs(np.arange(n) * 2, np.arange(n) * 2 + 1, init, want_reports=True)
+        tr = e.trust_region_reports(n)
+        kinds = {l["kind"] for l in e.last_launches()}
+        assert kinds == {"trust_region"}, kinds
+    ocfg = ref.oracle_config(cfg)
+    for k, p in enumerate(ps):
+        x0 = None if init is None else init[k]
+        xs, recs = ref.align(ocfg, p["K"], p["gray0"], p["depth0"], p["gray1"], opt, x0)
+        for L, rec in recs.items():
+            assert min(rec["margins"], default=1.0) > MARGIN, (k, L, rec["decisions"])
+        assert np.abs(states[k] - xs).max() <= POSE_TOL, (k, states[k], xs)
+        for L in range(cfg.num_levels):
+            if L not in recs:
+                assert tr["termination"][k, L] == native.TR_SKIPPED and tr["steps"][k, L] == 0
+                continue
+            rec = recs[L]
+            for f in ("initial_cost", "final_cost"):
+                assert abs(tr[f][k, L] - rec[f]) <= COST_TOL * abs(rec[f]), (k, L, f)
+            assert np.allclose(tr["jacobi_scaling"][k, L], rec["S"], rtol=1e-12, atol=0), (k, L)
+            if rec["noise_from"] is not None:
+                # The level reached its noise floor at step noise_from (trust_region_ref.NOISE): every decision before
+                # it is conditioned and taken alike; after it accept / reject is decided by rounding, so the counts
+                # can only be bounded and the radius (halved or grown by those decisions) is not compared.  The pose
+                # (above) and the final cost still agree.
+                NOISE_LEVELS.append((k, L, rec["noise_from"], rec["steps"]))
+                assert tr["steps"][k, L] >= rec["noise_from"], (k, L)
+                assert tr["accepted"][k, L] >= rec["accepted_before_noise"], (k, L)
+                assert tr["termination"][k, L] in (rec["termination"], native.TR_FUNCTION, native.TR_MAX_ITERATIONS), (k, L)
+                continue
+            assert tr["steps"][k, L] == rec["steps"], (k, L)
+            assert tr["accepted"][k, L] == rec["accepted"], (k, L)
+            assert tr["termination"][k, L] == rec["termination"], (k, L)
+            assert tr["rows"][k, L] == rec["rows"], (k, L)
+            # Every accepted step scales the radius by a function of rho = dcost / mcc, whose rounding is about
+            # eps * cost / |dcost|.  Where every accepted step changed the cost by more than 1e-4 of it, the radius is
+            # pinned to 1e-9; once a level runs at its noise floor dcost is a difference of nearly equal costs and
+            # rounding-level differences of the two implementations move the radius by up to ~1e-5 without changing a
+            # decision, so those levels are held to 1e-3.
+            rtol = 1e-9 if rec["min_rel_dc"] > 1e-4 else 1e-3
+            assert abs(tr["final_radius"][k, L] - rec["final_radius"]) <= rtol * rec["final_radius"], (k, L, rtol)
+            assert reps[k].iterations[L] == rec["steps"] and reps[k].valid_pixels[L] == rec["rows"]
+        last = min(recs)
+        assert abs(reps[k].gradient_norm - np.linalg.norm(recs[last]["g"])) <= 1e-9 * np.linalg.norm(recs[last]["g"])
+    return tr
+
+
+NOISE_LEVELS = []         # (pair, level, noise_from, steps) of the last _check: levels that reached their noise floor
+
+
+@pytest.mark.parametrize("fixed", [False, True])
+def test_four_level_fixture(pairs, fixed):
+    cfg, opt = _fixture("config_4_level_optimization_ceres.yml")
+    if fixed:
+        opt = _fixed(opt, cfg.num_levels)
+    tr = _check(cfg, opt, pairs)
+    if fixed:
+        # Levels 0-2 run their full 2 / 4 / 5 steps, conditioned throughout; level 3 (80x60, 50 steps) converges and may
+        # reach its noise floor, after which its accept / reject decisions are rounding (see _check).
+        assert np.array_equal(tr["steps"][:, :3], np.tile([2, 4, 5], (len(pairs), 1))), tr["steps"][:, :4]
+        assert {L for _, L, _, _ in NOISE_LEVELS} <= {3}, NOISE_LEVELS
+    else:
+        assert NOISE_LEVELS == [], NOISE_LEVELS           # the shipped tolerances stop every level before its floor
+
+
+def test_only_level_0_hbm_geometry(pairs):
+    cfg, opt = _fixture("config_only_level_0_ceres.yml")
+    _check(cfg, opt, pairs[:1])
+
+
+def test_three_level_blur_and_tolerances(pairs):
+    cfg, opt = _fixture("config_3_level_optimization_ceres.yml")
+    _check(cfg, opt, pairs[1:2], init=np.array([[0.01, -0.01, 0.02, 0.005, -0.004, 0.003]]))
+
+
+def test_200x150_level():
+    ps = [synthetic.make_pair(7, 200, 150)]
+    cfg, opt = _fixture("config_only_level_0_ceres.yml")
+    _check(cfg, opt, ps)
+
+
+@pytest.mark.parametrize("case, expect", [
+    (dict(max_num_iterations=3, function_tolerance=0.0, gradient_tolerance=0.0, parameter_tolerance=0.0),
+     native.TR_MAX_ITERATIONS),
+    (dict(gradient_tolerance=1e9), native.TR_GRADIENT),                  # met at the first point: no step
+    (dict(function_tolerance=0.99, parameter_tolerance=0.0), native.TR_FUNCTION),
+    (dict(parameter_tolerance=10.0), native.TR_PARAMETER),                # met by the first step: not evaluated
+])
+def test_device_reaches_each_termination(case, expect):
+    """Each of the four convergence / iteration terminations on the device, against the checker, at 200x150."""
+    ps = [synthetic.make_pair(7, 200, 150)]
+    cfg, opt = _fixture("config_only_level_0_ceres.yml")
+    case = dict(case)
+    cfg.max_num_iterations[0] = case.pop("max_num_iterations", 10)
+    for f, v in case.items():
+        getattr(opt, f)[0] = v
+    tr = _check(cfg, opt, ps)
+    assert tr["termination"][0, 0] == expect, tr["termination"][0, 0]
+    if expect in (native.TR_GRADIENT, native.TR_PARAMETER):
+        assert tr["steps"][0, 0] == (0 if expect == native.TR_GRADIENT else 1)
+
+
+def test_pair_bits_alone_in_a_batch_and_through_the_class(pairs):
+    cfg, opt = _fixture("config_4_level_optimization_ceres.yml")
+    p = pairs[1]
+    with _engine(cfg, opt, p["K"]) as e:
+        _upload(e, [p])
+        alone = e.align_pairs([0], [1])[0]
+        tr_alone = e.trust_region_reports(1)
+    many = [synthetic.make_pair(10 + s, 640, 480) for s in range(3)]
+    with _engine(cfg, opt, p["K"]) as e:
+        _upload(e, many + [p])
+        k = 37
+        src = np.array([2 * (i % 3) for i in range(64)])
+        tgt = src + 1
+        src[k], tgt[k] = 6, 7
+        states = e.align_pairs(src, tgt)
+        tr = e.trust_region_reports(64)
+        assert np.array_equal(states[k], alone)
+        assert np.array_equal(tr[k:k + 1], tr_alone)
+    with odometry.CPhotoconsistencyOdometryCeres(0) as c:
+        c.ReadConfigurationFile(os.path.join(CERES, "config_4_level_optimization_ceres.yml"))
+        c.SetIntrinsicMatrix(p["K"])
+        c.SetSourceFrame(p["gray0"], p["depth0"])
+        c.SetTargetFrame(p["gray1"], p["depth1"])
+        c.Optimize()
+        assert np.array_equal(c.GetOptimalStateVector(), alone)
+        rep = c.GetSolverReport()
+        assert [rep.level[L].steps for L in range(4)] == list(tr_alone["steps"][0, :4])
+
+
+def test_photometric_unchanged_and_frames_kept(pairs):
+    acfg = native.read_config_file(os.path.join(os.path.dirname(HERE), "config_files",
+                                                "config_4_level_optimization_analytic.yml"))
+    _, opt = _fixture("config_4_level_optimization_ceres.yml")
+    p = pairs[0]
+    with odometry.AlignmentEngine(0) as e:
+        e.set_config(acfg)
+        e.set_intrinsic_matrix(p["K"])
+        e.set_batch_invariant(True)
+        _upload(e, [p])
+        before = e.align_pairs([0], [1])
+        planes = e.get_level_planes(1, 3)
+        e.set_objective(native.OBJECTIVE_TRUST_REGION)
+        e.set_trust_region_options(opt)
+        after_switch = e.get_level_planes(1, 3)                          # the pool survived the switch
+        assert all(np.array_equal(a, b) for a, b in zip(planes, after_switch))
+        tr_state = e.align_pairs([0], [1])                               # on the frames uploaded before the switch
+        assert e.trust_region_reports(1)["steps"][0, 3] > 0
+        e.set_objective(native.OBJECTIVE_PHOTOMETRIC)
+        after = e.align_pairs([0], [1])
+        assert np.array_equal(before, after)
+        with pytest.raises(native.PhovoError) as ei:
+            e.trust_region_reports(1)
+        assert ei.value.status == 7
+    assert np.all(np.isfinite(tr_state))
+    # the same pair through a fresh trust-region engine gives the same bits as after the switch
+    with _engine(acfg, opt, p["K"]) as e:
+        _upload(e, [p])
+        assert np.array_equal(e.align_pairs([0], [1]), tr_state)
+
+
+def test_refusals(pairs):
+    cfg, opt = _fixture("config_4_level_optimization_ceres.yml")
+    p = pairs[0]
+    bad = [native.make_extensions(plane_storage=native.STORAGE_F32),
+           native.make_extensions(plane_storage=native.STORAGE_F16),
+           native.make_extensions(huber_delta=[0.1] * 4),
+           native.make_extensions(sampling=native.SAMPLING_BILINEAR),
+           native.make_extensions(sampling=native.SAMPLING_BILINEAR, jacobian_corrected=1)]
+    for ext in bad:
+        with odometry.AlignmentEngine(0) as e:                 # objective second
+            e.set_extensions(ext)
+            with pytest.raises(native.PhovoError) as ei:
+                e.set_objective(native.OBJECTIVE_TRUST_REGION)
+            assert ei.value.status == 7
+        with odometry.AlignmentEngine(0) as e:                 # extensions second
+            e.set_objective(native.OBJECTIVE_TRUST_REGION)
+            with pytest.raises(native.PhovoError) as ei:
+                e.set_extensions(ext)
+            assert ei.value.status == 7
+    with _engine(cfg, opt, p["K"]) as e:
+        _upload(e, [p])
+        with pytest.raises(native.PhovoError) as ei:
+            e.evaluate_pairs([0], [1], np.zeros((1, 6)), 0)
+        assert ei.value.status == 7

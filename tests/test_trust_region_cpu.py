@@ -1,0 +1,246 @@
+"""CPU checks of the trust-region checker (tests/trust_region_ref.py) and of the Ceres-key reader.
+
+* The vectorised rows (owner map, bilinear samples, hand-derived Jacobian) equal the literal per-pixel loop with dual
+  numbers on seeded tiny images, and the sweep reaches every branch: low-edge extrapolation, high-edge clamp, size-1
+  axes, collisions, the depth gate and out-of-bounds warps.
+* The Levenberg-Marquardt loop reaches every termination reason on stand-in problems, rejects steps, and ends at the
+  exact solution of a linear least-squares problem.
+* phovo_trust_region_read_file parses the reference's eight Ceres files (tests/golden/ceres), applies the short
+  min_trust_region_radius rule and refuses missing keys and analytic files; phovo_config_read_file refuses Ceres files.
+"""
+import os
+
+import numpy as np
+import pytest
+
+import trust_region_ref as ref
+
+import phovo_amd  # noqa: F401
+from phovo_amd import native
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+CERES = os.path.join(HERE, "golden", "ceres")
+ROOT = os.path.dirname(HERE)
+
+
+def _tiny_case(seed):
+    rs = np.random.RandomState(seed)
+    w, h = rs.randint(1, 10), rs.randint(1, 8)
+    i0 = rs.uniform(0, 1, (h, w))
+    d0 = rs.uniform(0.5, 4.0, (h, w))
+    d0[rs.uniform(size=(h, w)) < 0.15] = 0.0                                # holes
+    d0[rs.uniform(size=(h, w)) < 0.05] = 7.0                                # beyond max depth
+    i1, gx, gy = (rs.normal(0, 1, (h, w)) for _ in range(3))
+    f = rs.uniform(1.0, 6.0)
+    K = np.array([[f, 0, (w - 1) / 2.0], [0, f, (h - 1) / 2.0], [0, 0, 1.0]])
+    kind = seed % 4
+    if kind == 0:
+        state = np.zeros(6)
+    elif kind == 1:                                                         # zoom out: collisions
+        state = np.array([0, 0, rs.uniform(0.5, 3.0), 0, 0, 0])
+    elif kind == 2:                                                         # large motion: out of bounds
+        state = rs.uniform(-0.6, 0.6, 6)
+    else:
+        state = rs.normal(0, 0.05, 6)
+    return i0, d0, i1, gx, gy, K, state
+
+
+def test_vectorised_rows_equal_the_literal_loop():
+    seen = dict(low_edge=0, high_clamp=0, size1=0, collisions=0, gated=0, out_of_bounds=0)
+    for seed in range(300):
+        i0, d0, i1, gx, gy, K, state = _tiny_case(seed)
+        h, w = i0.shape
+        r0, J0, rows0 = ref.literal_rows(i0, d0, i1, gx, gy, 0, K, state)
+        ev = ref.evaluate(i0, d0, i1, gx, gy, 0, K, state)
+        assert ev["rows"] == rows0, seed
+        scale_r = max(np.abs(r0).max(initial=0.0), 1e-300)
+        scale_j = max(np.abs(J0).max(initial=0.0), 1e-300)
+        assert np.abs(ev["r"] - r0).max(initial=0.0) <= 1e-12 * scale_r, seed
+        assert np.abs(ev["J"] - J0).max(initial=0.0) <= 1e-12 * scale_j, seed
+        ok, u, v = ev["ok"], ev["u"], ev["v"]
+        d = d0.ravel()
+        gate = (0.3 < d) & (d < 5.0)
+        seen["gated"] += int((~gate).sum())
+        seen["out_of_bounds"] += int((gate & ~ok).sum())
+        seen["collisions"] += int(ok.sum()) - rows0
+        if ok.any():
+            seen["low_edge"] += int(((u[ok] < 0.5) | (v[ok] < 0.5)).sum())
+            seen["high_clamp"] += int(((u[ok] - 0.5 > w - 2) | (v[ok] - 0.5 > h - 2)).sum())
+            if w == 1 or h == 1:
+                seen["size1"] += int(ok.sum())
+    assert all(v > 0 for v in seen.values()), seen
+
+
+def test_rows_match_finite_differences():
+    """The hand-derived Jacobian is the derivative of the sampled residual where the sample is smooth (interior,
+    away from tap boundaries), using the gradient planes of an image that is linear in u and v."""
+    h, w = 12, 16
+    yy, xx = np.mgrid[0:h, 0:w].astype(np.float64)
+    i1 = 0.3 * xx - 0.2 * yy
+    gx, gy = np.full((h, w), 0.3), np.full((h, w), -0.2)
+    i0 = np.zeros((h, w))
+    d0 = np.full((h, w), 2.0)
+    K = np.array([[20.0, 0, 7.3], [0, 20.0, 5.6], [0, 0, 1]])
+    state = np.array([0.01, -0.02, 0.03, 0.02, -0.01, 0.015])
+    ev = ref.evaluate(i0, d0, i1, gx, gy, 0, K, state)
+    for k in range(6):
+        e = np.zeros(6)
+        e[k] = 1e-7
+        rp = ref.evaluate(i0, d0, i1, gx, gy, 0, K, state + e)["r"]
+        rm = ref.evaluate(i0, d0, i1, gx, gy, 0, K, state - e)["r"]
+        both = (rp != 0) & (rm != 0) & (ev["r"] != 0)
+        fd = (rp - rm)[both] / 2e-7
+        assert np.allclose(ev["J"][both, k], fd, rtol=1e-5, atol=1e-6), k
+
+
+def _linear_problem(seed, m=40):
+    rs = np.random.RandomState(seed)
+    A = rs.normal(0, 1, (m, 6))
+    b = rs.normal(0, 1, m)
+    return A, b, (lambda x: ref.system(A @ x - b, A.copy()))
+
+
+DEFAULTS = dict(function_tolerance=1e-6, gradient_tolerance=1e-10, parameter_tolerance=1e-8, initial_radius=1e4,
+                max_radius=1e16, min_radius=1e-32, min_relative_decrease=1e-3)
+
+
+def test_linear_least_squares_ends_at_the_exact_solution():
+    A, b, ev = _linear_problem(1)
+    # (the LM damping diag/radius keeps every step a little short: tight tolerances let the radius grow until it vanishes)
+    x, rec = ref.optimize_level(ev, np.zeros(6), 100, **dict(DEFAULTS, function_tolerance=0.0, parameter_tolerance=0.0,
+                                                             gradient_tolerance=1e-13))
+    exact = np.linalg.lstsq(A, b, rcond=None)[0]
+    assert np.abs(x - exact).max() <= 1e-8 * max(1.0, np.abs(exact).max())      # (cond(A^T A) x eps)
+    assert rec["termination"] in (ref.TR_GRADIENT, ref.TR_FUNCTION, ref.TR_PARAMETER), rec["termination"]
+    assert rec["accepted"] >= 1
+
+
+def _rosenbrock_like(x):
+    """A nonlinear stand-in (extended Rosenbrock residuals) with steps that get rejected from a far start."""
+    r = np.array([10 * (x[1] - x[0] ** 2), 1 - x[0], 10 * (x[3] - x[2] ** 2), 1 - x[2], 10 * (x[5] - x[4] ** 2), 1 - x[4]])
+    J = np.zeros((6, 6))
+    for k in (0, 2, 4):
+        J[k, k], J[k, k + 1] = -20 * x[k], 10
+        J[k + 1, k] = -1
+    return ref.system(r, J)
+
+
+def test_every_termination_reason_and_rejected_steps():
+    reached, rejected = set(), 0
+    x0 = np.array([-1.2, 1.0, -1.2, 1.0, 3.0, -2.0])
+    runs = [
+        (_rosenbrock_like, x0, 3, {}),                                                       # max_iterations
+        (_rosenbrock_like, np.array([5.0, -3, 4, 9, -6, 2]), 200, dict(initial_radius=1e8)),   # rejected steps
+        (_rosenbrock_like, x0, 200, dict(function_tolerance=0, parameter_tolerance=0)),       # gradient
+        (_linear_problem(2)[2], x0, 200, {}),                                                # function
+        (_rosenbrock_like, x0, 200, dict(parameter_tolerance=1e-2, function_tolerance=0)),   # parameter
+        (_rosenbrock_like, x0, 200, dict(min_radius=1e3, initial_radius=1.0)),              # min_radius (initial below)
+        (lambda x: ref.system(np.zeros(6), np.eye(6)), x0, 10, dict(gradient_tolerance=-1.0)),  # invalid step (mcc 0)
+        (lambda x: ref.system(np.full(6, np.nan), np.eye(6)), x0, 10, {}),                   # evaluation failed
+    ]
+    for ev, start, mi, over in runs:
+        opts = dict(DEFAULTS, **over)
+        x, rec = ref.optimize_level(ev, start, mi, **opts)
+        reached.add(rec["termination"])
+        rejected += rec["steps"] - rec["accepted"] - (1 if rec["termination"] in (ref.TR_FUNCTION, ref.TR_PARAMETER,
+                                                                                   ref.TR_INVALID_STEP) else 0)
+    assert reached == {ref.TR_MAX_ITERATIONS, ref.TR_GRADIENT, ref.TR_FUNCTION, ref.TR_PARAMETER, ref.TR_MIN_RADIUS,
+                       ref.TR_INVALID_STEP, ref.TR_EVALUATION_FAILED}, reached
+    assert rejected >= 1
+
+
+def test_rejected_candidate_leaves_x():
+    x0 = np.array([-1.2, 1.0, -1.2, 1.0, 3.0, -2.0])
+    seen = 0
+    for mi in range(1, 30):
+        x_prev, rec_prev = ref.optimize_level(_rosenbrock_like, x0, mi - 1, **DEFAULTS) if mi > 1 else (x0, None)
+        x, rec = ref.optimize_level(_rosenbrock_like, x0, mi, **DEFAULTS)
+        if rec_prev is not None and rec["accepted"] == rec_prev["accepted"]:
+            assert np.array_equal(x, x_prev)
+            seen += 1
+    assert seen >= 1
+
+
+# ---- the reader ----------------------------------------------------------------------------------------------------
+FILES = sorted(os.listdir(CERES))
+
+
+def test_eight_fixtures():
+    assert len(FILES) == 8 and all(f.endswith("_ceres.yml") for f in FILES)
+
+
+@pytest.mark.parametrize("name", FILES)
+def test_reader_parses_every_ceres_file(name):
+    cfg, opt = native.read_trust_region_file(os.path.join(CERES, name))
+    text = open(os.path.join(CERES, name)).read()
+    nl = int(text.split("numOptimizationLevels:")[1].split()[0])
+    assert cfg.num_levels == nl
+    lists = {}
+    for line in text.splitlines():
+        if "(at each level)" in line:
+            key, val = line.split(":", 1)
+            lists[key.replace(" (at each level)", "").strip()] = [float(v) for v in val.strip()[1:-1].split(",")]
+    for L in range(nl):
+        assert cfg.max_num_iterations[L] == int(lists["max_num_iterations"][L])
+        assert cfg.blur_filter_size[L] == int(lists["blurFilterSize"][L])
+        assert cfg.image_gradients_scaling_factor[L] == lists["imageGradientsScalingFactor"][L]
+        for f in native.TR_OPTION_FIELDS:
+            vals = lists[f]
+            expect = vals[L] if L < len(vals) else 1e-32                       # the short-list rule
+            assert getattr(opt, f)[L] == expect, (f, L)
+    assert cfg.visualize_iterations == 0
+
+
+def test_short_min_radius_rule_is_needed_by_four_files():
+    short = []
+    for name in FILES:
+        text = open(os.path.join(CERES, name)).read()
+        nl = int(text.split("numOptimizationLevels:")[1].split()[0])
+        line = [ln for ln in text.splitlines() if ln.startswith("min_trust_region_radius")][0]
+        if len(line.split("[")[1].split(",")) < nl:
+            short.append(name)
+    assert len(short) == 4, short
+
+
+def _write(tmp_path, text):
+    p = tmp_path / "c.yml"
+    p.write_text(text)
+    return str(p)
+
+
+def test_reader_refusals(tmp_path):
+    base = open(os.path.join(CERES, "config_4_level_optimization_ceres.yml")).read()
+    for key in ("function_tolerance", "gradient_tolerance", "parameter_tolerance", "initial_trust_region_radius",
+                "max_trust_region_radius", "min_trust_region_radius", "min_relative_decrease", "max_num_iterations",
+                "num_threads", "num_linear_solver_threads", "minimizer_progress_to_stdout", "visualizeIterations"):
+        text = "\n".join(ln for ln in base.splitlines() if not ln.startswith(key + " ") and not ln.startswith(key + ":"))
+        with pytest.raises(native.PhovoError) as ei:
+            native.read_trust_region_file(_write(tmp_path, text))
+        assert ei.value.status == 2, key
+    # a list short by more than the one allowed entry, or another short list
+    text = base.replace("min_trust_region_radius (at each level): [1e-32,1e-32,1e-32]",
+                        "min_trust_region_radius (at each level): [1e-32,1e-32]")
+    with pytest.raises(native.PhovoError):
+        native.read_trust_region_file(_write(tmp_path, text))
+    text = base.replace("function_tolerance (at each level): [1e-4, 1e-4, 1e-4, 1e-4]",
+                        "function_tolerance (at each level): [1e-4, 1e-4, 1e-4]")
+    with pytest.raises(native.PhovoError):
+        native.read_trust_region_file(_write(tmp_path, text))
+    # an analytic file is refused by the new reader, a Ceres file by the analytic one
+    with pytest.raises(native.PhovoError):
+        native.read_trust_region_file(os.path.join(ROOT, "config_files", "config_4_level_optimization_analytic.yml"))
+    with pytest.raises(native.PhovoError):
+        native.read_config_file(os.path.join(CERES, "config_4_level_optimization_ceres.yml"))
+    # longer lists are truncated
+    text = base.replace("function_tolerance (at each level): [1e-4, 1e-4, 1e-4, 1e-4]",
+                        "function_tolerance (at each level): [1e-4, 1e-4, 1e-4, 1e-4, 7, 8]")
+    cfg, opt = native.read_trust_region_file(_write(tmp_path, text))
+    assert list(opt.function_tolerance[:4]) == [1e-4] * 4
+
+
+def test_options_defaults():
+    opt = native.trust_region_options_default()
+    assert opt.function_tolerance[0] == 1e-6 and opt.gradient_tolerance[3] == 1e-10
+    assert opt.parameter_tolerance[15] == 1e-8 and opt.initial_trust_region_radius[0] == 1e4
+    assert opt.max_trust_region_radius[0] == 1e16 and opt.min_trust_region_radius[0] == 1e-32
+    assert opt.min_relative_decrease[0] == 1e-3
