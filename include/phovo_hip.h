@@ -170,8 +170,10 @@ typedef struct phovo_extensions {
  *                                sliding-window, wide and latency-form settings are accepted and have no effect.
  *                                phovo_pair_report: iterations[L] = LM steps (iteration 0 not counted), valid_pixels[L] =
  *                                owned targets at the final point, gradient_norm = ||J^T r||_2 there (of the last level
- *                                run), PHOVO_PAIR_NONFINITE when an evaluation was not finite, PHOVO_PAIR_RANK_DEFICIENT
- *                                when fewer than 6 rows remain.  The per-level solver record is phovo_trust_region_report. */
+ *                                run), PHOVO_PAIR_NONFINITE when an evaluation was not finite or the state is not (a
+ *                                NaN / inf initial state: no pixel warps, the level ends without a step and the state
+ *                                stays as given), PHOVO_PAIR_RANK_DEFICIENT when fewer than 6 rows remain.  The
+ *                                per-level solver record is phovo_trust_region_report. */
 #define PHOVO_OBJECTIVE_TRUST_REGION 2
 
 /* Solver options of the trust-region objective, per level (CPhotoconsistencyOdometryCeres.h:526-576).  num_levels, blur,

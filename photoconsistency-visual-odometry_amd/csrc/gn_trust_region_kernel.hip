@@ -467,8 +467,13 @@ __global__ __launch_bounds__(T, 2) void gn_level_kernel_trust_region(const GNTru
 #pragma unroll
       for (int j = 0; j < 6; j++) gn2 = fma(s_tr[TR_G + j], s_tr[TR_G + j], gn2);
       A.reports[pair].gradient_norm = term == PHOVO_TR_EVALUATION_FAILED ? __builtin_nan("") : sqrt(gn2);
+      // NONFINITE: an evaluation was not finite, or the state is (a NaN / inf initial state: no pixel warps, the system
+      // is finite and zero, and the level ends without a step)
+      bool x_finite = true;
+#pragma unroll
+      for (int j = 0; j < 6; j++) x_finite = x_finite && finite_f64(s_tr[TR_X + j]);
       uint32_t new_flags = 0;
-      if (term == PHOVO_TR_EVALUATION_FAILED) new_flags |= PHOVO_PAIR_NONFINITE;
+      if (term == PHOVO_TR_EVALUATION_FAILED || !x_finite) new_flags |= PHOVO_PAIR_NONFINITE;
       if (s_tri[TRI_ROWS] < 6) new_flags |= PHOVO_PAIR_RANK_DEFICIENT;
       if (new_flags) atomicOr(&A.reports[pair].flags, new_flags);
     }

@@ -205,7 +205,7 @@ def optimize(cfg, K, src_planes, tgt_planes, init_state=None, min_depth=0.3, max
             state = state - cfg.lambda_optimization_step[level] * step      # :638-639
             it += 1
             valid[level] = st["contributing"]
-            trace.append(dict(level=level, iteration=it, **st))
+            trace.append(dict(level=level, iteration=it, H=H, **st))
             if st["contributing"] < 6:
                 flags |= 4
             finite = bool(np.all(np.isfinite(state)))

@@ -15,6 +15,7 @@ import sys
 import numpy as np
 import pytest
 
+import edge_states
 import phovo_amd  # noqa: F401
 from phovo_amd import native, odometry, se3, synthetic
 from oracle import oracle
@@ -104,20 +105,7 @@ def _stored_planes(eng, mi, w, h):
     return planes
 
 
-def _initial_states():
-    """Per axis a handful of angles from each branch, both signs; pitch and roll at pi - 0.3 (the scene behind the camera)."""
-    out = []
-    for axis in range(3):
-        for a in (0.31, 0.55, 0.783, 0.80, 1.2):
-            for sg in (1.0, -1.0):
-                s = np.array([0.01, -0.02, 0.015, 0.002, -0.001, 0.003])
-                s[3 + axis] = sg * a
-                out.append(s)
-    for axis in (1, 2):
-        s = np.array([0.01, -0.02, 0.015, 0.002, -0.001, 0.003])
-        s[3 + axis] = np.pi - 0.3
-        out.append(s)
-    return out
+_initial_states = edge_states.initial_states
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -174,8 +162,7 @@ def test_initial_states_in_every_branch_through_the_fused_launch():
 # ------------------------------------------------------------------------------------------------------------------------
 # true in-plane motions of 0.5, 0.7, 0.9 rad, converging
 # ------------------------------------------------------------------------------------------------------------------------
-MOTIONS = [[0.01, -0.005, 0.004, yaw, 0.002, -0.003] for yaw in (0.5, 0.7, 0.9)]       # branches 2, 2, 3
-NEAR = np.array([0.004, 0.002, -0.003, 0.01, -0.004, 0.003])
+MOTIONS, NEAR = edge_states.MOTIONS, edge_states.NEAR                              # yaw 0.5, 0.7, 0.9: branches 2, 2, 3
 
 
 @pytest.mark.parametrize("bilinear,huber", [(False, None), (True, None), (True, [0.05])])

@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+import edge_states
 import phovo_amd  # noqa: F401
 from phovo_amd import native, odometry, synthetic
 from oracle import oracle
@@ -182,6 +183,57 @@ def test_nan_in_target_intensity_is_flagged(storage):
         s = eng.evaluate_pairs([0], [1], np.zeros((1, 6)), 0)
     assert s["flags"][0] & native.PAIR_NONFINITE
     assert np.isnan(s["cost"][0])
+
+
+@pytest.mark.parametrize("storage", STORAGES)
+def test_large_states_in_every_branch(storage):
+    """The 32 initial states of edge_states (every branch of the device's sin / cos, the scene behind the camera) and
+    three in-plane rotations of 0.5 to 0.9 rad, on the 640x480, 160x120 and 80x60 levels, against the oracle."""
+    p = synthetic.make_pair(43, 640, 480, holes=0.02, trans=0.01, rot=0.004)
+    states = np.stack(edge_states.initial_states() + [np.array(m) for m in edge_states.MOTIONS])
+    n = len(states)
+    seen = dict(empty=0, full=0)
+    with _engine(p, 4, MAX_ITER4, storage, build_all=True) as eng:
+        planes = _planes(eng, 4, 640, 480, range(4))
+        for level in (0, 2, 3):
+            s = eng.evaluate_pairs([0] * n, [1] * n, states, level)
+            for i in range(n):
+                rows, H, g = _oracle_trace_system(planes, level, p["K"], states[i], None)
+                _, _, cost = _numpy_system(planes, level, p["K"], states[i], None)
+                if rows == 0:
+                    assert s["rows"][i] == 0 and not s["information"][i].any() and not s["gradient"][i].any()
+                    assert s["flags"][i] == native.PAIR_RANK_DEFICIENT
+                    seen["empty"] += 1
+                    continue
+                _check_against(s["information"][i], s["gradient"][i], s["rows"][i], s["cost"][i], H, g, rows, cost)
+                assert s["flags"][i] == (native.PAIR_RANK_DEFICIENT if rows < 6 else 0), (level, i)
+                seen["full"] += rows >= 6
+    assert seen["empty"] > 0 and seen["full"] >= 3 * 24, seen
+
+
+@pytest.mark.parametrize("storage", STORAGES)
+def test_non_finite_state_in_one_pair(storage):
+    """A NaN yaw, +inf pitch or -inf roll in pair 4 of 9: no pixel warps, so that pair's system is the documented empty
+    one -- rows 0, every sum zero, flags exactly RANK_DEFICIENT -- and the other pairs are bit for bit what they are
+    without it."""
+    p = synthetic.make_pair(44, 160, 120, holes=0.02)
+    good = np.array([0.01, -0.02, 0.015, 0.02, -0.01, 0.015])
+    with _engine(p, 1, [1], storage) as eng:
+        states = np.tile(good, (9, 1))
+        clean = eng.evaluate_pairs([0] * 9, [1] * 9, states, 0, want_structs=True)
+        assert np.all(clean["rows"] > 1000) and not clean["flags"].any()
+        clean = _bytes(clean["structs"])
+        for axis, bad in ((0, np.nan), (1, np.inf), (2, -np.inf)):
+            st = states.copy()
+            st[4, 3 + axis] = bad
+            out = eng.evaluate_pairs([0] * 9, [1] * 9, st, 0, want_structs=True)
+            assert out["rows"][4] == 0 and out["cost"][4] == 0.0, (axis, out["rows"][4], out["cost"][4])
+            assert not out["information"][4].any() and not out["gradient"][4].any()
+            assert out["flags"][4] == native.PAIR_RANK_DEFICIENT, out["flags"][4]
+            got = _bytes(out["structs"])
+            for k in range(9):
+                if k != 4:
+                    assert got[k] == clean[k], (axis, k)
 
 
 # ---- 4: bit identity ---------------------------------------------------------------------------------------------

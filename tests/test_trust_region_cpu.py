@@ -13,6 +13,7 @@ import os
 import numpy as np
 import pytest
 
+import edge_states
 import trust_region_ref as ref
 
 import phovo_amd  # noqa: F401
@@ -244,3 +245,58 @@ def test_options_defaults():
     assert opt.parameter_tolerance[15] == 1e-8 and opt.initial_trust_region_radius[0] == 1e4
     assert opt.max_trust_region_radius[0] == 1e16 and opt.min_trust_region_radius[0] == 1e-32
     assert opt.min_relative_decrease[0] == 1e-3
+
+
+@pytest.mark.parametrize("state", edge_states.initial_states(), ids=lambda s: "angles=" + ",".join(f"{a:.3f}" for a in s[3:]))
+def test_rows_are_the_true_chain_rule_in_every_branch(state):
+    """J of every owned row equals GX1 du/dx + GY1 dv/dx from a sympy model of the projection, to 1e-10, at angles in every
+    branch of the device's sin / cos and with the scene behind the camera (q2 < 0: a mirrored projection that lands in
+    bounds).  The target is linear in u and v, so its gradient planes are constant and the samples are exact."""
+    f = edge_states.chain_rule_model()
+    h, w = 12, 16
+    yy, xx = np.mgrid[0:h, 0:w].astype(np.float64)
+    i1 = 0.3 * xx - 0.2 * yy
+    gx, gy = np.full((h, w), 0.3), np.full((h, w), -0.2)
+    i0 = np.zeros((h, w))
+    d0 = 2.0 + 0.05 * xx - 0.03 * yy                                  # a slanted plane: pz varies
+    K = np.array([[2.5, 0, 7.3], [0, 2.2, 5.6], [0, 0, 1]])           # a wide field of view keeps rows at every angle
+    fx, fy, ox, oy, ifx, ify = ref.level_intrinsics(K, 0)
+    ev = ref.evaluate(i0, d0, i1, gx, gy, 0, K, state)
+    owned = np.nonzero(ev["owner"] >= 0)[0]
+    assert ev["rows"] == owned.size >= 6, ev["rows"]
+    behind = 0
+    for t in owned:
+        i = int(ev["owner"][t])
+        d = d0.ravel()[i]
+        px, py = ((i % w) - ox) * d * ifx, ((i // w) - oy) * d * ify
+        vals = f(*state, px, py, d, fx, fy, ox, oy)
+        du, dv = np.array(vals[0:6]), np.array(vals[6:12])
+        R, tv, _ = ref.rotation(state)
+        behind += (R[2] @ [px, py, d] + tv[2]) < 0
+        expect = 0.3 * du - 0.2 * dv
+        np.testing.assert_allclose(ev["J"][t], expect, rtol=1e-10, atol=1e-10 * max(1.0, np.abs(expect).max()),
+                                   err_msg=f"target {t}")
+    if abs(state[4]) > 2.0 or abs(state[5]) > 2.0:
+        assert behind == owned.size, (behind, owned.size)             # every row is a mirrored projection
+
+
+@pytest.mark.parametrize("axis,bad", [(3, np.nan), (4, np.inf), (5, -np.inf)])
+def test_non_finite_state_ends_without_a_step_and_is_flagged(axis, bad):
+    """A NaN / inf angle: no pixel warps, the system is finite and zero, fmax skips the NaN coordinates of the gradient
+    test (as the device's fmax does), and the level stops there with the state as given -- flagged NONFINITE and
+    RANK_DEFICIENT.  With the gradient test off it stops at the zero step instead."""
+    i0, d0, i1, gx, gy, K, _ = _tiny_case(3)
+    x0 = np.array([0.01, -0.02, 0.03, 0.02, -0.01, 0.015])
+    x0[axis] = bad
+
+    def ev(x):
+        return ref.evaluate(i0, d0, i1, gx, gy, 0, K, x)
+
+    assert ev(x0)["rows"] == 0 and ev(x0)["finite"] and ev(x0)["cost"] == 0.0
+    x, rec = ref.optimize_level(ev, x0, 10, **DEFAULTS)
+    assert rec["termination"] == ref.TR_GRADIENT and rec["steps"] == 0
+    assert np.array_equal(x, x0, equal_nan=True) and ref.pair_flags(x, {0: rec}) == 5
+    x, rec = ref.optimize_level(ev, x0, 10, **dict(DEFAULTS, gradient_tolerance=-1.0))
+    assert rec["termination"] == ref.TR_INVALID_STEP and rec["steps"] == 1 and ref.pair_flags(x, {0: rec}) == 5
+    finite, rec = ref.optimize_level(ev, np.zeros(6), 10, **dict(DEFAULTS, gradient_tolerance=-1.0))
+    assert ref.pair_flags(finite, {0: rec}) == (4 if rec["rows"] < 6 else 0)

@@ -30,10 +30,18 @@ def level_intrinsics(K, level):
     return fx, fy, ox, oy, 1.0 / fx, 1.0 / fy
 
 
+def _sin(a):
+    return math.sin(a) if math.isfinite(a) else math.nan          # (math.sin raises on inf; the device gives NaN)
+
+
+def _cos(a):
+    return math.cos(a) if math.isfinite(a) else math.nan
+
+
 def rotation(state):
     """Rt of Ceres.h:179-202 (eigenPose's matrix), with the device's association."""
     x, y, z, yaw, pitch, roll = [float(v) for v in state]
-    sy, cy, sp, cp, sr, cr = math.sin(yaw), math.cos(yaw), math.sin(pitch), math.cos(pitch), math.sin(roll), math.cos(roll)
+    sy, cy, sp, cp, sr, cr = _sin(yaw), _cos(yaw), _sin(pitch), _cos(pitch), _sin(roll), _cos(roll)
     R = np.array([[cp * cy, cy * sp * sr - sy * cr, cy * sp * cr + sy * sr],
                   [cp * sy, sy * sp * sr + cy * cr, sy * sp * cr - cy * sr],
                   [-sp, cp * sr, cp * cr]])
@@ -264,7 +272,9 @@ def optimize_level(evaluate_at, x0, max_iterations, function_tolerance, gradient
         if it >= max_iterations:
             term = TR_MAX_ITERATIONS
             break
-        gmax = float(np.max(np.abs(x - (x - cur["g"]))))
+        # (fmax skips a NaN coordinate of x, as the device's fmax does: a NaN initial state meets a zero gradient here)
+        with np.errstate(invalid="ignore"):
+            gmax = float(np.fmax.reduce(np.abs(x - (x - cur["g"])), initial=0.0))
         if ok:
             note("gradient", gmax, gradient_tolerance)
             if gmax <= gradient_tolerance:
@@ -335,6 +345,17 @@ def optimize_level(evaluate_at, x0, max_iterations, function_tolerance, gradient
             ok = False
     rec.update(steps=it, termination=term, rows=cur["rows"], final_cost=cur["cost"], final_radius=radius, g=cur["g"])
     return x, rec
+
+
+def pair_flags(x, records):
+    """The PHOVO_PAIR_* bits of a pair's report after optimize(): NONFINITE (1) when an evaluation failed or the state is
+    not finite, RANK_DEFICIENT (4) when a level ended with fewer than 6 rows."""
+    flags = 0
+    if not np.all(np.isfinite(x)) or any(r["termination"] == TR_EVALUATION_FAILED for r in records.values()):
+        flags |= 1
+    if any(r["rows"] < 6 for r in records.values()):
+        flags |= 4
+    return flags
 
 
 def level_options(opt, level):
