@@ -81,19 +81,28 @@ class BiExpect:
     (1e-9 x max(1, cond(H) / 1e5)) and the same well-posedness guard: one ulp of fx moves the checker's own result by
     less than a quarter of the bar."""
 
-    def __init__(self, ocfg, p, init):
+    def __init__(self, ocfg, p, init, min_depth=0.3, max_depth=5.0, plane_max_depth=5.0, guard=True):
+        """min_depth / max_depth: the depth gate in force at the alignment; plane_max_depth: the max depth in force when
+        the target was uploaded (its depth-gradient planes).  guard=False leaves the well-posedness
+        check to the caller (sensitivity())."""
         self.max_iter = [ocfg.max_num_iterations[l] for l in range(ocfg.num_levels)]
-        src = oracle.build_source_pyramids(p["gray0"], p["depth0"], ocfg)
-        tgt = bref.target_planes(p["gray1"], p["depth1"], ocfg, 5.0)
-        self.state, self.its, self.valid, self.flags, tr = bref.optimize(ocfg, p["K"], src, tgt, init)
+        self._args = (ocfg, p["K"], oracle.build_source_pyramids(p["gray0"], p["depth0"], ocfg),
+                      bref.target_planes(p["gray1"], p["depth1"], ocfg, plane_max_depth), init, min_depth, max_depth)
+        self.state, self.its, self.valid, self.flags, tr = bref.optimize(*self._args)
         self.finite = bool(np.all(np.isfinite(self.state)))
-        self.bar = min(1e-5, 1e-9 * max(1.0, _cond([dict(hessian=t["H"]) for t in tr]) / 1e5))
-        if self.finite:
-            K1 = p["K"].copy()
-            K1[0, 0] = np.nextafter(K1[0, 0], 2.0 * K1[0, 0])
-            s1 = bref.optimize(ocfg, K1, src, tgt, init)[0]
-            sens = se3.state_distance(self.state, s1) if np.all(np.isfinite(s1)) else np.inf
+        self.cond = _cond([dict(hessian=t["H"]) for t in tr])
+        self.bar = min(1e-5, 1e-9 * max(1.0, self.cond / 1e5))
+        if self.finite and guard:
+            sens = self.sensitivity()
             assert sens < 0.25 * self.bar, f"chaotic case: one ulp of fx moves the checker by {sens:.3e}, bar {self.bar:.1e}"
+
+    def sensitivity(self):
+        """How far the checker's own pose moves when fx changes by one ulp."""
+        ocfg, K, src, tgt, init, lo, hi = self._args
+        K1 = K.copy()
+        K1[0, 0] = np.nextafter(K1[0, 0], 2.0 * K1[0, 0])
+        s1 = bref.optimize(ocfg, K1, src, tgt, init, lo, hi)[0]
+        return se3.state_distance(self.state, s1) if np.all(np.isfinite(s1)) else np.inf
 
     def check(self, state, rep, what):
         nl = len(self.its)

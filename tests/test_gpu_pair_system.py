@@ -51,10 +51,11 @@ def _planes(eng, nl, w, h, levels):
     return out
 
 
-def _numpy_system(planes, level, K, state, delta):
+def _numpy_system(planes, level, K, state, delta, min_depth=0.3, max_depth=5.0):
     """H, g, cost from the oracle's residuals and Jacobians at `state`, weighted in numpy."""
     i0p, d0p, i1p, gxp, gyp = planes
-    r, J = oracle.compute_residuals_and_jacobians(i0p[level], d0p[level], i1p[level], gxp[level], gyp[level], level, K, state)
+    r, J = oracle.compute_residuals_and_jacobians(i0p[level], d0p[level], i1p[level], gxp[level], gyp[level], level, K, state,
+                                                  min_depth, max_depth)
     w = np.ones_like(r)
     if delta is not None and delta > 0:
         ar = np.abs(r)
@@ -62,12 +63,12 @@ def _numpy_system(planes, level, K, state, delta):
     return (J * w) @ J.T, (J * w) @ r, float(np.sum(w * r * r))
 
 
-def _oracle_trace_system(planes, level, K, state, delta):
+def _oracle_trace_system(planes, level, K, state, delta, min_depth=0.3, max_depth=5.0):
     """rows, H, g of ONE oracle iteration on `level` from `state` (the aligner's system at that state)."""
     nl = len(planes[0])
     mi = [0] * nl
     mi[level] = 1
-    cfg = oracle.make_config(num_levels=nl, max_iter=mi, min_grad=[0.0] * nl)
+    cfg = oracle.make_config(num_levels=nl, max_iter=mi, min_grad=[0.0] * nl, min_depth=min_depth, max_depth=max_depth)
     hd = None
     if delta is not None:
         hd = [0.0] * nl

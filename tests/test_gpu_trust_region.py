@@ -77,42 +77,56 @@ def _check(cfg, opt, ps, init=None, relative_pose=False):
         xs, recs = ref.align(ocfg, p["K"], p["gray0"], p["depth0"], p["gray1"], opt, x0)
         for L, rec in recs.items():
             assert min(rec["margins"], default=1.0) > MARGIN, (k, L, rec["decisions"])
-        bar = POSE_TOL * (max(1.0, np.abs(xs).max()) if relative_pose else 1.0)
-        assert np.abs(states[k] - xs).max() <= bar, (k, states[k], xs)
-        assert reps[k].flags == ref.pair_flags(xs, recs), (k, reps[k].flags)
-        for L in range(cfg.num_levels):
-            if L not in recs:
-                assert tr["termination"][k, L] == native.TR_SKIPPED and tr["steps"][k, L] == 0
-                continue
-            rec = recs[L]
-            for f in ("initial_cost", "final_cost"):
-                assert abs(tr[f][k, L] - rec[f]) <= COST_TOL * abs(rec[f]), (k, L, f)
-            assert np.allclose(tr["jacobi_scaling"][k, L], rec["S"], rtol=1e-12, atol=0), (k, L)
-            if rec["noise_from"] is not None:
-                # The level reached its noise floor at step noise_from (trust_region_ref.NOISE): every decision before
-                # it is conditioned and taken alike; after it accept / reject is decided by rounding, so the counts
-                # can only be bounded and the radius (halved or grown by those decisions) is not compared.  The pose
-                # (above) and the final cost still agree.
-                NOISE_LEVELS.append((k, L, rec["noise_from"], rec["steps"]))
-                assert tr["steps"][k, L] >= rec["noise_from"], (k, L)
-                assert tr["accepted"][k, L] >= rec["accepted_before_noise"], (k, L)
-                assert tr["termination"][k, L] in (rec["termination"], native.TR_FUNCTION, native.TR_MAX_ITERATIONS), (k, L)
-                continue
-            assert tr["steps"][k, L] == rec["steps"], (k, L)
-            assert tr["accepted"][k, L] == rec["accepted"], (k, L)
-            assert tr["termination"][k, L] == rec["termination"], (k, L)
-            assert tr["rows"][k, L] == rec["rows"], (k, L)
-            # Every accepted step scales the radius by a function of rho = dcost / mcc, whose rounding is about
-            # eps * cost / |dcost|.  Where every accepted step changed the cost by more than 1e-4 of it, the radius is
-            # pinned to 1e-9; once a level runs at its noise floor dcost is a difference of nearly equal costs and
-            # rounding-level differences of the two implementations move the radius by up to ~1e-5 without changing a
-            # decision, so those levels are held to 1e-3.
-            rtol = 1e-9 if rec["min_rel_dc"] > 1e-4 else 1e-3
-            assert abs(tr["final_radius"][k, L] - rec["final_radius"]) <= rtol * rec["final_radius"], (k, L, rtol)
-            assert reps[k].iterations[L] == rec["steps"] and reps[k].valid_pixels[L] == rec["rows"]
-        last = min(recs)
-        assert abs(reps[k].gradient_norm - np.linalg.norm(recs[last]["g"])) <= 1e-9 * np.linalg.norm(recs[last]["g"])
+        compare_pair(k, states[k], reps[k], tr, xs, recs, cfg.num_levels, relative_pose)
     return tr
+
+
+def compare_pair(k, state, rep, tr, xs, recs, num_levels, relative_pose=False, allow=None):
+    """Pair k of a device alignment (its state, PairReport and the trust_region_reports array of the launch) against the
+    checker's (state, {level: record}): the rules of _check, which asserts before it that no decision is knife-edge.
+    Raises AssertionError on the first difference.  Returns the pose distance / bar.  allow (tests/tools/
+    fuzz_objectives.py: conditioned_allowance) widens the pose bar to one conditioned on the checker's systems and adds to
+    the cost, Jacobi-scaling, radius and gradient-norm bars what that pose bar carries into them to first order; every
+    decision, row count and flag is still compared exactly."""
+    allow = allow or {}
+    bar = max(POSE_TOL * (max(1.0, np.abs(xs).max()) if relative_pose else 1.0), allow.get("pose", 0.0))
+    assert np.abs(state - xs).max() <= bar, (k, "pose", state, xs, bar)
+    assert rep.flags == ref.pair_flags(xs, recs), (k, "flags", rep.flags)
+    for L in range(num_levels):
+        if L not in recs:
+            assert tr["termination"][k, L] == native.TR_SKIPPED and tr["steps"][k, L] == 0
+            continue
+        rec = recs[L]
+        for f in ("initial_cost", "final_cost"):
+            assert abs(tr[f][k, L] - rec[f]) <= COST_TOL * abs(rec[f]) + allow.get((L, f), 0.0), (k, L, f)
+        assert np.all(np.abs(tr["jacobi_scaling"][k, L] - rec["S"]) <= 1e-12 * np.abs(rec["S"]) + allow.get((L, "S"), 0.0)), \
+            (k, L, "jacobi_scaling")
+        if rec["noise_from"] is not None:
+            # The level reached its noise floor at step noise_from (trust_region_ref.NOISE): every decision before
+            # it is conditioned and taken alike; after it accept / reject is decided by rounding, so the counts
+            # can only be bounded and the radius (halved or grown by those decisions) is not compared.  The pose
+            # (above) and the final cost still agree.
+            NOISE_LEVELS.append((k, L, rec["noise_from"], rec["steps"]))
+            assert tr["steps"][k, L] >= rec["noise_from"], (k, L)
+            assert tr["accepted"][k, L] >= rec["accepted_before_noise"], (k, L)
+            assert tr["termination"][k, L] in (rec["termination"], native.TR_FUNCTION, native.TR_MAX_ITERATIONS), (k, L)
+            continue
+        assert tr["steps"][k, L] == rec["steps"], (k, L)
+        assert tr["accepted"][k, L] == rec["accepted"], (k, L)
+        assert tr["termination"][k, L] == rec["termination"], (k, L)
+        assert tr["rows"][k, L] == rec["rows"], (k, L)
+        # Every accepted step scales the radius by a function of rho = dcost / mcc, whose rounding is about
+        # eps * cost / |dcost|.  Where every accepted step changed the cost by more than 1e-4 of it, the radius is
+        # pinned to 1e-9; once a level runs at its noise floor dcost is a difference of nearly equal costs and
+        # rounding-level differences of the two implementations move the radius by up to ~1e-5 without changing a
+        # decision, so those levels are held to 1e-3.
+        rtol = max(1e-9 if rec["min_rel_dc"] > 1e-4 else 1e-3, allow.get((L, "radius"), 0.0))
+        assert abs(tr["final_radius"][k, L] - rec["final_radius"]) <= rtol * rec["final_radius"], (k, L, rtol)
+        assert rep.iterations[L] == rec["steps"] and rep.valid_pixels[L] == rec["rows"]
+    last = min(recs)
+    gn = np.linalg.norm(recs[last]["g"])
+    assert abs(rep.gradient_norm - gn) <= 1e-9 * gn + allow.get("gradient_norm", 0.0), (k, "gradient_norm")
+    return float(np.abs(state - xs).max()) / bar
 
 
 NOISE_LEVELS = []         # (pair, level, noise_from, steps) of the last _check: levels that reached their noise floor

@@ -1,0 +1,597 @@
+"""Randomised device-vs-checker sweep of the bi-objective (`bi`, gn_biobjective_kernel.hip), trust-region (`tr`,
+gn_trust_region_kernel.hip) and evaluate (`eval`, gn_evaluate_kernels.hip) kernels, in the style of fuzz_parity.py.
+
+    python tests/tools/fuzz_objectives.py [cases=100] [seed=0] [mode=bi|tr|eval] [big] [angles]
+
+Every case draws (draw_case, pure numpy, so that replay and coverage are testable without a GPU): an odd size with 1-3
+levels up to 330x250 (`big`: 340x260 ... 700x500 with 1-2 levels) or a strip 1-5 pixels wide; intrinsics perturbed off
+the half-integer grid; depth holes and, with some probability, NaN, negative, +inf, beyond-max source depth and depth
+exactly at the bounds of the gate; for `bi` zero, negative, beyond-max (rarely NaN) target depth; a depth range, sometimes
+changed between upload and alignment; lambda 1 or 0.7 (`bi`); fixed iteration counts or gradient thresholds; for `tr` the
+options of a shipped Ceres file (tests/golden/ceres) or fixed mode; initial states (tests/edge_states.py, and in `angles`
+mode fuzz_draws.draw_angle's branches under in-plane motions up to 0.9 rad); for `eval` states around the motion on every
+level, fp64 / fp32 / fp16 plane storage and Huber weights on or off; 1, 3 or 40 pairs per launch, whose replicas must be
+bit-identical.
+
+Checks: `bi` against biobjective_ref.optimize under test_gpu_objective_edges.BiExpect (iterations, valid pixels, flags,
+pose within 1e-9 x max(1, cond / 1e5), capped at 1e-5); `tr` against trust_region_ref under
+test_gpu_trust_region.compare_pair (steps, accepted steps, terminations, rows, costs to 1e-9, noise floor); `eval` against
+the oracle on the planes as the device stores them under test_gpu_pair_system._check_against.  Knife-edge cases are
+counted and printed, not failed: for `bi` and `eval` a case that misses its bar while one ulp of fx moves the checker by
+more than a quarter of the bar, for `tr` a case with a decision margin of at most 1e-6 (not compared).  A `tr` case that
+misses _check's flat bars is compared again under bars conditioned on the checker's cond(J^T J) (conditioned_allowance:
+the pose bar as `bi`'s, and what it carries into costs, Jacobi scaling and gradient norm), with every decision, row count
+and flag still exact; the summary counts those cases.  The `eval` tile classes are predicted from the level sizes (the
+evaluate path keeps no launch record).
+
+One line per failure, a summary, exit status 1 on any failure.  FUZZ_ONLY=12,345 runs only those cases, with the draws of
+the full sweep.  The checkers run in FUZZ_JOBS worker processes (default: up to 12), which never touch the GPU.
+"""
+import os
+import sys
+import types
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+TESTS = os.path.dirname(HERE)
+ROOT = os.path.dirname(TESTS)
+for p in (ROOT, TESTS, HERE):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+from fuzz_draws import draw_angle  # noqa: E402
+
+MODES = ("bi", "tr", "eval")
+CERES_FILES = ("config_3_level_optimization_ceres.yml", "config_4_level_optimization_ceres.yml",
+               "config_5_level_optimization_ceres.yml", "config_only_level_0_ceres.yml",
+               "config_only_level_1_ceres.yml", "config_only_level_2_ceres.yml")
+SRC_DEFECTS = ("nan", "negative", "inf", "beyond_max", "at_min", "at_max")
+TGT_DEFECTS = ("zero", "negative", "beyond_max", "nan")
+# LDS budget of one workgroup (gn_device.hpp LDS_LIMIT) and a bound of the fixed part: the host-side guess of the geometry
+# the planners (gn_plan_level_biobjective / _trust_region) choose, for the coverage test; the sweep records the real one
+LDS_LIMIT, LDS_FIXED = 160 * 1024, 4096
+STATES = None
+
+
+def _edge_states():
+    global STATES
+    if STATES is None:
+        import edge_states
+        STATES = edge_states.initial_states()
+    return STATES
+
+
+def level_size(w, h, level):
+    for _ in range(level):
+        w, h = (w + 1) // 2, (h + 1) // 2
+    return w, h
+
+
+def predicted_geometry(mode, n):
+    if mode == "eval":
+        tiles = -(-(-(-n // 64)) // 16)
+        return "tiles1" if tiles == 1 else "tiles2-16" if tiles <= 16 else "tiles17+"
+    own = 4 * n + 8 * -(-n // 64)
+    return "lds256" if LDS_FIXED + own <= LDS_LIMIT // 2 else "lds512" if LDS_FIXED + own <= LDS_LIMIT else "hbm512"
+
+
+def draw_case(rs, mode, flags):
+    """All random draws of one case, in a fixed order whatever is drawn: a dict of plain values (the images are rendered
+    from `seed` and the per-pixel defects from `defect_seed` when the case runs)."""
+    big, angles = "big" in flags, "angles" in flags
+    c = dict(mode=mode)
+    kind = rs.rand()
+    nl = int(rs.randint(1, 3 if big else 4))
+    unit = 2 ** (nl - 1)
+    w = int(rs.randint(340, 701) if big else rs.randint(16, 331)) // unit * unit + (unit if rs.rand() < 0.5 else 0)
+    h = int(rs.randint(260, 501) if big else rs.randint(12, 251)) // unit * unit + (unit if rs.rand() < 0.5 else 0)
+    w, h = max(w, 8 * unit), max(h, 8 * unit)
+    strip_w, strip_h = int(rs.randint(1, 6)), int(rs.randint(12, 121))
+    if kind < 0.12:
+        c.update(size_class="strip", nl=1, w=strip_w, h=strip_h)
+    else:
+        c.update(size_class="big" if big else "normal", nl=nl, w=w, h=h)
+    nl = c["nl"]
+    c["seed"] = int(rs.randint(0, 2 ** 31 - 1))
+    c["defect_seed"] = int(rs.randint(0, 2 ** 31 - 1))
+    c["holes"] = float(rs.choice([0.0, 0.02, 0.2]))
+    c["trans"] = float(rs.choice([0.002, 0.02, 0.08]))
+    c["rot"] = float(rs.choice([0.001, 0.01, 0.05]))
+    motion = np.concatenate([rs.uniform(-1, 1, 3) * c["trans"], [rs.uniform(-0.9, 0.9)], rs.uniform(-0.01, 0.01, 2)])
+    c["motion"] = motion.tolist() if angles else None
+    perturb = rs.rand() < 0.6
+    kp = [float(rs.uniform(-3, 3)), float(rs.uniform(-3, 3)), float(rs.uniform(0.9, 1.1)), float(rs.uniform(0.9, 1.1))]
+    c["k_perturb"] = kp if perturb else None
+    with_src = rs.rand() < 0.6
+    src = [d for d in SRC_DEFECTS if rs.rand() < 0.5]
+    c["src_defects"] = src if with_src else []
+    tgt = [d for d in TGT_DEFECTS if rs.rand() < (0.05 if d == "nan" else 0.5)]
+    with_tgt = rs.rand() < 0.6
+    c["tgt_defects"] = tgt if (with_tgt and mode == "bi") else []
+    rk = int(rs.randint(0, 4))
+    lo_hi = [float(rs.uniform(0.2, 0.9)), float(rs.uniform(2.5, 6.0))]
+    c["range"] = [0.3, 5.0] if rk < 2 else [0.5, 3.0] if rk == 2 else lo_hi
+    uk = rs.rand()
+    up = [float(rs.uniform(0.2, 0.9)), float(rs.uniform(2.5, 6.0))]
+    c["upload_range"] = up if uk < 0.35 else list(c["range"])
+    fixed = rs.rand() < 0.5
+    max_iter = [int(rs.randint(0, 7)) for _ in range(nl)]
+    if sum(max_iter) == 0:
+        max_iter[-1] = 3
+    mg = [float(rs.choice([1.0, 30.0, 300.0])) for _ in range(nl)]
+    c["max_iter"] = max_iter
+    c["min_grad"] = [0.0] * nl if fixed else mg
+    lam = [float(rs.choice([1.0, 0.7])) for _ in range(nl)]
+    c["lam"] = lam if mode == "bi" else [1.0] * nl
+    ceres = int(rs.randint(0, len(CERES_FILES) + 2))
+    c["ceres"] = CERES_FILES[ceres] if ceres < len(CERES_FILES) else "fixed"
+    c["tr_max_iter"] = [int(rs.randint(0, 7)) for _ in range(nl)]
+    if sum(c["tr_max_iter"]) == 0:
+        c["tr_max_iter"][-1] = 4
+    ik = rs.rand()
+    small = (rs.uniform(-1, 1, 6) * np.array([0.02, 0.02, 0.02, 0.01, 0.01, 0.01])).tolist()
+    edge = int(rs.randint(0, 32))
+    ang = [draw_angle(rs, axis, motion[3 + axis]) for axis in range(3)] if angles else None
+    if angles:
+        c["init"] = small[:3] + ang
+    else:
+        c["init"] = None if ik < 0.3 else small if ik < 0.75 else ("edge", edge)
+    c["storage"] = int(rs.randint(0, 3)) if mode == "eval" else 0
+    c["huber"] = [float(rs.choice([0.02, 0.05, 0.1])) for _ in range(nl)] if rs.rand() < 0.5 else None
+    if mode != "eval":
+        c["huber"] = None
+    c["eval_spread"] = float(rs.choice([0.0, 0.003, 0.02]))
+    c["eval_edge"] = int(rs.randint(0, 32)) if rs.rand() < 0.25 else None
+    c["n_pairs"] = int(rs.choice([1, 3, 40]))
+    return c
+
+
+def draw_cases(cases, seed, mode, flags, only=None):
+    """{case: draw} of the first `cases` cases of a sweep (those in `only`, when given): every case is drawn either way,
+    so that a replay draws exactly what the full sweep draws."""
+    rs = np.random.RandomState(seed)
+    out = {}
+    for case in range(cases):
+        d = draw_case(rs, mode, flags)
+        if only is None or case in only:
+            out[case] = d
+    return out
+
+
+def case_key(d):
+    return repr(sorted(d.items()))
+
+
+def level_geometries(d):
+    levels = [l for l in range(d["nl"]) if d["mode"] == "eval" or
+              (d["max_iter"] if d["mode"] == "bi" else d["tr_max_iter"])[l] > 0]
+    return {predicted_geometry(d["mode"], int(np.prod(level_size(d["w"], d["h"], l)))) for l in levels}
+
+
+def coverage(draws, mode):
+    """How often the draws reach each size class, geometry, depth defect and range change (for the coverage test)."""
+    cov = {f"size_{k}": 0 for k in ("normal", "strip", "big")}
+    cov.pop("size_big")
+    geos = ["tiles1", "tiles2-16", "tiles17+"] if mode == "eval" else ["lds256", "lds512", "hbm512"]
+    cov.update({g: 0 for g in geos})
+    cov.update({f"src_{k}": 0 for k in SRC_DEFECTS})
+    if mode == "bi":
+        cov.update({f"tgt_{k}": 0 for k in TGT_DEFECTS})
+        cov["lambda_0.7"] = 0
+    if mode == "eval":
+        cov.update({f"storage_{k}": 0 for k in range(3)})
+        cov["huber"] = 0
+    if mode == "tr":
+        cov.update({"ceres_file": 0, "ceres_fixed": 0})
+    cov.update(range_changed=0, range_non_default=0, pairs_1=0, pairs_3=0, pairs_40=0, init_edge=0)
+    for d in draws:
+        cov[f"size_{d['size_class']}"] = cov.get(f"size_{d['size_class']}", 0) + 1
+        for g in level_geometries(d):
+            cov[g] += 1
+        for k in d["src_defects"]:
+            cov[f"src_{k}"] += 1
+        for k in d["tgt_defects"]:
+            cov[f"tgt_{k}"] += 1
+        if mode == "bi":
+            cov["lambda_0.7"] += int(0.7 in d["lam"])
+        if mode == "eval":
+            cov[f"storage_{d['storage']}"] += 1
+            cov["huber"] += int(d["huber"] is not None)
+        if mode == "tr":
+            cov["ceres_fixed" if d["ceres"] == "fixed" else "ceres_file"] += 1
+        cov["range_changed"] += int(d["upload_range"] != d["range"])
+        cov["range_non_default"] += int(d["range"] != [0.3, 5.0])
+        cov[f"pairs_{d['n_pairs']}"] += 1
+        cov["init_edge"] += int(isinstance(d["init"], tuple) or d["eval_edge"] is not None)
+    return cov
+
+
+# ---- running a case ------------------------------------------------------------------------------------------------
+def render(d):
+    """The pair of a case: images, perturbed K, source and target depth with their defects, the initial state."""
+    from phovo_amd import synthetic
+    w, h = d["w"], d["h"]
+    rw = max(w, 64) if w < 8 else w
+    if d["motion"] is not None:
+        p = synthetic.render_pair_with_motion(d["seed"], rw, h, np.array(d["motion"]), d["holes"])
+    else:
+        p = synthetic.make_pair(d["seed"], rw, h, holes=d["holes"], trans=d["trans"], rot=d["rot"])
+    p = dict(p)
+    K = p["K"].copy()
+    if w < 8:                                       # a strip of a 64-pixel-wide render, principal point moved with the crop
+        for k in ("gray0", "depth0", "gray1", "depth1"):
+            p[k] = np.ascontiguousarray(p[k][:, 30:30 + w])
+        K[0, 2] -= 30.0
+    if d["k_perturb"] is not None:
+        K[0, 2] += d["k_perturb"][0]
+        K[1, 2] += d["k_perturb"][1]
+        K[0, 0] *= d["k_perturb"][2]
+        K[1, 1] *= d["k_perturb"][3]
+    p["K"] = K
+    lo, hi = d["range"]
+    rs = np.random.RandomState(d["defect_seed"])
+    d0 = np.array(p["depth0"], dtype=np.float64)
+    for k, v in (("nan", np.nan), ("negative", -1.0), ("inf", np.inf), ("beyond_max", hi + 2.5), ("at_min", lo),
+                 ("at_max", hi)):
+        m = rs.rand(h, w) < 0.01
+        if k in d["src_defects"]:
+            d0[m] = v
+    d1 = np.array(p["depth1"], dtype=np.float64)
+    for k, v in (("zero", 0.0), ("negative", -0.7), ("beyond_max", hi + 4.0), ("nan", np.nan)):
+        m = rs.rand(h, w) < 0.01
+        if k in d["tgt_defects"]:
+            d1[m] = v
+    p["depth0"], p["depth1"] = d0, d1
+    init = d["init"]
+    if isinstance(init, tuple):
+        init = _edge_states()[init[1]]
+    p["init"] = None if init is None else np.array(init, dtype=np.float64)
+    return p
+
+
+def _tr_options(d, nl):
+    """Per-level options: those of a shipped Ceres file (level L of the file, or its last level) or fixed mode (every
+    tolerance and the minimum radius 0, the default radii)."""
+    from phovo_amd import native
+    if d["ceres"] == "fixed":
+        src = native.trust_region_options_default()
+    else:
+        cfg, src = native.read_trust_region_file(os.path.join(TESTS, "golden", "ceres", d["ceres"]))
+    opt = native.TrustRegionOptions()
+    fields = native.TR_OPTION_FIELDS
+    for f in fields:
+        getattr(opt, f)[:] = getattr(src, f)[:]
+    if d["ceres"] == "fixed":
+        for L in range(nl):
+            opt.function_tolerance[L] = opt.gradient_tolerance[L] = opt.parameter_tolerance[L] = 0.0
+            opt.min_trust_region_radius[L] = 0.0
+    else:
+        last = cfg.num_levels - 1
+        for L in range(last + 1, nl):
+            for f in fields:
+                getattr(opt, f)[L] = getattr(opt, f)[last]
+    return opt, types.SimpleNamespace(**{f: list(getattr(opt, f)) for f in fields})
+
+
+def _plain_report(r):
+    return types.SimpleNamespace(flags=int(r.flags), iterations=list(r.iterations), valid_pixels=list(r.valid_pixels),
+                                 gradient_norm=float(r.gradient_norm))
+
+
+def run_device(d):
+    """The device's side of one case; returns a job for check_job (plain, picklable data) and the geometries it ran."""
+    from phovo_amd import native, odometry
+    p = render(d)
+    w, h, nl, n_pairs = d["w"], d["h"], d["nl"], d["n_pairs"]
+    lo, hi = d["range"]
+    ulo, uhi = d["upload_range"]
+    job = dict(d=d, p=p)
+    geos = set()
+    mode = d["mode"]
+    with odometry.AlignmentEngine(0) as e:
+        if mode == "bi":
+            e.set_config(native.make_config(num_levels=nl, max_iter=d["max_iter"], min_grad=d["min_grad"], lam=d["lam"]))
+            e.set_objective(native.OBJECTIVE_BIOBJECTIVE)
+        elif mode == "tr":
+            e.set_config(native.make_config(num_levels=nl, max_iter=d["tr_max_iter"], min_grad=[0.0] * nl))
+            e.set_objective(native.OBJECTIVE_TRUST_REGION)
+            opt, job["opt"] = _tr_options(d, nl)
+            e.set_trust_region_options(opt)
+            e.set_batch_invariant(True)
+        else:
+            e.set_config(native.make_config(num_levels=nl, max_iter=[1] * nl, min_grad=[0.0] * nl))
+            e.set_extensions(native.make_extensions(plane_storage=[native.STORAGE_F64, native.STORAGE_F32,
+                                                                   native.STORAGE_F16][d["storage"]],
+                                                    huber_delta=d["huber"]))
+            e.set_build_all_levels(True)
+        e.set_intrinsic_matrix(p["K"])
+        e.set_depth_range(ulo, uhi)
+        e.reserve_frames(2, w, h)
+        e.upload_frame(0, p["gray0"], p["depth0"], native.ROLE_SOURCE)
+        e.upload_frame(1, p["gray1"], p["depth1"] if mode == "bi" else None, native.ROLE_TARGET)
+        e.set_depth_range(lo, hi)
+        if mode in ("bi", "tr"):
+            inits = None if p["init"] is None else np.tile(p["init"], (n_pairs, 1))
+            s, reps = e.align_pairs([0] * n_pairs, [1] * n_pairs, init_states=inits, want_reports=True)
+            for r in e.last_launches():
+                n = int(np.prod(level_size(w, h, r["levels"][0])))
+                geos.add(f"lds{r['threads']}" if r["lds_bytes"] >= 4 * n else f"hbm{r['threads']}")
+            job["states"] = s
+            job["reps"] = [_plain_report(r) for r in reps]
+            if mode == "tr":
+                job["tr"] = e.trust_region_reports(n_pairs)
+        else:
+            planes = [[], [], [], [], []]
+            for l in range(nl):
+                i0, d0, _, _ = e.get_level_planes(0, l)
+                i1, _, gx, gy = e.get_level_planes(1, l)
+                for lst, a in zip(planes, (i0, d0, i1, gx, gy)):
+                    lst.append(a)
+            rs = np.random.RandomState(d["defect_seed"] + 1)
+            m = min(3, n_pairs)
+            base = np.array(p["motion"])
+            states = [base + rs.normal(0, d["eval_spread"], 6) for _ in range(m)]
+            if d["eval_edge"] is not None:
+                states[-1] = _edge_states()[d["eval_edge"]]
+            if p["init"] is not None and d["motion"] is not None:
+                states[0] = p["init"]
+            st = np.array([states[i % m] for i in range(n_pairs)])
+            job["planes"], job["eval_states"], job["eval"] = planes, st[:m], []
+            for l in range(nl):
+                out = e.evaluate_pairs([0] * n_pairs, [1] * n_pairs, st, l)
+                job["eval"].append(out)
+                geos.add(predicted_geometry("eval", int(np.prod(level_size(w, h, l)))))
+    return job, geos
+
+
+def _ok(status, ratio, msg=""):
+    return dict(status=status, ratio=ratio, msg=msg)
+
+
+def check_job(job):
+    """The checker's side of one case, in a worker process (no GPU): dict(status ok / fail / skip, ratio, msg)."""
+    try:
+        return {"bi": _check_bi, "tr": _check_tr, "eval": _check_eval}[job["d"]["mode"]](job)
+    except Exception as ex:                                     # a checker that raises is a failure, with its reason
+        import traceback
+        return _ok("fail", np.inf, "checker raised: " + "".join(traceback.format_exception_only(type(ex), ex)).strip())
+
+
+def _same_report(a, b):
+    """Two reports alike, a NaN gradient norm (a NaN target depth makes the gain NaN) equal to itself."""
+    return (a.flags == b.flags and a.iterations == b.iterations and a.valid_pixels == b.valid_pixels and
+            np.array_equal(a.gradient_norm, b.gradient_norm, equal_nan=True))
+
+
+def _tr_levels(tr, recs, nl):
+    """Device record against the checker's, level by level (printed with a failure)."""
+    out = []
+    for L in sorted(recs):
+        r = recs[L]
+        out.append(f"L{L}: steps {tr['steps'][0, L]}/{r['steps']} accepted {tr['accepted'][0, L]}/{r['accepted']} "
+                   f"term {tr['termination'][0, L]}/{r['termination']} rows {tr['rows'][0, L]}/{r['rows']} "
+                   f"cost {tr['initial_cost'][0, L]:.17g}/{r['initial_cost']:.17g} -> {tr['final_cost'][0, L]:.17g}/"
+                   f"{r['final_cost']:.17g} radius {tr['final_radius'][0, L]:.17g}/{r['final_radius']:.17g} "
+                   f"noise_from {r['noise_from']} min_rel_dc {r['min_rel_dc']:.2e} "
+                   f"margin {min(r['margins'], default=1.0):.2e} decisions {r['decisions'][-6:]}")
+    return "; ".join(out)
+
+
+def _check_bi(job):
+    from oracle import oracle
+    from test_gpu_objective_edges import BiExpect
+    d, p = job["d"], job["p"]
+    nl = d["nl"]
+    ocfg = oracle.make_config(num_levels=nl, max_iter=d["max_iter"], min_grad=d["min_grad"], lam=d["lam"])
+    ex = BiExpect(ocfg, p, p["init"], d["range"][0], d["range"][1], d["upload_range"][1], guard=False)
+    s, reps = job["states"], job["reps"]
+    for k in range(1, len(reps)):
+        if not (np.array_equal(s[k], s[0], equal_nan=True) and _same_report(reps[k], reps[0])):
+            return _ok("fail", np.inf, f"replica {k} differs from replica 0")
+    ratio = 0.0
+    if ex.finite and np.all(np.isfinite(s[0])):
+        from phovo_amd import se3
+        ratio = se3.state_distance(s[0], ex.state) / ex.bar
+    try:
+        ex.check(s[0], reps[0], "pair 0")
+        return _ok("ok", ratio)
+    except AssertionError as err:
+        sens = ex.sensitivity() if ex.finite else 0.0
+        detail = f"{err}; cond {ex.cond:.2e} bar {ex.bar:.1e} one-ulp sensitivity {sens:.2e}"
+        if sens > 0.25 * ex.bar:
+            return _ok("skip", ratio, detail)
+        return _ok("fail", ratio, detail)
+
+
+def _check_tr(job):
+    import test_gpu_trust_region as gtr
+    import trust_region_ref as tref
+    from oracle import oracle
+    d, p = job["d"], job["p"]
+    nl = d["nl"]
+    ocfg = oracle.make_config(num_levels=nl, max_iter=d["tr_max_iter"], min_grad=[0.0] * nl)
+    xs, recs = tref.align(ocfg, p["K"], p["gray0"], p["depth0"], p["gray1"], job["opt"], p["init"], *d["range"])
+    s, tr = job["states"], job["tr"]
+    for k in range(1, len(s)):
+        if not (np.array_equal(s[k], s[0], equal_nan=True) and tr[k:k + 1].tobytes() == tr[0:1].tobytes()):
+            return _ok("fail", np.inf, f"replica {k} differs from replica 0")
+    margin = min((min(r["margins"], default=1.0) for r in recs.values()), default=1.0)
+    if margin <= gtr.MARGIN:
+        return _ok("skip", 0.0, f"decision margin {margin:.2e}")
+    try:
+        return _ok("ok", gtr.compare_pair(0, s[0], job["reps"][0], tr, xs, recs, nl, relative_pose=True))
+    except AssertionError as err:
+        strict = err
+    # _check's bars hold the pose to 1e-9 x max(1, |x|) whatever the conditioning; as for `bi` (BiExpect), the pose bar
+    # scales with cond(J^T J) of the checker's systems above 1e5 and the cost, Jacobi-scaling and gradient-norm bars take
+    # what that pose bar carries into them to first order.  Decisions, rows and flags are still compared exactly.
+    i0p, d0p = oracle.build_source_pyramids(p["gray0"], p["depth0"], ocfg)
+    i1p, gxp, gyp = oracle.build_target_pyramids(p["gray1"], ocfg)
+    allow = conditioned_allowance(recs, xs, lambda L, x: tref.evaluate(i0p[L], d0p[L], i1p[L], gxp[L], gyp[L], L, p["K"], x,
+                                                                          *d["range"]))
+    try:
+        return _ok("conditioned", gtr.compare_pair(0, s[0], job["reps"][0], tr, xs, recs, nl, relative_pose=True,
+                                                   allow=allow), f"{strict}; cond {allow['cond']:.2e}")
+    except AssertionError as err:
+        detail = f"{err}; cond {allow['cond']:.2e}, pose bar {allow['pose']:.1e}; device / checker {_tr_levels(tr, recs, nl)}"
+        return _ok("fail", np.inf, detail)
+
+
+def conditioned_allowance(recs, xs, evaluate_at):
+    """Bars of a trust-region comparison conditioned on the checker's systems: the pose bar 1e-9 x max(1, cond / 1e5),
+    capped at 1e-5, times max(1, |x|) (cond: the largest cond(J^T J) of the states the checker accepted, inf where fewer
+    than six rows constrain it); what a pose difference e of that size adds to a cost (|g| |e| + |H| |e|^2 / 2), to a
+    level's Jacobi scaling (summed one-coordinate differences of S at the level's entering state; 0 on the first level,
+    which starts from the same state on both sides), to its final radius (through rho on every accepted step) and to the
+    gradient norm (|H| |e|).  evaluate_at(level, x) is the
+    checker's evaluation."""
+    from test_gpu_trust_region import POSE_TOL
+    cond = max(r["cond"] for r in recs.values())
+    pose = min(1e-5, POSE_TOL * max(1.0, cond / 1e5)) * max(1.0, float(np.abs(xs).max()))
+    e = np.sqrt(6.0) * pose
+    allow = dict(cond=cond, pose=pose)
+    first = max(recs)
+    for L, r in recs.items():
+        h2 = float(np.linalg.norm(r["H"], 2)) if np.all(np.isfinite(r["H"])) else np.inf
+        allow[(L, "initial_cost")] = float(np.linalg.norm(r["g0"])) * e + 0.5 * h2 * e * e
+        allow[(L, "final_cost")] = float(np.linalg.norm(r["g"])) * e + 0.5 * h2 * e * e
+        # the radius: each accepted step multiplies it by 1 / max(1/3, 1 - (2 rho - 1)^3), whose logarithmic derivative
+        # in rho is at most 6 x 0.763 / (1/3) = 13.7; rho = dc / mcc moves by at most 2 x (cost bar) / |dc|, and
+        # |dc| >= min_rel_dc x final cost on every accepted step
+        dc_min = r["min_rel_dc"] * r["final_cost"] if np.isfinite(r["min_rel_dc"]) else np.inf
+        cost_bar = max(allow[(L, "initial_cost")], allow[(L, "final_cost")])
+        allow[(L, "radius")] = (13.7 * r["accepted"] * 2.0 * cost_bar / dc_min if dc_min > 0 else np.inf) if r["accepted"] else 0.0
+        if L != first:
+            S0 = 1.0 / (1.0 + np.sqrt(np.diag(evaluate_at(L, r["x0"])["H"])))
+            dS = np.zeros(6)
+            for k in range(6):
+                x = np.array(r["x0"], dtype=np.float64)
+                x[k] += pose
+                dS += np.abs(1.0 / (1.0 + np.sqrt(np.diag(evaluate_at(L, x)["H"]))) - S0)
+            allow[(L, "S")] = dS
+    last = recs[min(recs)]
+    allow["gradient_norm"] = (float(np.linalg.norm(last["H"], 2)) if np.all(np.isfinite(last["H"])) else np.inf) * e
+    return allow
+
+
+def _eval_reference(planes, level, K, st, delta, lo, hi):
+    from test_gpu_pair_system import _numpy_system, _oracle_trace_system
+    rows, H, g = _oracle_trace_system(planes, level, K, st, delta, lo, hi)
+    _, _, cost = _numpy_system(planes, level, K, st, delta, lo, hi)
+    return rows, H, g, cost
+
+
+def _eval_ratio(got, ref):
+    """Distance / bar of a device system (H, g, rows, cost) from a reference, under test_gpu_pair_system's bars."""
+    H, g, rows, cost = got
+    rrows, rH, rg, rcost = ref
+    if rows != rrows:
+        return np.inf
+    if rrows == 0:
+        return 0.0 if not np.any(H) else np.inf
+    scale = np.max(np.abs(rH))
+    gbar = 1e-9 * np.sqrt(np.maximum(np.diag(rH) * rcost, 0.0))
+    with np.errstate(all="ignore"):
+        rg_ = np.max(np.where(gbar > 0, np.abs(g - rg) / gbar, np.where(g == rg, 0.0, np.inf)))
+    return max(np.max(np.abs(H - rH)) / (1e-10 * scale) if scale > 0 else 0.0, rg_,
+               abs(cost - rcost) / (1e-12 * abs(rcost)) if rcost != 0 else float(cost != 0))
+
+
+def _check_eval(job):
+    from test_gpu_pair_system import _check_against
+    d, p = job["d"], job["p"]
+    lo, hi = d["range"]
+    K, planes, states = p["K"], job["planes"], job["eval_states"]
+    m, worst, knife = len(states), 0.0, []
+    for level, out in enumerate(job["eval"]):
+        n = len(out["rows"])
+        for k in range(m, n):
+            j = k % m
+            if not (np.array_equal(out["information"][k], out["information"][j]) and
+                    np.array_equal(out["gradient"][k], out["gradient"][j]) and out["cost"][k] == out["cost"][j] and
+                    out["rows"][k] == out["rows"][j]):
+                return _ok("fail", np.inf, f"level {level}: replica {k} differs from {j}")
+        delta = None if d["huber"] is None else d["huber"][level]
+        for i in range(m):
+            ref = _eval_reference(planes, level, K, states[i], delta, lo, hi)
+            got = (out["information"][i], out["gradient"][i], int(out["rows"][i]), float(out["cost"][i]))
+            ratio = _eval_ratio(got, ref)
+            try:
+                if ref[0] == 0:
+                    assert got[2] == 0 and not np.any(got[0]), (got[2], ref[0])
+                else:
+                    _check_against(got[0], got[1], got[2], got[3], ref[1], ref[2], ref[0], ref[3])
+                worst = max(worst, ratio)
+            except AssertionError as err:
+                K1 = K.copy()
+                K1[0, 0] = np.nextafter(K1[0, 0], 2.0 * K1[0, 0])
+                ref1 = _eval_reference(planes, level, K1, states[i], delta, lo, hi)
+                moved = _eval_ratio((ref1[1], ref1[2], ref1[0], ref1[3]), ref)
+                detail = f"level {level} state {i}: {err}; distance / bar {ratio:.3g}, one ulp of fx moves the oracle {moved:.3g} bars"
+                if moved <= 0.25:
+                    return _ok("fail", ratio, detail)
+                knife.append(detail)                  # (and the remaining levels and states are still checked)
+    return _ok("skip", worst, "; ".join(knife)) if knife else _ok("ok", worst)
+
+
+def main(argv):
+    import concurrent.futures as cf
+    import multiprocessing as mp
+    cases = int(argv[1]) if len(argv) > 1 else 100
+    seed = int(argv[2]) if len(argv) > 2 else 0
+    mode = argv[3] if len(argv) > 3 else "bi"
+    if mode not in MODES:
+        raise SystemExit(f"mode must be one of {MODES}")
+    flags = set(argv[4:])
+    only = {int(c) for c in os.environ["FUZZ_ONLY"].split(",")} if os.environ.get("FUZZ_ONLY") else None
+    draws = draw_cases(cases, seed, mode, flags, only)
+
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import _variant
+    _variant.use_from_environment()       # PHOVO_TOOLS_LIBRARY=<another build>: sweep that build instead (tools/_variant.py)
+    import phovo_amd  # noqa: F401
+
+    jobs = int(os.environ.get("FUZZ_JOBS", min(12, os.cpu_count() or 1)))
+    for v in ("OMP_NUM_THREADS", "OPENBLAS_NUM_THREADS", "MKL_NUM_THREADS"):
+        os.environ[v] = "1"                 # (inherited by the workers: one thread each)
+    bad = skipped = done = conditioned = 0
+    worst, geos, pending = 0.0, {}, []
+
+    def settle(fut, case, d):
+        nonlocal bad, skipped, done, worst, conditioned
+        r = fut.result()
+        done += 1
+        desc = (f"case {case}: {d['w']}x{d['h']} levels {d['nl']} pairs {d['n_pairs']} range {d['range']} upload "
+                f"{d['upload_range']} src {d['src_defects']} tgt {d['tgt_defects']}")
+        if r["status"] == "fail":
+            bad += 1
+            print(f"FAIL {desc}: {r['msg']}", flush=True)
+        elif r["status"] == "skip":
+            skipped += 1
+            print(f"knife-edge {desc}: {r['msg']}", flush=True)
+        else:
+            worst = max(worst, r["ratio"])
+            conditioned += int(r["status"] == "conditioned")
+        if done % 100 == 0:
+            print(f"... {done} cases so far, {bad} failures, {skipped} skipped", flush=True)
+
+    with cf.ProcessPoolExecutor(max_workers=jobs, mp_context=mp.get_context("spawn")) as pool:
+        for case, d in draws.items():
+            job, g = run_device(d)
+            for x in g:
+                geos[x] = geos.get(x, 0) + 1
+            pending.append((pool.submit(check_job, job), case, d))
+            while len(pending) > 3 * jobs:
+                settle(*pending.pop(0))
+        for item in pending:
+            settle(*item)
+    n = len(draws)
+    print(f"{n} cases, {bad} failures, {skipped} skipped as knife-edge, worst distance / bar {worst:.3f}"
+          + (f"; {conditioned} passed only under the bars conditioned on cond(J^T J)" if mode == "tr" else ""))
+    what = "tile classes predicted from the level sizes" if mode == "eval" else "from the launch records"
+    print(f"geometries exercised ({mode}, {what}): " + ", ".join(f"{k}: {v}" for k, v in sorted(geos.items())))
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv))

@@ -41,6 +41,7 @@ _variant.use_from_environment()       # PHOVO_TOOLS_LIBRARY=<a diagnostic build>
 import phovo_amd  # noqa: E402,F401
 from phovo_amd import native, odometry, se3, synthetic  # noqa: E402
 from oracle import oracle  # noqa: E402
+from fuzz_draws import draw_angle, worst_condition  # noqa: E402,F401
 
 cases = int(sys.argv[1]) if len(sys.argv) > 1 else 150
 rs = np.random.RandomState(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
@@ -52,39 +53,6 @@ bad, worst, variants, fallbacks = 0, 0.0, {}, 0
 worst_ratio, worst_cond, ill = 0.0, 0.0, 0
 worst_ill, ill_only_by_scaling = 0.0, 0
 chaotic = 0
-
-
-def worst_condition(trace):
-    c = 1.0
-    for e in trace:
-        h = e["hessian"]
-        if np.all(np.isfinite(h)) and np.any(h != 0.0):
-            c = max(c, float(np.linalg.cond(h)))
-    return c
-
-
-P4 = 0.78539816339744828          # fl(pi/4): beyond it the device takes the library's sincos
-
-
-def draw_angle(rs, axis, truth):
-    """One Euler angle of an initial state (axis 0 = yaw): every branch of the device's sin / cos and both thresholds."""
-    kind, sign, u = int(rs.randint(0, 7)), float(rs.choice([-1.0, 1.0])), rs.rand()
-    if kind == 0:
-        return truth + 0.05 * (u - 0.5)                                   # near the truth (for yaw: up to 0.9 rad)
-    if kind == 1:
-        return sign * 0.3 * u                                             # branch 1
-    if kind == 2:
-        return sign * (0.3 + (P4 - 0.3) * u)                              # branch 2
-    if kind == 3:                                                         # within 3 ulp of 0.3, 0.78125, fl(pi/4)
-        a, steps = float(rs.choice([0.3, 0.78125, P4])), int(rs.randint(-3, 4))
-        for _ in range(abs(steps)):
-            a = float(np.nextafter(a, np.inf if steps > 0 else -np.inf))
-        return sign * a
-    if kind == 4:
-        return sign * (P4 + 0.5 * u)                                      # branch 3, just beyond
-    if kind == 5 and axis > 0:
-        return sign * (np.pi - 0.2 - 0.3 * u)                             # pitch / roll beyond pi/2: behind the camera
-    return sign * 0.01 * u
 
 
 # FUZZ_ONLY=12,345: replay the random draws of every case but run only these (to look at a failure again)

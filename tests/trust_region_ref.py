@@ -246,6 +246,14 @@ def _margin(a, b):
     return abs(a - b) / den if np.isfinite(den) else 1.0
 
 
+def _cond(ev):
+    """Condition number of an evaluation's J^T J (1 where it is zero or not finite; inf where it is singular)."""
+    H = ev["H"]
+    if not (np.all(np.isfinite(H)) and np.any(H != 0.0)):
+        return 1.0
+    return float(np.linalg.cond(H))
+
+
 def optimize_level(evaluate_at, x0, max_iterations, function_tolerance, gradient_tolerance, parameter_tolerance,
                    initial_radius, max_radius, min_radius, min_relative_decrease):
     """(c) One level.  evaluate_at(x) returns a dict of `system`.  Returns (x, record) with record
@@ -254,7 +262,7 @@ def optimize_level(evaluate_at, x0, max_iterations, function_tolerance, gradient
     ev = evaluate_at(x)
     rec = dict(steps=0, accepted=0, termination=None, rows=ev["rows"], initial_cost=ev["cost"], final_cost=ev["cost"],
                final_radius=initial_radius, g=ev["g"], S=np.zeros(6), decisions=[], margins=[], min_rel_dc=np.inf,
-               noise_from=None, accepted_before_noise=0)
+               noise_from=None, accepted_before_noise=0, x0=x.copy(), g0=ev["g"], H=ev["H"], cond=_cond(ev))
     if not (np.isfinite(ev["cost"]) and ev["finite"]):
         rec["termination"] = TR_EVALUATION_FAILED
         return x, rec
@@ -334,6 +342,7 @@ def optimize_level(evaluate_at, x0, max_iterations, function_tolerance, gradient
             x = cand
             cur = cev
             rec["accepted"] += 1
+            rec["cond"] = max(rec["cond"], _cond(cev))
             if not cev["finite"]:
                 term = TR_EVALUATION_FAILED
                 break
@@ -343,7 +352,7 @@ def optimize_level(evaluate_at, x0, max_iterations, function_tolerance, gradient
             radius /= decrease
             decrease *= 2.0
             ok = False
-    rec.update(steps=it, termination=term, rows=cur["rows"], final_cost=cur["cost"], final_radius=radius, g=cur["g"])
+    rec.update(steps=it, termination=term, rows=cur["rows"], final_cost=cur["cost"], final_radius=radius, g=cur["g"], H=cur["H"])
     return x, rec
 
 
