@@ -84,6 +84,24 @@ class CPhotoconsistencyOdometryAnalytic : public CPhotoconsistencyOdometry<TPixe
                                           intensityImage.cols, intensityImage.rows), "SetTargetFrame");
   }
 
+  // Not in the reference: Set*Frame for images that already live in DEVICE memory (phovo_device_image: pointer, strides in
+  // bytes, PHOVO_IMAGE_* format; phovo_hip.h has the ordering contract on `stream`, the hipStream_t of the producer).
+  // No host round trip and no host synchronisation.  The classes derived from this one inherit both; under the
+  // bi-objective the target's depth is required, otherwise it is ignored and may be NULL.
+  void SetSourceFrameDevice(const phovo_device_image &intensityImage, const phovo_device_image &depthImage, int width,
+                            int height, double depthScale = 1.0, void *stream = nullptr)
+  {
+    Check(phovo_odometry_set_source_frame_device(m_Handle, &intensityImage, &depthImage, depthScale, width, height, stream),
+          "SetSourceFrameDevice");
+  }
+
+  void SetTargetFrameDevice(const phovo_device_image &intensityImage, const phovo_device_image *depthImage, int width,
+                            int height, double depthScale = 1.0, void *stream = nullptr)
+  {
+    Check(phovo_odometry_set_target_frame_device(m_Handle, &intensityImage, depthImage, depthScale, width, height, stream),
+          "SetTargetFrameDevice");
+  }
+
   void SetInitialStateVector(const Vector6Type &initialStateVector)
   {
     double s[6];

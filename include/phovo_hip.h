@@ -427,6 +427,87 @@ int phovo_engine_upload_frames_u16(phovo_engine *e, int first_frame, int count, 
                                    const uint8_t *intensity, size_t intensity_stride, size_t intensity_frame_stride,
                                    const uint16_t *depth, size_t depth_stride, size_t depth_frame_stride,
                                    double depth_scale);
+/* ---- frames that already live in device memory ---------------------------------------
+ * A batch of images in DEVICE memory of the engine's device, with the caller's strides.  Formats:
+ *   intensity  PHOVO_IMAGE_U8_GRAY            1 byte per pixel
+ *              PHOVO_IMAGE_U8_RGB / _U8_BGR   3 interleaved bytes per pixel, reduced to gray on the device by
+ *                                             (9797 R + 19234 G + 3737 B + 16384) >> 15 -- the project's one colour
+ *                                             rule, the one apps/io/png_io.cpp applies to a colour PNG; integer
+ *                                             arithmetic, so the device result equals read_gray8 on the same pixels
+ *                                             exactly.  As that file says, the coefficients are RECALLED from OpenCV's
+ *                                             cvtColor and could not be checked against it (OpenCV is absent here): this
+ *                                             is NOT a claim of OpenCV parity.
+ *   depth      PHOVO_IMAGE_F64                metres; depth_scale must be 1
+ *              PHOVO_IMAGE_F32 / _F16 / _U16  depth = (double)value * depth_scale (one exact conversion, one fp64 multiply)
+ * Rows are row_stride_bytes apart (>= width * bytes per pixel), frames frame_stride_bytes apart; for count > 1 a frame
+ * must end before the next one starts (frame_stride_bytes >= (height - 1) * row_stride_bytes + width * bytes per
+ * pixel); with count == 1 frame_stride_bytes is not looked at.  No alignment is required; rows and frames that start on
+ * 16-byte boundaries (and a width of whole 16-byte groups) take the wide form of the packing kernel. */
+#define PHOVO_IMAGE_U8_GRAY 0
+#define PHOVO_IMAGE_U8_RGB  1
+#define PHOVO_IMAGE_U8_BGR  2
+#define PHOVO_IMAGE_F64     3
+#define PHOVO_IMAGE_F32     4
+#define PHOVO_IMAGE_F16     5
+#define PHOVO_IMAGE_U16     6
+typedef struct phovo_device_image {
+  const void *data;          /* device pointer, on the engine's device */
+  size_t row_stride_bytes;   /* >= width * bytes per pixel              */
+  size_t frame_stride_bytes; /* distance between consecutive frames     */
+  int    format;             /* PHOVO_IMAGE_*                            */
+  int    reserved;           /* 0                                         */
+} phovo_device_image;
+/* phovo_engine_upload_frames[_u16] for frames in device memory: no host round trip.  The pool slots
+ * first_frame .. first_frame + count - 1 end up holding exactly -- bit for bit, on every stored level, under every plane
+ * storage, blur setting, role and objective -- the planes that the host upload of the same pixel values gives (for F32 /
+ * F16 depth: of the fp64 values (double)value * depth_scale): one packing launch per kind and chunk of 32 frames writes
+ * the engine's raw-frame staging buffers, and the same pyramid producers run on them.  depth may be NULL for pure target
+ * frames (and is not read for them), except under the bi-objective.  `stream` is the hipStream_t on which the caller
+ * produced the images (NULL: the default stream); it must belong to the engine's device.
+ * Ordering -- there is no host synchronisation with the device work of this call (the first call, and a call that needs
+ * larger staging buffers than any before, allocate them and wait for the engine's stream once):
+ *   - the engine's stream waits, by event, for everything queued on `stream` before the call: the images need not be
+ *     complete, only queued, when the call is made;
+ *   - `stream` waits, by event, for the last kernel that reads the caller's memory: work queued on `stream` AFTER the
+ *     call returns may overwrite or free the buffers.  The caller must NOT touch them from another stream or from the
+ *     host, nor free them with hipFree from a thread that bypasses `stream`, until `stream` has passed that point
+ *     (hipStreamSynchronize(stream) or an event recorded on it after the call);
+ *   - the call waits on the host for every enqueue in flight before it queues anything, as the host uploads do;
+ *   - phovo_engine_enqueue_align / align_pairs / evaluate_pairs, plane reads and writes, and later uploads are ordered
+ *     behind the ingest on the device, as they are behind a host upload; the call itself returns before the pyramids exist.
+ * Refusals, all before anything is queued and with the pool untouched (phovo_last_error names the argument):
+ *   PHOVO_E_INVALID_ARGUMENT  NULL engine or intensity; a source role, or a bi-objective target, without depth; a frame
+ *                             range outside the pool; empty roles; an unknown format, a depth format in `intensity` or an
+ *                             intensity format in `depth`; row_stride_bytes smaller than a row; frames that overlap;
+ *                             reserved != 0; depth_scale not finite, or not 1 with PHOVO_IMAGE_F64; a data pointer that
+ *                             hipPointerGetAttributes does not report as plain device memory OF THE ENGINE'S DEVICE (a host
+ *                             pointer, pinned or not, managed memory, another device's memory), or whose allocation
+ *                             (hipMemGetAddressRange) is unknown or ends before the last frame does
+ *   PHOVO_E_NOT_READY         no frame pool (phovo_engine_reserve_frames) */
+int phovo_engine_upload_frames_device(phovo_engine *e, int first_frame, int count, int roles,
+                                      const phovo_device_image *intensity,
+                                      const phovo_device_image *depth /* NULL for pure targets */,
+                                      double depth_scale, void *stream /* hipStream_t of the producer, NULL = default */);
+/* What the last phovo_engine_upload_frames_device of this engine launched: staging chunks, and how many packing launches
+ * took the wide (16-byte) and the scalar form. */
+typedef struct phovo_ingest_record {
+  int chunks;
+  int wide_launches;
+  int scalar_launches;
+  int reserved;
+} phovo_ingest_record;
+int phovo_engine_last_ingest(const phovo_engine *e, phovo_ingest_record *out);
+/* Single pair: Set*Frame (phovo_odometry_set_source_frame / _set_target_frame) for images in device memory:
+ * phovo_engine_upload_frames_device with count 1 (same descriptors, same ordering on `stream`, same refusals -- checked before the pool is (re)allocated for a new size).  Like Set*Frame they drop the
+ * evaluated-system state (phovo_odometry_get_pair_system is PHOVO_E_NOT_READY until the next Optimize()); the target's
+ * depth is ignored (may be NULL) except under the bi-objective. */
+int phovo_odometry_set_source_frame_device(phovo_odometry *o, const phovo_device_image *intensity,
+                                           const phovo_device_image *depth, double depth_scale,
+                                           int width, int height, void *stream);
+int phovo_odometry_set_target_frame_device(phovo_odometry *o, const phovo_device_image *intensity,
+                                           const phovo_device_image *depth, double depth_scale,
+                                           int width, int height, void *stream);
+
 /* Direct access to the planes of one level of one frame as fp64 (w*h doubles each, NULL = skip): lets a
  * caller supply pyramids built elsewhere (e.g. by OpenCV) or read back the device-built ones.  With a narrower
  * plane_storage, set rounds to the storage type and get returns the stored (rounded) values. */

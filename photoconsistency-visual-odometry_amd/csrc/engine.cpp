@@ -104,6 +104,11 @@ struct phovo_engine {
   hipStream_t stream = nullptr;                // uploads, pyramid producers, plane access
   hipStream_t copy_stream = nullptr;           // batched uploads: host-to-device copies of chunk i+1 run beside the pyramid kernels of chunk i
   hipEvent_t ev_copied[2] = {}, ev_built[2] = {};     // per staging half
+  // phovo_engine_upload_frames_device: the producer's work so far (recorded on its stream), the last read of its memory
+  // and the end of the pyramid build (both recorded on `stream`)
+  hipEvent_t ev_ingest_produced = nullptr, ev_ingest_read = nullptr, ev_ingested = nullptr;
+  bool ingest_pending = false;                 // `stream` may still be building an ingest's pyramids: enqueues wait for ev_ingested
+  phovo_ingest_record last_ingest{};
   AlignSlot slots[PHOVO_ENQUEUE_DEPTH];
   int ticket = 0;                              // tickets handed out so far; enqueue t lives in slots[t % PHOVO_ENQUEUE_DEPTH]
 
@@ -149,6 +154,8 @@ namespace {
 
 void free_pool(phovo_engine *e)
 {
+  if (e->ingest_pending && e->stream) (void)hipStreamSynchronize(e->stream);      // a device ingest may still be building
+  e->ingest_pending = false;
   for (auto &lv : e->levels) {
     if (lv.planes) (void)hipFree(lv.planes);
     lv = LevelPool{};
@@ -529,6 +536,8 @@ int phovo_engine_create(int device, phovo_engine **out)
     he = hipEventCreateWithFlags(&e->ev_copied[i], hipEventDisableTiming);
     if (he == hipSuccess) he = hipEventCreateWithFlags(&e->ev_built[i], hipEventDisableTiming);
   }
+  for (hipEvent_t *ev : {&e->ev_ingest_produced, &e->ev_ingest_read, &e->ev_ingested})
+    if (he == hipSuccess) he = hipEventCreateWithFlags(ev, hipEventDisableTiming);
   for (AlignSlot &s : e->slots) {
     if (he == hipSuccess) he = hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking);
     if (he == hipSuccess) he = hipEventCreate(&s.ev_total_start);
@@ -577,6 +586,8 @@ int phovo_engine_destroy(phovo_engine *e)
     if (e->ev_copied[i]) (void)hipEventDestroy(e->ev_copied[i]);
     if (e->ev_built[i]) (void)hipEventDestroy(e->ev_built[i]);
   }
+  for (hipEvent_t ev : {e->ev_ingest_produced, e->ev_ingest_read, e->ev_ingested})
+    if (ev) (void)hipEventDestroy(ev);
   if (e->copy_stream) (void)hipStreamDestroy(e->copy_stream);
   if (e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
@@ -1032,6 +1043,7 @@ static int upload_batch(phovo_engine *e, int first_frame, int count, int roles,
   // the caller's buffers may be reused on return, and the staging buffers by the next upload
   PHOVO_HIP_CHECK(hipStreamSynchronize(e->copy_stream));
   PHOVO_HIP_CHECK(hipStreamSynchronize(e->stream));
+  e->ingest_pending = false;
   for (size_t i = (size_t)first_frame * PHOVO_MAX_LEVELS; i < (size_t)(first_frame + count) * PHOVO_MAX_LEVELS; i++)
     e->frame_roles[i] |= (unsigned char)(roles & PHOVO_ROLE_BOTH);
   return PHOVO_OK;
@@ -1066,6 +1078,146 @@ int phovo_engine_upload_frames_u16(phovo_engine *e, int first_frame, int count, 
 {
   return upload_batch(e, first_frame, count, roles, intensity, intensity_stride, intensity_frame_stride,
                       depth, depth_stride, depth_frame_stride, DEPTH_U16, depth_scale);
+}
+
+/* ---- frames in device memory (phovo_hip.h) ---- */
+
+// Everything phovo_engine_upload_frames_device refuses about one descriptor, for `count` frames of w x h.
+static int ingest_check_image(const phovo_engine *e, const char *which, const phovo_device_image *img, bool is_depth,
+                              int count, int w, int h)
+{
+  const std::string who = std::string("upload_frames_device: ") + which;
+  const int bpp = ingest_source_pixel_bytes(img->format);
+  if (bpp == 0) return fail(PHOVO_E_INVALID_ARGUMENT, who + ".format is not a PHOVO_IMAGE_* value");
+  const bool depth_format = img->format == PHOVO_IMAGE_F64 || img->format == PHOVO_IMAGE_F32 ||
+                            img->format == PHOVO_IMAGE_F16 || img->format == PHOVO_IMAGE_U16;
+  if (depth_format != is_depth)
+    return fail(PHOVO_E_INVALID_ARGUMENT, who + (is_depth ? ".format is an intensity format" : ".format is a depth format"));
+  if (img->reserved != 0) return fail(PHOVO_E_INVALID_ARGUMENT, who + ".reserved must be 0");
+  if (!img->data) return fail(PHOVO_E_INVALID_ARGUMENT, who + ".data is null");
+  const size_t row = (size_t)w * (size_t)bpp;
+  if (img->row_stride_bytes < row) return fail(PHOVO_E_INVALID_ARGUMENT, who + ".row_stride_bytes is smaller than a row");
+  const size_t frame_extent = (size_t)(h - 1) * img->row_stride_bytes + row;
+  if (count > 1 && img->frame_stride_bytes < frame_extent)
+    return fail(PHOVO_E_INVALID_ARGUMENT, who + ".frame_stride_bytes makes consecutive frames overlap");
+  hipPointerAttribute_t attr{};
+  const hipError_t he = hipPointerGetAttributes(&attr, img->data);
+  if (he != hipSuccess) {
+    (void)hipGetLastError();                     // (an unregistered host pointer is an error of the query, not of the device)
+    return fail(PHOVO_E_INVALID_ARGUMENT, who + ".data is not device memory (" + hipGetErrorString(he) + ")");
+  }
+  if (attr.type != hipMemoryTypeDevice || attr.isManaged)
+    return fail(PHOVO_E_INVALID_ARGUMENT, who + ".data is not plain device memory (host, pinned or managed memory)");
+  if (attr.device != e->device)
+    return fail(PHOVO_E_INVALID_ARGUMENT, who + ".data belongs to device " + std::to_string(attr.device) +
+                                              ", the engine to device " + std::to_string(e->device));
+  // the packing kernel reads [data, data + extent): it must lie inside the allocation (where the runtime knows its range)
+  hipDeviceptr_t base = nullptr;
+  size_t bytes = 0;
+  if (hipMemGetAddressRange(&base, &bytes, const_cast<void *>(img->data)) == hipSuccess) {
+    const size_t extent = (size_t)(count - 1) * (count > 1 ? img->frame_stride_bytes : 0) + frame_extent;
+    const size_t offset = (size_t)(static_cast<const char *>(img->data) - static_cast<const char *>(base));
+    if (offset > bytes || extent > bytes - offset)
+      return fail(PHOVO_E_INVALID_ARGUMENT, who + ".data: the frames reach beyond the end of the allocation");
+  } else {                                       // (no range, no bound on what the kernel would read)
+    (void)hipGetLastError();
+    return fail(PHOVO_E_INVALID_ARGUMENT, who + ".data: the runtime cannot name the allocation it belongs to");
+  }
+  return PHOVO_OK;
+}
+
+// All refusals that do not depend on the pool; w x h is the frame size the images are taken to have.
+static int ingest_check(const phovo_engine *e, int count, int roles, const phovo_device_image *intensity,
+                        const phovo_device_image *depth, double depth_scale, int w, int h)
+{
+  if (!e || !intensity) return fail(PHOVO_E_INVALID_ARGUMENT, "upload_frames_device: null engine or intensity");
+  if ((roles & PHOVO_ROLE_BOTH) == 0) return fail(PHOVO_E_INVALID_ARGUMENT, "upload_frames_device: roles empty");
+  if ((roles & PHOVO_ROLE_SOURCE) && !depth)
+    return fail(PHOVO_E_INVALID_ARGUMENT, "upload_frames_device: depth is null, a source frame needs it");
+  if (e->objective == PHOVO_OBJECTIVE_BIOBJECTIVE && (roles & PHOVO_ROLE_TARGET) && !depth)
+    return fail(PHOVO_E_INVALID_ARGUMENT, "upload_frames_device: depth is null, under the bi-objective a target frame needs it");
+  if (!std::isfinite(depth_scale)) return fail(PHOVO_E_INVALID_ARGUMENT, "upload_frames_device: depth_scale is not finite");
+  if (depth && depth->format == PHOVO_IMAGE_F64 && depth_scale != 1.0)
+    return fail(PHOVO_E_INVALID_ARGUMENT, "upload_frames_device: depth_scale must be 1 with PHOVO_IMAGE_F64");
+  PHOVO_HIP_CHECK(hipSetDevice(e->device));
+  int st = ingest_check_image(e, "intensity", intensity, false, count, w, h);
+  if (st == PHOVO_OK && depth) st = ingest_check_image(e, "depth", depth, true, count, w, h);
+  return st;
+}
+
+int phovo_engine_upload_frames_device(phovo_engine *e, int first_frame, int count, int roles,
+                                      const phovo_device_image *intensity, const phovo_device_image *depth,
+                                      double depth_scale, void *stream)
+{
+  if (!e || !intensity) return fail(PHOVO_E_INVALID_ARGUMENT, "upload_frames_device: null engine or intensity");
+  if (e->n_frames == 0) return fail(PHOVO_E_NOT_READY, "upload_frames_device: reserve_frames first");
+  if (count < 0 || first_frame < 0 || first_frame + count > e->n_frames)
+    return fail(PHOVO_E_INVALID_ARGUMENT, "upload_frames_device: first_frame / count out of the reserved pool");
+  int st = ingest_check(e, count, roles, intensity, depth, depth_scale, e->width, e->height);
+  if (st != PHOVO_OK) return st;
+  const bool bi_target = e->objective == PHOVO_OBJECTIVE_BIOBJECTIVE && (roles & PHOVO_ROLE_TARGET);
+  const bool want_depth = (roles & PHOVO_ROLE_SOURCE) || bi_target;
+  // u16 goes to the u16 staging and is scaled by the producers, as in a host u16 upload; everything else is staged as
+  // fp64 metres (f32 / f16 scaled by the packing kernel)
+  const DepthKind kind = !want_depth ? DEPTH_NONE : depth->format == PHOVO_IMAGE_U16 ? DEPTH_U16 : DEPTH_F64;
+  if (count == 0) return PHOVO_OK;
+  hipStream_t producer = static_cast<hipStream_t>(stream);
+  PHOVO_HIP_CHECK(quiesce(e));                 // (an alignment in flight may be reading the frames about to be replaced)
+  const int chunk_cap = count < STAGE_CHUNK ? count : STAGE_CHUNK;
+  const bool two_halves = count > chunk_cap;   // the host path's two staging halves, here both on the engine's stream
+  st = ensure_stage(e, two_halves ? 2 * chunk_cap : chunk_cap, kind == DEPTH_F64, kind == DEPTH_U16);
+  if (st != PHOVO_OK) return st;
+  const size_t px = (size_t)e->width * (size_t)e->height;
+  // nothing of the caller's may be read after an error return
+  auto drain = [&](int status) { (void)hipStreamSynchronize(e->stream); return status; };
+#define PHOVO_INGEST_CHECK(expr)                                                                              \
+  do {                                                                                                        \
+    hipError_t _e = (expr);                                                                                   \
+    if (_e != hipSuccess) return drain(fail(PHOVO_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e))); \
+  } while (0)
+  // the producer's work so far comes first
+  PHOVO_INGEST_CHECK(hipEventRecord(e->ev_ingest_produced, producer));
+  PHOVO_INGEST_CHECK(hipStreamWaitEvent(e->stream, e->ev_ingest_produced, 0));
+  phovo_ingest_record rec{};
+  for (int done = 0; done < count; done += chunk_cap, rec.chunks++) {
+    const int c = count - done < chunk_cap ? count - done : chunk_cap;
+    const int off = two_halves ? (rec.chunks & 1) * chunk_cap : 0;
+    bool wide = false;
+    PHOVO_INGEST_CHECK(ingest_pack(intensity->format,
+                                   static_cast<const char *>(intensity->data) + intensity->frame_stride_bytes * (size_t)done,
+                                   intensity->row_stride_bytes, intensity->frame_stride_bytes, c, e->width, e->height, 1.0,
+                                   e->d_gray + px * (size_t)off, &wide, e->stream));
+    (wide ? rec.wide_launches : rec.scalar_launches)++;
+    if (kind != DEPTH_NONE) {
+      void *dst = kind == DEPTH_U16 ? static_cast<void *>(e->d_depth16 + px * (size_t)off)
+                                    : static_cast<void *>(e->d_depth + px * (size_t)off);
+      PHOVO_INGEST_CHECK(ingest_pack(depth->format,
+                                     static_cast<const char *>(depth->data) + depth->frame_stride_bytes * (size_t)done,
+                                     depth->row_stride_bytes, depth->frame_stride_bytes, c, e->width, e->height, depth_scale,
+                                     dst, &wide, e->stream));
+      (wide ? rec.wide_launches : rec.scalar_launches)++;
+    }
+    if (done + c == count) {                   // the caller's memory has been read: its stream may go on behind this point
+      PHOVO_INGEST_CHECK(hipEventRecord(e->ev_ingest_read, e->stream));
+      PHOVO_INGEST_CHECK(hipStreamWaitEvent(producer, e->ev_ingest_read, 0));
+    }
+    st = build_pyramids(e, first_frame + done, c, roles, kind, kind == DEPTH_U16 ? depth_scale : 1.0, off);
+    if (st != PHOVO_OK) return drain(st);
+  }
+  PHOVO_INGEST_CHECK(hipEventRecord(e->ev_ingested, e->stream));
+#undef PHOVO_INGEST_CHECK
+  e->ingest_pending = true;
+  e->last_ingest = rec;
+  for (size_t i = (size_t)first_frame * PHOVO_MAX_LEVELS; i < (size_t)(first_frame + count) * PHOVO_MAX_LEVELS; i++)
+    e->frame_roles[i] |= (unsigned char)(roles & PHOVO_ROLE_BOTH);
+  return PHOVO_OK;
+}
+
+int phovo_engine_last_ingest(const phovo_engine *e, phovo_ingest_record *out)
+{
+  if (!e || !out) return fail(PHOVO_E_INVALID_ARGUMENT, "last_ingest: null");
+  *out = e->last_ingest;
+  return PHOVO_OK;
 }
 
 static int plane_access_check(const phovo_engine *e, int frame, int level)
@@ -1244,7 +1396,9 @@ int phovo_engine_enqueue_align(phovo_engine *e, int n_pairs, const int *source_f
     s.ticket = ticket;
     return PHOVO_OK;
   }
-  // planes written on the engine's own stream so far (uploads return synchronised; plane setters too): nothing to order
+  // planes written on the engine's own stream so far (uploads return synchronised; plane setters too): nothing to order --
+  // except behind a device ingest, which returns while the pyramids are still being built
+  if (e->ingest_pending) PHOVO_HIP_CHECK(hipStreamWaitEvent(s.stream, e->ev_ingested, 0));
   int st = ensure_pairs(s, n_pairs);
   if (st != PHOVO_OK) return st;
 
@@ -1508,6 +1662,7 @@ int phovo_engine_synchronize(phovo_engine *e)
   if (!e) return fail(PHOVO_E_INVALID_ARGUMENT, "synchronize: null");
   PHOVO_HIP_CHECK(hipSetDevice(e->device));
   PHOVO_HIP_CHECK(hipStreamSynchronize(e->stream));
+  e->ingest_pending = false;
   PHOVO_HIP_CHECK(quiesce(e));
   return PHOVO_OK;
 }
@@ -1775,6 +1930,27 @@ int odometry_set_frame(phovo_odometry *o, int slot, int role, const uint8_t *int
   return PHOVO_OK;
 }
 
+int odometry_set_frame_device(phovo_odometry *o, int slot, int role, const phovo_device_image *intensity,
+                              const phovo_device_image *depth, double depth_scale, int width, int height, void *stream)
+{
+  if (!o || !intensity) return fail(PHOVO_E_INVALID_ARGUMENT, "Set*FrameDevice: null odometry or intensity");
+  if (width < 1 || height < 1) return fail(PHOVO_E_INVALID_ARGUMENT, "Set*FrameDevice: empty image");
+  phovo_engine *e = o->engine;
+  if (e->n_frames == 0 || e->width != width || e->height != height) {
+    // (every refusal comes before the pool is dropped for the new size)
+    int st = ingest_check(e, 1, role, intensity, depth, depth_scale, width, height);
+    if (st != PHOVO_OK) return st;
+    st = phovo_engine_reserve_frames(e, 2, width, height);
+    if (st != PHOVO_OK) return st;
+    o->have_source = o->have_target = false;
+  }
+  const int st = phovo_engine_upload_frames_device(e, slot, 1, role, intensity, depth, depth_scale, stream);
+  if (st != PHOVO_OK) return st;
+  if (slot == 0) o->have_source = true; else o->have_target = true;
+  o->optimized = false;
+  return PHOVO_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1903,6 +2079,26 @@ int phovo_odometry_set_target_frame(phovo_odometry *o, const uint8_t *intensity,
   }
   (void)depth; (void)dstride;                      // "Depth image is ignored"  :478
   return odometry_set_frame(o, 1, PHOVO_ROLE_TARGET, intensity, istride, nullptr, 0, width, height);
+}
+
+int phovo_odometry_set_source_frame_device(phovo_odometry *o, const phovo_device_image *intensity,
+                                           const phovo_device_image *depth, double depth_scale, int width, int height,
+                                           void *stream)
+{
+  if (!depth) return fail(PHOVO_E_INVALID_ARGUMENT, "SetSourceFrameDevice: depth is required");
+  return odometry_set_frame_device(o, 0, PHOVO_ROLE_SOURCE, intensity, depth, depth_scale, width, height, stream);
+}
+
+int phovo_odometry_set_target_frame_device(phovo_odometry *o, const phovo_device_image *intensity,
+                                           const phovo_device_image *depth, double depth_scale, int width, int height,
+                                           void *stream)
+{
+  if (o && o->engine->objective == PHOVO_OBJECTIVE_BIOBJECTIVE) {       // the target keeps its depth
+    if (!depth) return fail(PHOVO_E_INVALID_ARGUMENT, "SetTargetFrameDevice: the bi-objective needs the target's depth");
+    return odometry_set_frame_device(o, 1, PHOVO_ROLE_TARGET, intensity, depth, depth_scale, width, height, stream);
+  }
+  // "Depth image is ignored"  :478
+  return odometry_set_frame_device(o, 1, PHOVO_ROLE_TARGET, intensity, nullptr, 1.0, width, height, stream);
 }
 
 int phovo_odometry_set_initial_state_vector(phovo_odometry *o, const double state[6])

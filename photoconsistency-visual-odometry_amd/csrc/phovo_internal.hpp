@@ -198,6 +198,12 @@ hipError_t pyr_gaussian_blur(double *img, double *tmp, int w, int h, int ksize,
                              const double *d_kernel, hipStream_t stream);
 hipError_t fill_i32(int *dst, size_t n, int value, hipStream_t stream);
 
+// ingest_kernels.hip: packs `frames` strided frames of a PHOVO_IMAGE_* format from device memory into packed staging
+// (u8 gray -> u8, u16 -> u16, f64 / f32 / f16 -> f64 with the scale applied to f32 and f16).  *wide tells which form ran.
+int ingest_source_pixel_bytes(int format);     // 0: unknown format
+hipError_t ingest_pack(int format, const void *src, size_t row_stride, size_t frame_stride, int frames, int w, int h,
+                       double scale, void *dst, bool *wide, hipStream_t stream);
+
 // Diagnostic switches read from the environment exist only in a -DPHOVO_TUNING build (tools/); the release library reads
 // PHOVO_VISUALIZE_DIR and nothing else.
 #ifdef PHOVO_TUNING

@@ -115,6 +115,26 @@ class LaunchRecord(C.Structure):
     ]
 
 
+# phovo_device_image.format
+IMAGE_U8_GRAY, IMAGE_U8_RGB, IMAGE_U8_BGR, IMAGE_F64, IMAGE_F32, IMAGE_F16, IMAGE_U16 = range(7)
+
+
+class DeviceImage(C.Structure):
+    """phovo_device_image: a batch of images in device memory, strides in bytes."""
+    _fields_ = [
+        ("data", C.c_void_p),
+        ("row_stride_bytes", C.c_size_t),
+        ("frame_stride_bytes", C.c_size_t),
+        ("format", C.c_int),
+        ("reserved", C.c_int),
+    ]
+
+
+class IngestRecord(C.Structure):
+    """phovo_ingest_record: what the last upload_frames_device launched."""
+    _fields_ = [("chunks", C.c_int), ("wide_launches", C.c_int), ("scalar_launches", C.c_int), ("reserved", C.c_int)]
+
+
 # name -> (restype, argtypes); every symbol include/phovo_hip.h declares
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)
@@ -187,6 +207,13 @@ SYMBOLS = {
     "phovo_engine_upload_frame_u16": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_size_t, _vp, C.c_size_t, C.c_double]),
     "phovo_engine_upload_frames": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_size_t, C.c_size_t, _vp, C.c_size_t, C.c_size_t]),
     "phovo_engine_upload_frames_u16": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_size_t, C.c_size_t, _vp, C.c_size_t, C.c_size_t, C.c_double]),
+    "phovo_engine_upload_frames_device": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(DeviceImage),
+                                                    C.POINTER(DeviceImage), C.c_double, _vp]),
+    "phovo_engine_last_ingest": (C.c_int, [_vp, C.POINTER(IngestRecord)]),
+    "phovo_odometry_set_source_frame_device": (C.c_int, [_vp, C.POINTER(DeviceImage), C.POINTER(DeviceImage), C.c_double,
+                                                         C.c_int, C.c_int, _vp]),
+    "phovo_odometry_set_target_frame_device": (C.c_int, [_vp, C.POINTER(DeviceImage), C.POINTER(DeviceImage), C.c_double,
+                                                         C.c_int, C.c_int, _vp]),
     "phovo_engine_set_level_planes": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "phovo_engine_get_level_planes": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "phovo_engine_get_level_depth_gradients": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),
@@ -257,6 +284,21 @@ def lib():
             fn.argtypes = args
         _lib = L
     return _lib
+
+
+def hip_runtimes_mapped():
+    """The distinct HIP runtime files (libamdhip64) mapped into this process.  More than one means that torch's wheel
+    brought its own runtime AFTER this library had loaded the system's: the two do not share devices or pointers, and the
+    device-memory entry points cannot work.  Import torch before the first use of this package and there is one."""
+    paths = set()
+    try:
+        with open("/proc/self/maps") as f:
+            for line in f:
+                if "libamdhip64" in line:
+                    paths.add(os.path.realpath(line.split(None, 5)[-1].strip()))
+    except OSError:
+        pass
+    return sorted(paths)
 
 
 def check(status, where):

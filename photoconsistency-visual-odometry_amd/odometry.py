@@ -28,6 +28,117 @@ def _f64img(a):
     return a
 
 
+def gray_from_colour(pixels, channel_order="rgb"):
+    """The project's one colour-to-gray rule, in numpy: (9797 R + 19234 G + 3737 B + 16384) >> 15 on u8 [..., 3] pixels --
+    what apps/io/png_io.cpp applies to a colour PNG and the device ingest to RGB / BGR frames (integer arithmetic: all
+    three agree exactly).  The coefficients are recalled from OpenCV's cvtColor, not checked against it."""
+    p = np.asarray(pixels)
+    if p.dtype != np.uint8 or p.shape[-1] != 3:
+        raise ValueError("pixels must be uint8 [..., 3]")
+    if channel_order not in ("rgb", "bgr"):
+        raise ValueError('channel_order must be "rgb" or "bgr"')
+    r, g, b = (p[..., i].astype(np.uint32) for i in ((0, 1, 2) if channel_order == "rgb" else (2, 1, 0)))
+    return ((9797 * r + 19234 * g + 3737 * b + 16384) >> 15).astype(np.uint8)
+
+
+def _depth_formats():
+    """torch dtype -> PHOVO_IMAGE_* of a depth tensor; int16 storage is read as uint16."""
+    import torch
+    formats = {torch.float64: native.IMAGE_F64, torch.float32: native.IMAGE_F32, torch.float16: native.IMAGE_F16,
+               torch.int16: native.IMAGE_U16}
+    if hasattr(torch, "uint16"):
+        formats[torch.uint16] = native.IMAGE_U16
+    return formats
+
+
+def _device_tensor(x, what, dtypes):
+    """x as a torch tensor in device memory, without a copy: a torch tensor, or anything torch can view through
+    __cuda_array_interface__ or DLPack.  A dtype outside `dtypes` and host memory are TypeErrors.  (torch is imported
+    here, not with the package.)"""
+    import torch
+    if isinstance(x, torch.Tensor):
+        t = x
+    elif hasattr(x, "__cuda_array_interface__"):
+        t = torch.as_tensor(x, device="cuda")
+    elif hasattr(x, "__dlpack__") and hasattr(x, "__dlpack_device__"):
+        t = torch.from_dlpack(x)
+    else:
+        raise TypeError(f"{what}: expected a torch tensor or an object with __cuda_array_interface__ / DLPack, got "
+                        f"{type(x).__name__}")
+    if t.dtype not in dtypes:
+        raise TypeError(f"{what} must be one of {', '.join(str(d) for d in dtypes)}, not {t.dtype}")
+    if t.device.type == "cuda" and len(native.hip_runtimes_mapped()) > 1:
+        raise RuntimeError("two HIP runtimes are loaded in this process (" + ", ".join(native.hip_runtimes_mapped()) + "): "
+                           "torch was imported after libphovo_hip.so had loaded the system's.  Import torch before the "
+                           "first use of phovo_amd so that both share one runtime")
+    if t.device.type != "cuda":
+        raise TypeError(f"{what} lives in host memory ({t.device}); upload_frames / Set*Frame take host arrays, the "
+                        "*_device / *Device forms take device memory")
+    return t
+
+
+def _torch_stream(stream, device):
+    """(torch stream object, raw hipStream_t handle) of `stream`: None = torch's current stream on `device`, a torch.cuda
+    stream, or a raw handle as int."""
+    import torch
+    if stream is None:
+        stream = torch.cuda.current_stream(device)
+    elif isinstance(stream, int):
+        stream = torch.cuda.ExternalStream(stream, device=device)
+    return stream, int(stream.cuda_stream)
+
+
+def _device_images(gray, depth, channel_order, stream, device, batched):
+    """phovo_device_image descriptors of gray ([F,H,W] u8 or [F,H,W,3] u8; without F unless batched) and depth ([F,H,W]
+    float64 / float32 / float16 / uint16, or int16 storage read as uint16; None).  Row and frame strides are the
+    tensors' own; only a pixel stride other than the element size (3 channels for colour) costs a .contiguous() copy, made
+    on `stream`.  Returns (intensity, depth or None, tensors to keep alive, (F, H, W), raw stream handle)."""
+    import torch
+    resolved = []
+
+    def the_stream():                        # (resolved after the tensors have been looked at: host memory is a TypeError
+        if not resolved:                     # on a machine without a device too)
+            resolved.extend(_torch_stream(stream, device))
+        return resolved
+
+    def packed(t, pixel_ok):
+        if pixel_ok:
+            return t
+        with torch.cuda.stream(the_stream()[0]):
+            return t.contiguous()
+
+    g = _device_tensor(gray, "gray", (torch.uint8,))
+    if not batched:
+        g = g.unsqueeze(0)
+    if g.ndim == 3:
+        fmt = native.IMAGE_U8_GRAY
+        g = packed(g, g.stride(2) == 1 or g.shape[2] == 1)
+    elif g.ndim == 4 and g.shape[3] == 3:
+        if channel_order not in ("rgb", "bgr"):
+            raise ValueError('channel_order must be "rgb" or "bgr"')
+        fmt = native.IMAGE_U8_RGB if channel_order == "rgb" else native.IMAGE_U8_BGR
+        g = packed(g, g.stride(3) == 1 and (g.stride(2) == 3 or g.shape[2] == 1))
+    else:
+        raise ValueError("gray must be [frames, height, width] or [frames, height, width, 3]"
+                         if batched else "gray must be [height, width] or [height, width, 3]")
+    f, h, w = int(g.shape[0]), int(g.shape[1]), int(g.shape[2])
+    gi = native.DeviceImage(g.data_ptr(), g.stride(1), g.stride(0), fmt, 0)
+    keep = [g]
+    di = None
+    if depth is not None:
+        formats = _depth_formats()
+        d = _device_tensor(depth, "depth", tuple(formats))
+        if not batched:
+            d = d.unsqueeze(0)
+        if d.ndim != 3 or tuple(d.shape) != (f, h, w):
+            raise ValueError(f"depth shape {tuple(d.shape)} does not match gray's frames x height x width {(f, h, w)}")
+        d = packed(d, d.stride(2) == 1 or w == 1)
+        es = d.element_size()
+        di = native.DeviceImage(d.data_ptr(), d.stride(1) * es, d.stride(0) * es, formats[d.dtype], 0)
+        keep.append(d)
+    return gi, di, keep, (f, h, w), the_stream()[1]
+
+
 def warpImage(intensityImage, depthImage, Rt, intrinsicMatrix, level=0, device=0):
     """phovo::warpImage (phovo/include/CPhotoconsistencyOdometry.h:73-134) on the device: forward warp of the source
     intensities into the target view (depth > 0 gate, truncating cast, last raster writer wins, zeros elsewhere).
@@ -53,6 +164,7 @@ class CPhotoconsistencyOdometryAnalytic:
         self._lib = native.lib()
         self._h = C.c_void_p()
         check(self._lib.phovo_odometry_create(int(device), C.byref(self._h)), "phovo_odometry_create")
+        self._device = int(device)
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
@@ -117,6 +229,26 @@ class CPhotoconsistencyOdometryAnalytic:
             d.ctypes.data if d is not None else None, d.strides[0] if d is not None else 0, w, h),
             "SetTargetFrame")
 
+    def SetSourceFrameDevice(self, intensityImage, depthImage, depth_scale=1.0, channel_order="rgb", stream=None):
+        """SetSourceFrame for images in device memory (torch tensors on this object's device, or anything torch views
+        through __cuda_array_interface__ / DLPack): [H,W] u8 or [H,W,3] u8 with channel_order, depth [H,W] float64, or
+        float32 / float16 / uint16 times depth_scale.  No host round trip and no synchronisation: the work is ordered
+        behind `stream` (None: torch's current stream), and `stream` may overwrite the tensors right after the call."""
+        if depthImage is None:
+            raise ValueError("a source frame needs its depth")
+        gi, di, _keep, (_, h, w), handle = _device_images(intensityImage, depthImage, channel_order, stream, self._device,
+                                                          batched=False)
+        check(self._lib.phovo_odometry_set_source_frame_device(self._h, C.byref(gi), C.byref(di), float(depth_scale), w, h,
+                                                               handle), "SetSourceFrameDevice")
+
+    def SetTargetFrameDevice(self, intensityImage, depthImage=None, depth_scale=1.0, channel_order="rgb", stream=None):
+        """SetTargetFrame for images in device memory (see SetSourceFrameDevice); the depth is ignored except under the
+        bi-objective."""
+        gi, di, _keep, (_, h, w), handle = _device_images(intensityImage, depthImage, channel_order, stream, self._device,
+                                                          batched=False)
+        check(self._lib.phovo_odometry_set_target_frame_device(self._h, C.byref(gi), C.byref(di) if di is not None else None,
+                                                               float(depth_scale), w, h, handle), "SetTargetFrameDevice")
+
     def SetInitialStateVector(self, initialStateVector):
         s = np.ascontiguousarray(initialStateVector, dtype=np.float64).reshape(6)
         check(self._lib.phovo_odometry_set_initial_state_vector(self._h, s.ctypes.data_as(C.POINTER(C.c_double))),
@@ -168,6 +300,11 @@ class CPhotoconsistencyOdometryBiObjective(CPhotoconsistencyOdometryAnalytic):
         if depthImage is None:
             raise ValueError("the bi-objective needs the target's depth")
         super().SetTargetFrame(intensityImage, depthImage)
+
+    def SetTargetFrameDevice(self, intensityImage, depthImage, depth_scale=1.0, channel_order="rgb", stream=None):
+        if depthImage is None:
+            raise ValueError("the bi-objective needs the target's depth")
+        super().SetTargetFrameDevice(intensityImage, depthImage, depth_scale, channel_order, stream)
 
 
 class CPhotoconsistencyOdometryCeres(CPhotoconsistencyOdometryAnalytic):
@@ -221,6 +358,7 @@ class AlignmentEngine:
         self._lib = native.lib()
         self._h = C.c_void_p()
         check(self._lib.phovo_engine_create(int(device), C.byref(self._h)), "phovo_engine_create")
+        self._device = int(device)
         self.n_frames = 0
 
     def close(self):
@@ -346,6 +484,37 @@ class AlignmentEngine:
             check(self._lib.phovo_engine_upload_frames_u16(self._h, int(first_frame), g.shape[0], int(roles), g.ctypes.data,
                                                            g.strides[1], g.strides[0], d.ctypes.data, d.strides[1], d.strides[0],
                                                            float(depth_scale)), "phovo_engine_upload_frames_u16")
+
+    def upload_frames_device(self, first_frame, gray, depth=None, depth_scale=1.0, roles=native.ROLE_BOTH, stream=None,
+                             channel_order="rgb"):
+        """upload_frames for frames that already live in device memory (phovo_engine_upload_frames_device): no host round
+        trip, no host synchronisation, and exactly the planes the host upload of the same pixel values gives.
+          gray   [F,H,W] uint8, or [F,H,W,3] uint8 with channel_order "rgb" | "bgr" (gray_from_colour's integer rule)
+          depth  [F,H,W] float64 (metres; depth_scale 1), or float32 / float16 / uint16: (double)value * depth_scale.
+                 int16 storage is accepted and read as uint16 (for torch builds without a uint16 dtype).
+        Both are torch tensors on the engine's device, or objects torch can view without a copy (__cuda_array_interface__,
+        DLPack).  Row and frame strides are passed through as they are (slices of larger tensors cost nothing); only a
+        pixel stride other than the element size makes a .contiguous() copy.  A CPU tensor or numpy array is a TypeError.
+        `stream`: the torch.cuda stream (or raw handle) the tensors were produced on, None = torch's current stream of
+        the engine's device.  The engine reads the tensors behind what that stream has queued, and the stream waits for
+        the read: the caller may overwrite or drop the tensors on that stream right after this returns.  Later align /
+        evaluate / plane calls are ordered behind the ingest.
+        In a process that uses torch, import it before the first use of this package (one HIP runtime for both:
+        native.hip_runtimes_mapped); a RuntimeError says so otherwise."""
+        gi, di, _keep, (f, h, w), handle = _device_images(gray, depth, channel_order, stream, self._device, batched=True)
+        if self.n_frames:
+            pw, ph = self.level_size(0)
+            if (w, h) != (pw, ph):
+                raise ValueError(f"frames are {w}x{h}, the pool was reserved for {pw}x{ph}")
+        check(self._lib.phovo_engine_upload_frames_device(self._h, int(first_frame), f, int(roles), C.byref(gi),
+                                                          C.byref(di) if di is not None else None, float(depth_scale),
+                                                          handle), "phovo_engine_upload_frames_device")
+
+    def last_ingest(self):
+        """What the last upload_frames_device launched: dict(chunks, wide_launches, scalar_launches)."""
+        rec = native.IngestRecord()
+        check(self._lib.phovo_engine_last_ingest(self._h, C.byref(rec)), "phovo_engine_last_ingest")
+        return dict(chunks=rec.chunks, wide_launches=rec.wide_launches, scalar_launches=rec.scalar_launches)
 
     def set_objective(self, objective):
         """native.OBJECTIVE_PHOTOMETRIC (default) or native.OBJECTIVE_BIOBJECTIVE; a change drops the frame pool."""
