@@ -1,6 +1,11 @@
 """ctypes loader for the CPU oracle (oracle/phovo_oracle.c).
 
-TEST INFRASTRUCTURE ONLY -- PARITY UNPINNED (see oracle/phovo_oracle.h).
+TEST INFRASTRUCTURE ONLY.
+PINNED to the reference's own compiled code (oracle/_ref/libphovo_ref.so, built by oracle/Makefile.ref from the
+reference's unmodified headers over the stand-ins of oracle/ref_standins/): the Analytic and BiObjective core
+arithmetic, termination tests (strict <, after the increment), scatter order, eigenPose and warpImage.  NOT pinned:
+OpenCV's resize / blur / Scharr / convertTo, Eigen's product and inverse order, Ceres, and the yml reader.
+(See oracle/phovo_oracle.h and oracle/reference_build.py.)
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg import this.
 """
 import ctypes as C
@@ -46,13 +51,15 @@ class TraceEntry(C.Structure):
 
 
 def build(force=False):
-    """Compile the oracle with its Makefile (gcc).  Building the checker is not using it."""
+    """Compile the oracle with its Makefile (gcc), and the reference build (oracle/reference_build.py) where the
+    reference tree is present.  Building the checker is not using it."""
     src = os.path.join(_HERE, "phovo_oracle.c")
-    if (not force and os.path.exists(_SO)
+    if not (not force and os.path.exists(_SO)
             and os.path.getmtime(_SO) >= os.path.getmtime(src)
             and os.path.getmtime(_SO) >= os.path.getmtime(os.path.join(_HERE, "phovo_oracle.h"))):
-        return _SO
-    subprocess.check_call(["make", "-s", "-C", _HERE, "-B" if force else "-s"])
+        subprocess.check_call(["make", "-s", "-C", _HERE, "-B" if force else "-s"])
+    from oracle import reference_build
+    reference_build.build()                    # nothing without the tree; raises if the tree is there and does not compile
     return _SO
 
 

@@ -1,6 +1,6 @@
 /*
- * phovo_oracle.c -- CPU oracle (TEST INFRASTRUCTURE ONLY, PARITY UNPINNED).
- * See phovo_oracle.h for what this restates and what pins it.
+ * phovo_oracle.c -- CPU oracle (TEST INFRASTRUCTURE ONLY; pinned to the reference build, see phovo_oracle.h).
+ * See phovo_oracle.h for what this restates, what pins it and what stays unpinned.
  *
  * All citations are into the reference tree (MiguelAlgaba/photoconsistency-visual-odometry).
  * Build: oracle/Makefile (gcc -O3 -mtune=native -ffp-contract=off, the reference's own
@@ -236,6 +236,13 @@ static void gaussian_blur_once(double *img, int w, int h, int ksize)
   }
   free(tmp);
   free(kern);
+}
+
+/* One cv::GaussianBlur(img, img, Size(k,k), 3) call (:146), for the reference build's stand-in of it. */
+void phovo_oracle_gaussian_blur_once(double *img, int w, int h, int ksize)
+{
+  g_unverified[2]++;                             /* UNVERIFIED-vs-OpenCV [2] */
+  gaussian_blur_once(img, w, h, ksize);
 }
 
 void phovo_oracle_gaussian_blur_twice(double *img, int w, int h, int ksize)

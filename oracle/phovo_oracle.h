@@ -4,23 +4,26 @@
  * TEST INFRASTRUCTURE ONLY.  Nothing under oracle/ is part of the product: only
  * tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may load it.
  *
- * PARITY UNPINNED: the reference (MiguelAlgaba/photoconsistency-visual-odometry)
- * ships no tests, golden vectors or fixtures, and it cannot be compiled in this
- * image (OpenCV, Eigen and Boost are absent).  This file is a plain-C, fp64
- * restatement of
+ * PINNED to the reference's own compiled code (oracle/_ref/libphovo_ref.so, built by oracle/Makefile.ref from the
+ * reference's unmodified headers over the stand-ins of oracle/ref_standins/): the Analytic and BiObjective core
+ * arithmetic, termination tests (strict <, after the increment), scatter order, eigenPose and warpImage.  NOT pinned:
+ * OpenCV's resize / blur / Scharr / convertTo, Eigen's product and inverse order, Ceres, and the yml reader.
+ *
+ * The reference (MiguelAlgaba/photoconsistency-visual-odometry) ships no tests, golden vectors or fixtures, and OpenCV,
+ * Eigen and Boost are not installed here.  This file is a plain-C, fp64 restatement of
  *   phovo/include/CPhotoconsistencyOdometryAnalytic.h:115-189  (pyramids, via OpenCV semantics)
  *   phovo/include/CPhotoconsistencyOdometryAnalytic.h:191-367  (ComputeResidualsAndJacobians)
  *   phovo/include/CPhotoconsistencyOdometryAnalytic.h:376-392  (TestTerminationCriteria)
  *   phovo/include/CPhotoconsistencyOdometryAnalytic.h:500-563  (Optimize)
  *   phovo/include/CPhotoconsistencyOdometry.h:47-71            (eigenPose)
  *   phovo/include/CPhotoconsistencyOdometry.h:73-134           (warpImage)
- * What pins it instead: an independent numpy restatement (oracle/numpy_twin.py)
- * whose outputs are committed under tests/golden/, and a symbolic known-answer
- * test of the warp Jacobian against the model in
+ * tests/test_reference_build_cpu.py holds it to the reference build (iteration counts equal, poses within 1e-9, eigenPose
+ * and warpImage bit for bit); tests/test_gpu_reference_parity.py holds the HIP path to the same library.  Also pinning
+ * it: an independent numpy restatement (oracle/numpy_twin.py) whose outputs are committed under tests/golden/, and a
+ * symbolic known-answer test of the warp Jacobian against the model in
  * phovo/Maxima/derivatives_photoconsistency.wxm:5-19 (tests/test_jacobian_kat.py).
- * The arithmetic that lives in Eigen / OpenCV (matrix products, 6x6 inverse,
- * resize, Scharr) is restated from those libraries' documented behaviour; the
- * summation order inside Eigen's products is not reproduced bit for bit.
+ * The arithmetic that lives in Eigen / OpenCV (matrix products, 6x6 inverse, resize, Scharr, blur) is restated from those
+ * libraries' documented behaviour, here and in the stand-ins alike: the reference build runs on the same restatement.
  */
 #ifndef PHOVO_ORACLE_H
 #define PHOVO_ORACLE_H
@@ -84,6 +87,8 @@ void phovo_oracle_resize_level(const double *src, int w, int h, int level, doubl
 
 /* cv::GaussianBlur(img, img, Size(k,k), 3) applied twice (:146-147). In place. */
 void phovo_oracle_gaussian_blur_twice(double *img, int w, int h, int ksize);
+/* One of the two calls, as the reference build's cv::GaussianBlur stand-in issues them. */
+void phovo_oracle_gaussian_blur_once(double *img, int w, int h, int ksize);
 
 /* cv::Scharr dx and dy with scale, delta 0, BORDER_DEFAULT (:181-187). */
 void phovo_oracle_scharr(const double *img, int w, int h, double scale,

@@ -171,10 +171,56 @@ def normal_equations(i0, d0, i1, d1, gx, gy, dgx, dgy, gain, level, K, state, mi
     stats = dict(contributing=int(contrib.sum()),
                  intensity_won=int(int_wins.sum()),
                  depth_won_below_n=int((dep_wins & below & (m > 0)).sum()),
-                 row0_tie=int(dep_wins[0] and c_int[0] == c_dep[0]),
+                 row0_tie=int(n > 0 and dep_wins[0] and c_int[0] == c_dep[0]),     # (a level of zero pixels has no row 0)
                  jdep_below_n=int((use_dep & below).sum()),
                  depth_rows_at_n=int((use_dep & ~below).sum()))
     return H, g, stats
+
+
+def reference_step(H, g):
+    """(J^T J).inverse() * g as the reference evaluates it (:629-630) on the reference build's matrix stand-in: LU with
+    partial pivoting on a row-major copy, one forward and one backward substitution per column of the identity (the
+    operations of inverse6 in oracle/phovo_oracle.c, in its order), then the product summed left to right.  A singular
+    matrix gives inf / NaN, as there, not an exception."""
+    n = 6
+    lu = [[float(H[i][j]) for j in range(n)] for i in range(n)]
+    perm = list(range(n))
+    f64 = np.float64
+    lu = [[f64(v) for v in row] for row in lu]
+    for k in range(n):
+        piv, best = k, abs(lu[k][k])
+        for r in range(k + 1, n):
+            if abs(lu[r][k]) > best:
+                best, piv = abs(lu[r][k]), r
+        if piv != k:
+            lu[k], lu[piv] = lu[piv], lu[k]
+            perm[k], perm[piv] = perm[piv], perm[k]
+        d = lu[k][k]
+        for r in range(k + 1, n):
+            lu[r][k] = lu[r][k] / d
+            f = lu[r][k]
+            for c in range(k + 1, n):
+                lu[r][c] = lu[r][c] - f * lu[k][c]
+    inv = [[f64(0.0)] * n for _ in range(n)]
+    for col in range(n):
+        y = [f64(0.0)] * n
+        for r in range(n):
+            s = f64(1.0 if perm[r] == col else 0.0)
+            for c in range(r):
+                s = s - lu[r][c] * y[c]
+            y[r] = s
+        for r in range(n - 1, -1, -1):
+            s = y[r]
+            for c in range(r + 1, n):
+                s = s - lu[r][c] * inv[c][col]
+            inv[r][col] = s / lu[r][r]
+    step = np.zeros(n)
+    for a in range(n):
+        s = inv[a][0] * f64(g[0])
+        for b in range(1, n):
+            s = s + inv[a][b] * f64(g[b])
+        step[a] = s
+    return step
 
 
 def optimize(cfg, K, src_planes, tgt_planes, init_state=None, min_depth=0.3, max_depth=5.0):
@@ -197,11 +243,8 @@ def optimize(cfg, K, src_planes, tgt_planes, init_state=None, min_depth=0.3, max
                                         tgt_planes["gx"][level], tgt_planes["gy"][level], tgt_planes["dgx"][level],
                                         tgt_planes["dgy"][level], tgt_planes["gain"][level], level, K, state,
                                         min_depth, max_depth)
-            try:
-                with np.errstate(all="ignore"):
-                    step = np.linalg.solve(H, g)
-            except np.linalg.LinAlgError:
-                step = np.full(6, np.nan)
+            with np.errstate(all="ignore"):
+                step = reference_step(H, g)
             state = state - cfg.lambda_optimization_step[level] * step      # :638-639
             it += 1
             valid[level] = st["contributing"]
