@@ -330,7 +330,18 @@ int phovo_engine_create(int device, phovo_engine **out);
 int phovo_engine_destroy(phovo_engine *e);
 int phovo_engine_set_config(phovo_engine *e, const phovo_config *cfg);
 int phovo_engine_get_config(const phovo_engine *e, phovo_config *cfg);
-/* Changing plane_storage drops the frame pool (like a configuration that changes the levels). */
+/* Changing plane_storage drops the frame pool (like a configuration that changes the levels).  So does changing `sampling`
+ * while plane_storage is PHOVO_STORAGE_F16 (before and after the call): fp16 planes carry bilinear tap records exactly under
+ * PHOVO_SAMPLING_BILINEAR, and the pool is laid out with or without them.  The call still returns PHOVO_OK; the frames are
+ * gone, and the next align / evaluate is refused with PHOVO_E_NOT_READY until phovo_engine_reserve_frames and the uploads
+ * have been repeated.  Every other change (Huber deltas, jacobian_corrected, sampling on fp64 / fp32 planes) keeps the
+ * resident frames.
+ * Precondition of PHOVO_SAMPLING_BILINEAR on PHOVO_STORAGE_F64 planes, for levels ONE COLUMN wide (width >> level == 1) only:
+ * all four planes of a target frame must be finite on that level, its depth included when the frame was uploaded with
+ * PHOVO_ROLE_BOTH or given a depth plane.  The fp64 kernel loads a row's two taps as one 16-byte pair and weights the
+ * second, which on a one-column row is the double stored behind the row, by zero: a NaN there (an invalid-depth marker)
+ * makes the sample NaN and the pair ends PHOVO_PAIR_NONFINITE.  The fp32 and fp16 storages clamp their taps and carry no
+ * such condition; nor do levels two or more columns wide on any storage. */
 int phovo_engine_set_extensions(phovo_engine *e, const phovo_extensions *ext);
 int phovo_engine_get_extensions(const phovo_engine *e, phovo_extensions *ext);
 int phovo_engine_set_intrinsic_matrix(phovo_engine *e, const double k[9]);

@@ -1329,7 +1329,7 @@ int phovo_engine_enqueue_align(phovo_engine *e, int n_pairs, const int *source_f
 {
   if (!e || !source_frames || !target_frames) return fail(PHOVO_E_INVALID_ARGUMENT, "align: null");
   if (n_pairs < 0) return fail(PHOVO_E_INVALID_ARGUMENT, "align: n_pairs < 0");
-  if (e->n_frames == 0) return fail(PHOVO_E_NOT_READY, "align: no frames uploaded");
+  if (e->n_frames == 0) return fail(PHOVO_E_NOT_READY, "align: no frames resident (reserve_frames and upload first; set_config, set_extensions and set_objective drop the pool when its layout changes)");
   if (!e->have_K) return fail(PHOVO_E_NOT_READY, "align: SetIntrinsicMatrix has not been called");
   for (int i = 0; i < n_pairs; i++) {
     if (source_frames[i] < 0 || source_frames[i] >= e->n_frames || target_frames[i] < 0 || target_frames[i] >= e->n_frames)

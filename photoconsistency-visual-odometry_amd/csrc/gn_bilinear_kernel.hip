@@ -386,7 +386,9 @@ __global__ __launch_bounds__(T, WPS) void gn_level_kernel_bilinear_dma(const GNL
         // band: the pair is (e, x)) or 1 (right band: (x, e)), so that the row gives 1 * e + 0 * x.  That is the value of
         // (1 - ax) * e + ax * e up to its rounding, i.e. within one ulp of the clamped-tap form the other storages and the oracle
         // use, in that band only; selecting the taps instead cost 24 v_cndmask per chunk in a kernel whose vector units are
-        // 93 % busy (profiles/r05_bilinear_pmc_sq.json).  x is a pixel of the plane, finite whenever the plane is.
+        // 93 % busy (profiles/r05_bilinear_pmc_sq.json).  x is a pixel of the plane, finite whenever the plane is -- except on
+        // a level one column wide, where x is the first double of the next row, and behind a plane's last row of the next
+        // plane (the target's depth behind its intensity): phovo_hip.h asks for finite target planes there.
         const int cb = min(max(ic, 0), max(W - 2, 0));
         w.off[0] = (r0w + cb) * 8; w.off[1] = (r1w + cb) * 8; w.off[2] = w.off[3] = 0;
         w.ax = (ic < 0 || W < 2) ? 0.0 : (ic > W - 2 ? 1.0 : tc - fc);       // (a one-column image: both taps are that column)

@@ -386,6 +386,9 @@ class AlignmentEngine:
         self.set_config(native.read_config_file(path))
 
     def set_extensions(self, ext):
+        """Changing plane_storage drops the frame pool; so does changing `sampling` on fp16 planes (their bilinear tap
+        records are added or removed).  The call succeeds, and the next align_pairs raises PhovoError with status
+        E_NOT_READY until reserve_frames and the uploads have been repeated.  Any other change keeps the frames."""
         check(self._lib.phovo_engine_set_extensions(self._h, C.byref(ext)), "phovo_engine_set_extensions")
 
     def get_extensions(self):

@@ -108,3 +108,86 @@ def test_sampling_keys_in_yml(tmp_path):
     bad.write_text(base + "sampling_bilinear: 2\n")
     with pytest.raises(native.PhovoError):
         native.read_extensions_file(str(bad))
+
+
+# ---- CPU pre-checks of every deterministic input of tests/test_gpu_extension_forms.py (tests/extension_forms.py) ---------
+import extension_forms as ef  # noqa: E402
+
+
+def _vouch(ocfg, K, planes, init, huber, what, **ext):
+    """Finite, well-posed for the pose bar (Expect's guard asserts it) and, with Huber weights, residuals beyond delta and a
+    result away from the unweighted one."""
+    e = ef.expect(ocfg, K, planes, init, huber, **ext)
+    assert e.finite, what
+    if huber is not None:
+        assert ef.huber_bites(ocfg, K, planes, init, huber) > 0.005, what
+        plain = ef.expect(ocfg, K, planes, init, None, **ext)
+        assert se3.state_distance(e.state, plain.state) > 1e-6, what
+    return e
+
+
+@pytest.mark.parametrize("name", list(ef.FORMS))
+def test_inputs_of_the_form_matrix_are_finite_well_posed_and_weighted(name):
+    f = ef.FORMS[name]
+    _, ocfg = ef.configs(f["max_iter"], f["min_grad"])
+    pairs = ef.form_pairs(name)
+    for st in f["settings"].get("storages", ef.STORAGES):
+        for hub in (False, True):
+            huber = ef.huber_deltas(f["max_iter"], hub)
+            for k, (p, init) in enumerate(pairs):
+                planes = ef.emulated_planes(ocfg, p, st, patched=(k == 0))
+                if k == 0 and st == native.STORAGE_F16:          # the patches did put fp16 subnormals into every plane
+                    l = max(l for l in range(len(f["max_iter"])) if f["max_iter"][l] > 0)
+                    assert all(ef.count_f16_subnormals(planes[j][l]) >= 8 for j in (0, 2, 3, 4)), name
+                _vouch(ocfg, p["K"], planes, init, huber, (name, st, hub, k))
+
+
+@pytest.mark.parametrize("size,max_iter", ef.BILINEAR_SIZES, ids=[f"{s[0]}x{s[1]}" for s, _ in ef.BILINEAR_SIZES])
+def test_inputs_of_the_bilinear_cells_are_finite_well_posed_and_weighted(size, max_iter):
+    _, ocfg = ef.configs(max_iter)
+    for st, corrected, hub in ef.bilinear_cells():
+        huber = ef.huber_deltas(max_iter, hub)
+        for k, (p, init) in enumerate(ef.bilinear_pairs(size)):
+            planes = ef.emulated_planes(ocfg, p, st)
+            _vouch(ocfg, p["K"], planes, init, huber, (size, st, corrected, hub, k), bilinear=True, corrected=corrected)
+
+
+def test_inputs_of_the_narrow_storage_edges():
+    # depth gate: the planted depths are inside the gate in fp64 and on it in fp32; the oracle counts exactly them
+    K, planes, planted = ef.depth_gate_problem()
+    _, ocfg = ef.configs([1], min_depth=ef.GATE[0], max_depth=ef.GATE[1])
+    assert planted > 100
+    e64 = _vouch(ocfg, K, planes, np.zeros(6), None, "gate f64")
+    for st in ef.STORAGES:
+        rounded = [[ef.round_depth(a[0], st) if j == 1 else ef.round_image(a[0], st)] for j, a in enumerate(planes)]
+        e = _vouch(ocfg, K, rounded, np.zeros(6), None, ("gate", st))
+        assert e64.valid[0] - e.valid[0] == planted, (e64.valid, e.valid, planted)
+    # strips: at most half of the cases may be non-finite on the oracle; the finite ones pass the guard
+    cases = bad = 0
+    for w, h in ef.STRIPS:
+        p, states = ef.strip_cases(w, h)
+        _, ocfg = ef.configs([3])
+        for st in ef.STORAGES:
+            planes = ef.emulated_planes(ocfg, p, st)
+            for hub in (False, True):
+                for init in states:
+                    e = ef.expect(ocfg, p["K"], planes, init, ef.huber_deltas([3], hub))
+                    cases += 1
+                    bad += not e.finite
+    assert cases == 72 and 2 * bad <= cases, (bad, cases)
+    # one-column / one-row bilinear levels on fp64 planes: finite on the oracle, which never reads the target's depth
+    for (w, h), K, planes, depth1 in ef.one_column_problem():
+        _, ocfg = ef.configs([2])
+        assert np.isnan(depth1.reshape(-1)[0]) and np.isnan(depth1.reshape(-1)[1])
+        e = _vouch(ocfg, K, planes, np.zeros(6), None, (w, h), bilinear=True, corrected=True)
+        assert e.valid[0] >= 38, (w, h, e.valid)
+    # fp16 overflow: a block of inf in the target's intensity leaves the oracle non-finite (the planted inf case)
+    pairs = ef.form_pairs("threads256_80x60")
+    _, ocfg = ef.configs([4])
+    planes = ef.emulated_planes(ocfg, pairs[1][0], native.STORAGE_F16)
+    planes[2][0][20:30, 30:50] = np.inf
+    es, _ = oracle.optimize(ocfg, pairs[1][0]["K"], *planes)
+    assert not np.all(np.isfinite(es))
+    # the state-change test's pair under bilinear sampling
+    _vouch(ocfg, pairs[0][0]["K"], ef.emulated_planes(ocfg, pairs[0][0], native.STORAGE_F16), np.zeros(6), None, "toggle",
+           bilinear=True)

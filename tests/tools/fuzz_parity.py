@@ -53,6 +53,7 @@ bad, worst, variants, fallbacks = 0, 0.0, {}, 0
 worst_ratio, worst_cond, ill = 0.0, 0.0, 0
 worst_ill, ill_only_by_scaling = 0.0, 0
 chaotic = 0
+combos, kinds = {}, {}                  # `ext`: drawn storage / sampling / Huber combinations (of all cases); launch kinds seen
 
 
 # FUZZ_ONLY=12,345: replay the random draws of every case but run only these (to look at a failure again)
@@ -99,22 +100,21 @@ for case in range(cases):
         init = rs.uniform(-1, 1, 6) * np.array([0.02, 0.02, 0.02, 0.01, 0.01, 0.01])
         init[3:] = [draw_angle(rs, axis, motion[3 + axis]) for axis in range(3)]
     storage, huber, bilinear, corrected = native.STORAGE_F64, None, False, False
-    if not active:                          # the remaining draws of this case, in order, and on to the next one
-        if with_ext:
-            rs.randint(0, 3)
-            if not rs.rand() < 0.4:
-                [rs.choice([0.0, 0.02, 0.1]) for _ in range(nl)]
-            if rs.rand() < 0.5:
-                rs.rand()
-        if int(rs.choice([40, 300] if big else [1, 3, 40])) <= 8:
-            rs.rand()                       # (the latency-forms draw of a small batch)
-        continue
     if with_ext:
         storage = [native.STORAGE_F64, native.STORAGE_F32, native.STORAGE_F16][int(rs.randint(0, 3))]
         huber = None if rs.rand() < 0.4 else [float(rs.choice([0.0, 0.02, 0.1])) for _ in range(nl)]
         bilinear = rs.rand() < 0.5
         corrected = bool(bilinear and rs.rand() < 0.5)
-    else:
+        # (Huber counts as drawn where a level that iterates has a delta above zero)
+        weighted = huber is not None and any(d > 0 and m > 0 for d, m in zip(huber, max_iter))
+        combo = "/".join((("f64", "f32", "f16")[storage], "bilinear-corrected" if corrected else "bilinear" if bilinear else "nearest",
+                          "huber" if weighted else "plain"))
+        combos[combo] = combos.get(combo, 0) + 1
+    if not active:                          # the remaining draws of this case, in order, and on to the next one
+        if int(rs.choice([40, 300] if big else [1, 3, 40])) <= 8:
+            rs.rand()                       # (the latency-forms draw of a small batch)
+        continue
+    if not with_ext:
         es, eits, otrace = oracle.align_frames(ocfg, K, p["gray0"], d0, p["gray1"], init_state=init, want_trace=True)
     with odometry.AlignmentEngine() as eng:
         eng.set_config(ncfg)
@@ -145,6 +145,8 @@ for case in range(cases):
             eng.set_latency_forms(True)         # half of the small batches: the forms that finish soonest (off by default)
         inits = None if init is None else np.tile(init, (n_pairs, 1))
         s, reps = eng.align_pairs([0] * n_pairs, [1] * n_pairs, init_states=inits, want_reports=True)
+        for rec in eng.last_launches():
+            kinds[rec["kind"]] = kinds.get(rec["kind"], 0) + 1
         for l in range(nl):
             if max_iter[l] > 0:
                 info = eng.level_launch_info(l)
@@ -201,4 +203,7 @@ print(f"largest cond(J^T J) {worst_cond:.2e}; {ill} cases above 1e5 (bar scaled,
 print(f"chaotic cases (beyond the scaled bar, within 4 x the oracle's own sensitivity to one ulp of fx; not failures): {chaotic}")
 print(f"pairs finished by the exact kernel after leaving the sliding window: {fallbacks} cases")
 print("launch geometries exercised (threads, owner in LDS, source in LDS, wide form): ", variants)
+print("launch kinds seen (launches):", dict(sorted(kinds.items())))
+if with_ext:
+    print("extension combinations drawn (storage/sampling/Huber: cases):", dict(sorted(combos.items())))
 sys.exit(1 if bad else 0)
