@@ -2,10 +2,12 @@
 // directory, writing a TUM trajectory file.
 //
 //   ./PhotoconsistencyVisualOdometry <config_file.yml> <rgbd_dataset_directory> <output_trajectory_file> [--batch [--gpus N] [--rccl]]
-//                                    [--method analytic|ceres|biobjective] [--information <file>]
+//                                    [--method analytic|ceres|biobjective|affine] [--information <file>]
 // --method picks the aligner as the reference's USE_PHOTOCONSISTENCY_ODOMETRY_METHOD does (0 = analytic, the default;
 // 1 = ceres: Levenberg-Marquardt on bilinear samples, CPhotoconsistencyOdometryCeres, which reads config_*_ceres.yml
-// files; 2 = bi-objective: photometric and depth error together, CPhotoconsistencyOdometryBiObjective), in every mode.
+// files; 2 = bi-objective: photometric and depth error together, CPhotoconsistencyOdometryBiObjective), in every mode;
+// affine is not in the reference: the photometric aligner with a per-pair gain and offset, CPhotoconsistencyOdometryAffine,
+// which reads the analytic files.
 // A configuration file of the other kind is refused with a message that says so.
 // --information <file> (not in the reference; analytic method, one device): one line per pair, stamped like its trajectory
 // line, with the Gauss-Newton system at the pair's optimal state on the finest level the configuration optimises --
@@ -47,6 +49,7 @@
 #include "rccl/rccl_gather.h"
 #include "rccl/shard_vote.h"
 #include "phovo/CPhotoconsistencyOdometryAnalytic.h"
+#include "phovo/CPhotoconsistencyOdometryAffine.h"
 #include "phovo/CPhotoconsistencyOdometryBiObjective.h"
 #include "phovo/CPhotoconsistencyOdometryCeres.h"
 
@@ -123,7 +126,7 @@ static bool writeSystem(std::ofstream &f, double timestamp, const phovo_pair_sys
 static void printHelp()
 {
   std::cout << "./PhotoconsistencyVisualOdometry <config_file.yml> <rgbd_dataset_directory> "
-               "<output_trajectory_file> [--batch [--gpus N] [--rccl]] [--method analytic|ceres|biobjective] "
+               "<output_trajectory_file> [--batch [--gpus N] [--rccl]] [--method analytic|ceres|biobjective|affine] "
                "[--information <file>]" << std::endl;
 }
 
@@ -147,6 +150,7 @@ int main(int argc, char *argv[])
       if (m == "analytic") objective = PHOVO_OBJECTIVE_PHOTOMETRIC;
       else if (m == "biobjective") objective = PHOVO_OBJECTIVE_BIOBJECTIVE;
       else if (m == "ceres") objective = PHOVO_OBJECTIVE_TRUST_REGION;
+      else if (m == "affine") objective = PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE;
       else { printHelp(); return EXIT_FAILURE; }
     }
     else if (a == "--rccl") rccl = true;
@@ -250,6 +254,9 @@ int main(int argc, char *argv[])
         if (runLoop(odometry) != EXIT_SUCCESS) return EXIT_FAILURE;
       } else if (objective == PHOVO_OBJECTIVE_TRUST_REGION) {
         phovo::Ceres::CPhotoconsistencyOdometryCeres<PixelType, CoordinateType> odometry;
+        if (runLoop(odometry) != EXIT_SUCCESS) return EXIT_FAILURE;
+      } else if (objective == PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE) {
+        phovo::Analytic::CPhotoconsistencyOdometryAffine<PixelType, CoordinateType> odometry;
         if (runLoop(odometry) != EXIT_SUCCESS) return EXIT_FAILURE;
       } else {
         phovo::Analytic::CPhotoconsistencyOdometryAnalytic<PixelType, CoordinateType> odometry;

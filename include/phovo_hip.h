@@ -175,6 +175,25 @@ typedef struct phovo_extensions {
  *                                stays as given), PHOVO_PAIR_RANK_DEFICIENT when fewer than 6 rows remain.  The
  *                                per-level solver record is phovo_trust_region_report. */
 #define PHOVO_OBJECTIVE_TRUST_REGION 2
+/*   PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE  not in the reference: the photometric residual with a per-pair gain and offset,
+ *                                r_k = I1(u_k, v_k) - (1 + alpha) I0_k - beta, estimated jointly with the pose (8 entries per
+ *                                pair: x, y, z, yaw, pitch, roll, alpha, beta; DESIGN.md §14 has the contract).  The rows are
+ *                                those of the bilinear extension with jacobian_corrected = 1 -- source pixels in raster
+ *                                order, bilinear samples of I1, GX1, GY1 at the real-valued warped position (clamped taps; in
+ *                                bounds iff the nearest pixel is), the true warp Jacobian -- with two columns appended,
+ *                                dr/dalpha = -I0_k and dr/dbeta = -1.  The level loop is that extension's with 8 in place
+ *                                of 6 (H = J^T J is 8 x 8; min_gradient_norm is tested on ||J^T r||_2 over all 8 entries);
+ *                                every pair starts at alpha = beta = 0 and both carry from level to level with the pose.
+ *                                Frames are the photometric objective's: switching between objectives 0, 2 and 3 keeps the
+ *                                frame pool.  Supported: fp64 planes, the default sampling setting, no Huber weights,
+ *                                jacobian_corrected 0 -- anything else is PHOVO_E_UNSUPPORTED, whichever setter comes
+ *                                second; phovo_engine_evaluate_pairs is PHOVO_E_UNSUPPORTED too.  Fusion, sliding-window,
+ *                                wide, latency-form and batch-invariant settings are accepted and have no effect.
+ *                                out_states and phovo_engine_device_states stay n x 6 (the pose); alpha and beta are read
+ *                                with phovo_engine_fetch_illumination.  phovo_pair_report keeps its meaning: valid_pixels[L]
+ *                                = rows of the level's last iteration, PHOVO_PAIR_RANK_DEFICIENT when fewer than 8 rows
+ *                                were filled in some iteration, PHOVO_PAIR_NONFINITE as under the photometric objective. */
+#define PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE 3
 
 /* Solver options of the trust-region objective, per level (CPhotoconsistencyOdometryCeres.h:526-576).  num_levels, blur,
  * gradient scale and max_num_iterations stay in phovo_config. */
@@ -294,6 +313,9 @@ int phovo_odometry_set_objective(phovo_odometry *o, int objective);
 int phovo_odometry_set_trust_region_options(phovo_odometry *o, const phovo_trust_region_options *opt);
 int phovo_odometry_get_trust_region_options(const phovo_odometry *o, phovo_trust_region_options *opt);
 int phovo_odometry_get_trust_region_report(const phovo_odometry *o, phovo_trust_region_report *report);
+/* Affine-illumination objective: (alpha, beta) of the last Optimize() (PHOVO_E_NOT_READY before a successful one;
+ * PHOVO_E_UNSUPPORTED under another objective).  The target's intensities are modelled as (1 + alpha) I0 + beta. */
+int phovo_odometry_get_illumination(const phovo_odometry *o, double alpha_beta[2]);
 int phovo_odometry_set_min_depth(phovo_odometry *o, double min_depth);     /* :448 */
 int phovo_odometry_set_max_depth(phovo_odometry *o, double max_depth);     /* :454 */
 int phovo_odometry_set_intrinsic_matrix(phovo_odometry *o, const double k[9]);     /* :460, row-major 3x3 */
@@ -403,6 +425,9 @@ int phovo_engine_get_objective(const phovo_engine *e, int *objective);
 int phovo_engine_set_trust_region_options(phovo_engine *e, const phovo_trust_region_options *opt);
 int phovo_engine_get_trust_region_options(const phovo_engine *e, phovo_trust_region_options *opt);
 int phovo_engine_fetch_trust_region_reports(phovo_engine *e, int n_pairs, phovo_trust_region_report *reports);
+/* Affine-illumination objective: (alpha, beta) of every pair of the LAST enqueue (n_pairs must be that enqueue's;
+ * PHOVO_E_NOT_READY before any enqueue, PHOVO_E_UNSUPPORTED if the last one ran under another objective). */
+int phovo_engine_fetch_illumination(phovo_engine *e, int n_pairs, double *alpha_beta /* [n_pairs][2] */);
 
 /* Page-locks (and releases) a host buffer the caller will hand to the upload entry points repeatedly: uploads from
  * registered memory are direct DMA at the link rate instead of going through the runtime's bounce buffers.  Optional;
@@ -614,7 +639,8 @@ enum { PHOVO_LAUNCH_PERSISTENT = 0,       /* gn_level_kernel: one level, one wor
        PHOVO_LAUNCH_WIDE = 4,             /* k_wide_pass1 / k_wide_pass2 per iteration, many workgroups per pair */
        PHOVO_LAUNCH_BILINEAR = 5,         /* gn_level_kernel_bilinear (extension) */
        PHOVO_LAUNCH_BIOBJECTIVE = 6,      /* gn_level_kernel_biobjective (PHOVO_OBJECTIVE_BIOBJECTIVE) */
-       PHOVO_LAUNCH_TRUST_REGION = 7 };   /* gn_level_kernel_trust_region (PHOVO_OBJECTIVE_TRUST_REGION) */
+       PHOVO_LAUNCH_TRUST_REGION = 7,     /* gn_level_kernel_trust_region (PHOVO_OBJECTIVE_TRUST_REGION) */
+       PHOVO_LAUNCH_AFFINE = 8 };         /* gn_level_kernel_affine (PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE) */
 typedef struct phovo_launch_record {
   int level_first, level_last;            /* pyramid levels the launch covers (level_first >= level_last) */
   int kind;                               /* PHOVO_LAUNCH_* */

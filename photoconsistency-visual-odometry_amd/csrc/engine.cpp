@@ -97,6 +97,9 @@ struct AlignSlot {
   phovo_trust_region_report *d_tr_reports = nullptr;   // trust-region objective: the solver records of the enqueue's pairs
   int tr_capacity = 0;
   bool tr_ran = false;                         // the enqueue ran under PHOVO_OBJECTIVE_TRUST_REGION
+  double *d_illum = nullptr;                   // affine-illumination objective: (alpha, beta) of the enqueue's pairs, [pairs][2]
+  int illum_capacity = 0;
+  bool affine_ran = false;                     // the enqueue ran under PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE
 };
 
 struct phovo_engine {
@@ -193,6 +196,8 @@ void free_slot(AlignSlot &s)
   if (s.d_wide_ws) (void)hipFree(s.d_wide_ws);
   if (s.d_tr_reports) (void)hipFree(s.d_tr_reports);
   s.d_tr_reports = nullptr; s.tr_capacity = 0;
+  if (s.d_illum) (void)hipFree(s.d_illum);
+  s.d_illum = nullptr; s.illum_capacity = 0;
   s.d_owner = nullptr; s.owner_capacity = 0; s.d_wide_ws = nullptr; s.wide_ws_capacity = 0;
   s.d_mask = nullptr; s.mask_capacity = 0;
 }
@@ -261,6 +266,8 @@ bool biobjective_supports(const phovo_extensions &x)
 
 // The trust-region objective likewise (the same four conditions: jacobian_corrected 0 included).
 bool trust_region_supports(const phovo_extensions &x) { return biobjective_supports(x); }
+// The affine-illumination objective likewise: its rows are fixed by the objective, not chosen by the extensions.
+bool affine_supports(const phovo_extensions &x) { return biobjective_supports(x); }
 
 // Depth gradients (with the max depth in force) and gain of `count` consecutive target frames of level l, from the
 // intensity and depth planes already in the pool (fp64, packed: the frame is frame_bytes / 8 doubles).
@@ -645,6 +652,9 @@ int phovo_engine_set_extensions(phovo_engine *e, const phovo_extensions *ext)
   if (e->objective == PHOVO_OBJECTIVE_TRUST_REGION && !trust_region_supports(*ext))
     return fail(PHOVO_E_UNSUPPORTED, "set_extensions: the trust-region objective runs on fp64 planes with the default "
                                      "sampling, no Huber weights and jacobian_corrected 0 only");
+  if (e->objective == PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE && !affine_supports(*ext))
+    return fail(PHOVO_E_UNSUPPORTED, "set_extensions: the affine-illumination objective runs on fp64 planes with the default "
+                                     "sampling setting, no Huber weights and jacobian_corrected 0 only");
   // the pool layout changes with the storage type, and -- fp16 planes under bilinear sampling carry tap records -- with the
   // sampling where that adds or removes the records
   auto has_records = [](const phovo_extensions &x) { return x.sampling == PHOVO_SAMPLING_BILINEAR && x.plane_storage == PHOVO_STORAGE_F16; };
@@ -662,15 +672,18 @@ int phovo_engine_set_objective(phovo_engine *e, int objective)
 {
   if (!e) return fail(PHOVO_E_INVALID_ARGUMENT, "set_objective: null");
   if (objective != PHOVO_OBJECTIVE_PHOTOMETRIC && objective != PHOVO_OBJECTIVE_BIOBJECTIVE &&
-      objective != PHOVO_OBJECTIVE_TRUST_REGION)
+      objective != PHOVO_OBJECTIVE_TRUST_REGION && objective != PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE)
     return fail(PHOVO_E_INVALID_ARGUMENT, "set_objective: unknown objective");
+  if (objective == PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE && !affine_supports(e->ext))
+    return fail(PHOVO_E_UNSUPPORTED, "set_objective: the affine-illumination objective runs on fp64 planes with the default "
+                                     "sampling setting, no Huber weights and jacobian_corrected 0 only");
   if (objective == PHOVO_OBJECTIVE_BIOBJECTIVE && !biobjective_supports(e->ext))
     return fail(PHOVO_E_UNSUPPORTED, "set_objective: the bi-objective runs on fp64 planes with nearest / scatter sampling "
                                      "and no Huber weights only");
   if (objective == PHOVO_OBJECTIVE_TRUST_REGION && !trust_region_supports(e->ext))
     return fail(PHOVO_E_UNSUPPORTED, "set_objective: the trust-region objective runs on fp64 planes with the default "
                                      "sampling, no Huber weights and jacobian_corrected 0 only");
-  // The photometric and trust-region objectives share the frame layout: a switch between them keeps the pool.
+  // The photometric, trust-region and affine-illumination objectives share the frame layout: a switch between them keeps the pool.
   auto bi = [](int o) { return o == PHOVO_OBJECTIVE_BIOBJECTIVE; };
   if (objective != e->objective && (bi(objective) || bi(e->objective))) {   // the pool layout changes (the bi-objective's target planes): dropped
     (void)hipSetDevice(e->device);
@@ -1357,6 +1370,7 @@ int phovo_engine_enqueue_align(phovo_engine *e, int n_pairs, const int *source_f
       if (!lv.plan_tr.owner_in_lds) owner_need = std::max(owner_need, wgs * (size_t)lv.n);
       continue;
     }
+    if (e->objective == PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE) continue;       // no owner map, no LDS limit
     if (e->ext.sampling == PHOVO_SAMPLING_BILINEAR) continue;       // no owner map, no LDS limit
     const bool wide = use_wide_level(e, n_pairs, lv) && !(e->ext.huber_delta[l] > 0.0);
     if (wide) {
@@ -1391,6 +1405,7 @@ int phovo_engine_enqueue_align(phovo_engine *e, int n_pairs, const int *source_f
   for (bool &b : s.level_launched) b = false;
   s.d_states = nullptr;
   s.tr_ran = e->objective == PHOVO_OBJECTIVE_TRUST_REGION;
+  s.affine_ran = e->objective == PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE;
   if (n_pairs == 0) {                    // nothing to run: a valid, empty enqueue (fetch of 0 pairs succeeds, no device buffer)
     e->ticket = ticket;
     s.ticket = ticket;
@@ -1446,6 +1461,11 @@ int phovo_engine_enqueue_align(phovo_engine *e, int n_pairs, const int *source_f
     PHOVO_HIP_CHECK(hipMalloc(&s.d_tr_reports, sizeof(phovo_trust_region_report) * (size_t)n_pairs));
     s.tr_capacity = n_pairs;
   }
+  if (s.affine_ran && n_pairs > s.illum_capacity) {
+    if (s.d_illum) { (void)hipFree(s.d_illum); s.d_illum = nullptr; s.illum_capacity = 0; }
+    PHOVO_HIP_CHECK(hipMalloc(&s.d_illum, sizeof(double) * 2 * (size_t)n_pairs));
+    s.illum_capacity = n_pairs;
+  }
   // The caller may reuse its arrays as soon as this returns and the copies below are asynchronous: the slot's pinned
   // mirror keeps them alive until the slot is used again (synchronised above).
   const PairLayout pl = pair_layout(n_pairs);
@@ -1465,6 +1485,8 @@ int phovo_engine_enqueue_align(phovo_engine *e, int n_pairs, const int *source_f
   PHOVO_HIP_CHECK(hipMemsetAsync(s.d_pairs + pl.reports, 0, pl.total - pl.reports, s.stream));
   if (s.tr_ran)          // (every level the configuration skips stays PHOVO_TR_SKIPPED = 0)
     PHOVO_HIP_CHECK(hipMemsetAsync(s.d_tr_reports, 0, sizeof(phovo_trust_region_report) * (size_t)n_pairs, s.stream));
+  if (s.affine_ran)      // every pair starts at alpha = beta = 0
+    PHOVO_HIP_CHECK(hipMemsetAsync(s.d_illum, 0, sizeof(double) * 2 * (size_t)n_pairs, s.stream));
   PHOVO_HIP_CHECK(hipEventRecord(s.ev_total_start, s.stream));
 
   const PairLayout lay = pair_layout(n_pairs);
@@ -1586,6 +1608,12 @@ int phovo_engine_enqueue_align(phovo_engine *e, int n_pairs, const int *source_f
       PHOVO_HIP_CHECK(gn_launch_level_trust_region(b, lv.plan_tr, e->cu_count, s.stream));
       record(l, l, PHOVO_LAUNCH_TRUST_REGION, lv.plan_tr.threads, lv.plan_tr.lds_bytes, persistent_grid(lv.plan_tr.wgs_per_cu));
       if (!lv.plan_tr.owner_in_lds) s.owner_tagged = true;    // tagged entries stay behind (the kernel wipes per pair)
+    } else if (e->objective == PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE) {
+      GNAffineArgs b{};
+      b.lv = a;
+      b.illum = s.d_illum;
+      PHOVO_HIP_CHECK(gn_launch_level_affine(b, e->cu_count, s.stream));
+      record(l, l, PHOVO_LAUNCH_AFFINE, 256, gn_affine_lds_bytes(), persistent_grid(gn_affine_wgs_per_cu()));
     } else if (e->ext.sampling == PHOVO_SAMPLING_BILINEAR) {
       PHOVO_HIP_CHECK(gn_launch_level_bilinear(a, e->ext.plane_storage, e->ext.jacobian_corrected != 0, e->cu_count, s.stream));
       record(l, l, PHOVO_LAUNCH_BILINEAR, 256, 0, persistent_grid(gn_bilinear_wgs_per_cu(e->ext.plane_storage)));
@@ -1716,6 +1744,21 @@ int phovo_engine_fetch_trust_region_reports(phovo_engine *e, int n_pairs, phovo_
   return PHOVO_OK;
 }
 
+int phovo_engine_fetch_illumination(phovo_engine *e, int n_pairs, double *alpha_beta)
+{
+  if (!e) return fail(PHOVO_E_INVALID_ARGUMENT, "fetch_illumination: null");
+  AlignSlot *s = slot_of(e, e->ticket);
+  if (!s) return fail(PHOVO_E_NOT_READY, "fetch_illumination: nothing has been enqueued");
+  if (!s->affine_ran) return fail(PHOVO_E_UNSUPPORTED, "fetch_illumination: the last enqueue ran under another objective");
+  if (n_pairs != s->last_pairs) return fail(PHOVO_E_INVALID_ARGUMENT, "fetch_illumination: n_pairs differs from that enqueue's");
+  if (n_pairs == 0) return PHOVO_OK;
+  if (!alpha_beta) return fail(PHOVO_E_INVALID_ARGUMENT, "fetch_illumination: null");
+  PHOVO_HIP_CHECK(hipSetDevice(e->device));
+  PHOVO_HIP_CHECK(hipStreamSynchronize(s->stream));
+  PHOVO_HIP_CHECK(hipMemcpy(alpha_beta, s->d_illum, sizeof(double) * 2 * (size_t)n_pairs, hipMemcpyDeviceToHost));
+  return PHOVO_OK;
+}
+
 int phovo_engine_fetch_results(phovo_engine *e, int n_pairs, double *out_states, phovo_pair_report *reports)
 {
   if (!e) return fail(PHOVO_E_INVALID_ARGUMENT, "fetch_results: null");
@@ -1757,8 +1800,8 @@ int phovo_engine_evaluate_pairs(phovo_engine *e, int n_pairs, const int *src, co
 {
   if (!e) return fail(PHOVO_E_INVALID_ARGUMENT, "evaluate_pairs: null engine");
   if (e->objective != PHOVO_OBJECTIVE_PHOTOMETRIC)
-    return fail(PHOVO_E_UNSUPPORTED, "evaluate_pairs: the bi-objective and the trust-region objective have no pair system "
-                                     "here (photometric objective only)");
+    return fail(PHOVO_E_UNSUPPORTED, "evaluate_pairs: the bi-objective, the trust-region and the affine-illumination objective "
+                                     "have no pair system here (photometric objective only)");
   if (e->ext.sampling != PHOVO_SAMPLING_NEAREST_SCATTER)
     return fail(PHOVO_E_UNSUPPORTED, "evaluate_pairs: bilinear sampling has no pair system here (nearest / scatter only)");
   if (n_pairs < 0) return fail(PHOVO_E_INVALID_ARGUMENT, "evaluate_pairs: n_pairs < 0");
@@ -1908,6 +1951,8 @@ struct phovo_odometry {
   phovo_pair_report report{};
   phovo_trust_region_report tr_report{};         // trust-region objective: the solver record of the last Optimize()
   bool have_tr_report = false;
+  double illumination[2] = {0, 0};               // affine-illumination objective: (alpha, beta) of the last Optimize()
+  bool have_illumination = false;
 };
 
 namespace {
@@ -2194,6 +2239,7 @@ static int optimize_visualized(phovo_odometry *o, const char *dir)
   e->cfg = full;
   if (st != PHOVO_OK) return st;
   o->report = total;
+  o->have_illumination = false;
   o->optimized = true;
   return PHOVO_OK;
 }
@@ -2203,7 +2249,8 @@ int phovo_odometry_optimize(phovo_odometry *o)
   if (!o) return fail(PHOVO_E_INVALID_ARGUMENT, "Optimize: null");
   if (!o->have_source || !o->have_target)
     return fail(PHOVO_E_NOT_READY, "Optimize: SetSourceFrame and SetTargetFrame must be called first");
-  if (o->engine->cfg.visualize_iterations) {
+  // (the affine-illumination objective carries alpha and beta inside an enqueue only: no one-iteration-per-launch form)
+  if (o->engine->cfg.visualize_iterations && o->engine->objective != PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE) {
     const char *dir = std::getenv("PHOVO_VISUALIZE_DIR");
     if (dir && *dir) return optimize_visualized(o, dir);
   }
@@ -2216,7 +2263,21 @@ int phovo_odometry_optimize(phovo_odometry *o)
     st = phovo_engine_fetch_trust_region_reports(o->engine, 1, &o->tr_report);
     if (st != PHOVO_OK) return st;
   }
+  o->have_illumination = o->engine->objective == PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE;
+  if (o->have_illumination) {
+    st = phovo_engine_fetch_illumination(o->engine, 1, o->illumination);
+    if (st != PHOVO_OK) return st;
+  }
   o->optimized = true;
+  return PHOVO_OK;
+}
+
+int phovo_odometry_get_illumination(const phovo_odometry *o, double alpha_beta[2])
+{
+  if (!o || !alpha_beta) return fail(PHOVO_E_INVALID_ARGUMENT, "get_illumination: null");
+  if (!o->optimized) return fail(PHOVO_E_NOT_READY, "get_illumination: Optimize has not run");
+  if (!o->have_illumination) return fail(PHOVO_E_UNSUPPORTED, "get_illumination: the last Optimize ran under another objective");
+  alpha_beta[0] = o->illumination[0]; alpha_beta[1] = o->illumination[1];
   return PHOVO_OK;
 }
 

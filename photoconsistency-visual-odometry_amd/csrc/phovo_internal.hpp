@@ -156,6 +156,16 @@ bool gn_plan_level_trust_region(int n, GNLaunchPlan *plan);
 hipError_t gn_prepare_trust_region_kernels();
 hipError_t gn_launch_level_trust_region(const GNTrustRegionArgs &args, const GNLaunchPlan &plan, int cu_count,
                                         hipStream_t stream);
+// Affine-illumination form (gn_affine_kernel.hip, PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE): fp64 planes, the photometric
+// objective's frames; the bilinear extension's rows with the true warp Jacobian, the residual I1 - (1 + alpha) I0 - beta and
+// an 8 x 8 system per iteration.  No owner map, any level size, 256 threads.
+struct GNAffineArgs {
+  GNLevelArgs lv;                    // (huber_delta and rec_off unused)
+  double *illum;                     // [pairs][2] alpha, beta: in: previous level (zeros at the first), out: updated
+};
+int gn_affine_wgs_per_cu();          // workgroups of the kernel that stay resident per CU
+int gn_affine_lds_bytes();
+hipError_t gn_launch_level_affine(const GNAffineArgs &args, int cu_count, hipStream_t stream);
 // Sliding-window form for levels whose owner map exceeds LDS (gn_slide_kernel.hip): owner ring in LDS; pairs whose
 // motion leaves the window are appended to args.handover_out for a follow-up gn_launch_level that takes that list.
 hipError_t gn_prepare_slide_kernels();

@@ -82,7 +82,9 @@ class PairSystem(C.Structure):
 
 FUSION_AUTO, FUSION_OFF, FUSION_SPLIT = 0, -1, -2
 OBJECTIVE_PHOTOMETRIC, OBJECTIVE_BIOBJECTIVE, OBJECTIVE_TRUST_REGION = 0, 1, 2
-LAUNCH_KINDS = ("persistent", "fused", "slide", "slide_fallback", "wide", "bilinear", "biobjective", "trust_region")
+OBJECTIVE_PHOTOMETRIC_AFFINE = 3
+LAUNCH_KINDS = ("persistent", "fused", "slide", "slide_fallback", "wide", "bilinear", "biobjective", "trust_region",
+                "affine")
 
 # phovo_trust_region_level.termination
 (TR_SKIPPED, TR_MAX_ITERATIONS, TR_GRADIENT, TR_FUNCTION, TR_PARAMETER, TR_MIN_RADIUS, TR_INVALID_STEP,
@@ -198,6 +200,8 @@ SYMBOLS = {
     "phovo_odometry_set_trust_region_options": (C.c_int, [_vp, C.POINTER(TrustRegionOptions)]),
     "phovo_odometry_get_trust_region_options": (C.c_int, [_vp, C.POINTER(TrustRegionOptions)]),
     "phovo_odometry_get_trust_region_report": (C.c_int, [_vp, C.POINTER(TrustRegionReport)]),
+    "phovo_engine_fetch_illumination": (C.c_int, [_vp, C.c_int, _vp]),
+    "phovo_odometry_get_illumination": (C.c_int, [_vp, C.POINTER(C.c_double)]),
     "phovo_host_register": (C.c_int, [_vp, C.c_size_t]),
     "phovo_host_unregister": (C.c_int, [_vp]),
     "phovo_engine_reserve_frames": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int]),

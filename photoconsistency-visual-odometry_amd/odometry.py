@@ -331,6 +331,24 @@ class CPhotoconsistencyOdometryCeres(CPhotoconsistencyOdometryAnalytic):
         return rep
 
 
+class CPhotoconsistencyOdometryAffine(CPhotoconsistencyOdometryAnalytic):
+    """One frame pair at a time; not in the reference: the photometric objective with a per-pair gain and offset estimated
+    jointly with the pose (native.OBJECTIVE_PHOTOMETRIC_AFFINE: bilinear samples, exact warp Jacobian, residual
+    I1 - (1 + alpha) I0 - beta).  Reads the analytic yml files; extensions and GetPairSystem() are refused
+    (PHOVO_E_UNSUPPORTED).  GetIllumination() returns what Optimize() found."""
+
+    def __init__(self, device=0):
+        super().__init__(device)
+        check(self._lib.phovo_odometry_set_objective(self._h, native.OBJECTIVE_PHOTOMETRIC_AFFINE), "SetObjective")
+
+    def GetIllumination(self):
+        """(alpha, beta) of the last Optimize(): the target's intensities are modelled as (1 + alpha) I0 + beta."""
+        ab = np.zeros(2)
+        check(self._lib.phovo_odometry_get_illumination(self._h, ab.ctypes.data_as(C.POINTER(C.c_double))),
+              "GetIllumination")
+        return ab
+
+
 # phovo_trust_region_report as a numpy record: one row of per-level fields per pair
 TRUST_REGION_REPORT_DTYPE = np.dtype([("steps", "<i4", (native.MAX_LEVELS,)), ("accepted", "<i4", (native.MAX_LEVELS,)),
                                       ("termination", "<i4", (native.MAX_LEVELS,)), ("rows", "<i4", (native.MAX_LEVELS,)),
@@ -544,6 +562,14 @@ class AlignmentEngine:
         cfg, opt = native.read_trust_region_file(path)
         self.set_trust_region_options(opt)
         self.set_config(cfg)
+
+    def fetch_illumination(self, n_pairs):
+        """(alpha, beta) of every pair of the last enqueue, which ran under native.OBJECTIVE_PHOTOMETRIC_AFFINE: an
+        (n_pairs, 2) float64 array."""
+        out = np.zeros((int(n_pairs), 2), dtype=np.float64)
+        check(self._lib.phovo_engine_fetch_illumination(self._h, int(n_pairs), out.ctypes.data),
+              "phovo_engine_fetch_illumination")
+        return out
 
     def trust_region_reports(self, n):
         """The solver records of the last enqueue's n pairs (trust-region objective) as one structured numpy array of
