@@ -1,0 +1,138 @@
+"""CPU pre-checks of the inputs of tests/test_gpu_affine_edges.py (tests/affine_edges.py), on the CPU pyramid of
+oracle/numpy_twin.py: every fixture the GPU file holds to the flat bar has cond(J^T J) <= 1e5 in the checker
+(affine_ref.pose_bar is then 1e-9 x max(1, |x|)) and stays MARGIN_FLOOR clear of its gradient thresholds, the exact
+positions give the row counts and clamp bands worked out by hand, and the large-angle starts leave at least one
+well-conditioned pair per axis, sign and branch.  No GPU."""
+import numpy as np
+import pytest
+
+import affine_edges as ae
+import affine_ref as ar
+import edge_states
+
+
+def _holds(ref, what):
+    assert np.all(np.isfinite(ref["state"])), what
+    assert ae.flat(ref), (what, ref["cond"])
+    assert ref["margin"] > ae.MARGIN_FLOOR, (what, ref["margin"])
+
+
+def test_work_queue_pairs_hold_the_flat_bar_from_every_start():
+    pairs = ae.work_queue_pairs()
+    cfg = ae.cfg(ae.WQ_MAX_ITER, ae.WQ_MIN_GRAD)
+    which = ae.work_queue_list(1541)
+    share = np.mean(which == ae.WQ_D)
+    assert 0.07 < share < 0.13 and set(which.tolist()) == {0, 1, 2, 3}
+    states, pick = ae.work_queue_inits(520)
+    assert np.all(states != 0.0) and set(pick.tolist()) == set(range(ae.WQ_INITS))
+    iterations = set()
+    for i, p in enumerate(pairs):
+        pyr = ae.twin_pyramid(p, ae.WQ_LEVELS)
+        assert [lv[0].size for lv in pyr] == [480, 120]
+        for init in [None] + list(states):
+            ref = ar.optimize(pyr, p["K"], cfg, init_pose=init)
+            if i == ae.WQ_D:
+                assert ref["valid_pixels"] == [0, 0] and ref["flags"] == ar.PAIR_RANK_DEFICIENT | ar.PAIR_NONFINITE
+                assert ref["iterations"] == [1, 1]
+                continue
+            _holds(ref, (i, init))
+            assert ref["flags"] == 0 and all(it < 8 for it in ref["iterations"])       # ended by the thresholds
+            iterations.add(tuple(ref["iterations"]))
+    assert len(iterations) >= 4               # the pairs differ in the work they take
+
+
+# (w, h, range) -> rows at +-0.25 and at +-0.5 / +-0.75
+EXACT_ROWS = {(24, 20, (0.3, 5.0)): (437, 396), (24, 20, (0.5, 2.0)): (396, 357),
+              (75, 53, (0.3, 5.0)): (3848, 3723), (75, 53, (0.5, 2.0)): (3723, 3600)}
+
+
+@pytest.mark.parametrize("depth_range", ae.RANGES, ids=["default_range", "range_0.5_2"])
+@pytest.mark.parametrize("w,h", list(ae.EXACT_SIZES), ids=["24x20", "75x53"])
+def test_exact_positions_rows_bands_and_conditioning(w, h, depth_range):
+    for shift in ae.EXACT_SIZES[(w, h)]:
+        K, planes, state = ae.exact_problem(w, h, shift, depth_range)
+        expected = ae.exact_rows(planes[1], shift)
+        assert expected == EXACT_ROWS[(w, h, depth_range)][0 if abs(shift) == 0.25 else 1], (shift, expected)
+        state8 = np.concatenate([state, [0.0, 0.0]])
+        _, _, rows, bands, stats = ar.rows_loop(planes, 0, K, state8, *depth_range)
+        assert int(rows.sum()) == expected
+        assert stats["gate"] == int(np.sum(planes[1] != 1.0)) and stats["oob"] == w * h - stats["gate"] - expected
+        seen = set().union(*bands.values())
+        assert seen == ae.exact_bands(shift), (shift, seen)
+        ref = ar.optimize([planes], K, ae.cfg([1], None, *depth_range), init_pose=state)
+        assert ref["valid_pixels"] == [expected] and ref["iterations"] == [1] and ref["flags"] == 0
+        _holds(ref, (w, h, shift, depth_range))
+        # 24x20: 3.5e4 ... 4.5e4; 75x53: 4.0e3 ... 5.4e3
+        assert (3e4 if w == 24 else 3e3) < ref["cond"] < (5e4 if w == 24 else 6e3), ref["cond"]
+
+
+def test_large_angle_starts_leave_a_flat_pair_per_axis_sign_and_branch():
+    """Of the 32 starts on the 80x60 scene of seed 64: 28 finite with cond <= 1e5 (the flat bar), none finite with a
+    larger cond (such a pair would get pose_bar as is), 4 that lose every row and go non-finite.  (Seed 61, the scene of
+    test_gpu_large_rotations.py, leaves no finite pair at roll -0.8 / -1.2.)"""
+    p = ae.angle_pair()
+    pyr = ae.twin_pyramid(p, 2)
+    classes = dict(flat=0, conditioned=0, nonfinite=0)
+    good = set()
+    for s in edge_states.initial_states():
+        ref = ar.optimize(pyr, p["K"], ae.cfg(ae.ANGLE_MAX_ITER), init_pose=s)
+        if not np.all(np.isfinite(ref["state"])):
+            classes["nonfinite"] += 1
+            assert ref["flags"] & ar.PAIR_NONFINITE
+        elif ref["cond"] <= 1e5:
+            classes["flat"] += 1
+            assert ae.flat(ref)
+            if min(ref["valid_pixels"]) > 100:
+                good.add(ae.angle_label(s))
+        else:
+            classes["conditioned"] += 1
+    print(classes)
+    assert sum(classes.values()) == 32                       # none is left uncompared
+    assert good == {(axis, sign, branch) for axis in range(3) for sign in (1, -1) for branch in (2, 3)}, good
+    assert classes == dict(flat=28, conditioned=0, nonfinite=4), classes
+
+
+def test_large_motions_and_nonfinite_starts():
+    for p, init in ae.motion_pairs():
+        ref = ar.optimize(ae.twin_pyramid(p, 1), p["K"], ae.cfg(ae.MOTION_MAX_ITER, ae.MOTION_MIN_GRAD), init_pose=init)
+        _holds(ref, p["motion"][3])
+        assert ref["iterations"][0] < ae.MOTION_MAX_ITER[0] and abs(ref["state"][3] - p["motion"][3]) < 0.05
+    p = ae.angle_pair()
+    pyr = ae.twin_pyramid(p, 2)
+    states, bad = ae.nonfinite_batch()
+    for k, s in enumerate(states):
+        ref = ar.optimize(pyr, p["K"], ae.cfg(ae.ANGLE_MAX_ITER), init_pose=s)
+        if k in bad:
+            assert ref["iterations"] == [1, 1] and ref["valid_pixels"] == [0, 0]
+            assert ref["flags"] == ar.PAIR_RANK_DEFICIENT | ar.PAIR_NONFINITE
+        else:
+            _holds(ref, k)
+            assert ref["flags"] == 0
+
+
+@pytest.mark.parametrize("mi", [ae.MIX_MAX_ITER, [0, 0, 4]], ids=["three_levels", "coarsest_only"])
+def test_mixed_batch_pairs(mi):
+    both = ar.PAIR_RANK_DEFICIENT | ar.PAIR_NONFINITE
+    assert set(ae.MIX_KINDS) == set(ae.MIX_SEEDS) and len(ae.MIX_KINDS) == 12
+    for kind, p in ae.mixed_pairs().items():
+        ref = ar.optimize(ae.mixed_pyramid(p), p["K"], ae.cfg(mi))
+        if kind.startswith("healthy"):
+            _holds(ref, kind)
+            assert ref["flags"] == 0
+            continue
+        rows = dict(black=300, nan_depth=0, seven=7, eight=8)[kind]
+        assert ref["valid_pixels"][2] == rows and ref["iterations"][2] == 1, (kind, ref["valid_pixels"])
+        one_level = sum(m > 0 for m in mi) == 1
+        assert ref["flags"] == (ar.PAIR_NONFINITE if one_level and rows >= ar.NP else both), (kind, ref["flags"])
+
+
+def test_skipped_level_carries_gain_and_offset():
+    p = ae.exposure_pair()
+    pyr = ae.twin_pyramid(p, 3)
+    skip = ar.optimize(pyr, p["K"], ae.cfg(ae.SKIP_MAX_ITER))
+    full = ar.optimize(pyr, p["K"], ae.cfg(ae.FULL_MAX_ITER))
+    for ref in (skip, full):
+        _holds(ref, ref["iterations"])
+        assert np.all(np.abs(ref["state"][6:]) > 1e-3)
+    assert skip["iterations"] == [5, 1, 5] and skip["valid_pixels"][1] == 0
+    assert not np.array_equal(skip["state"][6:], full["state"][6:])
