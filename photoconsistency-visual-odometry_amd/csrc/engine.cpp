@@ -100,6 +100,8 @@ struct AlignSlot {
   double *d_illum = nullptr;                   // affine-illumination objective: (alpha, beta) of the enqueue's pairs, [pairs][2]
   int illum_capacity = 0;
   bool affine_ran = false;                     // the enqueue ran under PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE
+  int num_levels = 0;                          // the configuration the enqueue ran under: its levels, and which of them it
+  bool level_skipped[PHOVO_MAX_LEVELS] = {};   // skipped (max_num_iterations == 0) -- a fetch may come after a set_config
 };
 
 struct phovo_engine {
@@ -1406,6 +1408,8 @@ int phovo_engine_enqueue_align(phovo_engine *e, int n_pairs, const int *source_f
   s.d_states = nullptr;
   s.tr_ran = e->objective == PHOVO_OBJECTIVE_TRUST_REGION;
   s.affine_ran = e->objective == PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE;
+  s.num_levels = e->cfg.num_levels;
+  for (int l = 0; l < PHOVO_MAX_LEVELS; l++) s.level_skipped[l] = l < e->cfg.num_levels && e->cfg.max_num_iterations[l] <= 0;
   if (n_pairs == 0) {                    // nothing to run: a valid, empty enqueue (fetch of 0 pairs succeeds, no device buffer)
     e->ticket = ticket;
     s.ticket = ticket;
@@ -1721,10 +1725,11 @@ int phovo_engine_fetch(phovo_engine *e, int ticket, int n_pairs, double *out_sta
   if (reports) {
     std::memcpy(reports, s->h_down + (pl.reports - pl.states), sizeof(phovo_pair_report) * (size_t)n_pairs);
     // Levels with max_num_iterations == 0 still run the loop body once in the reference (:510,547-549).  (The Ceres
-    // aligner skips them: 0 steps.)
+    // aligner skips them: 0 steps.)  The levels are those of the configuration the ENQUEUE ran under: with two enqueues
+    // in flight the caller may have set another one since.
     for (int i = 0; i < n_pairs && !s->tr_ran; i++)
-      for (int l = 0; l < e->cfg.num_levels; l++)
-        if (e->cfg.max_num_iterations[l] <= 0) reports[i].iterations[l] = 1;
+      for (int l = 0; l < s->num_levels; l++)
+        if (s->level_skipped[l]) reports[i].iterations[l] = 1;
   }
   return PHOVO_OK;
 }
