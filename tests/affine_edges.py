@@ -17,17 +17,25 @@ MARGIN_FLOOR = 1e-6                       # test_gpu_affine.MARGIN_FLOOR (the GP
 GRAD_SCALE = 0.0625                       # image_gradients_scaling_factor of native.make_config
 
 
-def cfg(mi, mg=None, lo=0.3, hi=5.0):
+def cfg(mi, mg=None, lo=0.3, hi=5.0, lam=None):
     """The checker's configuration: affine_ref.optimize hands min_depth / max_depth to system() in every call."""
     nl = len(mi)
-    return dict(num_levels=nl, lam=[1.0] * nl, max_iter=list(mi), min_grad=list(mg) if mg else [0.0] * nl,
-                min_depth=lo, max_depth=hi)
+    return dict(num_levels=nl, lam=list(lam) if lam else [1.0] * nl, max_iter=list(mi),
+                min_grad=list(mg) if mg else [0.0] * nl, min_depth=lo, max_depth=hi)
 
 
 def twin_pyramid(p, nl):
     """The CPU pyramid of a pair (sizes divisible by 2^(nl-1)): what the CPU pre-checks use in place of the planes the
     GPU tests read back from the device."""
     return twin.build_pyramids(p["gray0"], p["depth0"], p["gray1"], nl, [GRAD_SCALE] * nl)
+
+
+def oracle_pyramid(p, nl):
+    """The CPU pyramid of a pair of any size (75x53 halves to 38x27), built by the oracle's producers."""
+    ocfg = oracle.make_config(num_levels=nl, max_iter=[1] * nl, min_grad=[0.0] * nl)
+    i0p, d0p = oracle.build_source_pyramids(p["gray0"], p["depth0"], ocfg)
+    i1p, gxp, gyp = oracle.build_target_pyramids(p["gray1"], ocfg)
+    return [(i0p[l], d0p[l], i1p[l], gxp[l], gyp[l]) for l in range(nl)]
 
 
 def flat(ref):
@@ -188,3 +196,104 @@ def exposure_pair():
     """The 0.8 I + 20 / 255 pair of test_affine_cpu.py and test_gpu_affine.test_gain_and_offset_on_the_device."""
     from test_affine_cpu import exposure_pair as pair
     return pair(31, SKIP_W, SKIP_H)
+
+
+# ---- E. step length ------------------------------------------------------------------------------------------------
+# (every other affine fixture has lambda = 1 on every level: a kernel that ignored it, or took another level's, passes them)
+STEP_LAMS = ([0.7, 0.5], [1.0, 0.7])
+STEP_FIXED = [4, 4]                        # fixed iterations
+STEP_MAX_ITER = [12, 12]                   # under part A's thresholds (WQ_MIN_GRAD): 4-8 iterations per level with these lambdas
+STEP_WIDE_W, STEP_WIDE_H, STEP_WIDE_SEED = 75, 53, 45
+STEP_WIDE_MAX_ITER, STEP_WIDE_MIN_GRAD = [12, 16], [4.0, 2.0]      # 3-4 / 10-14 iterations
+
+
+def step_pairs():
+    """(24x20 pairs A, B, C of part A, the 75x53 pair): two levels each."""
+    wide = synthetic.make_pair(STEP_WIDE_SEED, STEP_WIDE_W, STEP_WIDE_H, holes=0.02, trans=0.01, rot=0.005)
+    return work_queue_pairs()[:WQ_D], wide
+
+
+def step_configs(wide):
+    """[(name, max_iter, min_grad)]: fixed iterations, and thresholds."""
+    return [("fixed", STEP_FIXED, None),
+            ("threshold", STEP_WIDE_MAX_ITER if wide else STEP_MAX_ITER, STEP_WIDE_MIN_GRAD if wide else WQ_MIN_GRAD)]
+
+
+# ---- F. intrinsics -------------------------------------------------------------------------------------------------
+# (every other affine fixture has fx == fy and a principal point on the half-integer grid)
+K_SIZES = ((75, 53), (80, 60))
+K_SHIFTS = ((0.37, -0.23), (-0.41, 0.29))   # of the principal point: not dyadic, both signs on either axis
+K_SEED, K_MAX_ITER = 47, [3, 1]
+# the start: the coarse level's only iteration counts its rows here, where fy moves the projected rows by a tenth of the
+# shift (a converged pose hides fy: unprojection and projection cancel it)
+K_INIT = np.array([0.03, -0.08, 0.01, 0.01, 0.0, 0.0])
+
+
+def intrinsics_problem(w, h, shift):
+    """A pair aligned under fy = 1.1 fx and a principal point moved by `shift`.  Returns (pair, K)."""
+    p = synthetic.make_pair(K_SEED, w, h, holes=0.02, trans=0.04, rot=0.02)     # (rows leave the image: the count depends on fy)
+    K = p["K"].copy()
+    K[1, 1] = 1.1 * K[0, 0]
+    K[0, 2] += shift[0]
+    K[1, 2] += shift[1]
+    return p, K
+
+
+def with_fy_equal_fx(K):
+    K = K.copy()
+    K[1, 1] = K[0, 0]
+    return K
+
+
+# ---- G. well-posed systems of 7, 8 and 9 rows ------------------------------------------------------------------------
+ROWS_W, ROWS_H = 24, 20                   # 480 pixels: 8 chunks of 64 (the last one half full), two per wave
+ROWS_LAYOUTS = ("one_chunk", "four_waves")
+ROWS_SEARCH = range(400)                  # tests/test_affine_edges_cpu.py searches these seeds again
+ROWS_SEED = dict(one_chunk=90, four_waves=275)   # the smallest worst cond(J^T J) of the range: 5.2e3, 4.2e3
+ROWS_ITER = 3
+
+
+def rows_problem(seed, layout, count):
+    """One 24x20 level, set plane by plane: depth NaN except `count` (7, 8 or 9) pixels at least two pixels from the border
+    with depths from U(0.5, 4.5) -- the first `count` of nine drawn once, so that 7, 8 and 9 share their planes -- I0 from
+    U(0, 1), I1 = I0 + N(0, 0.01), GX1 and GY1 from U(-1, 1).  `one_chunk`: all nine in chunk 2 (raster indices 128 ... 191,
+    wave 2); `four_waves`: pixel j in a chunk of wave j mod 4, so the row count is summed across all four waves.
+    Returns (K, planes)."""
+    w, h = ROWS_W, ROWS_H
+    rs = np.random.RandomState(seed)
+    inner = [r * w + c for r in range(2, h - 2) for c in range(2, w - 2)]
+    if layout == "one_chunk":
+        picks = rs.choice([k for k in inner if k // 64 == 2], 9, replace=False)
+    else:
+        picks = [rs.choice([k for k in inner if (k // 64) % 4 == j % 4]) for j in range(9)]
+    depths = rs.uniform(0.5, 4.5, 9)
+    i0 = rs.uniform(0.0, 1.0, (h, w))
+    i1 = i0 + rs.normal(0.0, 0.01, (h, w))
+    gx, gy = rs.uniform(-1.0, 1.0, (h, w)), rs.uniform(-1.0, 1.0, (h, w))
+    d0 = np.full((h, w), np.nan)
+    seen = []
+    for k, z in zip(picks, depths):
+        if int(k) in seen:                                       # (four_waves draws with replacement: such a seed is unusable)
+            return None
+        seen.append(int(k))
+    for k, z in list(zip(picks, depths))[:count]:
+        d0[divmod(int(k), w)] = z
+    return synthetic.intrinsics(w, h), (i0, d0, i1, gx, gy)
+
+
+def rows_worst_cond(seed, layout):
+    """The largest cond(J^T J) the checker meets on the 8- and the 9-row problem over ROWS_ITER iterations (inf: unusable --
+    a repeated pixel, a row lost on the way, a non-finite state)."""
+    worst = 0.0
+    for count in (8, 9):
+        prob = rows_problem(seed, layout, count)
+        if prob is None:
+            return np.inf
+        K, planes = prob
+        state = np.zeros(ar.NP)
+        for it in range(1, ROWS_ITER + 1):
+            ref = ar.optimize([planes], K, cfg([it]))
+            if ref["valid_pixels"] != [count] or ref["flags"] or not np.all(np.isfinite(ref["state"])):
+                return np.inf
+        worst = max(worst, ref["cond"])
+    return worst

@@ -111,15 +111,20 @@ def optimize(pyr, K, cfg, init_pose=None):
     to level with the pose; per iteration x <- x - lambda_L H^-1 g, the level ends when the iteration count is reached or
     ||g||_2 (all 8 entries) < min_gradient_norm[L], tested after the step; a state that is not finite ends the level too.
     Levels with max_num_iterations 0 are skipped (they report one iteration, like the photometric objective's).
-    Returns dict(state[8], iterations[L], valid_pixels[L], flags, gradient_norm, cond, margin):
+    Returns dict(state[8], iterations[L], valid_pixels[L], flags, gradient_norm, cond, margin, h_norm):
       cond     the largest cond(J^T J) over the states the loop accepted (inf: a singular system)
-      margin   the smallest |  ||g|| - min_gradient_norm | / min_gradient_norm over all iterations (inf with thresholds 0)."""
+      margin   the smallest |  ||g|| - min_gradient_norm | / min_gradient_norm over all iterations (inf with thresholds 0)
+      h_norm   ||H||_2 of the system gradient_norm belongs to (inf where H is not finite): a state difference e moves that
+               gradient norm by at most h_norm |e| to first order
+      noise_level  the first level (the coarsest such) with an iteration of 1 ... 7 rows, or None.  J^T J then has rank below
+               8 without being exactly zero: unless a pivot is an exact zero (a black source), its last pivots are rounding
+               noise on the device and here alike, and nothing after that step is defined."""
     nl = cfg["num_levels"]
     state = np.zeros(NP)
     if init_pose is not None:
         state[:6] = np.asarray(init_pose, dtype=np.float64)
     iters, valid = [0] * nl, [0] * nl
-    flags, gnorm, cond, margin = 0, 0.0, 0.0, np.inf
+    flags, gnorm, cond, margin, h_norm, noise_level = 0, 0.0, 0.0, np.inf, 0.0, None
     for L in range(nl - 1, -1, -1):
         if cfg["max_iter"][L] <= 0:
             iters[L] = 1
@@ -130,6 +135,8 @@ def optimize(pyr, K, cfg, init_pose=None):
             valid[L] = n_rows
             if n_rows < NP:
                 flags |= PAIR_RANK_DEFICIENT
+                if n_rows > 0 and noise_level is None:
+                    noise_level = L
             try:
                 with np.errstate(all="ignore"):
                     step = np.linalg.solve(Hm, g)
@@ -139,6 +146,7 @@ def optimize(pyr, K, cfg, init_pose=None):
                 cond = np.inf
             state = state - cfg["lam"][L] * step
             gnorm = float(np.linalg.norm(g))
+            h_norm = float(np.linalg.norm(Hm, 2)) if np.all(np.isfinite(Hm)) else np.inf
             thr = cfg["min_grad"][L]
             if thr > 0:
                 margin = min(margin, abs(gnorm - thr) / thr)
@@ -150,7 +158,7 @@ def optimize(pyr, K, cfg, init_pose=None):
                 break
         iters[L] = it
     return dict(state=state, iterations=iters, valid_pixels=valid, flags=flags, gradient_norm=gnorm, cond=cond,
-                margin=margin)
+                margin=margin, h_norm=h_norm, noise_level=noise_level)
 
 
 def pose_bar(cond, states, flat=1e-9):

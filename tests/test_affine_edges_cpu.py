@@ -136,3 +136,70 @@ def test_skipped_level_carries_gain_and_offset():
         assert np.all(np.abs(ref["state"][6:]) > 1e-3)
     assert skip["iterations"] == [5, 1, 5] and skip["valid_pixels"][1] == 0
     assert not np.array_equal(skip["state"][6:], full["state"][6:])
+
+
+# ---- E. step length ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("lam", ae.STEP_LAMS, ids=["lam_0.7_0.5", "lam_1.0_0.7"])
+def test_step_length_fixtures_depend_on_lambda(lam):
+    """Flat bar and threshold margin as everywhere; and the checker's own result under lambda = 1, or under the two levels'
+    lambdas exchanged, is further away than a thousand bars: a kernel that ignored lambda or took another level's cannot
+    pass."""
+    small, wide = ae.step_pairs()
+    for p, is_wide in [(q, False) for q in small] + [(wide, True)]:
+        pyr = ae.oracle_pyramid(p, 2)
+        if not is_wide:
+            twin = ae.twin_pyramid(p, 2)
+            assert all(np.array_equal(a, b) for lv, lt in zip(pyr, twin) for a, b in zip(lv, lt))
+        for name, mi, mg in ae.step_configs(is_wide):
+            ref = ar.optimize(pyr, p["K"], ae.cfg(mi, mg, lam=lam))
+            _holds(ref, (is_wide, name, lam))
+            assert ref["flags"] == 0
+            if name == "threshold":
+                assert any(it < m for it, m in zip(ref["iterations"], mi)), ref["iterations"]   # a threshold ends a level
+            bar = ar.pose_bar(ref["cond"], ref["state"])
+            for other in ([1.0, 1.0], lam[::-1]):
+                alt = ar.optimize(pyr, p["K"], ae.cfg(mi, mg, lam=other))
+                assert np.abs(alt["state"] - ref["state"]).max() > 1e3 * bar, (is_wide, name, lam, other)
+
+
+# ---- F. intrinsics -------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("shift", ae.K_SHIFTS, ids=["ox+_oy-", "ox-_oy+"])
+@pytest.mark.parametrize("w,h", ae.K_SIZES, ids=["75x53", "80x60"])
+def test_intrinsics_fixtures_depend_on_fy(w, h, shift):
+    """fy = 1.1 fx: the checker with fy := fx differs by more than a thousand bars and in the row count."""
+    p, K = ae.intrinsics_problem(w, h, shift)
+    assert K[1, 1] != K[0, 0] and (K[0, 2] * 2) % 1 != 0 and (K[1, 2] * 2) % 1 != 0
+    pyr = ae.oracle_pyramid(p, 2)
+    ref = ar.optimize(pyr, K, ae.cfg(ae.K_MAX_ITER), init_pose=ae.K_INIT)
+    _holds(ref, (w, h, shift))
+    assert ref["flags"] == 0 and min(ref["valid_pixels"]) > 500
+    alt = ar.optimize(pyr, ae.with_fy_equal_fx(K), ae.cfg(ae.K_MAX_ITER), init_pose=ae.K_INIT)
+    assert np.abs(alt["state"] - ref["state"]).max() > 1e3 * ar.pose_bar(ref["cond"], ref["state"])
+    assert alt["valid_pixels"] != ref["valid_pixels"]
+
+
+# ---- G. 7, 8 and 9 rows --------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("layout", ae.ROWS_LAYOUTS)
+def test_eight_row_problem_is_the_best_of_its_seed_range_and_well_posed(layout):
+    """The committed seed is the one the search finds; its 8- and 9-row systems keep their rows over ROWS_ITER iterations
+    with cond(J^T J) <= 1e5, one ulp of fx moves each state by less than a quarter of the flat bar, and the 7-row problem
+    has 7 rows."""
+    conds = [ae.rows_worst_cond(s, layout) for s in ae.ROWS_SEARCH]
+    seed = int(np.argmin(conds))
+    assert seed == ae.ROWS_SEED[layout] and conds[seed] <= 1e5, (seed, conds[seed])
+    print(layout, seed, conds[seed])
+    for count in (8, 9):
+        K, planes = ae.rows_problem(seed, layout, count)
+        chunks = {k // 64 for k in np.flatnonzero(np.isfinite(planes[1]).reshape(-1))}
+        assert len(chunks) == 1 if layout == "one_chunk" else {c % 4 for c in chunks} == {0, 1, 2, 3}, chunks
+        K1 = K.copy()
+        K1[0, 0] = np.nextafter(K1[0, 0], 2.0 * K1[0, 0])
+        for mi in ([1], [ae.ROWS_ITER]):
+            ref = ar.optimize([planes], K, ae.cfg(mi))
+            _holds(ref, (layout, count, mi))
+            assert ref["valid_pixels"] == [count] and ref["flags"] == 0 and ref["iterations"] == mi
+            moved = np.abs(ar.optimize([planes], K1, ae.cfg(mi))["state"] - ref["state"]).max()
+            assert moved < 0.25 * ar.pose_bar(ref["cond"], ref["state"]), moved
+    K, planes = ae.rows_problem(seed, layout, 7)
+    ref = ar.optimize([planes], K, ae.cfg([1]))
+    assert ref["valid_pixels"] == [7] and ref["iterations"] == [1] and ref["flags"] & ar.PAIR_RANK_DEFICIENT

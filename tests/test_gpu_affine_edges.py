@@ -1,7 +1,8 @@
 """The affine-illumination kernel (gn_affine_kernel.hip) where tests/test_gpu_affine.py does not reach: the
 second trip of its persistent loop and the eight-queue draw, rows and clamped taps at exact positions and depth exactly at
 the gate, initial states in every branch of the device's sin / cos, degenerate pairs beside healthy ones in one launch, a
-skipped level between two that run.  The reference of every comparison is tests/affine_ref.py in fp64 on the planes as the
+skipped level between two that run; step lengths other than 1 that differ between the levels, fy != fx with a principal
+point off the half-integer grid, and well-posed systems of exactly 8 and 9 rows beside one of 7.  The reference of every comparison is tests/affine_ref.py in fp64 on the planes as the
 device holds them; the bars are test_gpu_affine._compare's (iterations, valid_pixels and flags exact, state and gradient
 norm to affine_ref.pose_bar).  Every fixture (tests/affine_edges.py) is chosen to hold the flat bar and to stay clear of its
 gradient thresholds; tests/test_affine_edges_cpu.py asserts both without a device."""
@@ -22,10 +23,10 @@ assert ae.MARGIN_FLOOR == MARGIN_FLOOR
 pytestmark = pytest.mark.gpu
 
 
-def _engine(K, w, h, frames, mi, mg=None, depth_range=None):
+def _engine(K, w, h, frames, mi, mg=None, depth_range=None, lam=None):
     nl = len(mi)
     eng = odometry.AlignmentEngine()
-    eng.set_config(native.make_config(num_levels=nl, max_iter=mi, min_grad=mg if mg else [0.0] * nl))
+    eng.set_config(native.make_config(num_levels=nl, max_iter=mi, min_grad=mg if mg else [0.0] * nl, lam=lam))
     eng.set_objective(AFFINE)
     eng.set_intrinsic_matrix(K)
     if depth_range is not None:
@@ -268,3 +269,66 @@ def test_affine_skipped_level():
         got[tuple(mi)] = (_bits(ab[0]), list(reps[0].iterations[:nl]))
     assert got[tuple(ae.SKIP_MAX_ITER)][1] == [5, 1, 5]
     assert got[tuple(ae.SKIP_MAX_ITER)][0] != got[tuple(ae.FULL_MAX_ITER)][0]
+
+
+# ---- E. step length ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("lam", ae.STEP_LAMS, ids=["lam_0.7_0.5", "lam_1.0_0.7"])
+def test_affine_step_length(lam):
+    """lambda below 1 and different on the two levels, at fixed iterations and under thresholds: the checker's result under
+    lambda = 1 or under the levels' lambdas exchanged is more than a thousand bars away (tests/test_affine_edges_cpu.py)."""
+    small, wide = ae.step_pairs()
+    for pairs, w, h, is_wide in ((small, ae.WQ_W, ae.WQ_H, False), ([wide], ae.STEP_WIDE_W, ae.STEP_WIDE_H, True)):
+        for name, mi, mg in ae.step_configs(is_wide):
+            with _engine(pairs[0]["K"], w, h, 2 * len(pairs), mi, mg, lam=lam) as eng:
+                _upload(eng, pairs)
+                pyr = [_device_pyramid(eng, 2 * i, 2 * i + 1, 2, mi) for i in range(len(pairs))]
+                s, ab, reps = _align(eng, list(range(len(pairs))))
+            for i, p in enumerate(pairs):
+                ref = ar.optimize(pyr[i], p["K"], ae.cfg(mi, mg, lam=lam))
+                assert ref["flags"] == 0
+                _hold("E", f"{w}x{h} pair {i} {name} lambda {lam}", s[i], ab[i], reps[i], ref, 2)
+
+
+# ---- F. intrinsics -------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("shift", ae.K_SHIFTS, ids=["ox+_oy-", "ox-_oy+"])
+@pytest.mark.parametrize("w,h", ae.K_SIZES, ids=["75x53", "80x60"])
+def test_affine_fy_differs_from_fx(w, h, shift):
+    """fy = 1.1 fx, the principal point off the half-integer grid: fx, fy, 1 / fx, 1 / fy, ox and oy each reach the warp and
+    the Jacobian where they belong (the checker with fy := fx differs in state and rows)."""
+    p, K = ae.intrinsics_problem(w, h, shift)
+    with _engine(K, w, h, 2, ae.K_MAX_ITER) as eng:
+        _upload(eng, [p])
+        pyr = _device_pyramid(eng, 0, 1, 2, ae.K_MAX_ITER)
+        s, ab, reps = _align(eng, [0, 0, 0], np.tile(ae.K_INIT, (3, 1)))
+    ref = ar.optimize(pyr, K, ae.cfg(ae.K_MAX_ITER), init_pose=ae.K_INIT)
+    alt = ar.optimize(pyr, ae.with_fy_equal_fx(K), ae.cfg(ae.K_MAX_ITER), init_pose=ae.K_INIT)
+    assert alt["valid_pixels"] != ref["valid_pixels"] and ref["flags"] == 0
+    _hold("F", f"{w}x{h} shift {shift}", s[0], ab[0], reps[0], ref, 2)
+    for k in range(3):
+        assert _record(s[k], ab[k], reps[k], 2) == _record(s[0], ab[0], reps[0], 2)
+
+
+# ---- G. 7, 8 and 9 rows --------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("layout", ae.ROWS_LAYOUTS)
+def test_affine_well_posed_systems_of_eight_and_nine_rows(layout):
+    """Exactly NP rows of real data, well posed (cond(J^T J) 4e3 ... 5e3): flags 0 and the state within the flat bar after
+    one iteration and after three; nine rows alike; with seven the pair is RANK_DEFICIENT after its one iteration (its step
+    is rounding noise on either side: nothing is asserted on the state).  The rows sit in one chunk of one wave, or in all
+    four waves."""
+    seed = ae.ROWS_SEED[layout]
+    for count, mi in ((8, [1]), (8, [ae.ROWS_ITER]), (9, [1]), (9, [ae.ROWS_ITER]), (7, [1])):
+        K, planes = ae.rows_problem(seed, layout, count)
+        i0, d0, i1, gx, gy = planes
+        with _engine(K, ae.ROWS_W, ae.ROWS_H, 2, mi) as eng:
+            eng.set_level_planes(0, 0, intensity=i0, depth=d0)
+            eng.set_level_planes(1, 0, intensity=i1, grad_x=gx, grad_y=gy)
+            s, ab, reps = _align(eng, [0, 0, 0])
+        for k in range(3):
+            assert _record(s[k], ab[k], reps[k], 1) == _record(s[0], ab[0], reps[0], 1)
+        assert list(reps[0].valid_pixels[:1]) == [count] and list(reps[0].iterations[:1]) == mi
+        if count == 7:
+            assert reps[0].flags & ar.PAIR_RANK_DEFICIENT
+            continue
+        ref = ar.optimize([planes], K, ae.cfg(mi))
+        assert ref["valid_pixels"] == [count] and ref["flags"] == 0 and reps[0].flags == 0
+        _hold("G", f"{layout} {count} rows {mi[0]} iterations", s[0], ab[0], reps[0], ref, 1)

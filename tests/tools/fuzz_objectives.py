@@ -1,7 +1,8 @@
 """Randomised device-vs-checker sweep of the bi-objective (`bi`, gn_biobjective_kernel.hip), trust-region (`tr`,
-gn_trust_region_kernel.hip) and evaluate (`eval`, gn_evaluate_kernels.hip) kernels, in the style of fuzz_parity.py.
+gn_trust_region_kernel.hip), evaluate (`eval`, gn_evaluate_kernels.hip) and affine-illumination (`affine`,
+gn_affine_kernel.hip) kernels, in the style of fuzz_parity.py.
 
-    python tests/tools/fuzz_objectives.py [cases=100] [seed=0] [mode=bi|tr|eval] [big] [angles]
+    python tests/tools/fuzz_objectives.py [cases=100] [seed=0] [mode=bi|tr|eval|affine] [big] [angles]
 
 Every case draws (draw_case, pure numpy, so that replay and coverage are testable without a GPU): an odd size with 1-3
 levels up to 330x250 (`big`: 340x260 ... 700x500 with 1-2 levels) or a strip 1-5 pixels wide; intrinsics perturbed off
@@ -24,6 +25,23 @@ the pose bar as `bi`'s, and what it carries into costs, Jacobi scaling and gradi
 and flag still exact; the summary counts those cases.  The `eval` tile classes are predicted from the level sizes (the
 evaluate path keeps no launch record).
 
+`affine` takes `bi`'s draws (lambda 1 or 0.7 per level included; no target-depth defects) and adds its own after them
+(_draw_affine), so that the other modes' draws stay what they were: sizes that do not halve exactly, a quarter of the cases
+small enough to aim level 0 at one trip-count class of the kernel's pixel loop (CHUNK_CLASSES) with a full or a partial last
+chunk, an exposure change of the target (gain and offset before the u8 clip), gradient thresholds of this objective's
+scale.  Device side: objective 3 with the case's lambda and perturbed K, upload under one depth range and alignment under
+another, the planes of every level that runs read back, every launch of kind `affine`.  Checker side (_check_affine):
+affine_ref.optimize on those planes; every replica has replica 0's bits (state, (alpha, beta), report); iterations, valid
+pixels and flags equal; where the checker's state is not finite the device's is not finite in the same entries; otherwise
+all 8 entries within affine_ref.pose_bar (1e-9 x max(1, cond / 1e5), capped at 1e-5, x max(1, |x|)) and the gradient norm
+within 1e-9 x max(1, |g|), plus |H|_2 sqrt(8) x bar where the bar is scaled.  A case within MARGIN_FLOOR of a gradient
+threshold is not compared.  A case that misses is set aside, printed and counted, only if the checker itself is unstable
+there -- with fx one ulp larger its counts, flags or finiteness change, or its state moves by more than a quarter of the
+bar -- or if it met a system of 1 to 7 rows: the step of such a system is rounding noise on both sides and no report after
+it is defined, so RANK_DEFICIENT and the levels that ran before it are compared, nothing after.  The
+summary adds, from the checker's results, the cases that passed only under the scaled bar, those that ended non-finite,
+the levels under a threshold that ended by it and by their count, and the chunk classes run.
+
 One line per failure, a summary, exit status 1 on any failure.  FUZZ_ONLY=12,345 runs only those cases, with the draws of
 the full sweep.  The checkers run in FUZZ_JOBS worker processes (default: up to 12), which never touch the GPU.
 """
@@ -41,7 +59,7 @@ for p in (ROOT, TESTS, HERE):
         sys.path.insert(0, p)
 from fuzz_draws import draw_angle  # noqa: E402
 
-MODES = ("bi", "tr", "eval")
+MODES = ("bi", "tr", "eval", "affine")
 CERES_FILES = ("config_3_level_optimization_ceres.yml", "config_4_level_optimization_ceres.yml",
                "config_5_level_optimization_ceres.yml", "config_only_level_0_ceres.yml",
                "config_only_level_1_ceres.yml", "config_only_level_2_ceres.yml")
@@ -51,6 +69,14 @@ TGT_DEFECTS = ("zero", "negative", "beyond_max", "nan")
 # the planners (gn_plan_level_biobjective / _trust_region) choose, for the coverage test; the sweep records the real one
 LDS_LIMIT, LDS_FIXED = 160 * 1024, 4096
 STATES = None
+# gn_affine_kernel.hip has one geometry; what differs from level to level is the trip count of its pixel loop, a two-chunk
+# software pipeline over four waves: n_chunks = ceil(n / 64) of 1 (three idle waves), 2-3 (idle waves), 4 (one chunk per
+# wave), 5-7 (one or two chunks per wave), 8 (two per wave), 9-12 (the loop's second trip on some waves), 13 and more
+CHUNK_CLASSES = ("chunks1", "chunks2-3", "chunks4", "chunks5-7", "chunks8", "chunks9-12", "chunks13+")
+MARGIN_FLOOR = 1e-6                       # test_gpu_affine.MARGIN_FLOOR
+# the `affine` sweeps of tests/test_gpu_affine_sweep.py: (flags, cases, seed); tests/test_affine_sweep_cpu.py holds their
+# draws to full coverage, and the checker on the first one's to the caps, without a device
+AFFINE_SWEEPS = (((), 300, 14), (("angles",), 150, 41), (("big",), 40, 52))
 
 
 def _edge_states():
@@ -67,12 +93,49 @@ def level_size(w, h, level):
     return w, h
 
 
+def device_level_size(w, h, level):
+    """The size the engine gives a level of any image (engine.cpp level_dims: cvRound(w / 2^level), halves to even)."""
+    return int(np.rint(w / 2.0 ** level)), int(np.rint(h / 2.0 ** level))
+
+
 def predicted_geometry(mode, n):
     if mode == "eval":
         tiles = -(-(-(-n // 64)) // 16)
         return "tiles1" if tiles == 1 else "tiles2-16" if tiles <= 16 else "tiles17+"
     own = 4 * n + 8 * -(-n // 64)
     return "lds256" if LDS_FIXED + own <= LDS_LIMIT // 2 else "lds512" if LDS_FIXED + own <= LDS_LIMIT else "hbm512"
+
+
+def chunk_class(n):
+    nc = -(-n // 64)
+    return CHUNK_CLASSES[0 if nc == 1 else 1 if nc <= 3 else 2 if nc == 4 else 3 if nc <= 7 else 4 if nc == 8 else
+                         5 if nc <= 12 else 6]
+
+
+def _draw_affine(rs, c):
+    """The draws of `affine` alone, after all others (the other modes' streams do not see them): arbitrary sizes (the
+    planes are read back from the device, so a level need not halve exactly), a quarter of the cases small enough to aim
+    at one chunk class of the pixel loop, an exposure change of the target, thresholds of this objective's scale."""
+    unit = 2 ** (c["nl"] - 1)
+    odd = [int(rs.randint(0, unit)), int(rs.randint(0, unit))]
+    small = rs.rand() < 0.25
+    nc = [1, int(rs.randint(2, 4)), 4, int(rs.randint(5, 8)), 8, int(rs.randint(9, 13)), int(rs.randint(13, 30))][
+        int(rs.randint(0, len(CHUNK_CLASSES)))]
+    full = rs.rand() < 0.3
+    n = 64 * (nc - 1) + int(rs.randint(17, 64))
+    sh, fh = int(rs.randint(3, 17)), int(rs.choice([4, 8, 16]))
+    if c["size_class"] != "strip":
+        if small:                                   # level 0 has nc chunks, the last one full or partial
+            # (at least 3 wide: the coarsest of three levels then still has a pixel, device_level_size)
+            c.update(size_class="small", w=64 * nc // fh if full else max(n // sh, 3), h=fh if full else sh)
+        else:
+            c.update(w=c["w"] + odd[0], h=c["h"] + odd[1])
+    gain, offset = float(rs.uniform(-0.25, 0.2)), float(rs.uniform(-0.06, 0.1))
+    c["exposure"] = [gain, offset] if rs.rand() < 0.7 else None
+    # thresholds 0.05 ... 90 in place of 1 ... 300: with at most 6 iterations per level from these starts, ||g|| (a sum
+    # over the level's rows) passes 0.3 ... 2.0, where DESIGN.md §14's converged fixtures end, on few levels only
+    scale = float(rs.choice([0.05, 0.1, 0.3]))
+    c["min_grad"] = [m * scale for m in c["min_grad"]]
 
 
 def draw_case(rs, mode, flags):
@@ -122,7 +185,7 @@ def draw_case(rs, mode, flags):
     c["max_iter"] = max_iter
     c["min_grad"] = [0.0] * nl if fixed else mg
     lam = [float(rs.choice([1.0, 0.7])) for _ in range(nl)]
-    c["lam"] = lam if mode == "bi" else [1.0] * nl
+    c["lam"] = lam if mode in ("bi", "affine") else [1.0] * nl
     ceres = int(rs.randint(0, len(CERES_FILES) + 2))
     c["ceres"] = CERES_FILES[ceres] if ceres < len(CERES_FILES) else "fixed"
     c["tr_max_iter"] = [int(rs.randint(0, 7)) for _ in range(nl)]
@@ -143,6 +206,8 @@ def draw_case(rs, mode, flags):
     c["eval_spread"] = float(rs.choice([0.0, 0.003, 0.02]))
     c["eval_edge"] = int(rs.randint(0, 32)) if rs.rand() < 0.25 else None
     c["n_pairs"] = int(rs.choice([1, 3, 40]))
+    if mode == "affine":
+        _draw_affine(rs, c)
     return c
 
 
@@ -164,7 +229,10 @@ def case_key(d):
 
 def level_geometries(d):
     levels = [l for l in range(d["nl"]) if d["mode"] == "eval" or
-              (d["max_iter"] if d["mode"] == "bi" else d["tr_max_iter"])[l] > 0]
+              (d["tr_max_iter"] if d["mode"] == "tr" else d["max_iter"])[l] > 0]
+    if d["mode"] == "affine":
+        sizes = [int(np.prod(device_level_size(d["w"], d["h"], l))) for l in levels]
+        return {chunk_class(n) for n in sizes} | {"last_partial" if n % 64 else "last_full" for n in sizes}
     return {predicted_geometry(d["mode"], int(np.prod(level_size(d["w"], d["h"], l)))) for l in levels}
 
 
@@ -173,10 +241,14 @@ def coverage(draws, mode):
     cov = {f"size_{k}": 0 for k in ("normal", "strip", "big")}
     cov.pop("size_big")
     geos = ["tiles1", "tiles2-16", "tiles17+"] if mode == "eval" else ["lds256", "lds512", "hbm512"]
+    if mode == "affine":
+        geos = list(CHUNK_CLASSES) + ["last_partial", "last_full"]
+        cov.update(size_small=0, k_perturb=0, exposure=0, no_exposure=0)
     cov.update({g: 0 for g in geos})
     cov.update({f"src_{k}": 0 for k in SRC_DEFECTS})
     if mode == "bi":
         cov.update({f"tgt_{k}": 0 for k in TGT_DEFECTS})
+    if mode in ("bi", "affine"):
         cov["lambda_0.7"] = 0
     if mode == "eval":
         cov.update({f"storage_{k}": 0 for k in range(3)})
@@ -192,8 +264,11 @@ def coverage(draws, mode):
             cov[f"src_{k}"] += 1
         for k in d["tgt_defects"]:
             cov[f"tgt_{k}"] += 1
-        if mode == "bi":
+        if mode in ("bi", "affine"):
             cov["lambda_0.7"] += int(0.7 in d["lam"])
+        if mode == "affine":
+            cov["k_perturb"] += int(d["k_perturb"] is not None)
+            cov["exposure" if d["exposure"] is not None else "no_exposure"] += 1
         if mode == "eval":
             cov[f"storage_{d['storage']}"] += 1
             cov["huber"] += int(d["huber"] is not None)
@@ -202,7 +277,7 @@ def coverage(draws, mode):
         cov["range_changed"] += int(d["upload_range"] != d["range"])
         cov["range_non_default"] += int(d["range"] != [0.3, 5.0])
         cov[f"pairs_{d['n_pairs']}"] += 1
-        cov["init_edge"] += int(isinstance(d["init"], tuple) or d["eval_edge"] is not None)
+        cov["init_edge"] += int(isinstance(d["init"], tuple) or (mode != "affine" and d["eval_edge"] is not None))
     return cov
 
 
@@ -242,6 +317,10 @@ def render(d):
         if k in d["tgt_defects"]:
             d1[m] = v
     p["depth0"], p["depth1"] = d0, d1
+    if d.get("exposure") is not None:               # (affine) the target under another exposure, clipped like a camera's
+        gain, offset = d["exposure"]
+        g1 = (1.0 + gain) * p["gray1"].astype(np.float64) + 255.0 * offset
+        p["gray1"] = np.clip(np.rint(g1), 0, 255).astype(np.uint8)
     init = d["init"]
     if isinstance(init, tuple):
         init = _edge_states()[init[1]]
@@ -298,6 +377,9 @@ def run_device(d):
             opt, job["opt"] = _tr_options(d, nl)
             e.set_trust_region_options(opt)
             e.set_batch_invariant(True)
+        elif mode == "affine":
+            e.set_config(native.make_config(num_levels=nl, max_iter=d["max_iter"], min_grad=d["min_grad"], lam=d["lam"]))
+            e.set_objective(native.OBJECTIVE_PHOTOMETRIC_AFFINE)
         else:
             e.set_config(native.make_config(num_levels=nl, max_iter=[1] * nl, min_grad=[0.0] * nl))
             e.set_extensions(native.make_extensions(plane_storage=[native.STORAGE_F64, native.STORAGE_F32,
@@ -310,7 +392,22 @@ def run_device(d):
         e.upload_frame(0, p["gray0"], p["depth0"], native.ROLE_SOURCE)
         e.upload_frame(1, p["gray1"], p["depth1"] if mode == "bi" else None, native.ROLE_TARGET)
         e.set_depth_range(lo, hi)
-        if mode in ("bi", "tr"):
+        if mode == "affine":
+            # the planes as the device holds them, of every level that runs (odd sizes: tests/pyramid_exact.py pins them)
+            pyr = []
+            for l in range(nl):
+                if d["max_iter"][l] <= 0:
+                    pyr.append(None)
+                    continue
+                i0, d0, _, _ = e.get_level_planes(0, l)
+                i1, _, gx, gy = e.get_level_planes(1, l)
+                pyr.append((i0, d0, i1, gx, gy))
+                geos.update((chunk_class(i0.size), "last_partial" if i0.size % 64 else "last_full"))
+            inits = None if p["init"] is None else np.tile(p["init"], (n_pairs, 1))
+            s, reps = e.align_pairs([0] * n_pairs, [1] * n_pairs, init_states=inits, want_reports=True)
+            job.update(pyr=pyr, states=s, reps=[_plain_report(r) for r in reps], illum=e.fetch_illumination(n_pairs),
+                       kinds=sorted({r["kind"] for r in e.last_launches()}))
+        elif mode in ("bi", "tr"):
             inits = None if p["init"] is None else np.tile(p["init"], (n_pairs, 1))
             s, reps = e.align_pairs([0] * n_pairs, [1] * n_pairs, init_states=inits, want_reports=True)
             for r in e.last_launches():
@@ -351,7 +448,7 @@ def _ok(status, ratio, msg=""):
 def check_job(job):
     """The checker's side of one case, in a worker process (no GPU): dict(status ok / fail / skip, ratio, msg)."""
     try:
-        return {"bi": _check_bi, "tr": _check_tr, "eval": _check_eval}[job["d"]["mode"]](job)
+        return {"bi": _check_bi, "tr": _check_tr, "eval": _check_eval, "affine": _check_affine}[job["d"]["mode"]](job)
     except Exception as ex:                                     # a checker that raises is a failure, with its reason
         import traceback
         return _ok("fail", np.inf, "checker raised: " + "".join(traceback.format_exception_only(type(ex), ex)).strip())
@@ -534,6 +631,119 @@ def _check_eval(job):
     return _ok("skip", worst, "; ".join(knife)) if knife else _ok("ok", worst)
 
 
+def affine_reference(d, K, pyr, init):
+    """affine_ref.optimize on the case's planes under its configuration and the depth range in force at the alignment."""
+    import affine_ref as ar
+    nl = d["nl"]
+    cfg = dict(num_levels=nl, lam=d["lam"], max_iter=d["max_iter"], min_grad=d["min_grad"], min_depth=d["range"][0],
+               max_depth=d["range"][1])
+    return ar.optimize(pyr, K, cfg, init)
+
+
+def affine_outcome(d, ref):
+    """What the summary counts, from the checker's result alone: finite or not, flat or scaled bar, and of the levels that
+    ran under a gradient threshold how many ended by it and how many by their iteration count."""
+    import affine_ref as ar
+    finite = bool(np.all(np.isfinite(ref["state"])))
+    bar = ar.pose_bar(ref["cond"], ref["state"]) if finite else np.nan
+    big = max(1.0, float(np.abs(ref["state"]).max())) if finite else np.nan
+    thr = cnt = 0
+    for L in range(d["nl"]):
+        if d["max_iter"][L] > 0 and d["min_grad"][L] > 0 and finite:
+            thr += int(ref["iterations"][L] < d["max_iter"][L])
+            cnt += int(ref["iterations"][L] >= d["max_iter"][L])
+    return dict(finite=finite, bar=bar, scaled=finite and bar > 1e-9 * big, capped=finite and bar >= 1e-5 * big,
+                by_threshold=thr, by_count=cnt, no_rows=not finite and sum(ref["valid_pixels"]) == 0)
+
+
+def affine_unstable(d, K, pyr, init, ref):
+    """The knife-edge question: does one ulp of fx change the checker's own counts, flags or finiteness, or move its state
+    by more than a quarter of the bar?  Returns (unstable, why)."""
+    import affine_ref as ar
+    K1 = np.array(K, dtype=np.float64)
+    K1[0, 0] = np.nextafter(K1[0, 0], 2.0 * K1[0, 0])
+    ref1 = affine_reference(d, K1, pyr, init)
+    fin, fin1 = np.isfinite(ref["state"]), np.isfinite(ref1["state"])
+    if (ref1["iterations"] != ref["iterations"] or ref1["valid_pixels"] != ref["valid_pixels"] or
+            ref1["flags"] != ref["flags"] or not np.array_equal(fin, fin1)):
+        return True, (f"one ulp of fx changes the checker's counts: iterations {ref['iterations']} -> {ref1['iterations']}, "
+                      f"rows {ref['valid_pixels']} -> {ref1['valid_pixels']}, flags {ref['flags']} -> {ref1['flags']}")
+    if not np.all(fin):
+        return False, "one ulp of fx leaves the checker's counts and non-finite entries as they are"
+    moved = float(np.abs(ref1["state"] - ref["state"]).max())
+    bar = ar.pose_bar(ref["cond"], ref["state"])
+    return moved > 0.25 * bar, f"one ulp of fx moves the checker's state by {moved:.2e} (bar {bar:.1e})"
+
+
+def precheck_affine(d):
+    """The checker's side of an `affine` case on oracle-built pyramids in place of the device's (DESIGN.md §3.6 has them
+    bit-identical), for the CPU pre-check of the committed sweeps: affine_outcome's counts, whether the case is unstable
+    under the one-ulp question, whether it comes within MARGIN_FLOOR of a threshold, whether it meets a system of 1-7 rows."""
+    from oracle import oracle
+    p = render(d)
+    nl = d["nl"]
+    ocfg = oracle.make_config(num_levels=nl, max_iter=[1] * nl, min_grad=[0.0] * nl)
+    i0p, d0p = oracle.build_source_pyramids(p["gray0"], p["depth0"], ocfg)
+    i1p, gxp, gyp = oracle.build_target_pyramids(p["gray1"], ocfg)
+    pyr = [(i0p[l], d0p[l], i1p[l], gxp[l], gyp[l]) for l in range(nl)]
+    ref = affine_reference(d, p["K"], pyr, p["init"])
+    out = affine_outcome(d, ref)
+    out["unstable"] = affine_unstable(d, p["K"], pyr, p["init"], ref)[0]
+    out["near_threshold"] = bool(ref["margin"] <= MARGIN_FLOOR)
+    out["noise"] = ref["noise_level"] is not None
+    return out
+
+
+def _check_affine(job):
+    import affine_ref as ar
+    d, p = job["d"], job["p"]
+    nl = d["nl"]
+    if job["kinds"] != ["affine"]:
+        return _ok("fail", np.inf, f"launch kinds {job['kinds']}")
+    s, ab, reps = job["states"], job["illum"], job["reps"]
+    for k in range(1, len(reps)):
+        if not (np.array_equal(s[k], s[0], equal_nan=True) and np.array_equal(ab[k], ab[0], equal_nan=True) and
+                _same_report(reps[k], reps[0])):
+            return _ok("fail", np.inf, f"replica {k} differs from replica 0")
+    ref = affine_reference(d, p["K"], job["pyr"], p["init"])
+    info = affine_outcome(d, ref)
+    if ref["margin"] <= MARGIN_FLOOR:
+        return dict(_ok("skip", 0.0, f"threshold margin {ref['margin']:.2e}: not compared"), info=info)
+    dev, rep = np.concatenate([s[0], ab[0]]), reps[0]
+    ratio, bar = 0.0, info["bar"]
+    try:
+        assert list(rep.iterations[:nl]) == ref["iterations"], ("iterations", rep.iterations[:nl], ref["iterations"])
+        assert list(rep.valid_pixels[:nl]) == ref["valid_pixels"], ("rows", rep.valid_pixels[:nl], ref["valid_pixels"])
+        assert rep.flags == ref["flags"], ("flags", rep.flags, ref["flags"])
+        if not info["finite"]:
+            bad = ~np.isfinite(ref["state"])
+            assert not np.any(np.isfinite(dev[bad])), ("finite where the checker is not", dev, ref["state"])
+        else:
+            ratio = float(np.abs(dev - ref["state"]).max()) / bar if np.all(np.isfinite(dev)) else np.inf
+            assert ratio <= 1.0, ("state", dev, ref["state"])
+            gbar = 1e-9 * max(1.0, ref["gradient_norm"])
+            if info["scaled"]:                      # what the scaled pose bar carries into the gradient, to first order
+                gbar += ref["h_norm"] * np.sqrt(8.0) * bar
+            assert abs(rep.gradient_norm - ref["gradient_norm"]) <= gbar, ("gradient norm", rep.gradient_norm,
+                                                                           ref["gradient_norm"], gbar)
+        return dict(_ok("ok", ratio), info=info)
+    except AssertionError as err:
+        noise = ref["noise_level"]
+        if noise is not None:
+            # a system of 1 ... 7 rows on level `noise`: its step is rounding noise on both sides (DESIGN.md §14) and no
+            # report after it is defined.  What is: the flag, and the levels that ran before.  Counted as set aside.
+            before = [L for L in range(noise + 1, nl) if d["max_iter"][L] > 0]
+            if (rep.flags & ar.PAIR_RANK_DEFICIENT and all(rep.iterations[L] == ref["iterations"][L] and
+                                                           rep.valid_pixels[L] == ref["valid_pixels"][L] for L in before)):
+                return dict(_ok("skip", 0.0, f"{err}; undefined after a system of 1-7 rows on level {noise}: "
+                                             f"RANK_DEFICIENT set, levels {before} alike"), info=info)
+        unstable, why = affine_unstable(d, p["K"], job["pyr"], p["init"], ref)
+        detail = (f"{err}; device it {list(rep.iterations[:nl])} rows {list(rep.valid_pixels[:nl])} flags {rep.flags} "
+                  f"state {dev.tolist()}; checker {ref['iterations']} {ref['valid_pixels']} {ref['flags']} "
+                  f"{ref['state'].tolist()} cond {ref['cond']:.2e} bar {bar:.1e} distance / bar {ratio:.3g}; {why}")
+        return dict(_ok("skip" if unstable else "fail", ratio, detail), info=info)
+
+
 def main(argv):
     import concurrent.futures as cf
     import multiprocessing as mp
@@ -556,6 +766,7 @@ def main(argv):
         os.environ[v] = "1"                 # (inherited by the workers: one thread each)
     bad = skipped = done = conditioned = 0
     worst, geos, pending = 0.0, {}, []
+    tally = dict(scaled=0, nonfinite=0, by_threshold=0, by_count=0)          # (affine, from the checker's results)
 
     def settle(fut, case, d):
         nonlocal bad, skipped, done, worst, conditioned
@@ -563,6 +774,14 @@ def main(argv):
         done += 1
         desc = (f"case {case}: {d['w']}x{d['h']} levels {d['nl']} pairs {d['n_pairs']} range {d['range']} upload "
                 f"{d['upload_range']} src {d['src_defects']} tgt {d['tgt_defects']}")
+        if mode == "affine":
+            desc += f" max_iter {d['max_iter']} min_grad {d['min_grad']} lam {d['lam']} exposure {d['exposure']}"
+            if "info" in r:
+                i = r["info"]
+                tally["scaled"] += int(r["status"] == "ok" and i["scaled"])
+                tally["nonfinite"] += int(not i["finite"])
+                tally["by_threshold"] += i["by_threshold"]
+                tally["by_count"] += i["by_count"]
         if r["status"] == "fail":
             bad += 1
             print(f"FAIL {desc}: {r['msg']}", flush=True)
@@ -587,8 +806,11 @@ def main(argv):
             settle(*item)
     n = len(draws)
     print(f"{n} cases, {bad} failures, {skipped} skipped as knife-edge, worst distance / bar {worst:.3f}"
-          + (f"; {conditioned} passed only under the bars conditioned on cond(J^T J)" if mode == "tr" else ""))
-    what = "tile classes predicted from the level sizes" if mode == "eval" else "from the launch records"
+          + (f"; {conditioned} passed only under the bars conditioned on cond(J^T J)" if mode == "tr" else "")
+          + (f"; {tally['scaled']} passed only under the scaled bar, {tally['nonfinite']} ended non-finite; levels under a "
+             f"threshold ended by threshold: {tally['by_threshold']}, by count: {tally['by_count']}" if mode == "affine" else ""))
+    what = ("tile classes predicted from the level sizes" if mode == "eval" else
+            "chunk classes of the levels run" if mode == "affine" else "from the launch records")
     print(f"geometries exercised ({mode}, {what}): " + ", ".join(f"{k}: {v}" for k, v in sorted(geos.items())))
     return 1 if bad else 0
 
