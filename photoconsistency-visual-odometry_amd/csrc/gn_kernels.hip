@@ -167,6 +167,9 @@ __device__ __forceinline__ void level_body(const GNLevelArgs &A, const LevelLds 
 #else
 #define PHOVO_STAMP(i)
 #endif
+  // PARK: the first iteration this call executes (not `iteration == 0`: a continued pair enters with its count) fills the park
+  // block; from the second on pass 1 reads the parked chunks' depth from it.  Workgroup-uniform.
+  bool first_trip = true;
   while (true) {
 #ifdef PHOVO_PHASE_STAMPS
     stamp_last = wall_clock64();
@@ -204,7 +207,10 @@ __device__ __forceinline__ void level_body(const GNLevelArgs &A, const LevelLds 
       PHOVO_ROWCOL_BEGIN
       // software prefetch: the depth of the NEXT chunk is requested before this chunk is processed, so
       // every wave keeps a load in flight while it computes (the passes are bound by bytes in flight per CU)
-      double pz_next = plane_load<TD>(rS, k, oD);
+      // (PARK, after the first trip: a wave whose first chunk is parked finds that depth in the park block)
+      double pz_next;
+      if (PARK && OWNER_LDS && !first_trip && wave < depth_chunks) pz_next = s_i0[k];      // wave-uniform
+      else pz_next = plane_load<TD>(rS, k, oD);
       // the translation sits in vector registers during this pass (pass 1 has registers to spare): an fma takes one
       // scalar operand, and the rotation entry already is one
       double cxv = cx * fx, cyv = cyy * fy, czv = cz, oxv = oxi, oyv = oyi;
@@ -255,13 +261,18 @@ __device__ __forceinline__ void level_body(const GNLevelArgs &A, const LevelLds 
         }
       };
       if constexpr (OWNER_LDS) {
-        auto chunk_body = [&](const int chunk) {
+        // next_parked_tag: the NEXT chunk's depth is requested from the park block instead of memory; park_tag: this chunk's
+        // depth is stored there (both compile-time: the loops below exist in one copy per combination that occurs)
+        auto chunk_body = [&](const int chunk, auto next_parked_tag, auto park_tag) {
           const double pz = pz_next;                                      // :279
-          pz_next = plane_load<TD>(rS, k + NW * WAVE, oD);                   // (past the plane: masked out)
+          if constexpr (decltype(next_parked_tag)::value) pz_next = s_i0[k + NW * WAVE];
+          else pz_next = plane_load<TD>(rS, k + NW * WAVE, oD);              // (past the plane: masked out)
           // The depth plane is the one plane both passes read.  Whatever LDS this geometry leaves unused keeps the depth of
           // the image's LEADING chunks for pass 2 (the same lane reads back what it wrote); pass 2 walks backwards, so the
           // trailing chunks -- read last here -- still come from the XCD's L2.  The kernel is bound by bytes at the fabric.
-          if (PARK && chunk < depth_chunks) s_i0[k] = pz;                 // (wave-uniform; s_i0: the block behind the owner map)
+          if constexpr (decltype(park_tag)::value) {
+            if (chunk < depth_chunks) s_i0[k] = pz;                       // (wave-uniform; s_i0: the block behind the owner map)
+          }
           unsigned long long m;
           int t;
           warp_chunk(pz, chunk, m, t);
@@ -271,14 +282,40 @@ __device__ __forceinline__ void level_body(const GNLevelArgs &A, const LevelLds 
           j++;
           PHOVO_ROWCOL_NEXT
         };
-        // two chunks per trip, written out by hand: the ballot / lane accesses are convergent operations, which the
-        // compiler will not duplicate for a run-time trip count (#pragma unroll is refused); the bounds are wave-uniform
-        int chunk = wave;
-        for (; chunk + NW < A.n_chunks; chunk += 2 * NW) {
-          chunk_body(chunk);
-          chunk_body(chunk + NW);
+        if (!PARK || first_trip) {
+          // two chunks per trip, written out by hand: the ballot / lane accesses are convergent operations, which the
+          // compiler will not duplicate for a run-time trip count (#pragma unroll is refused); the bounds are wave-uniform
+          int chunk = wave;
+          for (; chunk + NW < A.n_chunks; chunk += 2 * NW) {
+            chunk_body(chunk, std::false_type{}, std::bool_constant<PARK>{});
+            chunk_body(chunk + NW, std::false_type{}, std::bool_constant<PARK>{});
+          }
+          if (chunk < A.n_chunks) chunk_body(chunk, std::false_type{}, std::bool_constant<PARK>{});
+        } else {
+          // Every later iteration of the pair on this level: the depth plane has not changed and a lane's pixels are the
+          // same, so the park block already holds what the first trip stored -- the parked chunks are read from there and
+          // nothing is stored.  As in pass 2 the loop is compiled as separate runs chosen by wave-uniform bounds outside
+          // the pixel loop (a select inside it cost 4 % twice: DESIGN.md 3.1): positions 0 .. parked - 2 of this wave's
+          // chunks request their successor from LDS, position parked - 1 (its own depth came from LDS) is the first to
+          // request from memory, and the positions behind it are the first trip's loop without the store.
+          const int my_chunks = wave < A.n_chunks ? (A.n_chunks - 1 - wave) / NW + 1 : 0;       // wave-uniform
+          const int parked = depth_chunks > wave ? min(my_chunks, (depth_chunks - 1 - wave) / NW + 1) : 0;
+          // positions c_lo .. c_end - 1, upwards, two per trip by hand as above (the loop is left at its head only: the
+          // depth in flight alternates between two registers, and an exit between the two bodies would cost a copy)
+          auto run = [&](int c_lo, int c_end, auto tag) {
+            int c = c_lo;
+            for (; c + 1 < c_end; c += 2) {
+              chunk_body(wave + c * NW, tag, std::false_type{});
+              chunk_body(wave + (c + 1) * NW, tag, std::false_type{});
+            }
+            if (c < c_end) chunk_body(wave + c * NW, tag, std::false_type{});
+          };
+          if (parked > 0) {
+            run(0, parked - 1, std::true_type{});
+            chunk_body(wave + (parked - 1) * NW, std::false_type{}, std::false_type{});
+          }
+          run(parked, my_chunks, std::false_type{});
         }
-        if (chunk < A.n_chunks) chunk_body(chunk);
       } else {
         // Owner map in HBM.  The memory counter of a wave retires in order, so a load issued behind a global atomic
         // waits for that atomic (about 2800 cycles with every CU issuing them): a loop of load - compute - atomic per
@@ -599,6 +636,7 @@ __device__ __forceinline__ void level_body(const GNLevelArgs &A, const LevelLds 
     __syncthreads();
     PHOVO_STAMP(5)
     iteration++;
+    first_trip = false;
     if (s_ctl[CTL_DONE]) break;
   }
 #ifdef PHOVO_PHASE_STAMPS
