@@ -2,7 +2,7 @@
 // directory, writing a TUM trajectory file.
 //
 //   ./PhotoconsistencyVisualOdometry <config_file.yml> <rgbd_dataset_directory> <output_trajectory_file> [--batch [--gpus N] [--rccl]]
-//                                    [--method analytic|ceres|biobjective|affine] [--information <file>]
+//                                    [--method analytic|ceres|biobjective|affine] [--information <file>] [--system <file>]
 // --method picks the aligner as the reference's USE_PHOTOCONSISTENCY_ODOMETRY_METHOD does (0 = analytic, the default;
 // 1 = ceres: Levenberg-Marquardt on bilinear samples, CPhotoconsistencyOdometryCeres, which reads config_*_ceres.yml
 // files; 2 = bi-objective: photometric and depth error together, CPhotoconsistencyOdometryBiObjective), in every mode;
@@ -14,6 +14,12 @@
 // `timestamp rows cost` and the 21 upper-triangle entries of J^T J (phovo_pair_system_format).  The loop takes it from the
 // class surface (GetPairSystem), --batch from phovo_engine_evaluate_pairs; both write the same bytes, and the trajectory
 // file is the same with and without the flag.  The printed times do not include the evaluation.
+// --system <file> (not in the reference; one device): the same for the aligners that sample the target bilinearly -- --method
+// affine, and --method analytic when the yml sets sampling_bilinear: 1 (which --batch then honours like the loop, with the
+// file's other extension keys).  One line per pair, `timestamp rows cost dim` and the dim (dim + 1) / 2 upper-triangle
+// entries of J^T W J (phovo_sampled_system_format; dim 8 under affine: pose, alpha, beta).  The loop takes it from the class
+// surface (GetSampledSystem), --batch from phovo_engine_evaluate_sampled_pairs (alpha and beta from
+// phovo_engine_fetch_illumination); both write the same bytes, and the trajectory file is the same with and without the flag.
 //
 // Behaviour kept from the reference's app (apps/PhotoconsistencyVisualOdometry/PhotoconsistencyVisualOdometry.cpp):
 //   * <dir>/rgb.txt and <dir>/depth.txt are read in lock step -- line n of one is paired with line n of the
@@ -123,11 +129,19 @@ static bool writeSystem(std::ofstream &f, double timestamp, const phovo_pair_sys
   return true;
 }
 
+static bool writeSystem(std::ofstream &f, double timestamp, const phovo_sampled_system &s)
+{
+  char line[1024];
+  if (phovo_sampled_system_format(timestamp, &s, line, sizeof(line)) != PHOVO_OK) return false;
+  f << line << std::endl;
+  return true;
+}
+
 static void printHelp()
 {
   std::cout << "./PhotoconsistencyVisualOdometry <config_file.yml> <rgbd_dataset_directory> "
                "<output_trajectory_file> [--batch [--gpus N] [--rccl]] [--method analytic|ceres|biobjective|affine] "
-               "[--information <file>]" << std::endl;
+               "[--information <file>] [--system <file>]" << std::endl;
 }
 
 #define PHOVO_OK_OR_FAIL(call)                                                              \
@@ -142,6 +156,7 @@ int main(int argc, char *argv[])
   bool rccl = false;                                  // ... --rccl: the shards' states meet through ONE RCCL all_gather
   int objective = PHOVO_OBJECTIVE_PHOTOMETRIC;        // --method analytic (default) | ceres | biobjective
   std::string informationPath;                        // --information <file>: the pairs' systems at their optimal states
+  std::string systemPath;                             // --system <file>: the same for the sampled aligners
   for (int i = 4; i < argc; i++) {
     const std::string a(argv[i]);
     if (a == "--batch") batch = true;
@@ -156,6 +171,7 @@ int main(int argc, char *argv[])
     else if (a == "--rccl") rccl = true;
     else if (a == "--gpus" && i + 1 < argc) nGpus = std::atoi(argv[++i]);
     else if (a == "--information" && i + 1 < argc) informationPath = argv[++i];
+    else if (a == "--system" && i + 1 < argc) systemPath = argv[++i];
     else { printHelp(); return EXIT_FAILURE; }
   }
   if (nGpus < 1 || (nGpus > 1 && !batch)) { std::cerr << "--gpus N needs --batch and N >= 1" << std::endl; return EXIT_FAILURE; }
@@ -169,6 +185,15 @@ int main(int argc, char *argv[])
     std::cerr << "--information needs --method analytic (the bi-objective and the Ceres method have no pair system)" << std::endl;
     return EXIT_FAILURE;
   }
+  const bool sampled = !systemPath.empty();
+  if (sampled && (nGpus > 1 || rccl)) {
+    std::cerr << "--system runs on one device: it cannot be combined with --gpus N > 1 or --rccl" << std::endl;
+    return EXIT_FAILURE;
+  }
+  if (sampled && objective != PHOVO_OBJECTIVE_PHOTOMETRIC && objective != PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE) {
+    std::cerr << "--system needs bilinear sampling or --method affine" << std::endl;
+    return EXIT_FAILURE;
+  }
   if (!fileExists(configFile)) { std::cerr << "Input config file " << configFile << " does not exist" << std::endl; return EXIT_FAILURE; }
   {   // the Ceres method reads the config_*_ceres.yml keys, the other two the config_*_analytic.yml keys
     phovo_config c;
@@ -180,6 +205,15 @@ int main(int argc, char *argv[])
                 << "the config_*_analytic.yml files" << std::endl;
       return EXIT_FAILURE;
     }
+  }
+  // --method analytic: the extension keys of the file (sampling_bilinear, jacobian_corrected, ...), which the class reads
+  // in ReadConfigurationFile and --batch hands to its engines
+  phovo_extensions extensions;
+  PHOVO_OK_OR_FAIL(phovo_extensions_default(&extensions));
+  if (objective == PHOVO_OBJECTIVE_PHOTOMETRIC) PHOVO_OK_OR_FAIL(phovo_extensions_read_file(configFile.c_str(), &extensions));
+  if (sampled && objective == PHOVO_OBJECTIVE_PHOTOMETRIC && extensions.sampling != PHOVO_SAMPLING_BILINEAR) {
+    std::cerr << "--system needs bilinear sampling or --method affine" << std::endl;
+    return EXIT_FAILURE;
   }
   if (!fileExists(datasetDir)) { std::cerr << "Input RGBD dataset directory " << datasetDir << " does not exist" << std::endl; return EXIT_FAILURE; }
   const std::string rgbList = datasetDir + "/rgb.txt", depthList = datasetDir + "/depth.txt";
@@ -209,6 +243,11 @@ int main(int argc, char *argv[])
   if (information) {
     informationFile.open(informationPath.c_str());
     if (!informationFile.is_open()) { std::cerr << "Cannot open output information file " << informationPath << std::endl; return EXIT_FAILURE; }
+  }
+  std::ofstream systemFile;
+  if (sampled) {
+    systemFile.open(systemPath.c_str());
+    if (!systemFile.is_open()) { std::cerr << "Cannot open output system file " << systemPath << std::endl; return EXIT_FAILURE; }
   }
   if (nFrames < 2) return EXIT_SUCCESS;
 
@@ -242,6 +281,7 @@ int main(int argc, char *argv[])
         PHOVO_OK_OR_FAIL(phovo_trajectory_chain(1, state.data(), pose.data(), nullptr));   // pose *= Rt^-1  :233-234
         if (!writePose(trajectoryFile, rgb[t].timestamp, pose)) return EXIT_FAILURE;
         if (information && !writeSystem(informationFile, rgb[t].timestamp, odometry.GetPairSystem())) return EXIT_FAILURE;
+        if (sampled && !writeSystem(systemFile, rgb[t].timestamp, odometry.GetSampledSystem())) return EXIT_FAILURE;
         std::cout << "Rt:" << std::endl << Rt << std::endl;
         prevGray = curGray.clone();
         prevDepth = curDepth.clone();
@@ -335,6 +375,9 @@ int main(int argc, char *argv[])
       for (int l = cfg.num_levels - 1; l >= 0; l--)
         if (cfg.max_num_iterations[l] > 0) finestLevel = l;
       if (information && finestLevel < 0) { std::cerr << "--information: the configuration optimises no level" << std::endl; return EXIT_FAILURE; }
+      if (sampled && finestLevel < 0) { std::cerr << "--system: the configuration optimises no level" << std::endl; return EXIT_FAILURE; }
+      const int systemDim = objective == PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE ? 8 : 6;
+      std::vector<phovo_sampled_system> sampledSystems(sampled ? (size_t)nPairs : 0);
       std::vector<std::string> shardError(nGpus);
       // --rccl: instead of every shard copying its states to the host itself, the shards' device buffers meet in ONE RCCL
       // all_gather (one communicator and one host thread per device in this one process) and rank 0 copies the lot out --
@@ -368,6 +411,8 @@ int main(int argc, char *argv[])
           if (phovo_engine_create(g % nDevices, &engine) != PHOVO_OK) return fail("phovo_engine_create");
           if (phovo_engine_set_config(engine, &cfg) != PHOVO_OK) return fail("phovo_engine_set_config");
           if (phovo_engine_set_objective(engine, objective) != PHOVO_OK) return fail("phovo_engine_set_objective");
+          if (objective == PHOVO_OBJECTIVE_PHOTOMETRIC && phovo_engine_set_extensions(engine, &extensions) != PHOVO_OK)
+            return fail("phovo_engine_set_extensions");
           if (objective == PHOVO_OBJECTIVE_TRUST_REGION && phovo_engine_set_trust_region_options(engine, &trOptions) != PHOVO_OK)
             return fail("phovo_engine_set_trust_region_options");
           // a pair's pose must not depend on the size of the shard it falls into (same trajectory file for every N)
@@ -383,10 +428,23 @@ int main(int argc, char *argv[])
           if (!rccl) {
             if (phovo_engine_align_pairs(engine, b - a, src.data(), tgt.data(), nullptr, states.data() + (size_t)a * 6, nullptr) != PHOVO_OK)
               return fail("phovo_engine_align_pairs");
-            if (information) tAligned = std::chrono::steady_clock::now();      // (the evaluation is not part of the timed run)
+            if (information || sampled) tAligned = std::chrono::steady_clock::now();      // (the evaluation is not part of the timed run)
             if (information && phovo_engine_evaluate_pairs(engine, b - a, src.data(), tgt.data(), states.data() + (size_t)a * 6,
                                                            finestLevel, systems.data() + a) != PHOVO_OK)
               return fail("phovo_engine_evaluate_pairs");
+            if (sampled) {                                // the states the systems are evaluated at: [pairs][6], or [pairs][8] with alpha, beta
+              const int n = b - a;
+              std::vector<double> at((size_t)n * systemDim), illum((size_t)n * 2);
+              if (systemDim == 8 && phovo_engine_fetch_illumination(engine, n, illum.data()) != PHOVO_OK)
+                return fail("phovo_engine_fetch_illumination");
+              for (int p = 0; p < n; p++) {
+                std::copy(states.begin() + (size_t)(a + p) * 6, states.begin() + (size_t)(a + p) * 6 + 6, at.begin() + (size_t)p * systemDim);
+                if (systemDim == 8) { at[(size_t)p * 8 + 6] = illum[(size_t)p * 2]; at[(size_t)p * 8 + 7] = illum[(size_t)p * 2 + 1]; }
+              }
+              if (phovo_engine_evaluate_sampled_pairs(engine, n, src.data(), tgt.data(), at.data(), systemDim, finestLevel,
+                                                      sampledSystems.data() + a) != PHOVO_OK)
+                return fail("phovo_engine_evaluate_sampled_pairs");
+            }
             return true;
           }
           if (phovo_engine_enqueue_align(engine, b - a, src.data(), tgt.data(), nullptr) != PHOVO_OK) return fail("phovo_engine_enqueue_align");
@@ -420,7 +478,7 @@ int main(int argc, char *argv[])
           std::copy(group.gathered(g), group.gathered(g) + (size_t)(b - a) * 6, states.begin() + (size_t)a * 6);
         }
       }
-      const auto t1 = information ? tAligned : std::chrono::steady_clock::now();
+      const auto t1 = (information || sampled) ? tAligned : std::chrono::steady_clock::now();
       std::cout << "Time = " << std::chrono::duration<double>(t1 - t0).count() << " sec. (" << nPairs << " pairs on " << nGpus
                 << " device(s), upload and pyramids included)" << std::endl;
       std::vector<double> poses((size_t)nPairs * 16);
@@ -430,6 +488,7 @@ int main(int argc, char *argv[])
         for (int i = 0; i < 16; i++) P(i) = poses[(size_t)p * 16 + i];
         if (!writePose(trajectoryFile, rgb[(size_t)p + 1].timestamp, P)) return EXIT_FAILURE;
         if (information && !writeSystem(informationFile, rgb[(size_t)p + 1].timestamp, systems[(size_t)p])) return EXIT_FAILURE;
+        if (sampled && !writeSystem(systemFile, rgb[(size_t)p + 1].timestamp, sampledSystems[(size_t)p])) return EXIT_FAILURE;
       }
     }
   } catch (const std::exception &e) {
@@ -438,5 +497,6 @@ int main(int argc, char *argv[])
   }
   trajectoryFile.close();
   if (information) informationFile.close();
+  if (sampled) systemFile.close();
   return EXIT_SUCCESS;
 }

@@ -8,7 +8,8 @@
 //
 // The types come from the same place as CPhotoconsistencyOdometryAnalytic.h's (PHOVO_HIP_USE_REFERENCE_TYPES or
 // phovo/compat/).  ReadConfigurationFile reads the config_*_analytic.yml keys.  Extensions are refused
-// (std::runtime_error, PHOVO_E_UNSUPPORTED), and so is the inherited GetPairSystem().
+// (std::runtime_error, PHOVO_E_UNSUPPORTED), and so is the inherited GetPairSystem(); the inherited GetSampledSystem()
+// returns the 8 x 8 system (pose, alpha, beta) at the optimum, at the (alpha, beta) of the last Optimize().
 #ifndef PHOVO_HIP_CPHOTOCONSISTENCY_ODOMETRY_AFFINE_H
 #define PHOVO_HIP_CPHOTOCONSISTENCY_ODOMETRY_AFFINE_H
 

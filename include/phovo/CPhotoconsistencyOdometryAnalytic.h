@@ -158,6 +158,15 @@ class CPhotoconsistencyOdometryAnalytic : public CPhotoconsistencyOdometry<TPixe
     Check(phovo_odometry_get_pair_system(m_Handle, &s), "GetPairSystem");
     return s;
   }
+  // Not in the reference: the same for the aligners that sample the target bilinearly (phovo_hip.h, phovo_sampled_system):
+  // dim 6 with bilinear sampling, dim 8 (pose, alpha, beta) under the affine-illumination objective.  Throws before
+  // Optimize() and, PHOVO_E_UNSUPPORTED, for nearest / scatter sampling, the bi-objective and the trust-region objective.
+  phovo_sampled_system GetSampledSystem() const
+  {
+    phovo_sampled_system s;
+    Check(phovo_odometry_get_sampled_system(m_Handle, &s), "GetSampledSystem");
+    return s;
+  }
   double GetLastOptimizeMilliseconds() const
   {
     double ms = 0;

@@ -113,6 +113,34 @@ typedef struct phovo_pair_system {
   uint32_t flags;           /* PHOVO_PAIR_RANK_DEFICIENT if rows < 6, PHOVO_PAIR_NONFINITE if any sum is inf/NaN */
 } phovo_pair_system;
 
+/* The Gauss-Newton system of one frame pair under the SAMPLED aligners at a given state on one level
+ * (phovo_engine_evaluate_sampled_pairs, phovo_odometry_get_sampled_system): the bilinear extension
+ * (PHOVO_SAMPLING_BILINEAR, dim 6) and the affine-illumination objective (PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE, dim 8:
+ * pose, alpha, beta).  Its rows are the ones those aligners fill at that state: every source pixel in raster order that
+ * passes the strict depth gate min_depth < D0 < max_depth and whose nearest target pixel is inside the image
+ * (-0.5 < u < W - 0.5, -0.5 < v < H - 0.5); I1, GX1 and GY1 sampled bilinearly from four taps with every index clamped to
+ * the image; residual and Jacobian row both belong to the source pixel.  Columns: with jacobian_corrected = 0 the
+ * reference's Jacobian including its temp11 slip (:253), with 1 the true warp Jacobian; under the affine objective the
+ * true one plus dr/dalpha = -I0 and dr/dbeta = -1, with r = I1(u, v) - (1 + alpha) I0 - beta.  With huber_delta[level] > 0
+ * (dim 6 only) the rows carry the aligner's IRLS weights at that state (w = 1 if |r| <= delta, delta/|r| otherwise) in
+ * information, gradient and cost.  The 8 x 8 system also yields the pose covariance with gain and offset marginalised
+ * out (a Schur complement on the caller's side).
+ * Relation to the aligner: the system it solves in iteration k of a level is this system at the state the iteration starts
+ * from (on fp64 planes up to one rounding of the sample in the outer half-pixel band, gn_bilinear_kernel.hip).
+ * Arithmetic: fp64 on the device; the sums are taken in an order that depends on the level size only, so a pair's result
+ * is the same bit for bit whatever the batch, its position in it, or the engine's settings. */
+#define PHOVO_SYSTEM_MAX_DIM 8
+typedef struct phovo_sampled_system {
+  double   information[64]; /* J^T W J, row-major with leading dimension 8, exactly symmetric (filled from the upper
+                               triangle); rows and columns >= dim are 0 */
+  double   gradient[8];     /* J^T W r; entries >= dim are 0 */
+  double   cost;            /* r^T W r over the rows */
+  int32_t  rows;            /* rows of J filled: the count phovo_pair_report.valid_pixels uses */
+  uint32_t flags;           /* PHOVO_PAIR_RANK_DEFICIENT if rows < dim, PHOVO_PAIR_NONFINITE if any sum is inf/NaN */
+  int32_t  dim;             /* 6 or 8 */
+  int32_t  reserved;
+} phovo_sampled_system;
+
 /* ---- extensions that are NOT in the reference (BASELINE.json configs[4]); all off by default -------------
  * plane_storage: how the pyramid planes are kept in HBM.  Arithmetic is fp64 in every mode; pyramids are built
  * in fp64 and rounded once when stored (fp64 -> fp32 by round-to-nearest-even, fp16 via fp32).
@@ -286,6 +314,12 @@ int phovo_trajectory_format_pose(double timestamp, const double pose[16], char *
  * newline.  Host only.  PHOVO_E_INVALID_ARGUMENT for NULL pointers or if `capacity` is too small (640 always suffices). */
 int phovo_pair_system_format(double timestamp, const phovo_pair_system *s, char *line, size_t capacity);
 
+/* One line of the VisualOdometry app's --system file: `timestamp rows cost dim` and the dim (dim + 1) / 2 upper-triangle
+ * entries of s->information in row-major order, every double as "%.17g" (round-trips exactly), no newline.  Host only.
+ * PHOVO_E_INVALID_ARGUMENT for NULL pointers, a dim that is neither 6 nor 8, or if `capacity` is too small (1024 always
+ * suffices). */
+int phovo_sampled_system_format(double timestamp, const phovo_sampled_system *s, char *line, size_t capacity);
+
 /* warpImage, CPhotoconsistencyOdometry.h:73-134 -- the forward warp both reference apps call after Optimize()
  * (...FrameAlignment.cpp:108, ...VisualOdometry.cpp:248-250) to show |I1 - warp(I0)|.  Host buffers in and out,
  * strides in bytes; rt row-major 4x4, k row-major 3x3, level scales the intrinsics by 2^-level as the reference does.
@@ -339,6 +373,11 @@ int phovo_odometry_get_report(const phovo_odometry *o, phovo_pair_report *report
  * PHOVO_E_NOT_READY before a successful Optimize() and after a Set*Frame since; PHOVO_E_UNSUPPORTED as for
  * phovo_engine_evaluate_pairs (bilinear sampling, bi-objective). */
 int phovo_odometry_get_pair_system(const phovo_odometry *o, phovo_pair_system *out);
+/* not in the reference: the system (phovo_sampled_system) of the sampled aligners at the optimal state on the finest
+ * level the configuration optimises, evaluated on demand; under the affine objective at the (alpha, beta) of the last
+ * Optimize().  PHOVO_E_NOT_READY before a successful Optimize() and after a Set*Frame since; PHOVO_E_UNSUPPORTED as for
+ * phovo_engine_evaluate_sampled_pairs (nearest / scatter sampling, bi-objective, trust region). */
+int phovo_odometry_get_sampled_system(const phovo_odometry *o, phovo_sampled_system *out);
 /* Device time of the last Optimize() in milliseconds (HIP events; the reference wraps the same
  * call in cv::TickMeter, apps/PhotoconsistencyFrameAlignment/PhotoconsistencyFrameAlignment.cpp:99-102). */
 int phovo_odometry_last_optimize_ms(const phovo_odometry *o, double *ms);
@@ -598,6 +637,22 @@ int phovo_engine_results_device_ptr(phovo_engine *e, void **states);
  * groups whose owner maps take at most 256 MB (218 pairs at 640x480). */
 int phovo_engine_evaluate_pairs(phovo_engine *e, int n_pairs, const int *src, const int *tgt,
                                 const double *states /* [n_pairs][6] */, int level, phovo_pair_system *out);
+
+/* The same for the aligners that sample the target bilinearly (phovo_sampled_system): the photometric objective with
+ * PHOVO_SAMPLING_BILINEAR (state_dim 6; either jacobian_corrected, any plane storage, with or without Huber weights) and
+ * PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE (state_dim 8: pose, alpha, beta).  Synchronous; ordered behind every enqueue in
+ * flight, and it changes nothing that phovo_engine_fetch / fetch_results / fetch_illumination return.
+ *   PHOVO_E_UNSUPPORTED       the photometric objective with nearest / scatter sampling (phovo_engine_evaluate_pairs
+ *                             serves it), the bi-objective, the trust-region objective
+ *   PHOVO_E_INVALID_ARGUMENT  a state_dim that is not the mode's, NULL pointers (with n_pairs > 0), n_pairs < 0, a frame
+ *                             index or level out of range
+ *   PHOVO_E_NOT_READY         as phovo_engine_evaluate_pairs
+ * n_pairs == 0 is OK.  Device memory: the evaluate workspace (shared with phovo_engine_evaluate_pairs, kept until the
+ * engine is destroyed) -- per pair of a group 256 bytes (state_dim 6) or 512 bytes (state_dim 8) of tile sums per 1024
+ * pixels; large batches run in groups whose tile sums take at most 64 MB. */
+int phovo_engine_evaluate_sampled_pairs(phovo_engine *e, int n_pairs, const int *src, const int *tgt,
+                                        const double *states /* [n_pairs][state_dim] */, int state_dim, int level,
+                                        phovo_sampled_system *out);
 
 /* Pipelining.  Pairs are independent, and with data-dependent termination a batch ends with a few long pairs on an
  * otherwise idle chip.  The engine therefore keeps PHOVO_ENQUEUE_DEPTH enqueues in flight, each with its own stream, pair

@@ -1891,6 +1891,93 @@ int phovo_engine_evaluate_pairs(phovo_engine *e, int n_pairs, const int *src, co
   return PHOVO_OK;
 }
 
+// Tile sums of one sampled-evaluation group take at most this much: 436 pairs of eight columns (873 of six) at 640x480.
+static constexpr size_t EVAL_SAMPLED_SLAB_CAP_BYTES = (size_t)64 << 20;
+
+int phovo_engine_evaluate_sampled_pairs(phovo_engine *e, int n_pairs, const int *src, const int *tgt, const double *states,
+                                        int state_dim, int level, phovo_sampled_system *out)
+{
+  if (!e) return fail(PHOVO_E_INVALID_ARGUMENT, "evaluate_sampled_pairs: null engine");
+  if (e->objective == PHOVO_OBJECTIVE_BIOBJECTIVE || e->objective == PHOVO_OBJECTIVE_TRUST_REGION)
+    return fail(PHOVO_E_UNSUPPORTED, "evaluate_sampled_pairs: the bi-objective and the trust-region objective have no sampled "
+                                     "system (bilinear sampling or the affine-illumination objective only)");
+  const bool affine = e->objective == PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE;
+  if (!affine && e->ext.sampling != PHOVO_SAMPLING_BILINEAR)
+    return fail(PHOVO_E_UNSUPPORTED, "evaluate_sampled_pairs: nearest / scatter sampling has its system in "
+                                     "phovo_engine_evaluate_pairs (bilinear sampling or the affine-illumination objective only)");
+  const int dim = affine ? 8 : 6;
+  if (state_dim != dim)
+    return fail(PHOVO_E_INVALID_ARGUMENT, affine ? "evaluate_sampled_pairs: the affine-illumination objective takes state_dim 8"
+                                                 : "evaluate_sampled_pairs: bilinear sampling takes state_dim 6");
+  if (n_pairs < 0) return fail(PHOVO_E_INVALID_ARGUMENT, "evaluate_sampled_pairs: n_pairs < 0");
+  if (n_pairs > 0 && (!src || !tgt || !states || !out)) return fail(PHOVO_E_INVALID_ARGUMENT, "evaluate_sampled_pairs: null");
+  if (level < 0 || level >= e->cfg.num_levels) return fail(PHOVO_E_INVALID_ARGUMENT, "evaluate_sampled_pairs: level out of range");
+  if (n_pairs == 0) return PHOVO_OK;
+  if (e->n_frames == 0) return fail(PHOVO_E_NOT_READY, "evaluate_sampled_pairs: no frames uploaded");
+  for (int i = 0; i < n_pairs; i++) {
+    if (src[i] < 0 || src[i] >= e->n_frames || tgt[i] < 0 || tgt[i] >= e->n_frames)
+      return fail(PHOVO_E_INVALID_ARGUMENT, "evaluate_sampled_pairs: frame index out of range");
+  }
+  if (!e->have_K) return fail(PHOVO_E_NOT_READY, "evaluate_sampled_pairs: SetIntrinsicMatrix has not been called");
+  const LevelPool &lv = e->levels[level];
+  if (!lv.stored) return fail(PHOVO_E_NOT_READY, "evaluate_sampled_pairs: the level is not resident (phovo_engine_level_is_stored)");
+  for (int i = 0; i < n_pairs; i++) {
+    if (!(e->frame_roles[(size_t)src[i] * PHOVO_MAX_LEVELS + (size_t)level] & PHOVO_ROLE_SOURCE))
+      return fail(PHOVO_E_NOT_READY, "evaluate_sampled_pairs: a source frame has no depth (upload it with PHOVO_ROLE_SOURCE)");
+    if (!(e->frame_roles[(size_t)tgt[i] * PHOVO_MAX_LEVELS + (size_t)level] & PHOVO_ROLE_TARGET))
+      return fail(PHOVO_E_NOT_READY, "evaluate_sampled_pairs: a target frame has no gradients (upload it with PHOVO_ROLE_TARGET)");
+  }
+  PHOVO_HIP_CHECK(hipSetDevice(e->device));
+  PHOVO_HIP_CHECK(quiesce(e));                 // behind every enqueue in flight; their slots are not touched
+
+  // Workspace for a group of G pairs, every region 256-byte aligned: tile sums, states, pair indices and the results.
+  const size_t slab_bytes = gn_eval_sampled_slab_doubles_per_pair(lv.n, dim) * sizeof(double);
+  const int group = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_pairs, EVAL_SAMPLED_SLAB_CAP_BYTES / slab_bytes));
+  auto align256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t G = (size_t)group;
+  const size_t st_off = align256(G * slab_bytes);
+  const size_t src_off = st_off + align256(G * (size_t)dim * sizeof(double));
+  const size_t tgt_off = src_off + align256(G * sizeof(int));
+  const size_t out_off = tgt_off + align256(G * sizeof(int));
+  const size_t need = out_off + align256(G * sizeof(phovo_sampled_system));
+  e->eval_owner_clean = 0;                     // (the tile sums lie where phovo_engine_evaluate_pairs keeps its owner maps)
+  if (need > e->eval_ws_capacity) {
+    if (e->d_eval_ws) { (void)hipFree(e->d_eval_ws); e->d_eval_ws = nullptr; e->eval_ws_capacity = 0; }
+    PHOVO_HIP_CHECK(hipMalloc(&e->d_eval_ws, need));
+    e->eval_ws_capacity = need;
+  }
+  unsigned char *ws = e->d_eval_ws;
+
+  GNSampledEvalArgs a{};
+  a.w = lv.w; a.h = lv.h; a.n = lv.n; a.n_chunks = (lv.n + 63) / 64;
+  a.state_dim = dim;
+  const double scaleFactor = 1.0 / std::pow(2, level);                               // :203
+  a.fx = e->K[0] * scaleFactor; a.fy = e->K[4] * scaleFactor;                        // :204-207
+  a.ox = e->K[2] * scaleFactor; a.oy = e->K[5] * scaleFactor;
+  a.ifx = 1.f / a.fx; a.ify = 1.f / a.fy;                                            // :208-209
+  a.min_depth = e->min_depth; a.max_depth = e->max_depth;
+  a.huber_delta = affine ? 0.0 : e->ext.huber_delta[level];
+  a.planes = lv.planes;
+  a.frame_bytes = lv.frame_bytes;
+  for (int p = 0; p < PLANES_PER_FRAME; p++) a.plane_off[p] = lv.plane_off[p];
+  a.states = reinterpret_cast<const double *>(ws + st_off);
+  a.src = reinterpret_cast<const int *>(ws + src_off);
+  a.tgt = reinterpret_cast<const int *>(ws + tgt_off);
+  auto *d_part = reinterpret_cast<double *>(ws);
+  auto *d_out = reinterpret_cast<phovo_sampled_system *>(ws + out_off);
+  const bool corrected = affine || e->ext.jacobian_corrected != 0;
+  for (int g0 = 0; g0 < n_pairs; g0 += group) {
+    const int c = std::min(group, n_pairs - g0);
+    PHOVO_HIP_CHECK(hipMemcpyAsync(ws + st_off, states + (size_t)g0 * dim, sizeof(double) * (size_t)dim * (size_t)c, hipMemcpyHostToDevice, e->stream));
+    PHOVO_HIP_CHECK(hipMemcpyAsync(ws + src_off, src + g0, sizeof(int) * (size_t)c, hipMemcpyHostToDevice, e->stream));
+    PHOVO_HIP_CHECK(hipMemcpyAsync(ws + tgt_off, tgt + g0, sizeof(int) * (size_t)c, hipMemcpyHostToDevice, e->stream));
+    PHOVO_HIP_CHECK(gn_eval_sampled_pairs(a, c, e->ext.plane_storage, corrected, d_part, d_out, e->stream));
+    PHOVO_HIP_CHECK(hipMemcpyAsync(out + g0, d_out, sizeof(phovo_sampled_system) * (size_t)c, hipMemcpyDeviceToHost, e->stream));
+    PHOVO_HIP_CHECK(hipStreamSynchronize(e->stream));      // (the next group's inputs overwrite this one's)
+  }
+  return PHOVO_OK;
+}
+
 int phovo_engine_align_ms(const phovo_engine *e, int ticket, double *total_ms, double level_ms[PHOVO_MAX_LEVELS])
 {
   if (!e) return fail(PHOVO_E_INVALID_ARGUMENT, "align_ms: null");
@@ -2327,6 +2414,25 @@ int phovo_odometry_get_pair_system(const phovo_odometry *o, phovo_pair_system *o
   if (finest < 0) return fail(PHOVO_E_NOT_READY, "get_pair_system: the configuration optimises no level");
   const int src = 0, tgt = 1;
   return phovo_engine_evaluate_pairs(o->engine, 1, &src, &tgt, o->state, finest, out);
+}
+
+int phovo_odometry_get_sampled_system(const phovo_odometry *o, phovo_sampled_system *out)
+{
+  if (!o || !out) return fail(PHOVO_E_INVALID_ARGUMENT, "get_sampled_system: null");
+  if (!o->optimized) return fail(PHOVO_E_NOT_READY, "get_sampled_system: Optimize has not run since the frames were set");
+  const phovo_engine *e = o->engine;
+  int finest = -1;                                        // the lowest level Optimize() iterates on
+  for (int l = e->cfg.num_levels - 1; l >= 0; l--)
+    if (e->cfg.max_num_iterations[l] > 0) finest = l;
+  if (finest < 0) return fail(PHOVO_E_NOT_READY, "get_sampled_system: the configuration optimises no level");
+  const int src = 0, tgt = 1;
+  double state[8];
+  std::memcpy(state, o->state, sizeof(double) * 6);
+  const bool affine = o->have_illumination && e->objective == PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE;
+  state[6] = affine ? o->illumination[0] : 0.0;
+  state[7] = affine ? o->illumination[1] : 0.0;
+  return phovo_engine_evaluate_sampled_pairs(o->engine, 1, &src, &tgt, state,
+                                             e->objective == PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE ? 8 : 6, finest, out);
 }
 
 int phovo_odometry_last_optimize_ms(const phovo_odometry *o, double *ms)

@@ -127,6 +127,25 @@ size_t gn_eval_slab_doubles_per_pair(int n);       // doubles of tile sums per p
 // g_part: [n_pairs][gn_eval_slab_doubles_per_pair(n)]; out: [n_pairs] on the device.
 hipError_t gn_eval_pairs(const GNEvalArgs &a, int n_pairs, int storage, int *g_owner, unsigned long long *g_mask,
                          double *g_part, phovo_pair_system *out, hipStream_t stream);
+// The same for the rows the sampled aligners define (gn_evaluate_sampled_kernels.hip, phovo_engine_evaluate_sampled_pairs):
+// bilinear sampling with either Jacobian (state_dim 6, any plane storage, optional Huber weights) and the
+// affine-illumination rows (state_dim 8: pose, alpha, beta; fp64 planes, no Huber weights).  No owner map, no ballots.
+struct GNSampledEvalArgs {
+  int w, h, n, n_chunks;
+  int state_dim;                     // 6 or 8
+  double fx, fy, ox, oy, ifx, ify;   // level-scaled intrinsics, as GNLevelArgs
+  double min_depth, max_depth;
+  double huber_delta;                // > 0: Huber IRLS weights at the given state (state_dim 6 only)
+  const unsigned char *planes;       // pool of the level (GNLevelArgs)
+  size_t frame_bytes;
+  size_t plane_off[PLANES_PER_FRAME];
+  const int *src, *tgt;              // [pairs of the group]
+  const double *states;              // [pairs of the group][state_dim]
+};
+size_t gn_eval_sampled_slab_doubles_per_pair(int n, int dim);      // doubles of tile sums per pair (dim 6 or 8)
+// g_part: [n_pairs][gn_eval_sampled_slab_doubles_per_pair(n, state_dim)]; out: [n_pairs] on the device.
+hipError_t gn_eval_sampled_pairs(const GNSampledEvalArgs &a, int n_pairs, int storage, bool corrected, double *g_part,
+                                 phovo_sampled_system *out, hipStream_t stream);
 // Bi-objective (intensity + depth) form (gn_biobjective_kernel.hip, PHOVO_OBJECTIVE_BIOBJECTIVE): fp64 planes, nearest /
 // scatter sampling.  Every frame of the level carries, beside the four planes, the target's depth gradients (fp64 planes at
 // dgx_off / dgy_off) and its depth gain mean(I) / mean(D) (one double at gain_off).

@@ -72,4 +72,24 @@ int phovo_pair_system_format(double timestamp, const phovo_pair_system *s, char 
   return PHOVO_OK;
 }
 
+// One line of the app's --system file (include/phovo_hip.h): every double as %.17g, which round-trips.
+int phovo_sampled_system_format(double timestamp, const phovo_sampled_system *s, char *line, size_t capacity)
+{
+  if (!s || !line) return fail(PHOVO_E_INVALID_ARGUMENT, "sampled_system_format: null");
+  if (s->dim != 6 && s->dim != PHOVO_SYSTEM_MAX_DIM) return fail(PHOVO_E_INVALID_ARGUMENT, "sampled_system_format: dim is neither 6 nor 8");
+  std::string out;
+  char buf[96];
+  std::snprintf(buf, sizeof(buf), "%.17g %d %.17g %d", timestamp, (int)s->rows, s->cost, (int)s->dim);
+  out += buf;
+  for (int a = 0; a < s->dim; a++)
+    for (int b = a; b < s->dim; b++) {
+      std::snprintf(buf, sizeof(buf), " %.17g", s->information[PHOVO_SYSTEM_MAX_DIM * a + b]);
+      out += buf;
+    }
+  if (out.size() + 1 > capacity) return fail(PHOVO_E_INVALID_ARGUMENT, "sampled_system_format: buffer too small");
+  out.copy(line, out.size());
+  line[out.size()] = '\0';
+  return PHOVO_OK;
+}
+
 }  // extern "C"

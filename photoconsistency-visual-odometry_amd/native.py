@@ -80,6 +80,23 @@ class PairSystem(C.Structure):
     ]
 
 
+SYSTEM_MAX_DIM = 8
+
+
+class SampledSystem(C.Structure):
+    """phovo_sampled_system: the Gauss-Newton system of one pair under the sampled aligners (bilinear sampling: dim 6; the
+    affine-illumination objective: dim 8) at a given state on one level; information has leading dimension 8."""
+    _fields_ = [
+        ("information", C.c_double * (SYSTEM_MAX_DIM * SYSTEM_MAX_DIM)),
+        ("gradient", C.c_double * SYSTEM_MAX_DIM),
+        ("cost", C.c_double),
+        ("rows", C.c_int32),
+        ("flags", C.c_uint32),
+        ("dim", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
 FUSION_AUTO, FUSION_OFF, FUSION_SPLIT = 0, -1, -2
 OBJECTIVE_PHOTOMETRIC, OBJECTIVE_BIOBJECTIVE, OBJECTIVE_TRUST_REGION = 0, 1, 2
 OBJECTIVE_PHOTOMETRIC_AFFINE = 3
@@ -154,6 +171,7 @@ SYMBOLS = {
     "phovo_trajectory_chain": (C.c_int, [C.c_int, _vp, _dp, _vp]),
     "phovo_trajectory_format_pose": (C.c_int, [C.c_double, _dp, C.c_char_p, C.c_size_t]),
     "phovo_pair_system_format": (C.c_int, [C.c_double, C.POINTER(PairSystem), C.c_char_p, C.c_size_t]),
+    "phovo_sampled_system_format": (C.c_int, [C.c_double, C.POINTER(SampledSystem), C.c_char_p, C.c_size_t]),
     "phovo_warp_image": (C.c_int, [C.c_int, _vp, C.c_size_t, _vp, C.c_size_t, C.c_int, C.c_int, _dp, _dp, C.c_int,
                                    _vp, C.c_size_t]),
     "phovo_odometry_create": (C.c_int, [C.c_int, C.POINTER(_vp)]),
@@ -175,6 +193,7 @@ SYMBOLS = {
     "phovo_odometry_get_report": (C.c_int, [_vp, C.POINTER(PairReport)]),
     "phovo_odometry_last_optimize_ms": (C.c_int, [_vp, _dp]),
     "phovo_odometry_get_pair_system": (C.c_int, [_vp, C.POINTER(PairSystem)]),
+    "phovo_odometry_get_sampled_system": (C.c_int, [_vp, C.POINTER(SampledSystem)]),
     "phovo_engine_create": (C.c_int, [C.c_int, C.POINTER(_vp)]),
     "phovo_engine_destroy": (C.c_int, [_vp]),
     "phovo_engine_set_config": (C.c_int, [_vp, C.POINTER(Config)]),
@@ -236,6 +255,7 @@ SYMBOLS = {
     "phovo_engine_device_states": (C.c_int, [_vp, C.c_int, C.POINTER(_vp)]),
     "phovo_engine_align_ms": (C.c_int, [_vp, C.c_int, _dp, _dp]),
     "phovo_engine_evaluate_pairs": (C.c_int, [_vp, C.c_int, _ip, _ip, _vp, C.c_int, _vp]),
+    "phovo_engine_evaluate_sampled_pairs": (C.c_int, [_vp, C.c_int, _ip, _ip, _vp, C.c_int, C.c_int, _vp]),
 }
 
 
@@ -361,6 +381,14 @@ def format_pair_system(timestamp, system):
     """phovo_pair_system_format: the line the VisualOdometry app writes per pair with --information."""
     buf = C.create_string_buffer(1024)
     check(lib().phovo_pair_system_format(float(timestamp), C.byref(system), buf, len(buf)), "phovo_pair_system_format")
+    return buf.value.decode()
+
+
+def format_sampled_system(timestamp, system):
+    """phovo_sampled_system_format: the line the VisualOdometry app writes per pair with --system."""
+    buf = C.create_string_buffer(1024)
+    check(lib().phovo_sampled_system_format(float(timestamp), C.byref(system), buf, len(buf)),
+          "phovo_sampled_system_format")
     return buf.value.decode()
 
 

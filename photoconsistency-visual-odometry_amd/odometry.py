@@ -282,6 +282,14 @@ class CPhotoconsistencyOdometryAnalytic:
         check(self._lib.phovo_odometry_get_pair_system(self._h, C.byref(ps)), "GetPairSystem")
         return ps
 
+    def GetSampledSystem(self):
+        """The Gauss-Newton system of the sampled aligners (bilinear sampling: dim 6; the affine-illumination objective:
+        dim 8, at the (alpha, beta) of the last Optimize()) at the optimal state on the finest level the configuration
+        optimises (native.SampledSystem); evaluated on demand after Optimize()."""
+        ss = native.SampledSystem()
+        check(self._lib.phovo_odometry_get_sampled_system(self._h, C.byref(ss)), "GetSampledSystem")
+        return ss
+
     def LastOptimizeMilliseconds(self):
         ms = C.c_double()
         check(self._lib.phovo_odometry_last_optimize_ms(self._h, C.byref(ms)), "LastOptimizeMilliseconds")
@@ -335,7 +343,7 @@ class CPhotoconsistencyOdometryAffine(CPhotoconsistencyOdometryAnalytic):
     """One frame pair at a time; not in the reference: the photometric objective with a per-pair gain and offset estimated
     jointly with the pose (native.OBJECTIVE_PHOTOMETRIC_AFFINE: bilinear samples, exact warp Jacobian, residual
     I1 - (1 + alpha) I0 - beta).  Reads the analytic yml files; extensions and GetPairSystem() are refused
-    (PHOVO_E_UNSUPPORTED).  GetIllumination() returns what Optimize() found."""
+    (PHOVO_E_UNSUPPORTED); GetSampledSystem() returns the 8 x 8 system.  GetIllumination() returns what Optimize() found."""
 
     def __init__(self, device=0):
         super().__init__(device)
@@ -367,6 +375,13 @@ assert _TR_LEVEL_DTYPE.itemsize * native.MAX_LEVELS == C.sizeof(native.TrustRegi
 PAIR_SYSTEM_DTYPE = np.dtype([("information", "<f8", (36,)), ("gradient", "<f8", (6,)), ("cost", "<f8"),
                               ("rows", "<i4"), ("flags", "<u4")])
 assert PAIR_SYSTEM_DTYPE.itemsize == C.sizeof(native.PairSystem)
+
+
+# phovo_sampled_system as a numpy record (the layout of native.SampledSystem): evaluate_sampled_pairs fills an array of these
+SAMPLED_SYSTEM_DTYPE = np.dtype([("information", "<f8", (native.SYSTEM_MAX_DIM * native.SYSTEM_MAX_DIM,)),
+                                 ("gradient", "<f8", (native.SYSTEM_MAX_DIM,)), ("cost", "<f8"), ("rows", "<i4"),
+                                 ("flags", "<u4"), ("dim", "<i4"), ("reserved", "<i4")])
+assert SAMPLED_SYSTEM_DTYPE.itemsize == C.sizeof(native.SampledSystem)
 
 
 class AlignmentEngine:
@@ -654,6 +669,30 @@ class AlignmentEngine:
                    cost=out["cost"].copy(), rows=out["rows"].astype(np.int64), flags=out["flags"].astype(np.int64))
         if want_structs:
             res["structs"] = list((native.PairSystem * n).from_buffer_copy(out.tobytes()))
+        return res
+
+    def evaluate_sampled_pairs(self, src, tgt, states, level, want_structs=False):
+        """The Gauss-Newton system of each (source, target) pair under the sampled aligners at states [n, 6] (bilinear
+        sampling) or [n, 8] (the affine-illumination objective: pose, alpha, beta) on `level`
+        (phovo_engine_evaluate_sampled_pairs).  Returns a dict of numpy arrays: information [n, dim, dim], gradient
+        [n, dim], cost [n], rows [n], flags [n] (with want_structs, also the native.SampledSystem records under "structs")."""
+        s, t = self._pairs(src, tgt)
+        n = s.size
+        st = np.ascontiguousarray(states, dtype=np.float64)
+        if st.ndim != 2 or st.shape[0] != n or st.shape[1] not in (6, native.SYSTEM_MAX_DIM):
+            raise ValueError("states must have shape [n, 6] or [n, 8]")
+        dim, ld = st.shape[1], native.SYSTEM_MAX_DIM
+        out = np.zeros(max(n, 1), dtype=SAMPLED_SYSTEM_DTYPE)      # the C records, written in place
+        ip = C.POINTER(C.c_int)
+        check(self._lib.phovo_engine_evaluate_sampled_pairs(self._h, n, s.ctypes.data_as(ip), t.ctypes.data_as(ip),
+                                                            st.ctypes.data, dim, int(level), out.ctypes.data),
+              "phovo_engine_evaluate_sampled_pairs")
+        out = out[:n]
+        res = dict(information=out["information"].reshape(n, ld, ld)[:, :dim, :dim].copy(),
+                   gradient=out["gradient"][:, :dim].copy(), cost=out["cost"].copy(), rows=out["rows"].astype(np.int64),
+                   flags=out["flags"].astype(np.int64))
+        if want_structs:
+            res["structs"] = list((native.SampledSystem * n).from_buffer_copy(out.tobytes()))
         return res
 
     def enqueue_align(self, src, tgt, init_states=None):
