@@ -88,6 +88,33 @@ def _bytes(structs):
     return [bytes(memoryview(r)) for r in structs]
 
 
+def _kind_engine(kind, K, w, h, nl, **kw):
+    return _engine(K, w, h, nl, corrected=kind != "slip", affine=kind == "affine", **kw)
+
+
+def _check_one(s, i, planes, level, K, state, kind, delta=None, depth_range=(0.3, 5.0)):
+    """Record i of `s` against the checker of its row kind on `planes` = (i0, d0, i1, gx1, gy1); returns the row count."""
+    dim = 8 if kind == "affine" else 6
+    if kind == "affine":
+        H, g, cost, rows = ref.system8(planes, level, K, state, *depth_range)
+    else:
+        H, g, cost, rows = ref.system6(planes, level, K, state, kind == "corrected", delta, *depth_range)
+    if rows == 0:
+        _zero_record(s, i, dim)
+        return 0
+    ref.check_against(s["information"][i], s["gradient"][i], s["rows"][i], s["cost"][i], H, g, rows, cost)
+    assert s["flags"][i] == (native.PAIR_RANK_DEFICIENT if rows < dim else 0)
+    return rows
+
+
+def _with_illumination(states, kind, ab=(-0.2, 0.08)):
+    states = np.asarray(states, dtype=np.float64)
+    return np.hstack([states, np.tile(ab, (len(states), 1))]) if kind == "affine" else states
+
+
+KINDS = ["slip", "corrected", "affine"]
+
+
 # ---- 1: the oracle's trace -------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def pair160():
@@ -143,6 +170,106 @@ def test_level_geometries(w, h):
         assert seen > 0
     if (w, h) == (41, 25):          # the second tile's only pixel is a row for this seed
         assert ref.row_mask(planes, 0, p["K"], np.zeros(6))[1024]
+
+
+def _covering_configurations(i):
+    """For the size of index i, one configuration per storage: with test_level_geometries (fp64, corrected, no weights)
+    every size meets every storage, both Jacobians and Huber weights; over the sizes every storage meets both Jacobians
+    with and without weights."""
+    return [(STORAGES[k], (i + k) % 2 == 1, 0.03 if (i + k) % 3 != 0 else None) for k in range(3)]
+
+
+def test_the_covering_set_covers():
+    seen = set()
+    for i in range(len(SIZES[:4] + STRIPS)):
+        cfgs = _covering_configurations(i)
+        assert {c[0] for c in cfgs} == set(STORAGES) and {c[1] for c in cfgs} == {False, True}
+        assert any(c[2] is not None for c in cfgs)
+        seen.update((c[0], c[1], c[2] is not None) for c in cfgs)
+    assert len(seen) == 12
+
+
+@pytest.mark.parametrize("k", range(3))
+@pytest.mark.parametrize("i", range(len(SIZES[:4] + STRIPS)), ids=[f"{w}x{h}" for w, h in SIZES[:4] + STRIPS])
+def test_level_geometries_under_the_other_configurations(i, k):
+    """The partial tile, the 1025th pixel, a last chunk of 7 pixels and the strips on fp32 and fp16 planes, under the slip
+    Jacobian and with Huber weights (a covering set)."""
+    w, h = (SIZES[:4] + STRIPS)[i]
+    storage, corrected, delta = _covering_configurations(i)[k]
+    p = _strip_pair(w, h)
+    kind = "corrected" if corrected else "slip"
+    with _pair_engine(p, 1, corrected=corrected, storage=storage, huber=None if delta is None else [delta]) as eng:
+        planes = _planes(eng, 0)
+        rs = np.random.RandomState(w * 1000 + h)
+        states = np.array([np.zeros(6), p["motion"], rs.uniform(-0.02, 0.02, 6)])
+        s = eng.evaluate_sampled_pairs([0] * 3, [1] * 3, states, 0, want_structs=True)
+        _check_record_shape(s["structs"], 6)
+        assert sum(_check_one(s, j, planes, 0, p["K"], states[j], kind, delta) > 0 for j in range(3)) > 0
+        if delta is not None and w * h > 1000:           # (the weights are at work: some rows above delta, some below)
+            r, _ = ref.twin.normal_equations_bilinear(planes, 0, p["K"], np.zeros(6), 0.3, 5.0, corrected=corrected)
+            r = np.abs(r[ref.row_mask(planes, 0, p["K"], np.zeros(6))])
+            assert (r > delta).any() and (r <= delta).any()
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_fy_differs_from_fx_and_the_principal_point_is_off_the_grid(kind):
+    """Every other pair of this file has fx == fy and the principal point on the half-integer grid.  75x53 on two levels:
+    level 1 (38x27) meets the checker too."""
+    p = synthetic.make_pair(33, 75, 53, holes=0.02)
+    K = p["K"].copy()
+    K[0, 0] *= 1.07
+    K[1, 1] *= 0.94
+    K[0, 2] += 1.3
+    K[1, 2] -= 0.7
+    assert K[0, 0] != K[1, 1]
+    p = dict(p, K=K)
+    rs = np.random.RandomState(7553)
+    states = _with_illumination([np.zeros(6), p["motion"], rs.uniform(-0.03, 0.03, 6)], kind)
+    with _pair_engine(p, 2, corrected=kind != "slip", affine=kind == "affine") as eng:
+        for level in range(2):
+            planes = _planes(eng, level)
+            s = eng.evaluate_sampled_pairs([0] * 3, [1] * 3, states, level, want_structs=True)
+            _check_record_shape(s["structs"], 8 if kind == "affine" else 6)
+            for i in range(3):
+                assert _check_one(s, i, planes, level, K, states[i], kind) > 500 >> level
+    # the checker tells fy from fx by far more than the bars: with fy := fx its H is more than 1e6 bars away
+    Kx = K.copy()
+    Kx[1, 1] = K[0, 0]
+    a = ref.system8(planes, 1, K, states[1]) if kind == "affine" else ref.system6(planes, 1, K, states[1], kind != "slip")
+    b = ref.system8(planes, 1, Kx, states[1]) if kind == "affine" else ref.system6(planes, 1, Kx, states[1], kind != "slip")
+    assert np.max(np.abs(a[0] - b[0])) > 1e6 * 1e-10 * np.max(np.abs(a[0]))
+
+
+PAIRS_OF_FOUR = [(0, 2), (3, 1), (2, 2), (1, 0), (0, 3)]
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_frame_pairs_of_every_order(kind):
+    """Every other call of this file has tgt == src + 1.  Four 41x25 frames, one batch of pairs with tgt > src + 1,
+    tgt < src and src == tgt, each at its own state (near the pair's true motion; the frame onto itself: near zero)."""
+    seq = synthetic.make_sequence(43, 4, 41, 25, holes=0.02)
+    rs = np.random.RandomState(4125)
+    poses = []
+    for s_, t_ in PAIRS_OF_FOUR:
+        T = seq["poses"][t_] @ np.linalg.inv(seq["poses"][s_])
+        R = T[:3, :3]                                      # R = Rz(yaw) Ry(pitch) Rx(roll), se3.eigen_pose
+        x = np.array([T[0, 3], T[1, 3], T[2, 3], np.arctan2(R[1, 0], R[0, 0]), -np.arcsin(R[2, 0]), np.arctan2(R[2, 1], R[2, 2])])
+        poses.append(x + rs.uniform(-0.01, 0.01, 6))
+    states = _with_illumination(poses, kind)
+    assert len({tuple(x) for x in states}) == len(states)
+    with _kind_engine(kind, seq["K"], 41, 25, 1, frames=4) as eng:
+        eng.upload_frames(0, seq["gray"], seq["depth"])
+        frames = [eng.get_level_planes(f, 0) for f in range(4)]
+        src, tgt = [a for a, _ in PAIRS_OF_FOUR], [b for _, b in PAIRS_OF_FOUR]
+        s = eng.evaluate_sampled_pairs(src, tgt, states, 0, want_structs=True)
+        _check_record_shape(s["structs"], 8 if kind == "affine" else 6)
+        for i, (a, b) in enumerate(PAIRS_OF_FOUR):
+            planes = (frames[a][0], frames[a][1], frames[b][0], frames[b][2], frames[b][3])
+            assert _check_one(s, i, planes, 0, seq["K"], states[i], kind) > 500, (a, b)
+        # (the frames differ by far more than the bars: pair (0, 2) against frame 1 as its target misses)
+        planes = (frames[0][0], frames[0][1], frames[1][0], frames[1][2], frames[1][3])
+        with pytest.raises(AssertionError):
+            _check_one(s, 0, planes, 0, seq["K"], states[0], kind)
 
 
 def test_four_levels_of_640x480():
@@ -284,6 +411,89 @@ def test_nan_in_target_intensity_is_flagged_affine():
     assert np.isnan(s["cost"][0])
 
 
+CONFIGS4 = [("f64", native.STORAGE_F64, False), ("f32", native.STORAGE_F32, False), ("f16", native.STORAGE_F16, False),
+            ("affine", native.STORAGE_F64, True)]
+
+
+@pytest.mark.parametrize("name,storage,affine", CONFIGS4, ids=[c[0] for c in CONFIGS4])
+def test_nan_in_a_target_gradient_is_flagged_with_a_finite_cost(name, storage, affine):
+    """NaN in GX1 alone: the residuals never see it, so rows and cost are the checker's and finite -- a finishing kernel
+    that looked at the cost alone would set no flag."""
+    p = synthetic.make_pair(36, 75, 53)
+    kind = "affine" if affine else "corrected"
+    state = _with_illumination([np.zeros(6)], kind)
+    with _pair_engine(p, 1, storage=storage, affine=affine) as eng:
+        _, _, gx, _ = eng.get_level_planes(1, 0)
+        gx[20:30, 30:50] = np.nan
+        eng.set_level_planes(1, 0, grad_x=gx)
+        planes = _planes(eng, 0)
+        assert np.isnan(planes[3]).sum() == 200 and not np.isnan(planes[2]).any() and not np.isnan(planes[4]).any()
+        s = eng.evaluate_sampled_pairs([0], [1], state, 0)
+    H, g, cost, rows = (ref.system8(planes, 0, p["K"], state[0]) if affine else ref.system6(planes, 0, p["K"], state[0], True))
+    assert rows > 1000 and np.isfinite(cost) and cost > 0 and np.isnan(H).any()
+    assert s["rows"][0] == rows and abs(s["cost"][0] - cost) <= 1e-12 * cost
+    assert s["flags"][0] == native.PAIR_NONFINITE
+    assert np.isnan(s["information"][0]).any()
+
+
+@pytest.mark.parametrize("name,storage,affine", CONFIGS4, ids=[c[0] for c in CONFIGS4])
+def test_nan_in_target_pixels_that_no_row_samples_leaves_the_record_alone(name, storage, affine):
+    """A 20x30 block of source pixels beyond the depth range; NaN in I1, GX1 and GY1 in its interior, 3 pixels in.  At the
+    zero state a row's taps lie within a pixel of its own position, so no row samples a NaN: no flag, and the record has
+    the bytes of the one from clean target planes."""
+    p = synthetic.make_pair(36, 75, 53)
+    state = np.zeros((1, 8 if affine else 6))
+    with _pair_engine(p, 1, storage=storage, affine=affine) as eng:
+        i0, d0, _, _ = eng.get_level_planes(0, 0)
+        d0[10:40, 25:45] = 7.0
+        eng.set_level_planes(0, 0, depth=d0)
+        clean = eng.evaluate_sampled_pairs([0], [1], state, 0, want_structs=True)
+        assert clean["flags"][0] == 0 and clean["rows"][0] == 75 * 53 - 30 * 20
+        i1, _, gx, gy = eng.get_level_planes(1, 0)
+        for a in (i1, gx, gy):
+            a[13:37, 28:42] = np.nan
+        eng.set_level_planes(1, 0, intensity=i1, grad_x=gx, grad_y=gy)
+        assert all(np.isnan(a).sum() == 24 * 14 for a in _planes(eng, 0)[2:])
+        dirty = eng.evaluate_sampled_pairs([0], [1], state, 0, want_structs=True)
+        assert dirty["flags"][0] == 0
+        assert _bytes(dirty["structs"]) == _bytes(clean["structs"])
+        # (one pixel nearer than the margin would have been sampled: the NaN block is not out of reach by chance)
+        d0[10:40, 25:45] = p["depth0"][10:40, 25:45]
+        eng.set_level_planes(0, 0, depth=d0)
+        assert eng.evaluate_sampled_pairs([0], [1], state, 0)["flags"][0] == native.PAIR_NONFINITE
+
+
+@pytest.mark.parametrize("storage", STORAGES)
+@pytest.mark.parametrize("corrected", [False, True])
+def test_huber_delta_above_every_residual_is_the_unweighted_record(storage, corrected):
+    """Weights of 1.0 are exact: bit for bit the record without weights, through the other compiled copy of the row loop."""
+    p = synthetic.make_pair(33, 75, 53, holes=0.02)
+    states = np.array([np.zeros(6), p["motion"], 3.0 * p["motion"]])
+    recs = []
+    for huber in (None, [10.0]):
+        with _pair_engine(p, 1, corrected=corrected, storage=storage, huber=huber) as eng:
+            s = eng.evaluate_sampled_pairs([0] * 3, [1] * 3, states, 0, want_structs=True)
+            assert np.all(s["rows"] > 1000) and not s["flags"].any()
+            recs.append(_bytes(s["structs"]))
+    assert recs[0] == recs[1]
+
+
+@pytest.mark.parametrize("storage", STORAGES)
+@pytest.mark.parametrize("corrected", [False, True])
+def test_huber_delta_below_almost_every_residual(storage, corrected):
+    p = synthetic.make_pair(33, 75, 53, holes=0.02)
+    states = np.array([np.zeros(6), p["motion"]])
+    kind = "corrected" if corrected else "slip"
+    with _pair_engine(p, 1, corrected=corrected, storage=storage, huber=[1e-6]) as eng:
+        planes = _planes(eng, 0)
+        s = eng.evaluate_sampled_pairs([0] * 2, [1] * 2, states, 0)
+        for i in range(2):
+            assert _check_one(s, i, planes, 0, p["K"], states[i], kind, 1e-6) > 1000
+    r, _ = ref.twin.normal_equations_bilinear(planes, 0, p["K"], states[1], 0.3, 5.0, corrected=corrected)
+    r = np.abs(r[ref.row_mask(planes, 0, p["K"], states[1])])
+    assert (r > 1e-6).mean() > 0.9
+
+
 @pytest.mark.parametrize("storage", STORAGES)
 def test_non_finite_state_in_one_pair(storage):
     p = synthetic.make_pair(44, 75, 53, holes=0.02)
@@ -354,16 +564,32 @@ def test_bit_identical_across_batches_positions_and_settings(affine):
 
 
 def test_bit_identical_across_a_group_boundary():
-    """A 640x480 affine batch one pair larger than a group (tile sums of at most 64 MB: 300 tiles x 512 B per pair)."""
-    p = synthetic.make_pair(33, 640, 480, holes=0.02)
+    """A 640x480 affine batch one pair larger than a group (tile sums of at most 64 MB: 300 tiles x 512 B per pair).  Pairs
+    0, 435 and 436 -- the last two of the first group and the only one of the second -- have their own frames and state."""
+    seq = synthetic.make_sequence(33, 3, 640, 480, holes=0.02)
     group = (64 << 20) // (300 * 64 * 8)
     assert group == 436
     n = group + 1
-    st = np.concatenate([p["motion"], [-0.05, 0.02]])
-    with _pair_engine(p, 1, affine=True) as eng:
-        one = _bytes(eng.evaluate_sampled_pairs([0], [1], st[None], 0, want_structs=True)["structs"])[0]
-        got = _bytes(eng.evaluate_sampled_pairs([0] * n, [1] * n, np.tile(st, (n, 1)), 0, want_structs=True)["structs"])
-    assert all(g == one for g in got)
+    st = np.array([0.01, -0.02, 0.015, 0.01, -0.005, 0.008, -0.05, 0.02])
+    own = {0: (1, 2, np.array([-0.015, 0.01, 0.02, -0.008, 0.006, 0.01, 0.03, -0.01])),
+           435: (2, 0, np.array([0.02, 0.015, -0.01, 0.004, 0.009, -0.007, -0.1, 0.04])),
+           436: (2, 1, np.array([-0.005, -0.012, 0.018, 0.012, -0.003, 0.005, 0.08, 0.06]))}
+    src, tgt, states = np.zeros(n, dtype=int), np.ones(n, dtype=int), np.tile(st, (n, 1))
+    for q, (a, b, x) in own.items():
+        src[q], tgt[q], states[q] = a, b, x
+    with _engine(seq["K"], 640, 480, 1, affine=True, frames=3) as eng:
+        eng.upload_frames(0, seq["gray"], seq["depth"])
+
+        def alone(a, b, x):
+            r = eng.evaluate_sampled_pairs([a], [b], x[None], 0, want_structs=True)
+            assert r["rows"][0] > 100000 and r["flags"][0] == 0
+            return _bytes(r["structs"])[0]
+        one = alone(0, 1, st)
+        singles = {q: alone(*own[q]) for q in own}
+        got = _bytes(eng.evaluate_sampled_pairs(src, tgt, states, 0, want_structs=True)["structs"])
+    assert len({one, *singles.values()}) == 4
+    for q in range(n):
+        assert got[q] == singles.get(q, one), q
 
 
 # ---- 8: no interference ------------------------------------------------------------------------------------------------

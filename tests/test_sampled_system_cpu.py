@@ -28,9 +28,9 @@ def problems():
     return out
 
 
-def _trace_system(planes, K, state, corrected, delta):
+def _trace_system(planes, K, state, corrected, delta, min_depth=0.3, max_depth=5.0):
     """rows, H, g of ONE oracle iteration of the bilinear extension from `state`."""
-    cfg = oracle.make_config(num_levels=1, max_iter=[1], min_grad=[0.0])
+    cfg = oracle.make_config(num_levels=1, max_iter=[1], min_grad=[0.0], min_depth=min_depth, max_depth=max_depth)
     _, _, tr = oracle.optimize(cfg, K, *[[a] for a in planes], init_state=state, want_trace=True,
                                huber_delta=None if delta is None else [delta], bilinear=True, corrected=corrected)
     assert len(tr) == 1

@@ -1,8 +1,9 @@
 """Randomised device-vs-checker sweep of the bi-objective (`bi`, gn_biobjective_kernel.hip), trust-region (`tr`,
-gn_trust_region_kernel.hip), evaluate (`eval`, gn_evaluate_kernels.hip) and affine-illumination (`affine`,
-gn_affine_kernel.hip) kernels, in the style of fuzz_parity.py.
+gn_trust_region_kernel.hip), evaluate (`eval`, gn_evaluate_kernels.hip), affine-illumination (`affine`,
+gn_affine_kernel.hip) and sampled-system (`sampled`, gn_evaluate_sampled_kernels.hip) kernels, in the style of
+fuzz_parity.py.
 
-    python tests/tools/fuzz_objectives.py [cases=100] [seed=0] [mode=bi|tr|eval|affine] [big] [angles]
+    python tests/tools/fuzz_objectives.py [cases=100] [seed=0] [mode=bi|tr|eval|affine|sampled] [big] [angles]
 
 Every case draws (draw_case, pure numpy, so that replay and coverage are testable without a GPU): an odd size with 1-3
 levels up to 330x250 (`big`: 340x260 ... 700x500 with 1-2 levels) or a strip 1-5 pixels wide; intrinsics perturbed off
@@ -42,6 +43,20 @@ it is defined, so RANK_DEFICIENT and the levels that ran 
 summary adds, from the checker's results, the cases that passed only under the scaled bar, those that ended non-finite,
 the levels under a threshold that ended by it and by their count, and the chunk classes run.
 
+`sampled` takes `eval`'s draws (sizes, strips, perturbed K, source-depth defects, both ranges, storage, Huber deltas per
+level, the spread and the edge state of the evaluated states, the batch size) and adds its own after them (_draw_sampled):
+the row kind -- slip, corrected or affine, the last on fp64 planes without weights as the engine requires --, (alpha,
+beta), 2-4 frames rendered as one sequence with every frame's depth carrying the defects, a (src, tgt) per state from all
+ordered pairs of frames (tgt < src and src == tgt included; a frame onto itself is evaluated at least 0.003 from the
+identity, where its residual would be rounding noise), small sizes of any parity, and in a tenth of the cases depth that
+is valid in 1-12 pixels only.  Device side: every level at up to 3 (src, tgt, state); further pairs are replicas, which
+must carry their original's bytes; the planes of every level and frame read back.  Checker side (_check_sampled):
+sampled_system_ref.system6 / system8 under sampled_system_ref.check_against; no rows: the all-zero record with
+RANK_DEFICIENT; fewer rows than columns: the flag and the values.  A miss is set aside, printed and counted, only under
+`eval`'s rule -- one ulp of fx moves the checker's own answer by more than a quarter of the bar or changes its row count.
+The summary adds the systems checked, the empty ones and those of fewer rows than columns, and the coverage classes
+(SAMPLED_CLASSES) of the draws.
+
 One line per failure, a summary, exit status 1 on any failure.  FUZZ_ONLY=12,345 runs only those cases, with the draws of
 the full sweep.  The checkers run in FUZZ_JOBS worker processes (default: up to 12), which never touch the GPU.
 """
@@ -59,7 +74,7 @@ for p in (ROOT, TESTS, HERE):
         sys.path.insert(0, p)
 from fuzz_draws import draw_angle  # noqa: E402
 
-MODES = ("bi", "tr", "eval", "affine")
+MODES = ("bi", "tr", "eval", "affine", "sampled")
 CERES_FILES = ("config_3_level_optimization_ceres.yml", "config_4_level_optimization_ceres.yml",
                "config_5_level_optimization_ceres.yml", "config_only_level_0_ceres.yml",
                "config_only_level_1_ceres.yml", "config_only_level_2_ceres.yml")
@@ -77,6 +92,10 @@ MARGIN_FLOOR = 1e-6                       # test_gpu_affine.MARGIN_FLOOR
 # the `affine` sweeps of tests/test_gpu_affine_sweep.py: (flags, cases, seed); tests/test_affine_sweep_cpu.py holds their
 # draws to full coverage, and the checker on the first one's to the caps, without a device
 AFFINE_SWEEPS = (((), 300, 14), (("angles",), 150, 41), (("big",), 40, 52))
+# the `sampled` sweeps of tests/test_gpu_sampled_sweep.py, held to full coverage by tests/test_sampled_sweep_cpu.py
+SAMPLED_SWEEPS = (((), 300, 14), (("angles",), 150, 41), (("big",), 40, 52))
+SAMPLED_KINDS = ("slip", "corrected", "affine")         # the row kinds of gn_evaluate_sampled_kernels.hip
+PAIR_RANK_DEFICIENT, PAIR_NONFINITE = 4, 1              # phovo_hip.h (tests/test_sampled_sweep_cpu.py holds them to native)
 
 
 def _edge_states():
@@ -136,6 +155,26 @@ def _draw_affine(rs, c):
     # over the level's rows) passes 0.3 ... 2.0, where DESIGN.md §14's converged fixtures end, on few levels only
     scale = float(rs.choice([0.05, 0.1, 0.3]))
     c["min_grad"] = [m * scale for m in c["min_grad"]]
+
+
+def _draw_sampled(rs, c):
+    """The draws of `sampled` alone, after all others: the row kind (affine: fp64 planes and no Huber weights, as the
+    engine requires), the (alpha, beta) of the eight-column states, 2-4 frames rendered as one sequence, a (src, tgt) per
+    state from ALL ordered pairs (tgt < src and src == tgt included), some small sizes of any parity (1 to 11 tiles) and,
+    in a tenth of the cases, source depth that is valid in 1-12 pixels of a frame only: systems of fewer rows than
+    columns."""
+    kind = SAMPLED_KINDS[int(rs.randint(0, 3))]
+    alpha, beta = float(rs.uniform(-0.25, 0.2)), float(rs.uniform(-0.06, 0.1))
+    nf = int(rs.randint(2, 5))
+    pairs = [[int(rs.randint(0, nf)), int(rs.randint(0, nf))] for _ in range(3)]
+    small = rs.rand() < 0.15
+    sw, sh = int(rs.randint(8, 121)), int(rs.randint(6, 91))
+    sparse, is_sparse = int(rs.randint(1, 13)), rs.rand() < 0.1
+    c.update(kind=kind, illum=[alpha, beta], n_frames=nf, pairs=pairs, sparse=sparse if is_sparse else None)
+    if kind == "affine":
+        c.update(storage=0, huber=None)
+    if small and c["size_class"] != "strip":
+        c.update(size_class="small", w=sw, h=sh)
 
 
 def draw_case(rs, mode, flags):
@@ -199,15 +238,17 @@ def draw_case(rs, mode, flags):
         c["init"] = small[:3] + ang
     else:
         c["init"] = None if ik < 0.3 else small if ik < 0.75 else ("edge", edge)
-    c["storage"] = int(rs.randint(0, 3)) if mode == "eval" else 0
+    c["storage"] = int(rs.randint(0, 3)) if mode in ("eval", "sampled") else 0
     c["huber"] = [float(rs.choice([0.02, 0.05, 0.1])) for _ in range(nl)] if rs.rand() < 0.5 else None
-    if mode != "eval":
+    if mode not in ("eval", "sampled"):
         c["huber"] = None
     c["eval_spread"] = float(rs.choice([0.0, 0.003, 0.02]))
     c["eval_edge"] = int(rs.randint(0, 32)) if rs.rand() < 0.25 else None
     c["n_pairs"] = int(rs.choice([1, 3, 40]))
     if mode == "affine":
         _draw_affine(rs, c)
+    if mode == "sampled":
+        _draw_sampled(rs, c)
     return c
 
 
@@ -228,6 +269,8 @@ def case_key(d):
 
 
 def level_geometries(d):
+    if d["mode"] == "sampled":
+        return {predicted_geometry("eval", int(np.prod(device_level_size(d["w"], d["h"], l)))) for l in range(d["nl"])}
     levels = [l for l in range(d["nl"]) if d["mode"] == "eval" or
               (d["tr_max_iter"] if d["mode"] == "tr" else d["max_iter"])[l] > 0]
     if d["mode"] == "affine":
@@ -240,6 +283,8 @@ def coverage(draws, mode):
     """How often the draws reach each size class, geometry, depth defect and range change (for the coverage test)."""
     cov = {f"size_{k}": 0 for k in ("normal", "strip", "big")}
     cov.pop("size_big")
+    if mode == "sampled":
+        return coverage_sampled(draws)
     geos = ["tiles1", "tiles2-16", "tiles17+"] if mode == "eval" else ["lds256", "lds512", "hbm512"]
     if mode == "affine":
         geos = list(CHUNK_CLASSES) + ["last_partial", "last_full"]
@@ -278,6 +323,41 @@ def coverage(draws, mode):
         cov["range_non_default"] += int(d["range"] != [0.3, 5.0])
         cov[f"pairs_{d['n_pairs']}"] += 1
         cov["init_edge"] += int(isinstance(d["init"], tuple) or (mode != "affine" and d["eval_edge"] is not None))
+    return cov
+
+
+SAMPLED_CLASSES = (tuple(f"kind_{k}" for k in SAMPLED_KINDS) + tuple(f"storage_{k}" for k in range(3)) +
+                   ("huber", "no_huber", "tiles1", "tiles2-16", "tiles17+", "k_perturb", "range_changed", "level1+",
+                    "size_strip", "tgt_not_src+1", "tgt_before_src", "src_is_tgt", "pairs_1", "pairs_3", "pairs_40"))
+
+
+def sampled_pairs_run(d):
+    """The (src, tgt) of the states a `sampled` case evaluates: the first min(3, n_pairs) of its drawn pairs."""
+    return d["pairs"][:min(3, d["n_pairs"])]
+
+
+def coverage_sampled(draws):
+    """How often the draws of `sampled` reach each class of SAMPLED_CLASSES (storage and Huber under the six-column kinds,
+    the frame-pair classes over the pairs that run)."""
+    cov = {k: 0 for k in SAMPLED_CLASSES}
+    for d in draws:
+        cov[f"kind_{d['kind']}"] += 1
+        if d["kind"] != "affine":
+            cov[f"storage_{d['storage']}"] += 1
+            cov["huber" if d["huber"] is not None else "no_huber"] += 1
+        for g in level_geometries(d):
+            cov[g] += 1
+        cov["k_perturb"] += int(d["k_perturb"] is not None)
+        cov["range_changed"] += int(d["upload_range"] != d["range"])
+        cov["level1+"] += int(d["nl"] > 1)
+        cov["size_strip"] += int(d["size_class"] == "strip")
+        run = sampled_pairs_run(d)
+        cov["tgt_not_src+1"] += int(any(t != s + 1 for s, t in run))
+        cov["tgt_before_src"] += int(any(t < s for s, t in run))
+        cov["src_is_tgt"] += int(any(t == s for s, t in run))
+        cov[f"pairs_{d['n_pairs']}"] += 1
+        if d["size_class"] == "big":                # (as coverage(): the class exists only where a draw has it)
+            cov["size_big"] = cov.get("size_big", 0) + 1
     return cov
 
 
@@ -326,6 +406,204 @@ def render(d):
         init = _edge_states()[init[1]]
     p["init"] = None if init is None else np.array(init, dtype=np.float64)
     return p
+
+
+def state_of_pose(T):
+    """(x, y, z, yaw, pitch, roll) of a 4x4 pose with R = Rz(yaw) Ry(pitch) Rx(roll), |pitch| < pi / 2 (se3.eigen_pose)."""
+    R = T[:3, :3]
+    return np.array([T[0, 3], T[1, 3], T[2, 3], np.arctan2(R[1, 0], R[0, 0]), np.arcsin(np.clip(-R[2, 0], -1.0, 1.0)),
+                     np.arctan2(R[2, 1], R[2, 2])])
+
+
+def render_sequence(d):
+    """The frames of a `sampled` case: n_frames views of one plane scene under chained motions of the case's size (in
+    `angles` mode the first step is the case's motion), the perturbed K, every frame's depth with the case's defects (and,
+    for `sparse`, valid in that many pixels only), the true relative state of every ordered pair, the states to evaluate."""
+    from phovo_amd import se3, synthetic
+    w, h, nf = d["w"], d["h"], d["n_frames"]
+    rw = max(w, 64) if w < 8 else w
+    rs = np.random.RandomState(d["seed"])
+    scene = synthetic.Scene(d["seed"])
+    K0 = synthetic.intrinsics(rw, h)
+    poses, T = [], np.eye(4)
+    for f in range(nf):
+        if f > 0:
+            m = synthetic.random_motion(rs, d["trans"], d["rot"])
+            T = se3.eigen_pose(d["motion"] if (f == 1 and d["motion"] is not None) else m) @ T
+        poses.append(T.copy())
+    frames = [synthetic.render(scene, poses[f], rw, h, K0, d["holes"], hole_seed=d["seed"] % 10007 * 100003 + f)
+              for f in range(nf)]
+    gray = [g for g, _ in frames]
+    depth = [np.array(z, dtype=np.float64) for _, z in frames]
+    K = K0.copy()
+    if w < 8:
+        gray = [np.ascontiguousarray(g[:, 30:30 + w]) for g in gray]
+        depth = [np.ascontiguousarray(z[:, 30:30 + w]) for z in depth]
+        K[0, 2] -= 30.0
+    if d["k_perturb"] is not None:
+        K[0, 2] += d["k_perturb"][0]
+        K[1, 2] += d["k_perturb"][1]
+        K[0, 0] *= d["k_perturb"][2]
+        K[1, 1] *= d["k_perturb"][3]
+    lo, hi = d["range"]
+    rs = np.random.RandomState(d["defect_seed"])
+    for z in depth:
+        for k, v in (("nan", np.nan), ("negative", -1.0), ("inf", np.inf), ("beyond_max", hi + 2.5), ("at_min", lo),
+                     ("at_max", hi)):
+            m = rs.rand(h, w) < 0.01
+            if k in d["src_defects"]:
+                z[m] = v
+        keep = rs.permutation(h * w)[:d["sparse"] or 0]
+        if d["sparse"] is not None:
+            flat = np.full(h * w, np.nan)
+            flat[keep] = z.reshape(-1)[keep]
+            z[...] = flat.reshape(h, w)
+    run = sampled_pairs_run(d)
+    rs = np.random.RandomState(d["defect_seed"] + 1)
+    states = []
+    for s, t in run:
+        base = np.zeros(6) if s == t else state_of_pose(poses[t] @ np.linalg.inv(poses[s]))
+        # a frame warped onto itself by the identity has a residual of rounding noise only (cost about 1e-28), under which
+        # the relative bars on gradient and cost say nothing: such a pair is evaluated at least 0.003 away
+        spread = max(d["eval_spread"], 0.003) if s == t else d["eval_spread"]
+        states.append(base + rs.normal(0, spread, 6))
+    if d["eval_edge"] is not None:
+        states[-1] = np.array(_edge_states()[d["eval_edge"]], dtype=np.float64)
+    if d["motion"] is not None:                     # (`angles`: the drawn start, a sin / cos branch per axis)
+        states[0] = np.array(d["init"], dtype=np.float64)
+    if d["kind"] == "affine":
+        a, b = d["illum"]
+        states = [np.concatenate([x, ab]) for x, ab in zip(states, ((a, b), (0.0, 0.0), (-a, -b)))]
+    return dict(gray=gray, depth=depth, K=K, pairs=run, states=np.array(states))
+
+
+def run_device_sampled(d):
+    """The device's side of a `sampled` case: every level evaluated at up to 3 (src, tgt, state), the pairs beyond them
+    replicas; the planes of every level and frame as the device holds them."""
+    from phovo_amd import native, odometry
+    q = render_sequence(d)
+    w, h, nl, n_pairs, nf = d["w"], d["h"], d["nl"], d["n_pairs"], d["n_frames"]
+    with odometry.AlignmentEngine(0) as e:
+        e.set_config(native.make_config(num_levels=nl, max_iter=[1] * nl, min_grad=[0.0] * nl))
+        if d["kind"] == "affine":
+            e.set_objective(native.OBJECTIVE_PHOTOMETRIC_AFFINE)
+        else:
+            e.set_extensions(native.make_extensions(plane_storage=[native.STORAGE_F64, native.STORAGE_F32,
+                                                                   native.STORAGE_F16][d["storage"]],
+                                                    huber_delta=d["huber"], sampling=native.SAMPLING_BILINEAR,
+                                                    jacobian_corrected=d["kind"] == "corrected"))
+        e.set_build_all_levels(True)
+        e.set_intrinsic_matrix(q["K"])
+        e.set_depth_range(*d["upload_range"])
+        e.reserve_frames(nf, w, h)
+        for f in range(nf):
+            e.upload_frame(f, q["gray"][f], q["depth"][f])
+        e.set_depth_range(*d["range"])
+        planes = [[e.get_level_planes(f, l) for f in range(nf)] for l in range(nl)]      # [level][frame] (i, d, gx, gy)
+        m = len(q["pairs"])
+        src = [q["pairs"][i % m][0] for i in range(n_pairs)]
+        tgt = [q["pairs"][i % m][1] for i in range(n_pairs)]
+        st = np.array([q["states"][i % m] for i in range(n_pairs)])
+        out, geos = [], set()
+        for l in range(nl):
+            r = e.evaluate_sampled_pairs(src, tgt, st, l, want_structs=True)
+            recs = [bytes(memoryview(x)) for x in r.pop("structs")]
+            r["replicas_alike"] = [k for k in range(m, n_pairs) if recs[k] != recs[k % m]]
+            out.append({k: (v[:m] if isinstance(v, np.ndarray) else v) for k, v in r.items()})
+            geos.add(predicted_geometry("eval", planes[l][0][0].size))
+    return dict(d=d, K=q["K"], pairs=q["pairs"], states=q["states"], planes=planes, out=out), geos
+
+
+def sampled_reference(d, planes_l, level, K, pair, state):
+    """(rows, H, g, cost) of sampled_system_ref on the planes of one level ([frame] (i, d, gx, gy)) for one pair."""
+    import sampled_system_ref as ssr
+    s, t = pair
+    pl = (planes_l[s][0], planes_l[s][1], planes_l[t][0], planes_l[t][2], planes_l[t][3])
+    lo, hi = d["range"]
+    if d["kind"] == "affine":
+        H, g, cost, rows = ssr.system8(pl, level, K, state, lo, hi)
+    else:
+        delta = None if d["huber"] is None else d["huber"][level]
+        H, g, cost, rows = ssr.system6(pl, level, K, state, d["kind"] == "corrected", delta, lo, hi)
+    return rows, H, g, cost
+
+
+def _one_ulp_of_fx(K):
+    K1 = np.array(K, dtype=np.float64)
+    K1[0, 0] = np.nextafter(K1[0, 0], 2.0 * K1[0, 0])
+    return K1
+
+
+def _check_sampled(job):
+    """sampled_system_ref.system6 / system8 under sampled_system_ref.check_against; rows == 0: the all-zero record with
+    RANK_DEFICIENT; 0 < rows < dim: the flag and the values.  A miss is set aside under `eval`'s rule only."""
+    import sampled_system_ref as ssr
+    d, K = job["d"], job["K"]
+    dim = 8 if d["kind"] == "affine" else 6
+    worst, knife, info = 0.0, [], dict(systems=0, empty=0, deficient=0)
+    for level, out in enumerate(job["out"]):
+        if out["replicas_alike"]:
+            return _ok("fail", np.inf, f"level {level}: replicas {out['replicas_alike'][:5]} differ from their originals")
+        for i, (pair, state) in enumerate(zip(job["pairs"], job["states"])):
+            ref = sampled_reference(d, job["planes"][level], level, K, pair, state)
+            rows = ref[0]
+            info["systems"] += 1
+            info["empty"] += int(rows == 0)
+            info["deficient"] += int(0 < rows < dim)
+            got = (out["information"][i], out["gradient"][i], int(out["rows"][i]), float(out["cost"][i]))
+            flags = int(out["flags"][i])
+            ratio = _eval_ratio(got, ref)
+            try:
+                if rows == 0:
+                    assert got[2] == 0 and not got[0].any() and not got[1].any() and got[3] == 0.0, ("empty", got[2])
+                    assert flags == PAIR_RANK_DEFICIENT, ("flags", flags)
+                else:
+                    ssr.check_against(got[0], got[1], got[2], got[3], ref[1], ref[2], rows, ref[3])
+                    finite = np.all(np.isfinite(ref[1])) and np.all(np.isfinite(ref[2])) and np.isfinite(ref[3])
+                    want = (PAIR_RANK_DEFICIENT if rows < dim else 0) | (0 if finite else PAIR_NONFINITE)
+                    assert flags == want, ("flags", flags, want)
+                worst = max(worst, ratio)
+            except AssertionError as err:
+                ref1 = sampled_reference(d, job["planes"][level], level, _one_ulp_of_fx(K), pair, state)
+                moved = _eval_ratio((ref1[1], ref1[2], ref1[0], ref1[3]), ref)
+                detail = (f"level {level} state {i} pair {pair}: {err}; rows {got[2]} / {rows}, distance / bar {ratio:.3g}, "
+                          f"one ulp of fx moves the checker {moved:.3g} bars")
+                if moved <= 0.25:
+                    return dict(_ok("fail", ratio, detail), info=info)
+                knife.append(detail)                  # (and the remaining levels and states are still checked)
+    return dict(_ok("skip", worst, "; ".join(knife)) if knife else _ok("ok", worst), info=info)
+
+
+def precheck_sampled(d):
+    """The checker's side of a `sampled` case alone, on oracle-built pyramids in place of the device's: per system its row
+    count and whether it is unstable under the one-ulp question (its own answer moves by more than a quarter of the bar, or
+    its row count changes).  Returns dict(systems, empty, deficient, unstable (cases: 0 or 1), worst_moved)."""
+    from oracle import oracle
+    q = render_sequence(d)
+    nl, nf = d["nl"], d["n_frames"]
+    ocfg = oracle.make_config(num_levels=nl, max_iter=[1] * nl, min_grad=[0.0] * nl)
+    pyr = []
+    for f in range(nf):
+        i0p, d0p = oracle.build_source_pyramids(q["gray"][f], q["depth"][f], ocfg)
+        i1p, gxp, gyp = oracle.build_target_pyramids(q["gray"][f], ocfg)
+        pyr.append([(i1p[l], d0p[l], gxp[l], gyp[l]) for l in range(nl)])
+    dim = 8 if d["kind"] == "affine" else 6
+    out = dict(systems=0, empty=0, deficient=0, unstable=0, worst_moved=0.0)
+    K1 = _one_ulp_of_fx(q["K"])
+    for level in range(nl):
+        planes_l = [pyr[f][level] for f in range(nf)]
+        for pair, state in zip(q["pairs"], q["states"]):
+            ref = sampled_reference(d, planes_l, level, q["K"], pair, state)
+            ref1 = sampled_reference(d, planes_l, level, K1, pair, state)
+            moved = _eval_ratio((ref1[1], ref1[2], ref1[0], ref1[3]), ref)
+            out["systems"] += 1
+            out["empty"] += int(ref[0] == 0)
+            out["deficient"] += int(0 < ref[0] < dim)
+            if moved > 0.25:
+                out["unstable"] = 1
+            elif ref[0] > 0:
+                out["worst_moved"] = max(out["worst_moved"], float(moved))
+    return out
 
 
 def _tr_options(d, nl):
@@ -448,7 +726,8 @@ def _ok(status, ratio, msg=""):
 def check_job(job):
     """The checker's side of one case, in a worker process (no GPU): dict(status ok / fail / skip, ratio, msg)."""
     try:
-        return {"bi": _check_bi, "tr": _check_tr, "eval": _check_eval, "affine": _check_affine}[job["d"]["mode"]](job)
+        return {"bi": _check_bi, "tr": _check_tr, "eval": _check_eval, "affine": _check_affine,
+                "sampled": _check_sampled}[job["d"]["mode"]](job)
     except Exception as ex:                                     # a checker that raises is a failure, with its reason
         import traceback
         return _ok("fail", np.inf, "checker raised: " + "".join(traceback.format_exception_only(type(ex), ex)).strip())
@@ -767,6 +1046,7 @@ def main(argv):
     bad = skipped = done = conditioned = 0
     worst, geos, pending = 0.0, {}, []
     tally = dict(scaled=0, nonfinite=0, by_threshold=0, by_count=0)          # (affine, from the checker's results)
+    systems = dict(systems=0, empty=0, deficient=0)                          # (sampled, from the checker's results)
 
     def settle(fut, case, d):
         nonlocal bad, skipped, done, worst, conditioned
@@ -782,6 +1062,11 @@ def main(argv):
                 tally["nonfinite"] += int(not i["finite"])
                 tally["by_threshold"] += i["by_threshold"]
                 tally["by_count"] += i["by_count"]
+        if mode == "sampled":
+            desc += (f" kind {d['kind']} storage {d['storage']} huber {d['huber']} frames {d['n_frames']} "
+                     f"(src, tgt) {sampled_pairs_run(d)} sparse {d['sparse']} k_perturb {d['k_perturb']}")
+            for k in systems:
+                systems[k] += r.get("info", {}).get(k, 0)
         if r["status"] == "fail":
             bad += 1
             print(f"FAIL {desc}: {r['msg']}", flush=True)
@@ -796,7 +1081,7 @@ def main(argv):
 
     with cf.ProcessPoolExecutor(max_workers=jobs, mp_context=mp.get_context("spawn")) as pool:
         for case, d in draws.items():
-            job, g = run_device(d)
+            job, g = run_device_sampled(d) if mode == "sampled" else run_device(d)
             for x in g:
                 geos[x] = geos.get(x, 0) + 1
             pending.append((pool.submit(check_job, job), case, d))
@@ -808,8 +1093,13 @@ def main(argv):
     print(f"{n} cases, {bad} failures, {skipped} skipped as knife-edge, worst distance / bar {worst:.3f}"
           + (f"; {conditioned} passed only under the bars conditioned on cond(J^T J)" if mode == "tr" else "")
           + (f"; {tally['scaled']} passed only under the scaled bar, {tally['nonfinite']} ended non-finite; levels under a "
-             f"threshold ended by threshold: {tally['by_threshold']}, by count: {tally['by_count']}" if mode == "affine" else ""))
+             f"threshold ended by threshold: {tally['by_threshold']}, by count: {tally['by_count']}" if mode == "affine" else "")
+          + (f"; {systems['systems']} systems checked, {systems['empty']} empty, {systems['deficient']} of fewer rows than "
+             f"columns" if mode == "sampled" else ""))
+    if mode == "sampled":
+        print("coverage (sampled, of the draws run): " + ", ".join(f"{k}: {v}" for k, v in coverage_sampled(draws.values()).items()))
     what = ("tile classes predicted from the level sizes" if mode == "eval" else
+            "tile classes of the levels as the device sized them" if mode == "sampled" else
             "chunk classes of the levels run" if mode == "affine" else "from the launch records")
     print(f"geometries exercised ({mode}, {what}): " + ", ".join(f"{k}: {v}" for k, v in sorted(geos.items())))
     return 1 if bad else 0
