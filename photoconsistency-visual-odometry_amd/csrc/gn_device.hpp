@@ -43,6 +43,26 @@ __device__ __forceinline__ double uniform_f64(double v)
   return __hiloint2double(hi, lo);
 }
 
+// Data-parallel-primitive moves (v_mov_b32 with a DPP modifier): a lane reads another lane of its own 16-lane row straight
+// from the register file -- no LDS crossbar (ds_bpermute, what __shfl compiles to) and no round trip to wait for.
+// Controls: quad_perm is its four 2-bit selectors, row_ror:n is 0x120 + n and means "lane l reads lane (l - n) mod 16 of
+// its row".  The bank mask enables the destination's banks of four lanes (bit b: lanes 4b .. 4b+3 of every row); a lane it
+// leaves out keeps `old`.  Every lane of the wave must be active where these are used.
+constexpr int DPP_QUAD_XOR1 = 0xB1;       // quad_perm:[1,0,3,2]
+constexpr int DPP_QUAD_XOR2 = 0x4E;       // quad_perm:[2,3,0,1]
+constexpr int DPP_QUAD_BCAST1 = 0x55;     // quad_perm:[1,1,1,1]
+constexpr int DPP_QUAD_BCAST2 = 0xAA;     // quad_perm:[2,2,2,2]
+constexpr int DPP_ROW_ROR = 0x120;
+template <int CTRL, int BANKS = 0xf>
+__device__ __forceinline__ double dpp_f64(double old, double src)
+{
+  const int lo = __builtin_amdgcn_update_dpp(__double2loint(old), __double2loint(src), CTRL, 0xf, BANKS, false);
+  const int hi = __builtin_amdgcn_update_dpp(__double2hiint(old), __double2hiint(src), CTRL, 0xf, BANKS, false);
+  return __hiloint2double(hi, lo);
+}
+template <int CTRL>
+__device__ __forceinline__ double dpp_f64(double src) { return dpp_f64<CTRL>(src, src); }
+
 // Pose constants from the state: Rt (:219-241) and temp1..temp24 (:243-266), written with the
 // reference's association.  temp7 = -temp6, temp9 = -temp8, temp21 = -temp5, temp22 = temp2,
 // temp23 = temp1 hold exactly in IEEE arithmetic and are not stored; Rt(0,0) = temp15,
@@ -88,9 +108,11 @@ __device__ __forceinline__ void write_pose_constants(double x, double y, double 
   } else {
     sincos(ang, &sn, &cs);
   }
-  const double sy = __shfl(sn, 0, WAVE), cy = __shfl(cs, 0, WAVE);
-  const double sp = __shfl(sn, 1, WAVE), cp = __shfl(cs, 1, WAVE);
-  const double sr = __shfl(sn, 2, WAVE), cr = __shfl(cs, 2, WAVE);
+  // Only lane 0 goes on: it has yaw's pair itself and takes pitch's and roll's from lanes 1 and 2 of its own quad with
+  // two DPP moves per value (quad_perm), not through the LDS crossbar (twelve ds_bpermute and their round trip before).
+  const double sy = sn, cy = cs;
+  const double sp = dpp_f64<DPP_QUAD_BCAST1>(sn), cp = dpp_f64<DPP_QUAD_BCAST1>(cs);
+  const double sr = dpp_f64<DPP_QUAD_BCAST2>(sn), cr = dpp_f64<DPP_QUAD_BCAST2>(cs);
   if (lane != 0) return;
   cst[C_X] = x; cst[C_Y] = y; cst[C_Z] = z;
   cst[C_R01] = cy * sp * sr - sy * cr;
@@ -114,21 +136,41 @@ __device__ __forceinline__ void write_pose_constants(double x, double y, double 
   cst[C_SY] = sy;
 }
 
-// One butterfly stage of the transposed wave reduction: N values in, N/2 out.  The stage is issued in
-// groups of G exchanges with a scheduling fence between groups: left alone, the scheduler hoists all
-// N/2 select pairs in front of the shuffles and the live range grows by 4 VGPRs per exchange
+// One butterfly stage of the transposed wave reduction at a distance inside a 16-lane row: N values in, N/2 out.  For the
+// pair (v[i], v[i + N/2]) a lane with bit DIST of its index clear keeps v[i] and receives its partner's v[i] (the partner
+// is lane ^ DIST), a lane with the bit set keeps v[i + N/2] and receives its partner's: v[i] = keep + received.
+// Nothing travels through the LDS crossbar (the four stages were four dependent ds_bpermute round trips, which the last
+// wave of a workgroup pays in the open in front of the barrier):
+//   DIST 8, 4  the bit splits a row into whole banks of four lanes, so two DPP moves per dword under bank masks build
+//              A = { own v[i] | partner's v[i + N/2] } and B = { partner's v[i] | own v[i + N/2] } (clear | set) without a
+//              select, and A + B is keep + received (as in reduce_stage_swap below).  xor 8 is row_ror:8 for every lane;
+//              xor 4 is row_ror:12 (reads lane + 4) for the clear banks and row_ror:4 (reads lane - 4) for the set ones.
+//   DIST 2, 1  inside a quad: select what to send, one quad_perm move per dword.
+// The stage is issued in groups of G exchanges with a scheduling fence between groups: left alone, the scheduler hoists
+// all N/2 exchanges' moves in front of the adds and the live range grows by 4 VGPRs per exchange
 // (179 VGPRs and spills under the 128-register budget of a 1024-thread workgroup).
-template <int N, int G>
-__device__ __forceinline__ void reduce_stage(double (&v)[NRED], int lane, int dist)
+// (In the lanes with the bit set A + B is received + keep, in the others keep + received: the same sum bit for bit unless
+// both are NaNs of different payloads; reduce_stage_swap has the same property.)
+template <int N, int G, int DIST>
+__device__ __forceinline__ void reduce_stage(double (&v)[NRED], int lane)
 {
-  const bool up = (lane & dist) != 0;
+  static_assert(DIST == 8 || DIST == 4 || DIST == 2 || DIST == 1, "a distance inside a 16-lane row");
 #pragma unroll
   for (int base = 0; base < N / 2; base += G) {
 #pragma unroll
     for (int i = base; i < base + G && i < N / 2; i++) {
-      const double send = up ? v[i] : v[i + N / 2];
-      const double keep = up ? v[i + N / 2] : v[i];
-      v[i] = keep + __shfl_xor(send, dist, WAVE);
+      if constexpr (DIST >= 4) {
+        constexpr int SET = DIST == 8 ? 0xc : 0xa, CLEAR = 0xf ^ SET;       // banks of the lanes with the bit set / clear
+        constexpr int FROM_BELOW = DPP_ROW_ROR + DIST, FROM_ABOVE = DPP_ROW_ROR + 16 - DIST;
+        const double a = dpp_f64<FROM_BELOW, SET>(v[i], v[i + N / 2]);
+        const double b = dpp_f64<FROM_ABOVE, CLEAR>(v[i + N / 2], v[i]);
+        v[i] = a + b;
+      } else {
+        const bool up = (lane & DIST) != 0;
+        const double send = up ? v[i] : v[i + N / 2];
+        const double keep = up ? v[i + N / 2] : v[i];
+        v[i] = keep + dpp_f64<DIST == 2 ? DPP_QUAD_XOR2 : DPP_QUAD_XOR1>(send);
+      }
     }
     if (N / 2 > G) __builtin_amdgcn_sched_barrier(0);
   }
@@ -406,42 +448,74 @@ __device__ __forceinline__ void rowcol_from_index_floor(double kd, const RowColF
   cd = fma(-rd, m.w, kd);
 }
 
-// A wave's 27 sums (+ the row count) folded over its 64 lanes and written to row `row` of s_red (transposed butterfly).
-__device__ __forceinline__ void reduce_wave_to_row(double (&acc)[NRED], int lane, int row, double *s_red)
+// The transposed butterfly over a wave's 64 lanes: 32 values per lane in, one total per lane out -- lane l returns the sum
+// over the wave of value idx(l) = bit-reversed (l >> 1) (lanes l and l ^ 1 hold the same total).  Six stages: distance 32
+// and 16 by lane swaps, 8 .. 1 by DPP moves; no stage goes through LDS.
+__device__ __forceinline__ double wave_butterfly(double (&acc)[NRED], int lane)
 {
   reduce_stage_swap<32, false>(acc);
   reduce_stage_swap<16, true>(acc);
-  reduce_stage<8, 4>(acc, lane, 8);
-  reduce_stage<4, 4>(acc, lane, 4);
-  reduce_stage<2, 4>(acc, lane, 2);
-  const double total = acc[0] + __shfl_xor(acc[0], 1, WAVE);
+  reduce_stage<8, 4, 8>(acc, lane);
+  reduce_stage<4, 4, 4>(acc, lane);
+  reduce_stage<2, 4, 2>(acc, lane);
+  return acc[0] + dpp_f64<DPP_QUAD_XOR1>(acc[0]);
+}
+
+// A wave's 27 sums (+ the row count) folded over its 64 lanes and written to row `row` of s_red (transposed butterfly).
+__device__ __forceinline__ void reduce_wave_to_row(double (&acc)[NRED], int lane, int row, double *s_red)
+{
+  const double total = wave_butterfly(acc, lane);
   const int idx = ((lane >> 5) & 1) * 16 + ((lane >> 4) & 1) * 8 + ((lane >> 3) & 1) * 4 +
                   ((lane >> 2) & 1) * 2 + ((lane >> 1) & 1);
   if ((lane & 1) == 0) s_red[row * NRED + idx] = total;
 }
 
+// Called by ONE whole wave behind the barrier that follows the butterflies' row stores: the 28 totals of the NROWS rows of
+// s_red, in a fixed order -- lane l adds value (l & 31) over the first (l < 32) or the second half of the rows, row by row,
+// and the halves meet in one exchange, first + second -- handed to every lane as h, g and the row count.
+// The exchange is a lane swap (one v_permlane32_swap per dword); the 28 values then reach every lane through LDS: lanes
+// 0 .. 31 store their totals over row 0 and all lanes read them back at wave-uniform addresses, 14 wide reads behind one
+// another.  Nobody else touches s_red between the two barriers around this wave's section, and the store and the reads are
+// the same wave's: a wave's LDS instructions execute and return in the order it issued them (one in-order queue per wave,
+// which is also what lets lgkmcnt count them), so the reads see the store without a barrier or a wait between them.
+// Through the crossbar it was 58 ds_bpermute_b32 (27 __shfl and the exchange), in wave 0's serial section.
+// NROWS = 1 (one wave per pair): the row already is the total and is read in place.
+template <int NROWS>
+__device__ __forceinline__ void sum_rows_broadcast(int lane, double *s_red, double (&h)[21], double (&g)[6], int &n_valid)
+{
+  static_assert(NROWS == 1 || NROWS % 2 == 0, "the rows are summed in two halves");
+  if constexpr (NROWS > 1) {
+    const int j = lane & (NRED - 1);
+    const int w0 = (lane >> 5) * (NROWS / 2);
+    double r[NROWS / 2];
+#pragma unroll
+    for (int w2 = 0; w2 < NROWS / 2; w2++) r[w2] = s_red[(w0 + w2) * NRED + j];      // (the loads go out together)
+    double v = 0.0;
+#pragma unroll
+    for (int w2 = 0; w2 < NROWS / 2; w2++) v += r[w2];
+    // lanes 0 .. 31: own + partner's, as v += __shfl_xor(v, 32); the upper lanes' sums are not used
+    const unsigned vlo = (unsigned)__double2loint(v), vhi = (unsigned)__double2hiint(v);
+    const auto lo = __builtin_amdgcn_permlane32_swap(vlo, vlo, false, false);
+    const auto hi = __builtin_amdgcn_permlane32_swap(vhi, vhi, false, false);
+    v = __hiloint2double((int)hi[0], (int)lo[0]) + __hiloint2double((int)hi[1], (int)lo[1]);
+    if (lane < NRED) s_red[lane] = v;
+  }
+#pragma unroll
+  for (int q = 0; q < 21; q++) h[q] = s_red[q];
+#pragma unroll
+  for (int i = 0; i < 6; i++) g[i] = s_red[21 + i];
+  n_valid = (int)s_red[RED_VALID];
+}
+
 // Called by ONE wave behind the barrier that follows reduce_wave_to_row: sum of the NROWS rows, solve, update, termination
 // (as gn_level_kernel's tail); the caller closes with a barrier and reads s_ctl[CTL_DONE].
 template <int NROWS>
-__device__ __forceinline__ void sum_rows_solve_update(int lane, const double *s_red, double *s_state, double *s_cst, int *s_ctl,
+__device__ __forceinline__ void sum_rows_solve_update(int lane, double *s_red, double *s_state, double *s_cst, int *s_ctl,
                                                       double lambda, int max_iter, double min_grad_norm,
                                                       int iteration, double &last_gnorm, int &last_valid)
 {
-  static_assert(NROWS % 2 == 0, "the rows are summed in two halves");
-  double v = 0.0;
-  {
-    const int j = lane & (NRED - 1);
-    const int w0 = (lane >> 5) * (NROWS / 2);
-#pragma unroll
-    for (int w2 = 0; w2 < NROWS / 2; w2++) v += s_red[(w0 + w2) * NRED + j];
-    v += __shfl_xor(v, 32, WAVE);
-  }
   double h[21], g[6];
-#pragma unroll
-  for (int q = 0; q < 21; q++) h[q] = __shfl(v, q, WAVE);
-#pragma unroll
-  for (int i = 0; i < 6; i++) g[i] = __shfl(v, 21 + i, WAVE);
-  last_valid = (int)__shfl(v, RED_VALID, WAVE);
+  sum_rows_broadcast<NROWS>(lane, s_red, h, g, last_valid);
   double step[6];
   solve6_ldlt(h, g, step);
   double st[6];

@@ -546,14 +546,9 @@ __device__ __forceinline__ void level_body(const GNLevelArgs &A, const LevelLds 
     acc[RED_VALID] = MASK_REG ? (double)(__popc((unsigned)inb_lo) + __popc((unsigned)inb_hi)) : (lane == 0 ? (double)n_rows : 0.0);
 
 
-    // ---- wave-level transposed butterfly: 32 shuffles, lane l ends with value index idx(l) ----
-    reduce_stage_swap<32, false>(acc);
-    reduce_stage_swap<16, true>(acc);
-    reduce_stage<8, 4>(acc, lane, 8);
-    reduce_stage<4, 4>(acc, lane, 4);
-    reduce_stage<2, 4>(acc, lane, 2);
+    // ---- wave-level transposed butterfly: 32 exchanges (lane swaps and DPP moves), lane l ends with value index idx(l) ----
     {
-      const double total = acc[0] + __shfl_xor(acc[0], 1, WAVE);
+      const double total = wave_butterfly(acc, lane);
       // (the lane is made opaque here: the row address below is loop-invariant, and hoisted out of the iteration loop it
       // does not survive pass 2's register pressure -- it came back as a scratch reload behind an s_waitcnt vmcnt(0),
       // in every wave, right in front of the barrier wave 0's solve waits at; five integer instructions instead)
@@ -568,24 +563,9 @@ __device__ __forceinline__ void level_body(const GNLevelArgs &A, const LevelLds 
 
     // ---- wave 0: cross-wave sum (fixed order), solve, update, terminate ------------------------
     if (wave == 0) {
-      // lane l sums value (l & 31) over half of the waves, the halves meet in one shuffle
-      double v = 0.0;
-      if constexpr (NW == 1) {
-        v = s_red[lane & (NRED - 1)];                     // a single wave: its own row is the total
-      } else {
-        const int j = lane & (NRED - 1);
-        const int w0 = (lane >> 5) * (NW / 2);
-#pragma unroll
-        for (int w2 = 0; w2 < NW / 2; w2++) v += s_red[(w0 + w2) * NRED + j];
-        v += __shfl_xor(v, 32, WAVE);
-      }
+      // lane l sums value (l & 31) over half of the waves, the halves meet in one exchange (sum_rows_broadcast)
       double h[21], g[6];
-#pragma unroll
-      for (int q = 0; q < 21; q++) h[q] = __shfl(v, q, WAVE);
-#pragma unroll
-      for (int i = 0; i < 6; i++) g[i] = __shfl(v, 21 + i, WAVE);
-
-      last_valid = (int)__shfl(v, RED_VALID, WAVE);
+      sum_rows_broadcast<NW>(lane, s_red, h, g, last_valid);
 #ifdef PHOVO_PHASE_STAMPS
       asm volatile("" :: "v"(h[0]), "v"(g[5]));
       const unsigned long long solve_t0 = wall_clock64();
@@ -686,8 +666,18 @@ __device__ __forceinline__ LevelLds carve_lds(unsigned char *lds_raw, int n_max,
 // It is padded to whole chunks plus one round of the workgroup (owner_lds_entries): pass 2 fetches the owner a chunk
 // ahead without asking whether that chunk still exists -- the padding reads -1, "nobody", and pass 1 never writes there.
 template <int T, int WPS, bool SRC_LDS, bool OWNER_LDS, bool MASK_REG, typename TI, typename TD, bool PARK = false>
-__global__ __launch_bounds__(T, WPS) void gn_level_kernel(const GNLevelArgs A)
+__global__ __launch_bounds__(T, WPS) __attribute__((aligned(T == WAVE ? 4096 : 256))) void gn_level_kernel(const GNLevelArgs A)
 {
+  // Placement of the one-wave-per-pair kernel.  Its sixteen workgroups per CU stand in sixteen different places of a 23 KB
+  // loop nest, and how that code lies relative to 4 KB boundaries decides up to 9 % of a 40x30 launch: the SAME
+  // instructions ran it in 2.95 and in 3.20 ms in two builds that differed only in the kernel's address (0x20e00 / 0x20b00),
+  // and wherever anything in front of it in the code object changed size, it moved (profiles/r07_runs/serial_section_ab.txt).
+  // So this instantiation starts on a 4 KB boundary and a run of s_nop, executed once per workgroup, puts its code 0xe00
+  // bytes behind it -- the best of four placements measured (0, 0x400, 0x800, 0xe00: 2.97 - 3.00, 2.90 - 2.99, 2.91, 2.83 -
+  // 2.91 ms; the 5-level file +1.8 % against the build before instead of +-0), in which only the longest pass-2 loop crosses
+  // a page.  A change to level_body moves the loops behind the pad: measure the 5-level file again then
+  // (tests/test_gpu_reduction_order.py::test_one_wave_kernel_is_pinned holds the alignment and the pad).
+  if constexpr (T == WAVE) asm volatile(".fill 896, 4, 0xbf800000");       // 896 x s_nop 0
   extern __shared__ __align__(16) unsigned char lds_raw[];
   const LevelLds L = carve_lds<T, SRC_LDS, OWNER_LDS, MASK_REG>(lds_raw, A.n, A.g_mask ? 0 : A.n_chunks);
   int *const s_ctl = L.ctl;

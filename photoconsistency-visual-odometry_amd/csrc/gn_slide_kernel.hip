@@ -312,13 +312,8 @@ __global__ __launch_bounds__(T, T / 256) void gn_level_kernel_slide(const GNLeve
       acc[RED_VALID] = lane == 0 ? (double)n_rows : 0.0;
 
       // ---- wave-level transposed butterfly (as gn_level_kernel) ----------------------------------------------------
-      reduce_stage_swap<32, false>(acc);
-      reduce_stage_swap<16, true>(acc);
-      reduce_stage<8, 4>(acc, lane, 8);
-      reduce_stage<4, 4>(acc, lane, 4);
-      reduce_stage<2, 4>(acc, lane, 2);
       {
-        const double total = acc[0] + __shfl_xor(acc[0], 1, WAVE);
+        const double total = wave_butterfly(acc, lane);
         const int idx = ((lane >> 5) & 1) * 16 + ((lane >> 4) & 1) * 8 + ((lane >> 3) & 1) * 4 +
                         ((lane >> 2) & 1) * 2 + ((lane >> 1) & 1);
         if ((lane & 1) == 0) s_red[wave2 * NRED + idx] = total;
@@ -328,20 +323,9 @@ __global__ __launch_bounds__(T, T / 256) void gn_level_kernel_slide(const GNLeve
 
     // ---- cross-wave sum, solve, update, terminate (as gn_level_kernel) --------------------------------------------
     if (wave == 0) {
-      double v = 0.0;
-      {
-        const int j = lane & (NRED - 1);
-        const int w0 = (lane >> 5) * (NW2 / 2);
-#pragma unroll
-        for (int w2 = 0; w2 < NW2 / 2; w2++) v += s_red[(w0 + w2) * NRED + j];
-        v += __shfl_xor(v, 32, WAVE);
-      }
       double h[21], g[6];
-#pragma unroll
-      for (int q = 0; q < 21; q++) h[q] = __shfl(v, q, WAVE);
-#pragma unroll
-      for (int i = 0; i < 6; i++) g[i] = __shfl(v, 21 + i, WAVE);
-      const int n_valid = (int)__shfl(v, RED_VALID, WAVE);
+      int n_valid;
+      sum_rows_broadcast<NW2>(lane, s_red, h, g, n_valid);
       const bool void_iteration = s_ctl[CTL_OOW] != 0;                  // wave-uniform
       double step[6];
       solve6_ldlt(h, g, step);

@@ -318,13 +318,8 @@ __global__ __launch_bounds__(WT) void k_wide_pass2(const GNLevelArgs A, const do
   }
   acc[RED_VALID] = lane == 0 ? (double)n_rows : 0.0;
   // tile sums: wave butterfly, then the four waves in fixed order
-  reduce_stage_swap<32, false>(acc);
-  reduce_stage_swap<16, true>(acc);
-  reduce_stage<8, 4>(acc, lane, 8);
-  reduce_stage<4, 4>(acc, lane, 4);
-  reduce_stage<2, 4>(acc, lane, 2);
   {
-    const double total = acc[0] + __shfl_xor(acc[0], 1, WAVE);
+    const double total = wave_butterfly(acc, lane);
     const int idx = ((lane >> 5) & 1) * 16 + ((lane >> 4) & 1) * 8 + ((lane >> 3) & 1) * 4 +
                     ((lane >> 2) & 1) * 2 + ((lane >> 1) & 1);
     if ((lane & 1) == 0) s_red[wave * NRED + idx] = total;
