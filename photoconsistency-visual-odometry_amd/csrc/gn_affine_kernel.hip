@@ -21,53 +21,12 @@ namespace phovo_hip {
 
 namespace {
 
-constexpr int NP = 8;                       // parameters: the pose and (alpha, beta)
 // second block of sums (slots of acc2)
 enum { X_JI0 = 0, X_J = 6, X_I0I0 = 12, X_I0 = 13, X_RI0 = 14, X_R = 15 };
 
 __host__ __device__ constexpr size_t affine_lds_bytes(int threads)
 {
   return sizeof(double) * (32 + 8 + 2 * (size_t)(threads / WAVE) * NRED) + sizeof(int) * CTL_COUNT;
-}
-
-// The 6 x 6 solve of gn_device.hpp (unpivoted LDL^T, every index a compile-time constant) extended to 8 x 8.
-__device__ __forceinline__ constexpr int tri8(int i, int j) { return i * NP - (i * (i - 1)) / 2 + (j - i); }
-
-__device__ __forceinline__ void solve8_ldlt(const double (&h)[36], const double (&g)[NP], double (&x)[NP])
-{
-  double L[NP][NP];     // strictly lower part used
-  double Ld[NP][NP];    // L[i][k] * d[k]
-  double inv[NP];
-#pragma unroll
-  for (int j = 0; j < NP; j++) {
-    double dj = h[tri8(j, j)];
-#pragma unroll
-    for (int k = 0; k < j; k++) dj = fma(-L[j][k], Ld[j][k], dj);
-    inv[j] = 1.0 / dj;
-#pragma unroll
-    for (int i = j + 1; i < NP; i++) {
-      double t = h[tri8(j, i)];
-#pragma unroll
-      for (int k = 0; k < j; k++) t = fma(-L[i][k], Ld[j][k], t);
-      Ld[i][j] = t;
-      L[i][j] = t * inv[j];
-    }
-  }
-  double y[NP];
-#pragma unroll
-  for (int i = 0; i < NP; i++) {
-    double t = g[i];
-#pragma unroll
-    for (int k = 0; k < i; k++) t = fma(-L[i][k], y[k], t);
-    y[i] = t;
-  }
-#pragma unroll
-  for (int i = NP - 1; i >= 0; i--) {
-    double t = y[i] * inv[i];
-#pragma unroll
-    for (int k = i + 1; k < NP; k++) t = fma(-L[k][i], x[k], t);
-    x[i] = t;
-  }
 }
 
 // Called by wave 0 behind the barrier that follows the two reduce_wave_to_row: sum of the NROWS rows of both blocks, the

@@ -201,7 +201,8 @@ __device__ __forceinline__ void reduce_stage_swap(double (&v)[NRED])
 // symmetric positive semi-definite, for which LDL^T is backward stable, needs 6 reciprocals instead of
 // the 21 divisions + 15 row swaps of pivoted elimination and only the 21 upper-triangular sums.
 // (The reference forms H^-1 with Eigen's PartialPivLU, ...Analytic.h:540; both are accurate to
-// cond(H)*eps, far inside the 1e-5 pose bar -- tests/test_gpu_parity.py holds 1e-9.)
+// cond(H)*eps, far inside the 1e-5 pose bar -- tests/test_gpu_parity.py holds 1e-9.  tests/test_gpu_device_arith.py holds
+// this solver and the two below to |x - x_exact| <= c cond2(H) 2^-53 |x_exact| directly)
 // h is the upper triangle, row-major: h[idx(i,j)], i <= j.  Fully unrolled: every index is a
 // compile-time constant, nothing goes to scratch.
 __device__ __forceinline__ constexpr int tri(int i, int j) { return i * 6 - (i * (i - 1)) / 2 + (j - i); }
@@ -243,6 +244,90 @@ __device__ __forceinline__ void solve6_ldlt(const double (&h)[21], const double 
   }
 }
 
+// (The trust-region kernel's; gn_trust_region_kernel.hip compiles it, as everything it includes, with fp contraction off.)
+__device__ __forceinline__ bool finite_f64(double v) { return fabs(v) <= 1.79769313486231570815e308; }
+
+// 6x6 Cholesky factorisation in place (a: upper triangle, row-major, becomes L^T) and solve of A y = b.  False if a pivot
+// is not positive (or not finite).
+__device__ __forceinline__ bool solve6_cholesky(double (&a)[21], const double (&b)[6], double (&y)[6])
+{
+  bool ok = true;
+#pragma unroll
+  for (int j = 0; j < 6; j++) {
+    double d = a[tri(j, j)];
+#pragma unroll
+    for (int k = 0; k < j; k++) d = fma(-a[tri(k, j)], a[tri(k, j)], d);
+    ok = ok && d > 0.0 && finite_f64(d);
+    const double ljj = sqrt(d);
+    a[tri(j, j)] = ljj;
+#pragma unroll
+    for (int i = j + 1; i < 6; i++) {
+      double t = a[tri(j, i)];
+#pragma unroll
+      for (int k = 0; k < j; k++) t = fma(-a[tri(k, i)], a[tri(k, j)], t);
+      a[tri(j, i)] = t / ljj;                   // L[i][j]
+    }
+  }
+  double z[6];
+#pragma unroll
+  for (int i = 0; i < 6; i++) {
+    double t = b[i];
+#pragma unroll
+    for (int k = 0; k < i; k++) t = fma(-a[tri(k, i)], z[k], t);
+    z[i] = t / a[tri(i, i)];
+  }
+#pragma unroll
+  for (int i = 5; i >= 0; i--) {
+    double t = z[i];
+#pragma unroll
+    for (int k = i + 1; k < 6; k++) t = fma(-a[tri(i, k)], y[k], t);
+    y[i] = t / a[tri(i, i)];
+  }
+  return ok;
+}
+
+// The affine-illumination kernel's parameters (gn_affine_kernel.hip): the pose and (alpha, beta)
+constexpr int NP = 8;
+// The 6 x 6 solve above (unpivoted LDL^T, every index a compile-time constant) extended to 8 x 8.
+__device__ __forceinline__ constexpr int tri8(int i, int j) { return i * NP - (i * (i - 1)) / 2 + (j - i); }
+
+__device__ __forceinline__ void solve8_ldlt(const double (&h)[36], const double (&g)[NP], double (&x)[NP])
+{
+  double L[NP][NP];     // strictly lower part used
+  double Ld[NP][NP];    // L[i][k] * d[k]
+  double inv[NP];
+#pragma unroll
+  for (int j = 0; j < NP; j++) {
+    double dj = h[tri8(j, j)];
+#pragma unroll
+    for (int k = 0; k < j; k++) dj = fma(-L[j][k], Ld[j][k], dj);
+    inv[j] = 1.0 / dj;
+#pragma unroll
+    for (int i = j + 1; i < NP; i++) {
+      double t = h[tri8(j, i)];
+#pragma unroll
+      for (int k = 0; k < j; k++) t = fma(-L[i][k], Ld[j][k], t);
+      Ld[i][j] = t;
+      L[i][j] = t * inv[j];
+    }
+  }
+  double y[NP];
+#pragma unroll
+  for (int i = 0; i < NP; i++) {
+    double t = g[i];
+#pragma unroll
+    for (int k = 0; k < i; k++) t = fma(-L[i][k], y[k], t);
+    y[i] = t;
+  }
+#pragma unroll
+  for (int i = NP - 1; i >= 0; i--) {
+    double t = y[i] * inv[i];
+#pragma unroll
+    for (int k = i + 1; k < NP; k++) t = fma(-L[k][i], x[k], t);
+    x[i] = t;
+  }
+}
+
 // Plane loads go through buffer descriptors: the four planes of a chunk share ONE 32-bit byte offset
 // (8*k) in a VGPR while the bases sit in SGPRs, and a read past the plane returns 0 instead of needing
 // a branch (raw buffer, num_records = plane bytes).  Flat loads cost a 64-bit VGPR address per plane.
@@ -256,12 +341,17 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t frame_rsrc(const unsigned char
 {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned char *>(frame), 0, (int)frame_bytes, 0x00020000);
 }
-// Element `idx` of a plane stored as T, widened to fp64 (all arithmetic stays fp64; narrower storage is the
-// opt-in extension of include/phovo_hip.h, PHOVO_STORAGE_*).  idx = -1 or past the plane reads 0.
-// soff: a wave-uniform byte offset (the instruction's scalar offset; it takes part in the range check): one descriptor
+// Element `idx` of a plane stored as T, widened to fp64 exactly, subnormals included (all arithmetic stays fp64; narrower
+// storage is the opt-in extension of include/phovo_hip.h, PHOVO_STORAGE_*).  idx = -1 or past the DESCRIPTOR reads 0.
+// soff: a wave-uniform byte offset (the instruction's scalar offset; it takes part in the range check: a read is served
+// iff soff + idx * sizeof(T) + sizeof(T) <= num_records, tests/test_gpu_device_arith.py): one descriptor
 // per FRAME (frame_rsrc) serves every plane of it -- base = the frame, soff = the plane's offset in it.  Four SGPRs per
 // frame plus one per plane instead of four per plane: the level kernels run out of scalar registers, and every spilled
 // one costs a v_readlane per use in the pixel loops.
+// With a frame descriptor "past the plane" is therefore NOT 0 while the address is still inside the frame: it is the
+// element of the plane that lies there (behind the frame it is 0 again, so nothing outside the frame is ever read).
+// Every read of that kind is a chunk-ahead prefetch or the tail of the last, partial chunk, whose lanes the in-image
+// mask drops; an owner of -1 is an offset of 4 GiB less 8 bytes and reads 0 with either descriptor.
 template <typename T>
 __device__ __forceinline__ double plane_load(__amdgpu_buffer_rsrc_t r, int idx, int soff = 0);
 template <>
@@ -287,6 +377,10 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 // 1/x to within one ulp: v_rcp_f64 seeds two Newton steps.  The IEEE-exact division sequence is
 // 11 instructions, this is 5; the half-ulp it gives up is far below the fp64 noise floor of the sums
 // that follow (tests/test_gpu_parity.py holds the poses to 1e-9 against the oracle's exact divisions).
+// Contract, for 2^-1000 <= |x| <= 2^1000: STEPS = 2 is within one ulp of the IEEE quotient, STEPS = 1 has a relative
+// error of at most 2^-48 (what its call sites quote); +-0, +-inf and NaN all give NaN (the seed is the IEEE quotient, the
+// first step forms 0 x inf), which fails the callers' bounds tests.  tests/test_gpu_device_arith.py holds all three
+// against IEEE division; DESIGN.md §4.1 has the measured figures.
 template <int STEPS = 2>
 __device__ __forceinline__ double fast_rcp(double x)
 {
@@ -327,7 +421,8 @@ __device__ __forceinline__ int mad24_uniform_b(int a, int b, int c)
 
 // C round() -- half away from zero (...Analytic.h:297-298) -- for arguments > -0.5, which is all the bounds test lets
 // through, in TWO instructions: floor(v + p) with p = 0.49999999999999994, the largest double below one half.  Exact, not
-// approximately right (tests/test_oracle_properties.py checks every neighbour of every tie against exact arithmetic):
+// approximately right (tests/test_oracle_properties.py checks every neighbour of every tie against exact arithmetic in a
+// numpy emulation, tests/test_gpu_device_arith.py the same table through these two instructions on the device):
 //   * a tie v = n + 0.5 gives n + 1 - 2^-54, which rounds to n + 1 (the next double below n + 1 is at least 2^-53 away for
 //     n >= 1; for n = 0 the sum is halfway between 1 - 2^-53 and 1 and ties-to-even picks 1): round() says n + 1;
 //   * the largest double below a tie, n + 0.5 - ulp, gives a sum that rounds to at most n + 1 - ulp: floor is n -- also
@@ -424,6 +519,8 @@ __device__ __forceinline__ void rowcol_advance(double &cd, double &rd, const Row
 // (row, column) of pixel k from k itself, all in fp64: row = trunc((k + 0.5) / W), column = k - row * W.  Exact: k < 2^21
 // and W are integers, (k + 0.5) / W lies at least 0.5 / W >= 2.4e-7 away from every integer while the fma below is off by
 // less than (k / W) * 2^-52 < 1e-12, so the truncation cannot land on the wrong side; the column is an exact integer fma.
+// (Every row boundary of 711 widths in exact rational arithmetic, tests/test_device_arith_cpu.py, and on the device,
+// tests/test_gpu_device_arith.py.)
 struct RowColFromIndex {
   double inv_w, half_inv_w, w;
 };

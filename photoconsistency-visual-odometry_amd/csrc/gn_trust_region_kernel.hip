@@ -114,47 +114,6 @@ __device__ __forceinline__ double bilinear(__amdgpu_buffer_rsrc_t r, int soff, i
   return wy * (wx * p11 + (1.0 - wx) * p12) + (1.0 - wy) * (wx * p21 + (1.0 - wx) * p22);   // sample.h:79-80
 }
 
-__device__ __forceinline__ bool finite_f64(double v) { return fabs(v) <= 1.79769313486231570815e308; }
-
-// 6x6 Cholesky factorisation in place (a: upper triangle, row-major, becomes L^T) and solve of A y = b.  False if a pivot
-// is not positive (or not finite).
-__device__ __forceinline__ bool solve6_cholesky(double (&a)[21], const double (&b)[6], double (&y)[6])
-{
-  bool ok = true;
-#pragma unroll
-  for (int j = 0; j < 6; j++) {
-    double d = a[tri(j, j)];
-#pragma unroll
-    for (int k = 0; k < j; k++) d = fma(-a[tri(k, j)], a[tri(k, j)], d);
-    ok = ok && d > 0.0 && finite_f64(d);
-    const double ljj = sqrt(d);
-    a[tri(j, j)] = ljj;
-#pragma unroll
-    for (int i = j + 1; i < 6; i++) {
-      double t = a[tri(j, i)];
-#pragma unroll
-      for (int k = 0; k < j; k++) t = fma(-a[tri(k, i)], a[tri(k, j)], t);
-      a[tri(j, i)] = t / ljj;                   // L[i][j]
-    }
-  }
-  double z[6];
-#pragma unroll
-  for (int i = 0; i < 6; i++) {
-    double t = b[i];
-#pragma unroll
-    for (int k = 0; k < i; k++) t = fma(-a[tri(k, i)], z[k], t);
-    z[i] = t / a[tri(i, i)];
-  }
-#pragma unroll
-  for (int i = 5; i >= 0; i--) {
-    double t = z[i];
-#pragma unroll
-    for (int k = i + 1; k < 6; k++) t = fma(-a[tri(i, k)], y[k], t);
-    y[i] = t / a[tri(i, i)];
-  }
-  return ok;
-}
-
 // The serial section: wave 0, every lane with the same values, lane 0 writes.  Called behind the barrier that follows the
 // reduction of an evaluation (at x when the phase is 0, at the candidate when it is 1).  Returns through LDS: s_ctl[CTL_DONE]
 // and, when the level goes on, the pose constants of the next candidate in s_cst.  The evaluation's sums stay spread over
