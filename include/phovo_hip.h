@@ -428,7 +428,7 @@ int phovo_engine_set_slide_policy(phovo_engine *e, int policy);
  * (CPhotoconsistencyOdometryAnalytic.h:502-563); with a gradient threshold (min_gradient_norm > 0, :388) a pair leaves a
  * level after a data-dependent number of iterations, and one launch per level would make every level boundary a boundary
  * for the whole batch.  PHOVO_FUSION_AUTO (default): where two or more consecutive active levels each fit the 512-thread
- * scatter kernel with its owner map in half a CU's LDS (more than 2048 and up to about 19 700 pixels: 80x60 and 160x120 of
+ * scatter kernel with its owner map in half a CU's LDS (more than 2048 and up to 19 328 pixels: 80x60 and 160x120 of
  * a 640x480 pyramid) and at least one of them has a gradient threshold, those levels are one persistent launch in which a
  * workgroup runs a pair through all of them back to back.  PHOVO_FUSION_OFF: one launch per level, each in the geometry
  * that suits it alone (what a configuration without thresholds gets anyway).  PHOVO_FUSION_SPLIT: one launch per level in
