@@ -2,12 +2,14 @@
 // directory, writing a TUM trajectory file.
 //
 //   ./PhotoconsistencyVisualOdometry <config_file.yml> <rgbd_dataset_directory> <output_trajectory_file> [--batch [--gpus N] [--rccl]]
-//                                    [--method analytic|ceres|biobjective|affine] [--information <file>] [--system <file>]
+//                                    [--method analytic|ceres|biobjective|affine|geometric] [--information <file>] [--system <file>]
 // --method picks the aligner as the reference's USE_PHOTOCONSISTENCY_ODOMETRY_METHOD does (0 = analytic, the default;
 // 1 = ceres: Levenberg-Marquardt on bilinear samples, CPhotoconsistencyOdometryCeres, which reads config_*_ceres.yml
 // files; 2 = bi-objective: photometric and depth error together, CPhotoconsistencyOdometryBiObjective), in every mode;
 // affine is not in the reference: the photometric aligner with a per-pair gain and offset, CPhotoconsistencyOdometryAffine,
 // which reads the analytic files.
+// geometric is not in the reference either: intensity and depth rows together on the bilinear samples,
+// CPhotoconsistencyOdometryGeometric, which reads the analytic files and their optional depth_weight / max_depth_residual keys.
 // A configuration file of the other kind is refused with a message that says so.
 // --information <file> (not in the reference; analytic method, one device): one line per pair, stamped like its trajectory
 // line, with the Gauss-Newton system at the pair's optimal state on the finest level the configuration optimises --
@@ -56,6 +58,7 @@
 #include "rccl/shard_vote.h"
 #include "phovo/CPhotoconsistencyOdometryAnalytic.h"
 #include "phovo/CPhotoconsistencyOdometryAffine.h"
+#include "phovo/CPhotoconsistencyOdometryGeometric.h"
 #include "phovo/CPhotoconsistencyOdometryBiObjective.h"
 #include "phovo/CPhotoconsistencyOdometryCeres.h"
 
@@ -140,7 +143,7 @@ static bool writeSystem(std::ofstream &f, double timestamp, const phovo_sampled_
 static void printHelp()
 {
   std::cout << "./PhotoconsistencyVisualOdometry <config_file.yml> <rgbd_dataset_directory> "
-               "<output_trajectory_file> [--batch [--gpus N] [--rccl]] [--method analytic|ceres|biobjective|affine] "
+               "<output_trajectory_file> [--batch [--gpus N] [--rccl]] [--method analytic|ceres|biobjective|affine|geometric] "
                "[--information <file>] [--system <file>]" << std::endl;
 }
 
@@ -166,6 +169,7 @@ int main(int argc, char *argv[])
       else if (m == "biobjective") objective = PHOVO_OBJECTIVE_BIOBJECTIVE;
       else if (m == "ceres") objective = PHOVO_OBJECTIVE_TRUST_REGION;
       else if (m == "affine") objective = PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE;
+      else if (m == "geometric") objective = PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC;
       else { printHelp(); return EXIT_FAILURE; }
     }
     else if (a == "--rccl") rccl = true;
@@ -298,6 +302,9 @@ int main(int argc, char *argv[])
       } else if (objective == PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE) {
         phovo::Analytic::CPhotoconsistencyOdometryAffine<PixelType, CoordinateType> odometry;
         if (runLoop(odometry) != EXIT_SUCCESS) return EXIT_FAILURE;
+      } else if (objective == PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC) {
+        phovo::Analytic::CPhotoconsistencyOdometryGeometric<PixelType, CoordinateType> odometry;
+        if (runLoop(odometry) != EXIT_SUCCESS) return EXIT_FAILURE;
       } else {
         phovo::Analytic::CPhotoconsistencyOdometryAnalytic<PixelType, CoordinateType> odometry;
         if (runLoop(odometry) != EXIT_SUCCESS) return EXIT_FAILURE;
@@ -309,6 +316,10 @@ int main(int argc, char *argv[])
         PHOVO_OK_OR_FAIL(phovo_trust_region_read_file(configFile.c_str(), &cfg, &trOptions));
       else
         PHOVO_OK_OR_FAIL(phovo_config_read_file(configFile.c_str(), &cfg));
+      phovo_geometric_options geoOptions;             // --method geometric: the two optional keys of the file
+      PHOVO_OK_OR_FAIL(phovo_geometric_options_default(&geoOptions));
+      if (objective == PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC)
+        PHOVO_OK_OR_FAIL(phovo_geometric_read_file(configFile.c_str(), &geoOptions));
       const int nDevices = phovo_device_count();
       if (nDevices < 1) { std::cerr << "phovo_engine_create: no HIP device available: this library has no CPU path" << std::endl; return EXIT_FAILURE; }
       // PHOVO_VO_SHARE_DEVICES=1 lets more shards than devices run (a rehearsal of --gpus N on a smaller machine)
@@ -413,6 +424,8 @@ int main(int argc, char *argv[])
           if (phovo_engine_set_objective(engine, objective) != PHOVO_OK) return fail("phovo_engine_set_objective");
           if (objective == PHOVO_OBJECTIVE_PHOTOMETRIC && phovo_engine_set_extensions(engine, &extensions) != PHOVO_OK)
             return fail("phovo_engine_set_extensions");
+          if (objective == PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC && phovo_engine_set_geometric_options(engine, &geoOptions) != PHOVO_OK)
+            return fail("phovo_engine_set_geometric_options");
           if (objective == PHOVO_OBJECTIVE_TRUST_REGION && phovo_engine_set_trust_region_options(engine, &trOptions) != PHOVO_OK)
             return fail("phovo_engine_set_trust_region_options");
           // a pair's pose must not depend on the size of the shard it falls into (same trajectory file for every N)

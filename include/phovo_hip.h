@@ -222,6 +222,48 @@ typedef struct phovo_extensions {
  *                                = rows of the level's last iteration, PHOVO_PAIR_RANK_DEFICIENT when fewer than 8 rows
  *                                were filled in some iteration, PHOVO_PAIR_NONFINITE as under the photometric objective. */
 #define PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE 3
+/*   PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC  not in the reference: intensity and depth together on the bilinear rows (6 entries
+ *                                per pair, the pose; DESIGN.md §16 has the contract).  The photometric rows are those of the
+ *                                affine-illumination objective at alpha = beta = 0: r_I = I1(u, v) - I0 on every source pixel
+ *                                that passes the depth gate and whose nearest target pixel is inside the image, bilinear
+ *                                samples on clamped taps, the true warp Jacobian.  Such a pixel adds a depth row
+ *                                r_D = sigma_L (D1(u, v) - Z') iff the four taps of the TARGET's depth all pass
+ *                                min_depth < d < max_depth (NaN fails) and, with max_depth_residual[L] > 0,
+ *                                |D1(u, v) - Z'| <= max_depth_residual[L]; Z' is the third coordinate of the moved point,
+ *                                D1(u, v) the bilinear sample with the intensity's taps and weights, and
+ *                                J_D = sigma_L (dgx dU/dp + dgy dV/dp - dZ'/dp) with (dgx, dgy) the exact derivative of
+ *                                that interpolant (at an integer u or v the cell towards +u / +v: floor).  H = sum J_I
+ *                                J_I^T + sum J_D J_D^T, g likewise; the level loop is the
+ *                                bilinear extension's.  sigma_L and the residual limit are phovo_geometric_options.
+ *                                The target's depth on level L is the depth plane a SOURCE upload of that frame leaves
+ *                                there (what phovo_engine_get_level_planes returns as depth): target frames need
+ *                                PHOVO_ROLE_BOTH, and an enqueue whose target lacks the source role on an active level is
+ *                                PHOVO_E_NOT_READY.  No new planes: switching between objectives 0, 2, 3 and 4 keeps the
+ *                                frame pool.  Supported: fp64 planes, the default sampling setting, no Huber weights,
+ *                                jacobian_corrected 0 -- anything else is PHOVO_E_UNSUPPORTED, whichever setter comes
+ *                                second; both evaluate calls are PHOVO_E_UNSUPPORTED too.  Fusion, sliding-window, wide,
+ *                                latency-form and batch-invariant settings are accepted and have no effect.
+ *                                phovo_pair_report: valid_pixels[L] = photometric rows of the level's last iteration,
+ *                                PHOVO_PAIR_RANK_DEFICIENT when fewer than 6 photometric rows were filled in some iteration,
+ *                                PHOVO_PAIR_NONFINITE as under the photometric objective, gradient_norm = ||g||_2 of the
+ *                                last system.  Depth rows and the two costs: phovo_geometric_report. */
+#define PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC 4
+
+/* Options of the photometric-geometric objective, per level.  Both are settings to tune for the sensor and the scene, not
+ * measured optima: depth_weight trades metres of depth error against intensity error (intensities are in [0, 1]), and
+ * max_depth_residual is the occlusion gate -- without one, depth rows across a depth discontinuity pull the pose away
+ * (DESIGN.md §16). */
+typedef struct phovo_geometric_options {
+  double depth_weight[PHOVO_MAX_LEVELS];        /* sigma_L: finite and > 0.  yml: "depth_weight (at each level)"          */
+  double max_depth_residual[PHOVO_MAX_LEVELS];  /* metres; <= 0 switches the gate off.  yml: "max_depth_residual (at each level)" */
+} phovo_geometric_options;
+
+/* Per pair and level, from the level's LAST system (levels with max_num_iterations 0 stay 0). */
+typedef struct phovo_geometric_report {
+  int32_t depth_rows[PHOVO_MAX_LEVELS];         /* depth rows (phovo_pair_report.valid_pixels has the photometric rows) */
+  double  photometric_cost[PHOVO_MAX_LEVELS];   /* sum r_I^2 */
+  double  depth_cost[PHOVO_MAX_LEVELS];         /* sum r_D^2 (sigma_L included) */
+} phovo_geometric_report;
 
 /* Solver options of the trust-region objective, per level (CPhotoconsistencyOdometryCeres.h:526-576).  num_levels, blur,
  * gradient scale and max_num_iterations stay in phovo_config. */
@@ -287,6 +329,15 @@ int phovo_trust_region_read_file(const char *path, phovo_config *cfg, phovo_trus
  * min_relative_decrease 1e-3. */
 int phovo_trust_region_options_default(phovo_trust_region_options *opt);
 
+/* Photometric-geometric objective: depth_weight 1.0 and max_depth_residual 0.1 m on every level (starting points, not
+ * measured optima). */
+int phovo_geometric_options_default(phovo_geometric_options *opt);
+/* The two optional keys of an ANALYTIC yml file, "depth_weight (at each level): [..]" and "max_depth_residual (at each
+ * level): [..]" (the reference's loader ignores keys it does not ask for, as it does the extension keys).  An absent key
+ * leaves the defaults; a list shorter than the file's numOptimizationLevels (where the file has that key), a malformed one
+ * or a weight that is not finite and > 0 is PHOVO_E_CONFIG.  The rest of the file is not read: phovo_config_read_file. */
+int phovo_geometric_read_file(const char *path, phovo_geometric_options *opt);
+
 int phovo_extensions_default(phovo_extensions *ext);
 /* Optional keys in the same yml file (the reference's cv::FileStorage lookups ignore keys they do not ask for,
  * so such a file still loads there): "huber_delta (at each level): [..]", "plane_storage_bits: 64|32|16",
@@ -350,6 +401,14 @@ int phovo_odometry_get_trust_region_report(const phovo_odometry *o, phovo_trust_
 /* Affine-illumination objective: (alpha, beta) of the last Optimize() (PHOVO_E_NOT_READY before a successful one;
  * PHOVO_E_UNSUPPORTED under another objective).  The target's intensities are modelled as (1 + alpha) I0 + beta. */
 int phovo_odometry_get_illumination(const phovo_odometry *o, double alpha_beta[2]);
+/* Photometric-geometric objective: its options (defaults: phovo_geometric_options_default; kept under every objective,
+ * used by this one; a weight that is not finite and > 0 is PHOVO_E_INVALID_ARGUMENT) and the record of the last Optimize()
+ * (PHOVO_E_NOT_READY before a successful one; PHOVO_E_UNSUPPORTED under another objective).  Under this objective
+ * phovo_odometry_set_target_frame needs depth (NULL: PHOVO_E_INVALID_ARGUMENT) and uploads the target with both roles, and
+ * phovo_odometry_read_configuration_file reads the two optional keys as well (phovo_geometric_read_file). */
+int phovo_odometry_set_geometric_options(phovo_odometry *o, const phovo_geometric_options *opt);
+int phovo_odometry_get_geometric_options(const phovo_odometry *o, phovo_geometric_options *opt);
+int phovo_odometry_get_geometric_report(const phovo_odometry *o, phovo_geometric_report *report);
 int phovo_odometry_set_min_depth(phovo_odometry *o, double min_depth);     /* :448 */
 int phovo_odometry_set_max_depth(phovo_odometry *o, double max_depth);     /* :454 */
 int phovo_odometry_set_intrinsic_matrix(phovo_odometry *o, const double k[9]);     /* :460, row-major 3x3 */
@@ -467,6 +526,12 @@ int phovo_engine_fetch_trust_region_reports(phovo_engine *e, int n_pairs, phovo_
 /* Affine-illumination objective: (alpha, beta) of every pair of the LAST enqueue (n_pairs must be that enqueue's;
  * PHOVO_E_NOT_READY before any enqueue, PHOVO_E_UNSUPPORTED if the last one ran under another objective). */
 int phovo_engine_fetch_illumination(phovo_engine *e, int n_pairs, double *alpha_beta /* [n_pairs][2] */);
+/* Photometric-geometric objective: options (kept under every objective, used by this one; every depth_weight must be finite
+ * and > 0, else PHOVO_E_INVALID_ARGUMENT; a max_depth_residual <= 0 switches that level's gate off) and the per-pair records
+ * of the LAST enqueue, with the call-order rules of phovo_engine_fetch_illumination. */
+int phovo_engine_set_geometric_options(phovo_engine *e, const phovo_geometric_options *opt);
+int phovo_engine_get_geometric_options(const phovo_engine *e, phovo_geometric_options *opt);
+int phovo_engine_fetch_geometric_reports(phovo_engine *e, int n_pairs, phovo_geometric_report *reports);
 
 /* Page-locks (and releases) a host buffer the caller will hand to the upload entry points repeatedly: uploads from
  * registered memory are direct DMA at the link rate instead of going through the runtime's bounce buffers.  Optional;
@@ -695,7 +760,8 @@ enum { PHOVO_LAUNCH_PERSISTENT = 0,       /* gn_level_kernel: one level, one wor
        PHOVO_LAUNCH_BILINEAR = 5,         /* gn_level_kernel_bilinear (extension) */
        PHOVO_LAUNCH_BIOBJECTIVE = 6,      /* gn_level_kernel_biobjective (PHOVO_OBJECTIVE_BIOBJECTIVE) */
        PHOVO_LAUNCH_TRUST_REGION = 7,     /* gn_level_kernel_trust_region (PHOVO_OBJECTIVE_TRUST_REGION) */
-       PHOVO_LAUNCH_AFFINE = 8 };         /* gn_level_kernel_affine (PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE) */
+       PHOVO_LAUNCH_AFFINE = 8,           /* gn_level_kernel_affine (PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE) */
+       PHOVO_LAUNCH_GEOMETRIC = 9 };      /* gn_level_kernel_geometric (PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC) */
 typedef struct phovo_launch_record {
   int level_first, level_last;            /* pyramid levels the launch covers (level_first >= level_last) */
   int kind;                               /* PHOVO_LAUNCH_* */

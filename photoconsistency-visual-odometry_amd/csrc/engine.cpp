@@ -100,6 +100,9 @@ struct AlignSlot {
   double *d_illum = nullptr;                   // affine-illumination objective: (alpha, beta) of the enqueue's pairs, [pairs][2]
   int illum_capacity = 0;
   bool affine_ran = false;                     // the enqueue ran under PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE
+  phovo_geometric_report *d_geo_reports = nullptr;     // photometric-geometric objective: the records of the enqueue's pairs
+  int geo_capacity = 0;
+  bool geometric_ran = false;                  // the enqueue ran under PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC
   int num_levels = 0;                          // the configuration the enqueue ran under: its levels, and which of them it
   bool level_skipped[PHOVO_MAX_LEVELS] = {};   // skipped (max_num_iterations == 0) -- a fetch may come after a set_config
 };
@@ -145,6 +148,7 @@ struct phovo_engine {
   bool batch_invariant = false;                // every batch takes the same kernels and geometries (phovo_engine_set_batch_invariant)
   int objective = PHOVO_OBJECTIVE_PHOTOMETRIC;  // phovo_engine_set_objective
   phovo_trust_region_options tr_opt{};         // phovo_engine_set_trust_region_options (Ceres's defaults at creation)
+  phovo_geometric_options geo_opt{};           // phovo_engine_set_geometric_options (phovo_geometric_options_default at creation)
   bool latency_forms = false;                  // a handful of pairs may take the forms that finish soonest also where a level has a one-workgroup form with its owner map in LDS (phovo_engine_set_latency_forms)
   std::vector<unsigned char> frame_roles;      // [frame][PHOVO_MAX_LEVELS]: PHOVO_ROLE_* each level of each frame has been given since the
                                                // pool was reserved (an upload: every level; a plane write: its level)
@@ -200,6 +204,8 @@ void free_slot(AlignSlot &s)
   s.d_tr_reports = nullptr; s.tr_capacity = 0;
   if (s.d_illum) (void)hipFree(s.d_illum);
   s.d_illum = nullptr; s.illum_capacity = 0;
+  if (s.d_geo_reports) (void)hipFree(s.d_geo_reports);
+  s.d_geo_reports = nullptr; s.geo_capacity = 0;
   s.d_owner = nullptr; s.owner_capacity = 0; s.d_wide_ws = nullptr; s.wide_ws_capacity = 0;
   s.d_mask = nullptr; s.mask_capacity = 0;
 }
@@ -270,6 +276,8 @@ bool biobjective_supports(const phovo_extensions &x)
 bool trust_region_supports(const phovo_extensions &x) { return biobjective_supports(x); }
 // The affine-illumination objective likewise: its rows are fixed by the objective, not chosen by the extensions.
 bool affine_supports(const phovo_extensions &x) { return biobjective_supports(x); }
+// The photometric-geometric objective likewise.
+bool geometric_supports(const phovo_extensions &x) { return biobjective_supports(x); }
 
 // Depth gradients (with the max depth in force) and gain of `count` consecutive target frames of level l, from the
 // intensity and depth planes already in the pool (fp64, packed: the frame is frame_bytes / 8 doubles).
@@ -539,6 +547,7 @@ int phovo_engine_create(int device, phovo_engine **out)
   phovo_config_default(&e->cfg);
   phovo_extensions_default(&e->ext);
   phovo_trust_region_options_default(&e->tr_opt);
+  phovo_geometric_options_default(&e->geo_opt);
   hipError_t he = hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking);
   if (he == hipSuccess) he = hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking);
   for (int i = 0; i < 2 && he == hipSuccess; i++) {
@@ -657,6 +666,9 @@ int phovo_engine_set_extensions(phovo_engine *e, const phovo_extensions *ext)
   if (e->objective == PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE && !affine_supports(*ext))
     return fail(PHOVO_E_UNSUPPORTED, "set_extensions: the affine-illumination objective runs on fp64 planes with the default "
                                      "sampling setting, no Huber weights and jacobian_corrected 0 only");
+  if (e->objective == PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC && !geometric_supports(*ext))
+    return fail(PHOVO_E_UNSUPPORTED, "set_extensions: the photometric-geometric objective runs on fp64 planes with the default "
+                                     "sampling setting, no Huber weights and jacobian_corrected 0 only");
   // the pool layout changes with the storage type, and -- fp16 planes under bilinear sampling carry tap records -- with the
   // sampling where that adds or removes the records
   auto has_records = [](const phovo_extensions &x) { return x.sampling == PHOVO_SAMPLING_BILINEAR && x.plane_storage == PHOVO_STORAGE_F16; };
@@ -674,8 +686,12 @@ int phovo_engine_set_objective(phovo_engine *e, int objective)
 {
   if (!e) return fail(PHOVO_E_INVALID_ARGUMENT, "set_objective: null");
   if (objective != PHOVO_OBJECTIVE_PHOTOMETRIC && objective != PHOVO_OBJECTIVE_BIOBJECTIVE &&
-      objective != PHOVO_OBJECTIVE_TRUST_REGION && objective != PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE)
+      objective != PHOVO_OBJECTIVE_TRUST_REGION && objective != PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE &&
+      objective != PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC)
     return fail(PHOVO_E_INVALID_ARGUMENT, "set_objective: unknown objective");
+  if (objective == PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC && !geometric_supports(e->ext))
+    return fail(PHOVO_E_UNSUPPORTED, "set_objective: the photometric-geometric objective runs on fp64 planes with the default "
+                                     "sampling setting, no Huber weights and jacobian_corrected 0 only");
   if (objective == PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE && !affine_supports(e->ext))
     return fail(PHOVO_E_UNSUPPORTED, "set_objective: the affine-illumination objective runs on fp64 planes with the default "
                                      "sampling setting, no Huber weights and jacobian_corrected 0 only");
@@ -685,7 +701,8 @@ int phovo_engine_set_objective(phovo_engine *e, int objective)
   if (objective == PHOVO_OBJECTIVE_TRUST_REGION && !trust_region_supports(e->ext))
     return fail(PHOVO_E_UNSUPPORTED, "set_objective: the trust-region objective runs on fp64 planes with the default "
                                      "sampling, no Huber weights and jacobian_corrected 0 only");
-  // The photometric, trust-region and affine-illumination objectives share the frame layout: a switch between them keeps the pool.
+  // The photometric, trust-region, affine-illumination and photometric-geometric objectives share the frame layout: a switch
+  // between them keeps the pool.
   auto bi = [](int o) { return o == PHOVO_OBJECTIVE_BIOBJECTIVE; };
   if (objective != e->objective && (bi(objective) || bi(e->objective))) {   // the pool layout changes (the bi-objective's target planes): dropped
     (void)hipSetDevice(e->device);
@@ -729,6 +746,25 @@ int phovo_engine_get_trust_region_options(const phovo_engine *e, phovo_trust_reg
 {
   if (!e || !opt) return fail(PHOVO_E_INVALID_ARGUMENT, "get_trust_region_options: null");
   *opt = e->tr_opt;
+  return PHOVO_OK;
+}
+
+int phovo_geometric_read_file(const char *path, phovo_geometric_options *opt) { return read_geometric_file(path, opt); }
+
+int phovo_engine_set_geometric_options(phovo_engine *e, const phovo_geometric_options *opt)
+{
+  if (!e || !opt) return fail(PHOVO_E_INVALID_ARGUMENT, "set_geometric_options: null");
+  for (int l = 0; l < PHOVO_MAX_LEVELS; l++)
+    if (!(opt->depth_weight[l] > 0.0 && std::isfinite(opt->depth_weight[l])))
+      return fail(PHOVO_E_INVALID_ARGUMENT, "set_geometric_options: every depth_weight must be finite and > 0");
+  e->geo_opt = *opt;
+  return PHOVO_OK;
+}
+
+int phovo_engine_get_geometric_options(const phovo_engine *e, phovo_geometric_options *opt)
+{
+  if (!e || !opt) return fail(PHOVO_E_INVALID_ARGUMENT, "get_geometric_options: null");
+  *opt = e->geo_opt;
   return PHOVO_OK;
 }
 
@@ -1373,6 +1409,13 @@ int phovo_engine_enqueue_align(phovo_engine *e, int n_pairs, const int *source_f
       continue;
     }
     if (e->objective == PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE) continue;       // no owner map, no LDS limit
+    if (e->objective == PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC) {            // likewise; the target's depth is a source upload's
+      for (int i = 0; i < n_pairs; i++)
+        if (!(e->frame_roles[(size_t)target_frames[i] * PHOVO_MAX_LEVELS + (size_t)l] & PHOVO_ROLE_SOURCE))
+          return fail(PHOVO_E_NOT_READY, "align: the photometric-geometric objective reads the target's depth (upload target "
+                                         "frames with PHOVO_ROLE_BOTH)");
+      continue;
+    }
     if (e->ext.sampling == PHOVO_SAMPLING_BILINEAR) continue;       // no owner map, no LDS limit
     const bool wide = use_wide_level(e, n_pairs, lv) && !(e->ext.huber_delta[l] > 0.0);
     if (wide) {
@@ -1408,6 +1451,7 @@ int phovo_engine_enqueue_align(phovo_engine *e, int n_pairs, const int *source_f
   s.d_states = nullptr;
   s.tr_ran = e->objective == PHOVO_OBJECTIVE_TRUST_REGION;
   s.affine_ran = e->objective == PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE;
+  s.geometric_ran = e->objective == PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC;
   s.num_levels = e->cfg.num_levels;
   for (int l = 0; l < PHOVO_MAX_LEVELS; l++) s.level_skipped[l] = l < e->cfg.num_levels && e->cfg.max_num_iterations[l] <= 0;
   if (n_pairs == 0) {                    // nothing to run: a valid, empty enqueue (fetch of 0 pairs succeeds, no device buffer)
@@ -1470,6 +1514,11 @@ int phovo_engine_enqueue_align(phovo_engine *e, int n_pairs, const int *source_f
     PHOVO_HIP_CHECK(hipMalloc(&s.d_illum, sizeof(double) * 2 * (size_t)n_pairs));
     s.illum_capacity = n_pairs;
   }
+  if (s.geometric_ran && n_pairs > s.geo_capacity) {
+    if (s.d_geo_reports) { (void)hipFree(s.d_geo_reports); s.d_geo_reports = nullptr; s.geo_capacity = 0; }
+    PHOVO_HIP_CHECK(hipMalloc(&s.d_geo_reports, sizeof(phovo_geometric_report) * (size_t)n_pairs));
+    s.geo_capacity = n_pairs;
+  }
   // The caller may reuse its arrays as soon as this returns and the copies below are asynchronous: the slot's pinned
   // mirror keeps them alive until the slot is used again (synchronised above).
   const PairLayout pl = pair_layout(n_pairs);
@@ -1491,6 +1540,8 @@ int phovo_engine_enqueue_align(phovo_engine *e, int n_pairs, const int *source_f
     PHOVO_HIP_CHECK(hipMemsetAsync(s.d_tr_reports, 0, sizeof(phovo_trust_region_report) * (size_t)n_pairs, s.stream));
   if (s.affine_ran)      // every pair starts at alpha = beta = 0
     PHOVO_HIP_CHECK(hipMemsetAsync(s.d_illum, 0, sizeof(double) * 2 * (size_t)n_pairs, s.stream));
+  if (s.geometric_ran)   // (every level the configuration skips stays 0)
+    PHOVO_HIP_CHECK(hipMemsetAsync(s.d_geo_reports, 0, sizeof(phovo_geometric_report) * (size_t)n_pairs, s.stream));
   PHOVO_HIP_CHECK(hipEventRecord(s.ev_total_start, s.stream));
 
   const PairLayout lay = pair_layout(n_pairs);
@@ -1618,6 +1669,14 @@ int phovo_engine_enqueue_align(phovo_engine *e, int n_pairs, const int *source_f
       b.illum = s.d_illum;
       PHOVO_HIP_CHECK(gn_launch_level_affine(b, e->cu_count, s.stream));
       record(l, l, PHOVO_LAUNCH_AFFINE, 256, gn_affine_lds_bytes(), persistent_grid(gn_affine_wgs_per_cu()));
+    } else if (e->objective == PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC) {
+      GNGeometricArgs b{};
+      b.lv = a;
+      b.depth_weight = e->geo_opt.depth_weight[l];
+      b.max_depth_residual = e->geo_opt.max_depth_residual[l];
+      b.geo_reports = s.d_geo_reports;
+      PHOVO_HIP_CHECK(gn_launch_level_geometric(b, e->cu_count, s.stream));
+      record(l, l, PHOVO_LAUNCH_GEOMETRIC, 256, gn_geometric_lds_bytes(), persistent_grid(gn_geometric_wgs_per_cu()));
     } else if (e->ext.sampling == PHOVO_SAMPLING_BILINEAR) {
       PHOVO_HIP_CHECK(gn_launch_level_bilinear(a, e->ext.plane_storage, e->ext.jacobian_corrected != 0, e->cu_count, s.stream));
       record(l, l, PHOVO_LAUNCH_BILINEAR, 256, 0, persistent_grid(gn_bilinear_wgs_per_cu(e->ext.plane_storage)));
@@ -1764,6 +1823,21 @@ int phovo_engine_fetch_illumination(phovo_engine *e, int n_pairs, double *alpha_
   return PHOVO_OK;
 }
 
+int phovo_engine_fetch_geometric_reports(phovo_engine *e, int n_pairs, phovo_geometric_report *reports)
+{
+  if (!e) return fail(PHOVO_E_INVALID_ARGUMENT, "fetch_geometric_reports: null");
+  AlignSlot *s = slot_of(e, e->ticket);
+  if (!s) return fail(PHOVO_E_NOT_READY, "fetch_geometric_reports: nothing has been enqueued");
+  if (!s->geometric_ran) return fail(PHOVO_E_UNSUPPORTED, "fetch_geometric_reports: the last enqueue ran under another objective");
+  if (n_pairs != s->last_pairs) return fail(PHOVO_E_INVALID_ARGUMENT, "fetch_geometric_reports: n_pairs differs from that enqueue's");
+  if (n_pairs == 0) return PHOVO_OK;
+  if (!reports) return fail(PHOVO_E_INVALID_ARGUMENT, "fetch_geometric_reports: null");
+  PHOVO_HIP_CHECK(hipSetDevice(e->device));
+  PHOVO_HIP_CHECK(hipStreamSynchronize(s->stream));
+  PHOVO_HIP_CHECK(hipMemcpy(reports, s->d_geo_reports, sizeof(phovo_geometric_report) * (size_t)n_pairs, hipMemcpyDeviceToHost));
+  return PHOVO_OK;
+}
+
 int phovo_engine_fetch_results(phovo_engine *e, int n_pairs, double *out_states, phovo_pair_report *reports)
 {
   if (!e) return fail(PHOVO_E_INVALID_ARGUMENT, "fetch_results: null");
@@ -1901,6 +1975,8 @@ int phovo_engine_evaluate_sampled_pairs(phovo_engine *e, int n_pairs, const int 
   if (e->objective == PHOVO_OBJECTIVE_BIOBJECTIVE || e->objective == PHOVO_OBJECTIVE_TRUST_REGION)
     return fail(PHOVO_E_UNSUPPORTED, "evaluate_sampled_pairs: the bi-objective and the trust-region objective have no sampled "
                                      "system (bilinear sampling or the affine-illumination objective only)");
+  if (e->objective == PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC)
+    return fail(PHOVO_E_UNSUPPORTED, "evaluate_sampled_pairs: the photometric-geometric objective has no sampled system");
   const bool affine = e->objective == PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE;
   if (!affine && e->ext.sampling != PHOVO_SAMPLING_BILINEAR)
     return fail(PHOVO_E_UNSUPPORTED, "evaluate_sampled_pairs: nearest / scatter sampling has its system in "
@@ -2045,6 +2121,8 @@ struct phovo_odometry {
   bool have_tr_report = false;
   double illumination[2] = {0, 0};               // affine-illumination objective: (alpha, beta) of the last Optimize()
   bool have_illumination = false;
+  phovo_geometric_report geo_report{};           // photometric-geometric objective: the record of the last Optimize()
+  bool have_geo_report = false;
 };
 
 namespace {
@@ -2152,6 +2230,18 @@ int phovo_odometry_get_trust_region_options(const phovo_odometry *o, phovo_trust
   return phovo_engine_get_trust_region_options(o->engine, opt);
 }
 
+int phovo_odometry_set_geometric_options(phovo_odometry *o, const phovo_geometric_options *opt)
+{
+  if (!o) return fail(PHOVO_E_INVALID_ARGUMENT, "set_geometric_options: null");
+  return phovo_engine_set_geometric_options(o->engine, opt);
+}
+
+int phovo_odometry_get_geometric_options(const phovo_odometry *o, phovo_geometric_options *opt)
+{
+  if (!o) return fail(PHOVO_E_INVALID_ARGUMENT, "get_geometric_options: null");
+  return phovo_engine_get_geometric_options(o->engine, opt);
+}
+
 int phovo_odometry_set_latency_forms(phovo_odometry *o, int on)
 {
   if (!o) return fail(PHOVO_E_INVALID_ARGUMENT, "set_latency_forms: null");
@@ -2172,6 +2262,13 @@ int phovo_odometry_read_configuration_file(phovo_odometry *o, const char *path)
   }
   int st = read_config_file(path, &c);
   if (st != PHOVO_OK) return st;
+  if (o->engine->objective == PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC) {      // its two optional keys; absent: the defaults
+    phovo_geometric_options g;
+    st = read_geometric_file(path, &g);
+    if (st != PHOVO_OK) return st;
+    st = phovo_engine_set_geometric_options(o->engine, &g);
+    if (st != PHOVO_OK) return st;
+  }
   phovo_extensions x;                        // optional keys; a reference yml has none -> everything stays off
   st = read_extensions_file(path, &x);
   if (st != PHOVO_OK) return st;
@@ -2214,6 +2311,10 @@ int phovo_odometry_set_target_frame(phovo_odometry *o, const uint8_t *intensity,
     if (!depth) return fail(PHOVO_E_INVALID_ARGUMENT, "SetTargetFrame: the bi-objective needs the target's depth");
     return odometry_set_frame(o, 1, PHOVO_ROLE_TARGET, intensity, istride, depth, dstride, width, height);
   }
+  if (o && o->engine->objective == PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC) {      // the target's depth plane is a source upload's
+    if (!depth) return fail(PHOVO_E_INVALID_ARGUMENT, "SetTargetFrame: the photometric-geometric objective needs the target's depth");
+    return odometry_set_frame(o, 1, PHOVO_ROLE_BOTH, intensity, istride, depth, dstride, width, height);
+  }
   (void)depth; (void)dstride;                      // "Depth image is ignored"  :478
   return odometry_set_frame(o, 1, PHOVO_ROLE_TARGET, intensity, istride, nullptr, 0, width, height);
 }
@@ -2233,6 +2334,10 @@ int phovo_odometry_set_target_frame_device(phovo_odometry *o, const phovo_device
   if (o && o->engine->objective == PHOVO_OBJECTIVE_BIOBJECTIVE) {       // the target keeps its depth
     if (!depth) return fail(PHOVO_E_INVALID_ARGUMENT, "SetTargetFrameDevice: the bi-objective needs the target's depth");
     return odometry_set_frame_device(o, 1, PHOVO_ROLE_TARGET, intensity, depth, depth_scale, width, height, stream);
+  }
+  if (o && o->engine->objective == PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC) {
+    if (!depth) return fail(PHOVO_E_INVALID_ARGUMENT, "SetTargetFrameDevice: the photometric-geometric objective needs the target's depth");
+    return odometry_set_frame_device(o, 1, PHOVO_ROLE_BOTH, intensity, depth, depth_scale, width, height, stream);
   }
   // "Depth image is ignored"  :478
   return odometry_set_frame_device(o, 1, PHOVO_ROLE_TARGET, intensity, nullptr, 1.0, width, height, stream);
@@ -2332,6 +2437,7 @@ static int optimize_visualized(phovo_odometry *o, const char *dir)
   if (st != PHOVO_OK) return st;
   o->report = total;
   o->have_illumination = false;
+  o->have_geo_report = false;
   o->optimized = true;
   return PHOVO_OK;
 }
@@ -2342,7 +2448,9 @@ int phovo_odometry_optimize(phovo_odometry *o)
   if (!o->have_source || !o->have_target)
     return fail(PHOVO_E_NOT_READY, "Optimize: SetSourceFrame and SetTargetFrame must be called first");
   // (the affine-illumination objective carries alpha and beta inside an enqueue only: no one-iteration-per-launch form)
-  if (o->engine->cfg.visualize_iterations && o->engine->objective != PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE) {
+  // (the photometric-geometric objective's per-level record belongs to one enqueue: likewise)
+  if (o->engine->cfg.visualize_iterations && o->engine->objective != PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE &&
+      o->engine->objective != PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC) {
     const char *dir = std::getenv("PHOVO_VISUALIZE_DIR");
     if (dir && *dir) return optimize_visualized(o, dir);
   }
@@ -2360,7 +2468,21 @@ int phovo_odometry_optimize(phovo_odometry *o)
     st = phovo_engine_fetch_illumination(o->engine, 1, o->illumination);
     if (st != PHOVO_OK) return st;
   }
+  o->have_geo_report = o->engine->objective == PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC;
+  if (o->have_geo_report) {
+    st = phovo_engine_fetch_geometric_reports(o->engine, 1, &o->geo_report);
+    if (st != PHOVO_OK) return st;
+  }
   o->optimized = true;
+  return PHOVO_OK;
+}
+
+int phovo_odometry_get_geometric_report(const phovo_odometry *o, phovo_geometric_report *report)
+{
+  if (!o || !report) return fail(PHOVO_E_INVALID_ARGUMENT, "get_geometric_report: null");
+  if (!o->optimized) return fail(PHOVO_E_NOT_READY, "get_geometric_report: Optimize has not run");
+  if (!o->have_geo_report) return fail(PHOVO_E_UNSUPPORTED, "get_geometric_report: the last Optimize ran under another objective");
+  *report = o->geo_report;
   return PHOVO_OK;
 }
 

@@ -185,6 +185,18 @@ struct GNAffineArgs {
 int gn_affine_wgs_per_cu();          // workgroups of the kernel that stay resident per CU
 int gn_affine_lds_bytes();
 hipError_t gn_launch_level_affine(const GNAffineArgs &args, int cu_count, hipStream_t stream);
+// Photometric-geometric form (gn_geometric_kernel.hip, PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC): fp64 planes, the photometric
+// objective's frames; the affine form's rows at alpha = beta = 0 and, per row, a depth row on the target's depth plane (the
+// one a source upload of the target frame left in the pool).  No owner map, any level size, 256 threads.
+struct GNGeometricArgs {
+  GNLevelArgs lv;                    // (huber_delta and rec_off unused)
+  double depth_weight;               // sigma_L (> 0)
+  double max_depth_residual;         // the residual gate of the level; <= 0: off
+  phovo_geometric_report *geo_reports;   // [pairs], zeroed before the first level
+};
+int gn_geometric_wgs_per_cu();       // workgroups of the kernel that stay resident per CU
+int gn_geometric_lds_bytes();
+hipError_t gn_launch_level_geometric(const GNGeometricArgs &args, int cu_count, hipStream_t stream);
 // Sliding-window form for levels whose owner map exceeds LDS (gn_slide_kernel.hip): owner ring in LDS; pairs whose
 // motion leaves the window are appended to args.handover_out for a follow-up gn_launch_level that takes that list.
 hipError_t gn_prepare_slide_kernels();
@@ -249,5 +261,6 @@ int fail(int status, const std::string &msg);
 int read_config_file(const char *path, phovo_config *cfg);
 int read_extensions_file(const char *path, phovo_extensions *ext);
 int read_trust_region_file(const char *path, phovo_config *cfg, phovo_trust_region_options *opt);
+int read_geometric_file(const char *path, phovo_geometric_options *opt);
 
 }  // namespace phovo_hip

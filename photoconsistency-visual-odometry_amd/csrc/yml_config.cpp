@@ -204,7 +204,50 @@ int read_extensions_file(const char *path, phovo_extensions *ext)
   return PHOVO_OK;
 }
 
+// The photometric-geometric objective's two optional keys in an analytic file.  Everything else in the file is ignored here
+// (read_config_file reads it), except numOptimizationLevels, which says how many entries a list must have.
+int read_geometric_file(const char *path, phovo_geometric_options *opt)
+{
+  if (!path || !opt) return fail(PHOVO_E_INVALID_ARGUMENT, "read_geometric_file: null argument");
+  std::map<std::string, std::string> kv;
+  const int rst = read_key_values(path, kv);
+  if (rst != PHOVO_OK) return rst;
+  phovo_geometric_options o;
+  phovo_geometric_options_default(&o);
+  int levels = 0;
+  std::vector<double> v;
+  auto nl = kv.find("numOptimizationLevels");
+  if (nl != kv.end() && parse_values(nl->second, &v) && v.size() == 1 && v[0] >= 1 && v[0] <= PHOVO_MAX_LEVELS) levels = to_int(v[0]);
+  struct DblKey { const char *key; double *dst; bool positive; };
+  const DblKey keys[] = {{"depth_weight (at each level)", o.depth_weight, true},
+                         {"max_depth_residual (at each level)", o.max_depth_residual, false}};
+  for (const DblKey &k : keys) {
+    auto it = kv.find(k.key);
+    if (it == kv.end()) continue;
+    if (!parse_values(it->second, &v)) return fail(PHOVO_E_CONFIG, std::string("configuration key malformed: '") + k.key + "'");
+    if ((int)v.size() < levels)
+      return fail(PHOVO_E_CONFIG, std::string("'") + k.key + "' has fewer entries than numOptimizationLevels");
+    for (int i = 0; i < PHOVO_MAX_LEVELS && i < (int)v.size(); i++) {
+      if (k.positive && !(v[i] > 0.0 && std::isfinite(v[i])))
+        return fail(PHOVO_E_CONFIG, std::string("'") + k.key + "': every entry must be finite and > 0");
+      k.dst[i] = v[i];
+    }
+  }
+  *opt = o;
+  return PHOVO_OK;
+}
+
 }  // namespace phovo_hip
+
+extern "C" int phovo_geometric_options_default(phovo_geometric_options *opt)
+{
+  if (!opt) return phovo_hip::fail(PHOVO_E_INVALID_ARGUMENT, "geometric_options_default: null");
+  for (int l = 0; l < PHOVO_MAX_LEVELS; l++) {          // starting points, not measured optima (include/phovo_hip.h)
+    opt->depth_weight[l] = 1.0;
+    opt->max_depth_residual[l] = 0.1;
+  }
+  return PHOVO_OK;
+}
 
 extern "C" int phovo_trust_region_options_default(phovo_trust_region_options *opt)
 {

@@ -100,8 +100,9 @@ class SampledSystem(C.Structure):
 FUSION_AUTO, FUSION_OFF, FUSION_SPLIT = 0, -1, -2
 OBJECTIVE_PHOTOMETRIC, OBJECTIVE_BIOBJECTIVE, OBJECTIVE_TRUST_REGION = 0, 1, 2
 OBJECTIVE_PHOTOMETRIC_AFFINE = 3
+OBJECTIVE_PHOTOMETRIC_GEOMETRIC = 4
 LAUNCH_KINDS = ("persistent", "fused", "slide", "slide_fallback", "wide", "bilinear", "biobjective", "trust_region",
-                "affine")
+                "affine", "geometric")
 
 # phovo_trust_region_level.termination
 (TR_SKIPPED, TR_MAX_ITERATIONS, TR_GRADIENT, TR_FUNCTION, TR_PARAMETER, TR_MIN_RADIUS, TR_INVALID_STEP,
@@ -125,6 +126,17 @@ class TrustRegionLevel(C.Structure):
 
 class TrustRegionReport(C.Structure):
     _fields_ = [("level", TrustRegionLevel * MAX_LEVELS)]
+
+
+class GeometricOptions(C.Structure):
+    """phovo_geometric_options: the photometric-geometric objective's per-level depth weight and residual gate."""
+    _fields_ = [("depth_weight", C.c_double * MAX_LEVELS), ("max_depth_residual", C.c_double * MAX_LEVELS)]
+
+
+class GeometricReport(C.Structure):
+    """phovo_geometric_report: depth rows and the two costs of every level's last system."""
+    _fields_ = [("depth_rows", C.c_int32 * MAX_LEVELS), ("photometric_cost", C.c_double * MAX_LEVELS),
+                ("depth_cost", C.c_double * MAX_LEVELS)]
 
 
 class LaunchRecord(C.Structure):
@@ -221,6 +233,14 @@ SYMBOLS = {
     "phovo_odometry_get_trust_region_report": (C.c_int, [_vp, C.POINTER(TrustRegionReport)]),
     "phovo_engine_fetch_illumination": (C.c_int, [_vp, C.c_int, _vp]),
     "phovo_odometry_get_illumination": (C.c_int, [_vp, C.POINTER(C.c_double)]),
+    "phovo_geometric_options_default": (C.c_int, [C.POINTER(GeometricOptions)]),
+    "phovo_geometric_read_file": (C.c_int, [C.c_char_p, C.POINTER(GeometricOptions)]),
+    "phovo_engine_set_geometric_options": (C.c_int, [_vp, C.POINTER(GeometricOptions)]),
+    "phovo_engine_get_geometric_options": (C.c_int, [_vp, C.POINTER(GeometricOptions)]),
+    "phovo_engine_fetch_geometric_reports": (C.c_int, [_vp, C.c_int, _vp]),
+    "phovo_odometry_set_geometric_options": (C.c_int, [_vp, C.POINTER(GeometricOptions)]),
+    "phovo_odometry_get_geometric_options": (C.c_int, [_vp, C.POINTER(GeometricOptions)]),
+    "phovo_odometry_get_geometric_report": (C.c_int, [_vp, C.POINTER(GeometricReport)]),
     "phovo_host_register": (C.c_int, [_vp, C.c_size_t]),
     "phovo_host_unregister": (C.c_int, [_vp]),
     "phovo_engine_reserve_frames": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int]),
@@ -417,3 +437,24 @@ def read_trust_region_file(path):
     check(lib().phovo_trust_region_read_file(str(path).encode(), C.byref(cfg), C.byref(opt)),
           "phovo_trust_region_read_file")
     return cfg, opt
+
+
+def make_geometric_options(depth_weight=None, max_depth_residual=None):
+    """phovo_geometric_options_default, with either field given as a per-level list (or one value for every level)."""
+    opt = GeometricOptions()
+    check(lib().phovo_geometric_options_default(C.byref(opt)), "phovo_geometric_options_default")
+    for name, vals in (("depth_weight", depth_weight), ("max_depth_residual", max_depth_residual)):
+        if vals is None:
+            continue
+        arr = getattr(opt, name)
+        vals = [vals] * MAX_LEVELS if np.isscalar(vals) else list(vals)
+        for i, v in enumerate(vals[:MAX_LEVELS]):
+            arr[i] = float(v)
+    return opt
+
+
+def read_geometric_file(path):
+    """phovo_geometric_read_file: GeometricOptions from the two optional keys of an analytic yml."""
+    opt = GeometricOptions()
+    check(lib().phovo_geometric_read_file(os.fsencode(path), C.byref(opt)), "phovo_geometric_read_file")
+    return opt

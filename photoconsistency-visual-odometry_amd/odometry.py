@@ -357,6 +357,48 @@ class CPhotoconsistencyOdometryAffine(CPhotoconsistencyOdometryAnalytic):
         return ab
 
 
+class CPhotoconsistencyOdometryGeometric(CPhotoconsistencyOdometryAnalytic):
+    """One frame pair at a time; not in the reference: intensity and depth rows together on the bilinear samples
+    (native.OBJECTIVE_PHOTOMETRIC_GEOMETRIC: residuals I1 - I0 and sigma (D1 - Z'), exact warp Jacobian).  The
+    target frame's depth is used: SetTargetFrame requires it.  Reads the analytic yml files and their two optional keys;
+    extensions, GetPairSystem() and GetSampledSystem() are refused (PHOVO_E_UNSUPPORTED)."""
+
+    def __init__(self, device=0):
+        super().__init__(device)
+        check(self._lib.phovo_odometry_set_objective(self._h, native.OBJECTIVE_PHOTOMETRIC_GEOMETRIC), "SetObjective")
+
+    def SetTargetFrame(self, intensityImage, depthImage):
+        if depthImage is None:
+            raise ValueError("the photometric-geometric objective needs the target's depth")
+        super().SetTargetFrame(intensityImage, depthImage)
+
+    def SetTargetFrameDevice(self, intensityImage, depthImage, depth_scale=1.0, channel_order="rgb", stream=None):
+        if depthImage is None:
+            raise ValueError("the photometric-geometric objective needs the target's depth")
+        super().SetTargetFrameDevice(intensityImage, depthImage, depth_scale, channel_order, stream)
+
+    def SetGeometricOptions(self, opt):
+        """native.GeometricOptions (native.make_geometric_options / read_geometric_file)."""
+        check(self._lib.phovo_odometry_set_geometric_options(self._h, C.byref(opt)), "SetGeometricOptions")
+
+    def GetGeometricOptions(self):
+        opt = native.GeometricOptions()
+        check(self._lib.phovo_odometry_get_geometric_options(self._h, C.byref(opt)), "GetGeometricOptions")
+        return opt
+
+    def GetGeometricReport(self):
+        """native.GeometricReport of the last Optimize(): per level depth_rows, photometric_cost, depth_cost."""
+        rep = native.GeometricReport()
+        check(self._lib.phovo_odometry_get_geometric_report(self._h, C.byref(rep)), "GetGeometricReport")
+        return rep
+
+
+# phovo_geometric_report as a numpy record: one row of per-level fields per pair
+GEOMETRIC_REPORT_DTYPE = np.dtype([("depth_rows", "<i4", (native.MAX_LEVELS,)),
+                                   ("photometric_cost", "<f8", (native.MAX_LEVELS,)),
+                                   ("depth_cost", "<f8", (native.MAX_LEVELS,))])
+assert GEOMETRIC_REPORT_DTYPE.itemsize == C.sizeof(native.GeometricReport)
+
 # phovo_trust_region_report as a numpy record: one row of per-level fields per pair
 TRUST_REGION_REPORT_DTYPE = np.dtype([("steps", "<i4", (native.MAX_LEVELS,)), ("accepted", "<i4", (native.MAX_LEVELS,)),
                                       ("termination", "<i4", (native.MAX_LEVELS,)), ("rows", "<i4", (native.MAX_LEVELS,)),
@@ -584,6 +626,24 @@ class AlignmentEngine:
         out = np.zeros((int(n_pairs), 2), dtype=np.float64)
         check(self._lib.phovo_engine_fetch_illumination(self._h, int(n_pairs), out.ctypes.data),
               "phovo_engine_fetch_illumination")
+        return out
+
+    def set_geometric_options(self, opt):
+        """native.GeometricOptions (native.make_geometric_options / read_geometric_file)."""
+        check(self._lib.phovo_engine_set_geometric_options(self._h, C.byref(opt)), "phovo_engine_set_geometric_options")
+
+    def get_geometric_options(self):
+        opt = native.GeometricOptions()
+        check(self._lib.phovo_engine_get_geometric_options(self._h, C.byref(opt)), "phovo_engine_get_geometric_options")
+        return opt
+
+    def fetch_geometric_reports(self, n_pairs):
+        """The records of the last enqueue's pairs, which ran under native.OBJECTIVE_PHOTOMETRIC_GEOMETRIC, as one
+        structured numpy array of GEOMETRIC_REPORT_DTYPE: out["depth_rows"][p, L], out["photometric_cost"][p, L],
+        out["depth_cost"][p, L]."""
+        out = np.zeros(int(n_pairs), dtype=GEOMETRIC_REPORT_DTYPE)
+        check(self._lib.phovo_engine_fetch_geometric_reports(self._h, int(n_pairs), out.ctypes.data),
+              "phovo_engine_fetch_geometric_reports")
         return out
 
     def trust_region_reports(self, n):
