@@ -3,6 +3,7 @@
 //
 //   ./PhotoconsistencyVisualOdometry <config_file.yml> <rgbd_dataset_directory> <output_trajectory_file> [--batch [--gpus N] [--rccl]]
 //                                    [--method analytic|ceres|biobjective|affine|geometric] [--information <file>] [--system <file>]
+//                                    [--geometric-system <file>]
 // --method picks the aligner as the reference's USE_PHOTOCONSISTENCY_ODOMETRY_METHOD does (0 = analytic, the default;
 // 1 = ceres: Levenberg-Marquardt on bilinear samples, CPhotoconsistencyOdometryCeres, which reads config_*_ceres.yml
 // files; 2 = bi-objective: photometric and depth error together, CPhotoconsistencyOdometryBiObjective), in every mode;
@@ -22,6 +23,12 @@
 // entries of J^T W J (phovo_sampled_system_format; dim 8 under affine: pose, alpha, beta).  The loop takes it from the class
 // surface (GetSampledSystem), --batch from phovo_engine_evaluate_sampled_pairs (alpha and beta from
 // phovo_engine_fetch_illumination); both write the same bytes, and the trajectory file is the same with and without the flag.
+// --geometric-system <file> (not in the reference; --method geometric, one device): the same for that method -- one line per
+// pair, `timestamp rows depth_rows photometric_cost depth_cost`, the 21 upper-triangle entries of the photometric block
+// sum J_I J_I^T and the 21 of the depth block sum J_D J_D^T (phovo_geometric_system_format; the system the aligner solves is
+// their entry-by-entry sum).  The loop takes it from the class surface (GetGeometricSystem), --batch from
+// phovo_engine_evaluate_geometric_pairs; both write the same bytes, the trajectory file is the same with and without the
+// flag, and the printed times do not include the evaluation.
 //
 // Behaviour kept from the reference's app (apps/PhotoconsistencyVisualOdometry/PhotoconsistencyVisualOdometry.cpp):
 //   * <dir>/rgb.txt and <dir>/depth.txt are read in lock step -- line n of one is paired with line n of the
@@ -49,6 +56,7 @@
 #include <iostream>
 #include <limits>
 #include <sstream>
+#include <stdexcept>
 #include <string>
 #include <thread>
 #include <vector>
@@ -140,11 +148,32 @@ static bool writeSystem(std::ofstream &f, double timestamp, const phovo_sampled_
   return true;
 }
 
+static bool writeSystem(std::ofstream &f, double timestamp, const phovo_geometric_system &s)
+{
+  char line[PHOVO_GEOMETRIC_SYSTEM_LINE_CAPACITY];
+  if (phovo_geometric_system_format(timestamp, &s, line, sizeof(line)) != PHOVO_OK) return false;
+  f << line << std::endl;
+  return true;
+}
+
+// GetGeometricSystem() of the class that has one (the loop is one generic lambda over every --method's class; the flag is
+// refused before the loop for the others)
+template <class Odometry>
+static auto geometricSystemOf(Odometry &odometry, int) -> decltype(odometry.GetGeometricSystem())
+{
+  return odometry.GetGeometricSystem();
+}
+template <class Odometry>
+static phovo_geometric_system geometricSystemOf(Odometry &, long)
+{
+  throw std::runtime_error("--geometric-system needs --method geometric");
+}
+
 static void printHelp()
 {
   std::cout << "./PhotoconsistencyVisualOdometry <config_file.yml> <rgbd_dataset_directory> "
                "<output_trajectory_file> [--batch [--gpus N] [--rccl]] [--method analytic|ceres|biobjective|affine|geometric] "
-               "[--information <file>] [--system <file>]" << std::endl;
+               "[--information <file>] [--system <file>] [--geometric-system <file>]" << std::endl;
 }
 
 #define PHOVO_OK_OR_FAIL(call)                                                              \
@@ -160,6 +189,7 @@ int main(int argc, char *argv[])
   int objective = PHOVO_OBJECTIVE_PHOTOMETRIC;        // --method analytic (default) | ceres | biobjective
   std::string informationPath;                        // --information <file>: the pairs' systems at their optimal states
   std::string systemPath;                             // --system <file>: the same for the sampled aligners
+  std::string geometricSystemPath;                    // --geometric-system <file>: the same for --method geometric
   for (int i = 4; i < argc; i++) {
     const std::string a(argv[i]);
     if (a == "--batch") batch = true;
@@ -176,6 +206,7 @@ int main(int argc, char *argv[])
     else if (a == "--gpus" && i + 1 < argc) nGpus = std::atoi(argv[++i]);
     else if (a == "--information" && i + 1 < argc) informationPath = argv[++i];
     else if (a == "--system" && i + 1 < argc) systemPath = argv[++i];
+    else if (a == "--geometric-system" && i + 1 < argc) geometricSystemPath = argv[++i];
     else { printHelp(); return EXIT_FAILURE; }
   }
   if (nGpus < 1 || (nGpus > 1 && !batch)) { std::cerr << "--gpus N needs --batch and N >= 1" << std::endl; return EXIT_FAILURE; }
@@ -196,6 +227,15 @@ int main(int argc, char *argv[])
   }
   if (sampled && objective != PHOVO_OBJECTIVE_PHOTOMETRIC && objective != PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE) {
     std::cerr << "--system needs bilinear sampling or --method affine" << std::endl;
+    return EXIT_FAILURE;
+  }
+  const bool geometricSystem = !geometricSystemPath.empty();
+  if (geometricSystem && (nGpus > 1 || rccl)) {
+    std::cerr << "--geometric-system runs on one device: it cannot be combined with --gpus N > 1 or --rccl" << std::endl;
+    return EXIT_FAILURE;
+  }
+  if (geometricSystem && objective != PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC) {
+    std::cerr << "--geometric-system needs --method geometric" << std::endl;
     return EXIT_FAILURE;
   }
   if (!fileExists(configFile)) { std::cerr << "Input config file " << configFile << " does not exist" << std::endl; return EXIT_FAILURE; }
@@ -253,6 +293,11 @@ int main(int argc, char *argv[])
     systemFile.open(systemPath.c_str());
     if (!systemFile.is_open()) { std::cerr << "Cannot open output system file " << systemPath << std::endl; return EXIT_FAILURE; }
   }
+  std::ofstream geometricSystemFile;
+  if (geometricSystem) {
+    geometricSystemFile.open(geometricSystemPath.c_str());
+    if (!geometricSystemFile.is_open()) { std::cerr << "Cannot open output geometric system file " << geometricSystemPath << std::endl; return EXIT_FAILURE; }
+  }
   if (nFrames < 2) return EXIT_SUCCESS;
 
   Matrix44Type pose = Matrix44Type::Identity();
@@ -286,6 +331,7 @@ int main(int argc, char *argv[])
         if (!writePose(trajectoryFile, rgb[t].timestamp, pose)) return EXIT_FAILURE;
         if (information && !writeSystem(informationFile, rgb[t].timestamp, odometry.GetPairSystem())) return EXIT_FAILURE;
         if (sampled && !writeSystem(systemFile, rgb[t].timestamp, odometry.GetSampledSystem())) return EXIT_FAILURE;
+        if (geometricSystem && !writeSystem(geometricSystemFile, rgb[t].timestamp, geometricSystemOf(odometry, 0))) return EXIT_FAILURE;
         std::cout << "Rt:" << std::endl << Rt << std::endl;
         prevGray = curGray.clone();
         prevDepth = curDepth.clone();
@@ -387,6 +433,8 @@ int main(int argc, char *argv[])
         if (cfg.max_num_iterations[l] > 0) finestLevel = l;
       if (information && finestLevel < 0) { std::cerr << "--information: the configuration optimises no level" << std::endl; return EXIT_FAILURE; }
       if (sampled && finestLevel < 0) { std::cerr << "--system: the configuration optimises no level" << std::endl; return EXIT_FAILURE; }
+      if (geometricSystem && finestLevel < 0) { std::cerr << "--geometric-system: the configuration optimises no level" << std::endl; return EXIT_FAILURE; }
+      std::vector<phovo_geometric_system> geometricSystems(geometricSystem ? (size_t)nPairs : 0);
       const int systemDim = objective == PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE ? 8 : 6;
       std::vector<phovo_sampled_system> sampledSystems(sampled ? (size_t)nPairs : 0);
       std::vector<std::string> shardError(nGpus);
@@ -441,7 +489,10 @@ int main(int argc, char *argv[])
           if (!rccl) {
             if (phovo_engine_align_pairs(engine, b - a, src.data(), tgt.data(), nullptr, states.data() + (size_t)a * 6, nullptr) != PHOVO_OK)
               return fail("phovo_engine_align_pairs");
-            if (information || sampled) tAligned = std::chrono::steady_clock::now();      // (the evaluation is not part of the timed run)
+            if (information || sampled || geometricSystem) tAligned = std::chrono::steady_clock::now();      // (the evaluation is not part of the timed run)
+            if (geometricSystem && phovo_engine_evaluate_geometric_pairs(engine, b - a, src.data(), tgt.data(), states.data() + (size_t)a * 6,
+                                                                         finestLevel, geometricSystems.data() + a) != PHOVO_OK)
+              return fail("phovo_engine_evaluate_geometric_pairs");
             if (information && phovo_engine_evaluate_pairs(engine, b - a, src.data(), tgt.data(), states.data() + (size_t)a * 6,
                                                            finestLevel, systems.data() + a) != PHOVO_OK)
               return fail("phovo_engine_evaluate_pairs");
@@ -491,7 +542,7 @@ int main(int argc, char *argv[])
           std::copy(group.gathered(g), group.gathered(g) + (size_t)(b - a) * 6, states.begin() + (size_t)a * 6);
         }
       }
-      const auto t1 = (information || sampled) ? tAligned : std::chrono::steady_clock::now();
+      const auto t1 = (information || sampled || geometricSystem) ? tAligned : std::chrono::steady_clock::now();
       std::cout << "Time = " << std::chrono::duration<double>(t1 - t0).count() << " sec. (" << nPairs << " pairs on " << nGpus
                 << " device(s), upload and pyramids included)" << std::endl;
       std::vector<double> poses((size_t)nPairs * 16);
@@ -502,6 +553,7 @@ int main(int argc, char *argv[])
         if (!writePose(trajectoryFile, rgb[(size_t)p + 1].timestamp, P)) return EXIT_FAILURE;
         if (information && !writeSystem(informationFile, rgb[(size_t)p + 1].timestamp, systems[(size_t)p])) return EXIT_FAILURE;
         if (sampled && !writeSystem(systemFile, rgb[(size_t)p + 1].timestamp, sampledSystems[(size_t)p])) return EXIT_FAILURE;
+        if (geometricSystem && !writeSystem(geometricSystemFile, rgb[(size_t)p + 1].timestamp, geometricSystems[(size_t)p])) return EXIT_FAILURE;
       }
     }
   } catch (const std::exception &e) {
@@ -511,5 +563,6 @@ int main(int argc, char *argv[])
   trajectoryFile.close();
   if (information) informationFile.close();
   if (sampled) systemFile.close();
+  if (geometricSystem) geometricSystemFile.close();
   return EXIT_SUCCESS;
 }

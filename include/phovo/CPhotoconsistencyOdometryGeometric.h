@@ -9,7 +9,8 @@
 // The types come from the same place as CPhotoconsistencyOdometryAnalytic.h's (PHOVO_HIP_USE_REFERENCE_TYPES or
 // phovo/compat/).  SetTargetFrame USES the target's depth here.  ReadConfigurationFile reads the config_*_analytic.yml keys
 // and the two optional keys "depth_weight (at each level)" and "max_depth_residual (at each level)".  Extensions are refused
-// (std::runtime_error, PHOVO_E_UNSUPPORTED), and so are the inherited GetPairSystem() and GetSampledSystem().
+// (std::runtime_error, PHOVO_E_UNSUPPORTED), and so are the inherited GetPairSystem() and GetSampledSystem(); this
+// objective's system, with the photometric and the depth block apart, is GetGeometricSystem().
 #ifndef PHOVO_HIP_CPHOTOCONSISTENCY_ODOMETRY_GEOMETRIC_H
 #define PHOVO_HIP_CPHOTOCONSISTENCY_ODOMETRY_GEOMETRIC_H
 
@@ -53,6 +54,15 @@ class CPhotoconsistencyOdometryGeometric : public CPhotoconsistencyOdometryAnaly
     phovo_geometric_report r;
     Base::Check(phovo_odometry_get_geometric_report(Base::Handle(), &r), "GetGeometricReport");
     return r;
+  }
+
+  // The Gauss-Newton system at the optimal state on the finest level the configuration optimises: the photometric and the
+  // depth block apart, and their sum; evaluated on demand after Optimize().
+  phovo_geometric_system GetGeometricSystem() const
+  {
+    phovo_geometric_system s;
+    Base::Check(phovo_odometry_get_geometric_system(Base::Handle(), &s), "GetGeometricSystem");
+    return s;
   }
 };
 

@@ -241,8 +241,11 @@ typedef struct phovo_extensions {
  *                                PHOVO_E_NOT_READY.  No new planes: switching between objectives 0, 2, 3 and 4 keeps the
  *                                frame pool.  Supported: fp64 planes, the default sampling setting, no Huber weights,
  *                                jacobian_corrected 0 -- anything else is PHOVO_E_UNSUPPORTED, whichever setter comes
- *                                second; both evaluate calls are PHOVO_E_UNSUPPORTED too.  Fusion, sliding-window, wide,
- *                                latency-form and batch-invariant settings are accepted and have no effect.
+ *                                second; both evaluate calls are PHOVO_E_UNSUPPORTED too: this objective's system, with
+ *                                the photometric and the depth block kept apart, is phovo_geometric_system
+ *                                (phovo_engine_evaluate_geometric_pairs, phovo_odometry_get_geometric_system).  Fusion,
+ *                                sliding-window, wide, latency-form and batch-invariant settings are accepted and have no
+ *                                effect.
  *                                phovo_pair_report: valid_pixels[L] = photometric rows of the level's last iteration,
  *                                PHOVO_PAIR_RANK_DEFICIENT when fewer than 6 photometric rows were filled in some iteration,
  *                                PHOVO_PAIR_NONFINITE as under the photometric objective, gradient_norm = ||g||_2 of the
@@ -264,6 +267,34 @@ typedef struct phovo_geometric_report {
   double  photometric_cost[PHOVO_MAX_LEVELS];   /* sum r_I^2 */
   double  depth_cost[PHOVO_MAX_LEVELS];         /* sum r_D^2 (sigma_L included) */
 } phovo_geometric_report;
+
+/* The Gauss-Newton system of one frame pair under the photometric-geometric objective at a given state on one level
+ * (phovo_engine_evaluate_geometric_pairs, phovo_odometry_get_geometric_system), with the photometric and
+ * the depth block kept apart.  Its rows are the ones gn_level_kernel_geometric fills at that state: the photometric rows
+ * are the bilinear extension's with the true warp Jacobian, and a depth row sits beside a photometric row iff the four
+ * clamped taps of the target's depth pass min_depth < d < max_depth (NaN fails) and, with max_depth_residual[level] > 0,
+ * |D1(u, v) - Z'| <= max_depth_residual[level].  sigma and the gate are the engine's phovo_geometric_options at that
+ * level.  The gate acts on the UNWEIGHTED residual, so the system under another weight sigma' is
+ * photometric_information + (sigma'/sigma)^2 depth_information (gradient and cost likewise) without another pass.
+ * Relation to the aligner: the system it solves in iteration k of a level is information / gradient at the state the
+ * iteration starts from.  The photometric block is bit for bit the phovo_sampled_system that
+ * phovo_engine_evaluate_sampled_pairs returns for the same pool and state under the photometric objective with
+ * PHOVO_SAMPLING_BILINEAR and jacobian_corrected = 1.  Arithmetic: fp64 on the device; the sums are taken in an order that
+ * depends on the level size only, so a pair's result is the same bit for bit whatever the batch, its position in it, or
+ * the engine's settings. */
+typedef struct phovo_geometric_system {
+  double   information[36];              /* photometric_information + depth_information, entry by entry, ONE fp64 add each */
+  double   gradient[6];                  /* photometric_gradient + depth_gradient, likewise */
+  double   photometric_information[36];  /* sum J_I J_I^T, row-major, exactly symmetric (filled from the upper triangle) */
+  double   photometric_gradient[6];      /* sum J_I r_I */
+  double   depth_information[36];        /* sum J_D J_D^T, sigma_L included */
+  double   depth_gradient[6];            /* sum J_D r_D */
+  double   photometric_cost;             /* sum r_I^2 */
+  double   depth_cost;                   /* sum r_D^2 (sigma_L included) */
+  int32_t  rows, depth_rows;             /* as phovo_pair_report.valid_pixels / phovo_geometric_report.depth_rows count them */
+  uint32_t flags;                        /* PHOVO_PAIR_RANK_DEFICIENT if rows < 6; PHOVO_PAIR_NONFINITE if any sum of either block is inf/NaN */
+  int32_t  reserved;
+} phovo_geometric_system;
 
 /* Solver options of the trust-region objective, per level (CPhotoconsistencyOdometryCeres.h:526-576).  num_levels, blur,
  * gradient scale and max_num_iterations stay in phovo_config. */
@@ -371,6 +402,15 @@ int phovo_pair_system_format(double timestamp, const phovo_pair_system *s, char 
  * suffices). */
 int phovo_sampled_system_format(double timestamp, const phovo_sampled_system *s, char *line, size_t capacity);
 
+/* One line of the VisualOdometry app's --geometric-system file: `timestamp rows depth_rows photometric_cost depth_cost`,
+ * the 21 upper-triangle entries of s->photometric_information in row-major order, then the 21 of s->depth_information;
+ * every double as "%.17g" (round-trips exactly), no newline.  A reader recovers s->information bit for bit with the one
+ * add per entry that built it.  Host only.  PHOVO_E_INVALID_ARGUMENT for NULL pointers or a `capacity` below
+ * PHOVO_GEOMETRIC_SYSTEM_LINE_CAPACITY, which always suffices: 45 doubles of at most 24 characters, two integers of at most
+ * 11, 46 blanks and the terminator are 1149 bytes. */
+#define PHOVO_GEOMETRIC_SYSTEM_LINE_CAPACITY 1280
+int phovo_geometric_system_format(double timestamp, const phovo_geometric_system *s, char *line, size_t capacity);
+
 /* warpImage, CPhotoconsistencyOdometry.h:73-134 -- the forward warp both reference apps call after Optimize()
  * (...FrameAlignment.cpp:108, ...VisualOdometry.cpp:248-250) to show |I1 - warp(I0)|.  Host buffers in and out,
  * strides in bytes; rt row-major 4x4, k row-major 3x3, level scales the intrinsics by 2^-level as the reference does.
@@ -437,6 +477,10 @@ int phovo_odometry_get_pair_system(const phovo_odometry *o, phovo_pair_system *o
  * Optimize().  PHOVO_E_NOT_READY before a successful Optimize() and after a Set*Frame since; PHOVO_E_UNSUPPORTED as for
  * phovo_engine_evaluate_sampled_pairs (nearest / scatter sampling, bi-objective, trust region). */
 int phovo_odometry_get_sampled_system(const phovo_odometry *o, phovo_sampled_system *out);
+/* not in the reference: the system (phovo_geometric_system) of the photometric-geometric objective at the optimal state
+ * on the finest level the configuration optimises, evaluated on demand.  PHOVO_E_NOT_READY before a successful Optimize()
+ * and after a Set*Frame since; PHOVO_E_UNSUPPORTED under another objective. */
+int phovo_odometry_get_geometric_system(const phovo_odometry *o, phovo_geometric_system *out);
 /* Device time of the last Optimize() in milliseconds (HIP events; the reference wraps the same
  * call in cv::TickMeter, apps/PhotoconsistencyFrameAlignment/PhotoconsistencyFrameAlignment.cpp:99-102). */
 int phovo_odometry_last_optimize_ms(const phovo_odometry *o, double *ms);
@@ -718,6 +762,20 @@ int phovo_engine_evaluate_pairs(phovo_engine *e, int n_pairs, const int *src, co
 int phovo_engine_evaluate_sampled_pairs(phovo_engine *e, int n_pairs, const int *src, const int *tgt,
                                         const double *states /* [n_pairs][state_dim] */, int state_dim, int level,
                                         phovo_sampled_system *out);
+
+/* The system of PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC (phovo_geometric_system): the photometric and the depth block of
+ * n_pairs pairs at the states [n_pairs][6] on one level, under the engine's phovo_geometric_options at that level.
+ * Synchronous; ordered behind every enqueue in flight, and it changes nothing that phovo_engine_fetch / fetch_results /
+ * fetch_geometric_reports return.
+ *   PHOVO_E_UNSUPPORTED       any objective but PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC
+ *   PHOVO_E_INVALID_ARGUMENT  as phovo_engine_evaluate_sampled_pairs
+ *   PHOVO_E_NOT_READY         as phovo_engine_evaluate_sampled_pairs; also when a target frame lacks PHOVO_ROLE_SOURCE on
+ *                             that level (its depth plane is a source upload's: the enqueue's rule)
+ * n_pairs == 0 is OK.  Device memory: the evaluate workspace (shared with the other two evaluate calls, kept until the
+ * engine is destroyed) -- per pair of a group 256 bytes of photometric and 256 bytes of depth tile sums per 1024 pixels;
+ * large batches run in groups whose tile sums take at most 64 MB together (436 pairs at 640x480). */
+int phovo_engine_evaluate_geometric_pairs(phovo_engine *e, int n_pairs, const int *src, const int *tgt,
+                                          const double *states /* [n_pairs][6] */, int level, phovo_geometric_system *out);
 
 /* Pipelining.  Pairs are independent, and with data-dependent termination a batch ends with a few long pairs on an
  * otherwise idle chip.  The engine therefore keeps PHOVO_ENQUEUE_DEPTH enqueues in flight, each with its own stream, pair

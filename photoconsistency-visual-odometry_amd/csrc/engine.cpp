@@ -2054,6 +2054,96 @@ int phovo_engine_evaluate_sampled_pairs(phovo_engine *e, int n_pairs, const int 
   return PHOVO_OK;
 }
 
+// Tile sums of one geometric-evaluation group (the sampled and the depth slab together) take at most this much: 436 pairs
+// at 640x480.
+static constexpr size_t EVAL_GEOMETRIC_SLAB_CAP_BYTES = (size_t)64 << 20;
+
+int phovo_engine_evaluate_geometric_pairs(phovo_engine *e, int n_pairs, const int *src, const int *tgt, const double *states,
+                                          int level, phovo_geometric_system *out)
+{
+  if (!e) return fail(PHOVO_E_INVALID_ARGUMENT, "evaluate_geometric_pairs: null engine");
+  if (e->objective != PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC)
+    return fail(PHOVO_E_UNSUPPORTED, "evaluate_geometric_pairs: the photometric-geometric objective only");
+  if (n_pairs < 0) return fail(PHOVO_E_INVALID_ARGUMENT, "evaluate_geometric_pairs: n_pairs < 0");
+  if (n_pairs > 0 && (!src || !tgt || !states || !out)) return fail(PHOVO_E_INVALID_ARGUMENT, "evaluate_geometric_pairs: null");
+  if (level < 0 || level >= e->cfg.num_levels) return fail(PHOVO_E_INVALID_ARGUMENT, "evaluate_geometric_pairs: level out of range");
+  if (n_pairs == 0) return PHOVO_OK;
+  if (e->n_frames == 0) return fail(PHOVO_E_NOT_READY, "evaluate_geometric_pairs: no frames uploaded");
+  for (int i = 0; i < n_pairs; i++) {
+    if (src[i] < 0 || src[i] >= e->n_frames || tgt[i] < 0 || tgt[i] >= e->n_frames)
+      return fail(PHOVO_E_INVALID_ARGUMENT, "evaluate_geometric_pairs: frame index out of range");
+  }
+  if (!e->have_K) return fail(PHOVO_E_NOT_READY, "evaluate_geometric_pairs: SetIntrinsicMatrix has not been called");
+  const LevelPool &lv = e->levels[level];
+  if (!lv.stored) return fail(PHOVO_E_NOT_READY, "evaluate_geometric_pairs: the level is not resident (phovo_engine_level_is_stored)");
+  for (int i = 0; i < n_pairs; i++) {
+    if (!(e->frame_roles[(size_t)src[i] * PHOVO_MAX_LEVELS + (size_t)level] & PHOVO_ROLE_SOURCE))
+      return fail(PHOVO_E_NOT_READY, "evaluate_geometric_pairs: a source frame has no depth (upload it with PHOVO_ROLE_SOURCE)");
+    if (!(e->frame_roles[(size_t)tgt[i] * PHOVO_MAX_LEVELS + (size_t)level] & PHOVO_ROLE_TARGET))
+      return fail(PHOVO_E_NOT_READY, "evaluate_geometric_pairs: a target frame has no gradients (upload it with PHOVO_ROLE_TARGET)");
+    if (!(e->frame_roles[(size_t)tgt[i] * PHOVO_MAX_LEVELS + (size_t)level] & PHOVO_ROLE_SOURCE))
+      return fail(PHOVO_E_NOT_READY, "evaluate_geometric_pairs: the photometric-geometric objective reads the target's depth "
+                                     "(upload target frames with PHOVO_ROLE_BOTH)");
+  }
+  // (set_objective / set_extensions hold this objective to fp64 planes without Huber weights)
+  PHOVO_HIP_CHECK(hipSetDevice(e->device));
+  PHOVO_HIP_CHECK(quiesce(e));                 // behind every enqueue in flight; their slots are not touched
+
+  // Workspace for a group of G pairs, every region 256-byte aligned: the sampled tile sums, the depth tile sums, states,
+  // pair indices, the sampled records and the results.  One group size serves both launches.
+  const size_t slab_bytes = gn_eval_sampled_slab_doubles_per_pair(lv.n, 6) * sizeof(double);
+  const int group = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_pairs, EVAL_GEOMETRIC_SLAB_CAP_BYTES / (2 * slab_bytes)));
+  auto align256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t G = (size_t)group;
+  const size_t depth_off = align256(G * slab_bytes);
+  const size_t st_off = depth_off + align256(G * slab_bytes);
+  const size_t src_off = st_off + align256(G * 6 * sizeof(double));
+  const size_t tgt_off = src_off + align256(G * sizeof(int));
+  const size_t smp_off = tgt_off + align256(G * sizeof(int));
+  const size_t out_off = smp_off + align256(G * sizeof(phovo_sampled_system));
+  const size_t need = out_off + align256(G * sizeof(phovo_geometric_system));
+  e->eval_owner_clean = 0;                     // (the tile sums lie where phovo_engine_evaluate_pairs keeps its owner maps)
+  if (need > e->eval_ws_capacity) {
+    if (e->d_eval_ws) { (void)hipFree(e->d_eval_ws); e->d_eval_ws = nullptr; e->eval_ws_capacity = 0; }
+    PHOVO_HIP_CHECK(hipMalloc(&e->d_eval_ws, need));
+    e->eval_ws_capacity = need;
+  }
+  unsigned char *ws = e->d_eval_ws;
+
+  GNGeometricEvalArgs b{};
+  GNSampledEvalArgs &a = b.s;
+  a.w = lv.w; a.h = lv.h; a.n = lv.n; a.n_chunks = (lv.n + 63) / 64;
+  a.state_dim = 6;
+  const double scaleFactor = 1.0 / std::pow(2, level);                               // :203
+  a.fx = e->K[0] * scaleFactor; a.fy = e->K[4] * scaleFactor;                        // :204-207
+  a.ox = e->K[2] * scaleFactor; a.oy = e->K[5] * scaleFactor;
+  a.ifx = 1.f / a.fx; a.ify = 1.f / a.fy;                                            // :208-209
+  a.min_depth = e->min_depth; a.max_depth = e->max_depth;
+  a.huber_delta = 0.0;
+  a.planes = lv.planes;
+  a.frame_bytes = lv.frame_bytes;
+  for (int p = 0; p < PLANES_PER_FRAME; p++) a.plane_off[p] = lv.plane_off[p];
+  a.states = reinterpret_cast<const double *>(ws + st_off);
+  a.src = reinterpret_cast<const int *>(ws + src_off);
+  a.tgt = reinterpret_cast<const int *>(ws + tgt_off);
+  b.depth_weight = e->geo_opt.depth_weight[level];
+  b.max_depth_residual = e->geo_opt.max_depth_residual[level];
+  auto *d_part_sampled = reinterpret_cast<double *>(ws);
+  auto *d_part_depth = reinterpret_cast<double *>(ws + depth_off);
+  auto *d_sampled = reinterpret_cast<phovo_sampled_system *>(ws + smp_off);
+  auto *d_out = reinterpret_cast<phovo_geometric_system *>(ws + out_off);
+  for (int g0 = 0; g0 < n_pairs; g0 += group) {
+    const int c = std::min(group, n_pairs - g0);
+    PHOVO_HIP_CHECK(hipMemcpyAsync(ws + st_off, states + (size_t)g0 * 6, sizeof(double) * 6 * (size_t)c, hipMemcpyHostToDevice, e->stream));
+    PHOVO_HIP_CHECK(hipMemcpyAsync(ws + src_off, src + g0, sizeof(int) * (size_t)c, hipMemcpyHostToDevice, e->stream));
+    PHOVO_HIP_CHECK(hipMemcpyAsync(ws + tgt_off, tgt + g0, sizeof(int) * (size_t)c, hipMemcpyHostToDevice, e->stream));
+    PHOVO_HIP_CHECK(gn_eval_geometric_pairs(b, c, d_part_sampled, d_sampled, d_part_depth, d_out, e->stream));
+    PHOVO_HIP_CHECK(hipMemcpyAsync(out + g0, d_out, sizeof(phovo_geometric_system) * (size_t)c, hipMemcpyDeviceToHost, e->stream));
+    PHOVO_HIP_CHECK(hipStreamSynchronize(e->stream));      // (the next group's inputs overwrite this one's)
+  }
+  return PHOVO_OK;
+}
+
 int phovo_engine_align_ms(const phovo_engine *e, int ticket, double *total_ms, double level_ms[PHOVO_MAX_LEVELS])
 {
   if (!e) return fail(PHOVO_E_INVALID_ARGUMENT, "align_ms: null");
@@ -2555,6 +2645,21 @@ int phovo_odometry_get_sampled_system(const phovo_odometry *o, phovo_sampled_sys
   state[7] = affine ? o->illumination[1] : 0.0;
   return phovo_engine_evaluate_sampled_pairs(o->engine, 1, &src, &tgt, state,
                                              e->objective == PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE ? 8 : 6, finest, out);
+}
+
+int phovo_odometry_get_geometric_system(const phovo_odometry *o, phovo_geometric_system *out)
+{
+  if (!o || !out) return fail(PHOVO_E_INVALID_ARGUMENT, "get_geometric_system: null");
+  const phovo_engine *e = o->engine;
+  if (e->objective != PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC)
+    return fail(PHOVO_E_UNSUPPORTED, "get_geometric_system: the photometric-geometric objective only");
+  if (!o->optimized) return fail(PHOVO_E_NOT_READY, "get_geometric_system: Optimize has not run since the frames were set");
+  int finest = -1;                                        // the lowest level Optimize() iterates on
+  for (int l = e->cfg.num_levels - 1; l >= 0; l--)
+    if (e->cfg.max_num_iterations[l] > 0) finest = l;
+  if (finest < 0) return fail(PHOVO_E_NOT_READY, "get_geometric_system: the configuration optimises no level");
+  const int src = 0, tgt = 1;
+  return phovo_engine_evaluate_geometric_pairs(o->engine, 1, &src, &tgt, o->state, finest, out);
 }
 
 int phovo_odometry_last_optimize_ms(const phovo_odometry *o, double *ms)

@@ -197,6 +197,19 @@ struct GNGeometricArgs {
 int gn_geometric_wgs_per_cu();       // workgroups of the kernel that stay resident per CU
 int gn_geometric_lds_bytes();
 hipError_t gn_launch_level_geometric(const GNGeometricArgs &args, int cu_count, hipStream_t stream);
+// Evaluation of that objective's system at given states (gn_evaluate_geometric_kernels.hip,
+// phovo_engine_evaluate_geometric_pairs): the photometric block through gn_eval_sampled_pairs (corrected rows, fp64 planes,
+// no Huber weights), the depth block through a tile kernel of the same form, both into one phovo_geometric_system.
+struct GNGeometricEvalArgs {
+  GNSampledEvalArgs s;               // state_dim 6, huber_delta 0
+  double depth_weight;               // sigma_L (> 0)
+  double max_depth_residual;         // the residual gate of the level; <= 0: off
+};
+// g_part_sampled, g_part_depth: [n_pairs][gn_eval_sampled_slab_doubles_per_pair(n, 6)] each; sampled, out: [n_pairs] on
+// the device.
+hipError_t gn_eval_geometric_pairs(const GNGeometricEvalArgs &args, int n_pairs, double *g_part_sampled,
+                                   phovo_sampled_system *sampled, double *g_part_depth, phovo_geometric_system *out,
+                                   hipStream_t stream);
 // Sliding-window form for levels whose owner map exceeds LDS (gn_slide_kernel.hip): owner ring in LDS; pairs whose
 // motion leaves the window are appended to args.handover_out for a follow-up gn_launch_level that takes that list.
 hipError_t gn_prepare_slide_kernels();

@@ -92,4 +92,27 @@ int phovo_sampled_system_format(double timestamp, const phovo_sampled_system *s,
   return PHOVO_OK;
 }
 
+int phovo_geometric_system_format(double timestamp, const phovo_geometric_system *s, char *line, size_t capacity)
+{
+  if (!s || !line) return fail(PHOVO_E_INVALID_ARGUMENT, "geometric_system_format: null");
+  // 45 doubles of at most 24 characters ("%.17g": sign, 17 digits, point, e-308), two integers of at most 11, 46 blanks, NUL
+  if (capacity < PHOVO_GEOMETRIC_SYSTEM_LINE_CAPACITY)
+    return fail(PHOVO_E_INVALID_ARGUMENT, "geometric_system_format: buffer too small (PHOVO_GEOMETRIC_SYSTEM_LINE_CAPACITY)");
+  std::string out;
+  char buf[128];
+  std::snprintf(buf, sizeof(buf), "%.17g %d %d %.17g %.17g", timestamp, (int)s->rows, (int)s->depth_rows, s->photometric_cost,
+                s->depth_cost);
+  out += buf;
+  for (const double *h : {s->photometric_information, s->depth_information})
+    for (int a = 0; a < 6; a++)
+      for (int b = a; b < 6; b++) {
+        std::snprintf(buf, sizeof(buf), " %.17g", h[6 * a + b]);
+        out += buf;
+      }
+  if (out.size() + 1 > capacity) return fail(PHOVO_E_INVALID_ARGUMENT, "geometric_system_format: buffer too small");
+  out.copy(line, out.size());
+  line[out.size()] = '\0';
+  return PHOVO_OK;
+}
+
 }  // extern "C"

@@ -139,6 +139,28 @@ class GeometricReport(C.Structure):
                 ("depth_cost", C.c_double * MAX_LEVELS)]
 
 
+GEOMETRIC_SYSTEM_LINE_CAPACITY = 1280
+
+
+class GeometricSystem(C.Structure):
+    """phovo_geometric_system: the Gauss-Newton system of one pair under the photometric-geometric objective at a given state
+    on one level, the photometric and the depth block apart and their entry-by-entry sum."""
+    _fields_ = [
+        ("information", C.c_double * 36),
+        ("gradient", C.c_double * 6),
+        ("photometric_information", C.c_double * 36),
+        ("photometric_gradient", C.c_double * 6),
+        ("depth_information", C.c_double * 36),
+        ("depth_gradient", C.c_double * 6),
+        ("photometric_cost", C.c_double),
+        ("depth_cost", C.c_double),
+        ("rows", C.c_int32),
+        ("depth_rows", C.c_int32),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_int32),
+    ]
+
+
 class LaunchRecord(C.Structure):
     _fields_ = [
         ("level_first", C.c_int), ("level_last", C.c_int), ("kind", C.c_int),
@@ -184,6 +206,7 @@ SYMBOLS = {
     "phovo_trajectory_format_pose": (C.c_int, [C.c_double, _dp, C.c_char_p, C.c_size_t]),
     "phovo_pair_system_format": (C.c_int, [C.c_double, C.POINTER(PairSystem), C.c_char_p, C.c_size_t]),
     "phovo_sampled_system_format": (C.c_int, [C.c_double, C.POINTER(SampledSystem), C.c_char_p, C.c_size_t]),
+    "phovo_geometric_system_format": (C.c_int, [C.c_double, C.POINTER(GeometricSystem), C.c_char_p, C.c_size_t]),
     "phovo_warp_image": (C.c_int, [C.c_int, _vp, C.c_size_t, _vp, C.c_size_t, C.c_int, C.c_int, _dp, _dp, C.c_int,
                                    _vp, C.c_size_t]),
     "phovo_odometry_create": (C.c_int, [C.c_int, C.POINTER(_vp)]),
@@ -206,6 +229,7 @@ SYMBOLS = {
     "phovo_odometry_last_optimize_ms": (C.c_int, [_vp, _dp]),
     "phovo_odometry_get_pair_system": (C.c_int, [_vp, C.POINTER(PairSystem)]),
     "phovo_odometry_get_sampled_system": (C.c_int, [_vp, C.POINTER(SampledSystem)]),
+    "phovo_odometry_get_geometric_system": (C.c_int, [_vp, C.POINTER(GeometricSystem)]),
     "phovo_engine_create": (C.c_int, [C.c_int, C.POINTER(_vp)]),
     "phovo_engine_destroy": (C.c_int, [_vp]),
     "phovo_engine_set_config": (C.c_int, [_vp, C.POINTER(Config)]),
@@ -276,6 +300,7 @@ SYMBOLS = {
     "phovo_engine_align_ms": (C.c_int, [_vp, C.c_int, _dp, _dp]),
     "phovo_engine_evaluate_pairs": (C.c_int, [_vp, C.c_int, _ip, _ip, _vp, C.c_int, _vp]),
     "phovo_engine_evaluate_sampled_pairs": (C.c_int, [_vp, C.c_int, _ip, _ip, _vp, C.c_int, C.c_int, _vp]),
+    "phovo_engine_evaluate_geometric_pairs": (C.c_int, [_vp, C.c_int, _ip, _ip, _vp, C.c_int, _vp]),
 }
 
 
@@ -409,6 +434,14 @@ def format_sampled_system(timestamp, system):
     buf = C.create_string_buffer(1024)
     check(lib().phovo_sampled_system_format(float(timestamp), C.byref(system), buf, len(buf)),
           "phovo_sampled_system_format")
+    return buf.value.decode()
+
+
+def format_geometric_system(timestamp, system):
+    """phovo_geometric_system_format: the line the VisualOdometry app writes per pair with --geometric-system."""
+    buf = C.create_string_buffer(GEOMETRIC_SYSTEM_LINE_CAPACITY)
+    check(lib().phovo_geometric_system_format(float(timestamp), C.byref(system), buf, len(buf)),
+          "phovo_geometric_system_format")
     return buf.value.decode()
 
 

@@ -361,7 +361,8 @@ class CPhotoconsistencyOdometryGeometric(CPhotoconsistencyOdometryAnalytic):
     """One frame pair at a time; not in the reference: intensity and depth rows together on the bilinear samples
     (native.OBJECTIVE_PHOTOMETRIC_GEOMETRIC: residuals I1 - I0 and sigma (D1 - Z'), exact warp Jacobian).  The
     target frame's depth is used: SetTargetFrame requires it.  Reads the analytic yml files and their two optional keys;
-    extensions, GetPairSystem() and GetSampledSystem() are refused (PHOVO_E_UNSUPPORTED)."""
+    extensions, GetPairSystem() and GetSampledSystem() are refused (PHOVO_E_UNSUPPORTED); GetGeometricSystem() returns this
+    objective's system with the photometric and the depth block apart."""
 
     def __init__(self, device=0):
         super().__init__(device)
@@ -391,6 +392,13 @@ class CPhotoconsistencyOdometryGeometric(CPhotoconsistencyOdometryAnalytic):
         rep = native.GeometricReport()
         check(self._lib.phovo_odometry_get_geometric_report(self._h, C.byref(rep)), "GetGeometricReport")
         return rep
+
+    def GetGeometricSystem(self):
+        """native.GeometricSystem at the optimal state on the finest level the configuration optimises: the photometric and
+        the depth block of the Gauss-Newton system apart, and their sum; evaluated on demand after Optimize()."""
+        gs = native.GeometricSystem()
+        check(self._lib.phovo_odometry_get_geometric_system(self._h, C.byref(gs)), "GetGeometricSystem")
+        return gs
 
 
 # phovo_geometric_report as a numpy record: one row of per-level fields per pair
@@ -424,6 +432,16 @@ SAMPLED_SYSTEM_DTYPE = np.dtype([("information", "<f8", (native.SYSTEM_MAX_DIM *
                                  ("gradient", "<f8", (native.SYSTEM_MAX_DIM,)), ("cost", "<f8"), ("rows", "<i4"),
                                  ("flags", "<u4"), ("dim", "<i4"), ("reserved", "<i4")])
 assert SAMPLED_SYSTEM_DTYPE.itemsize == C.sizeof(native.SampledSystem)
+
+
+# phovo_geometric_system as a numpy record (the layout of native.GeometricSystem): evaluate_geometric_pairs returns an array
+# of these
+GEOMETRIC_SYSTEM_DTYPE = np.dtype([("information", "<f8", (36,)), ("gradient", "<f8", (6,)),
+                                   ("photometric_information", "<f8", (36,)), ("photometric_gradient", "<f8", (6,)),
+                                   ("depth_information", "<f8", (36,)), ("depth_gradient", "<f8", (6,)),
+                                   ("photometric_cost", "<f8"), ("depth_cost", "<f8"), ("rows", "<i4"),
+                                   ("depth_rows", "<i4"), ("flags", "<u4"), ("reserved", "<i4")])
+assert GEOMETRIC_SYSTEM_DTYPE.itemsize == C.sizeof(native.GeometricSystem)
 
 
 class AlignmentEngine:
@@ -754,6 +772,21 @@ class AlignmentEngine:
         if want_structs:
             res["structs"] = list((native.SampledSystem * n).from_buffer_copy(out.tobytes()))
         return res
+
+    def evaluate_geometric_pairs(self, src, tgt, states, level):
+        """The Gauss-Newton system of each (source, target) pair under the photometric-geometric objective at states [n, 6]
+        on `level`, under the engine's geometric options there (phovo_engine_evaluate_geometric_pairs).  Returns a numpy
+        record array of GEOMETRIC_SYSTEM_DTYPE, the C records themselves: out["depth_information"][p] is the 36 row-major
+        entries of pair p's depth block."""
+        s, t = self._pairs(src, tgt)
+        n = s.size
+        st = np.ascontiguousarray(states, dtype=np.float64).reshape(n, 6)
+        out = np.zeros(max(n, 1), dtype=GEOMETRIC_SYSTEM_DTYPE)    # the C records, written in place
+        ip = C.POINTER(C.c_int)
+        check(self._lib.phovo_engine_evaluate_geometric_pairs(self._h, n, s.ctypes.data_as(ip), t.ctypes.data_as(ip),
+                                                              st.ctypes.data, int(level), out.ctypes.data),
+              "phovo_engine_evaluate_geometric_pairs")
+        return out[:n].copy()
 
     def enqueue_align(self, src, tgt, init_states=None):
         s, t = self._pairs(src, tgt)
