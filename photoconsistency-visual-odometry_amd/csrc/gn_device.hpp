@@ -63,14 +63,9 @@ __device__ __forceinline__ double dpp_f64(double old, double src)
 template <int CTRL>
 __device__ __forceinline__ double dpp_f64(double src) { return dpp_f64<CTRL>(src, src); }
 
-// Pose constants from the state: Rt (:219-241) and temp1..temp24 (:243-266), written with the
-// reference's association.  temp7 = -temp6, temp9 = -temp8, temp21 = -temp5, temp22 = temp2,
-// temp23 = temp1 hold exactly in IEEE arithmetic and are not stored; Rt(0,0) = temp15,
-// Rt(1,0) = temp14, Rt(2,0) = -temp3, Rt(2,1) = temp1, Rt(2,2) = temp2 likewise.  temp10, temp12, temp13 are
-// temp1, temp2, temp3 times cos(yaw) and temp18, temp19, temp20 the same times sin(yaw): the kernel applies
-// those two factors to the sum instead (see pass 2), so only cos(yaw) and sin(yaw) are stored.
-__device__ __forceinline__ void write_pose_constants(double x, double y, double z, double yaw, double pitch,
-                                                     double roll, double *cst, int lane)
+// sin / cos of the three Euler angles: valid in lane 0 on return (the whole wave executes this with a wave-uniform state).
+__device__ __forceinline__ void pose_sincos_lane0(double yaw, double pitch, double roll, int lane, double &sy, double &cy,
+                                                  double &sp, double &cp, double &sr, double &cr)
 {
   // Lanes 0, 1, 2 take yaw, pitch, roll: ONE sincos issue instead of three dependent ones; the six
   // results are then broadcast (the whole wave executes this with a wave-uniform state).
@@ -110,9 +105,22 @@ __device__ __forceinline__ void write_pose_constants(double x, double y, double 
   }
   // Only lane 0 goes on: it has yaw's pair itself and takes pitch's and roll's from lanes 1 and 2 of its own quad with
   // two DPP moves per value (quad_perm), not through the LDS crossbar (twelve ds_bpermute and their round trip before).
-  const double sy = sn, cy = cs;
-  const double sp = dpp_f64<DPP_QUAD_BCAST1>(sn), cp = dpp_f64<DPP_QUAD_BCAST1>(cs);
-  const double sr = dpp_f64<DPP_QUAD_BCAST2>(sn), cr = dpp_f64<DPP_QUAD_BCAST2>(cs);
+  sy = sn; cy = cs;
+  sp = dpp_f64<DPP_QUAD_BCAST1>(sn); cp = dpp_f64<DPP_QUAD_BCAST1>(cs);
+  sr = dpp_f64<DPP_QUAD_BCAST2>(sn); cr = dpp_f64<DPP_QUAD_BCAST2>(cs);
+}
+
+// Pose constants from the state: Rt (:219-241) and temp1..temp24 (:243-266), written with the
+// reference's association.  temp7 = -temp6, temp9 = -temp8, temp21 = -temp5, temp22 = temp2,
+// temp23 = temp1 hold exactly in IEEE arithmetic and are not stored; Rt(0,0) = temp15,
+// Rt(1,0) = temp14, Rt(2,0) = -temp3, Rt(2,1) = temp1, Rt(2,2) = temp2 likewise.  temp10, temp12, temp13 are
+// temp1, temp2, temp3 times cos(yaw) and temp18, temp19, temp20 the same times sin(yaw): the kernel applies
+// those two factors to the sum instead (see pass 2), so only cos(yaw) and sin(yaw) are stored.
+__device__ __forceinline__ void write_pose_constants(double x, double y, double z, double yaw, double pitch,
+                                                     double roll, double *cst, int lane)
+{
+  double sy, cy, sp, cp, sr, cr;
+  pose_sincos_lane0(yaw, pitch, roll, lane, sy, cy, sp, cp, sr, cr);
   if (lane != 0) return;
   cst[C_X] = x; cst[C_Y] = y; cst[C_Z] = z;
   cst[C_R01] = cy * sp * sr - sy * cr;
@@ -134,6 +142,55 @@ __device__ __forceinline__ void write_pose_constants(double x, double y, double 
   cst[C_T24] = cp;
   cst[C_CY] = cy;
   cst[C_SY] = sy;
+}
+
+// The same block as the level kernels (gn_kernels.hip, level_body) keep it: what their two passes CONSUME, in the order
+// they read it, so that every read is one half of a 16-byte pair at a wave-uniform address.  Pass 1 takes slots
+// P_FR00 .. P_T3: the rotation entries as scalars, the translation and the unprojection offsets P_XF .. P_Z as
+// lane-uniform values in vector registers (a value read from LDS is in a vector register already: handing it to the
+// scalar file and back cost two v_readfirstlane_b32 and a v_mov_b64 per constant, in every wave and iteration); pass 2,
+// at the register cap, takes P_OXI .. P_Y, all but three of them as scalars, and keeps pass 1's P_T1 .. P_T3.
+// The focal products are Rt's two projected rows and the translation times fx / fy: each the one product of
+// the same two operands that every wave used to form for itself, now formed once, by the lane that writes the block.
+// P_OXI, P_OYI belong to the level, not to the pose: written by the level's prologue (level_body), never here.
+enum {
+  P_FR00 = 0, P_FR01, P_FR02, P_FR10, P_FR11, P_FR12, P_XF, P_YF,
+  P_OXI, P_OYI, P_Z, P_T1, P_T2, P_T3,
+  P_T4, P_T5, P_T6, P_T8, P_T11, P_T14, P_T16, P_T17, P_T24, P_CY, P_SY, P_X, P_Y, P_COUNT
+};
+static_assert(P_COUNT <= 32 && P_OXI % 2 == 0, "the block has 32 slots; pass 2's first read starts a 16-byte pair");
+
+__device__ __forceinline__ void write_pass_constants(double x, double y, double z, double yaw, double pitch, double roll,
+                                                     double fx, double fy, double *cst, int lane)
+{
+  double sy, cy, sp, cp, sr, cr;
+  pose_sincos_lane0(yaw, pitch, roll, lane, sy, cy, sp, cp, sr, cr);
+  if (lane != 0) return;
+  // (the factors of the focal products are rounded values of their own, as they were when they came out of the block:
+  // opaque, so that no product is folded into the expression in front of it)
+  auto rounded = [](double v) { asm volatile("" : "+v"(v)); return v; };
+  const double r01 = rounded(cy * sp * sr - sy * cr), r02 = rounded(cy * sp * cr + sy * sr);
+  const double r11 = rounded(sy * sp * sr + cy * cr), r12 = rounded(sy * sp * cr - cy * sr);
+  const double t14 = rounded(cp * sy), t15 = rounded(cp * cy);
+  cst[P_FR00] = t15 * fx; cst[P_FR01] = r01 * fx; cst[P_FR02] = r02 * fx;
+  cst[P_FR10] = t14 * fy; cst[P_FR11] = r11 * fy; cst[P_FR12] = r12 * fy;
+  cst[P_XF] = x * fx; cst[P_YF] = y * fy;
+  cst[P_Z] = z;
+  cst[P_T1] = cp * sr;
+  cst[P_T2] = cp * cr;
+  cst[P_T3] = sp;
+  cst[P_T4] = sr * sy + sp * cr * cy;
+  cst[P_T5] = sp * sr * cy - cr * sy;
+  cst[P_T6] = sp * sr * sy + cr * cy;
+  cst[P_T8] = sr * cy - sp * cr * sy;
+  cst[P_T11] = cp * cy + x;          // the reference's bug, kept (:253)
+  cst[P_T14] = t14;
+  cst[P_T16] = sp * sr;
+  cst[P_T17] = sp * cr;
+  cst[P_T24] = cp;
+  cst[P_CY] = cy;
+  cst[P_SY] = sy;
+  cst[P_X] = x; cst[P_Y] = y;
 }
 
 // One butterfly stage of the transposed wave reduction at a distance inside a 16-lane row: N values in, N/2 out.  For the

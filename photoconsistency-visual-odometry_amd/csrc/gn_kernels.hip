@@ -88,7 +88,11 @@ __device__ __forceinline__ void level_body(const GNLevelArgs &A, const LevelLds 
   // (ballots in global memory: written and read back by the same wave, chunk by chunk -- program order is all it needs)
   unsigned long long *const s_mask = (!MASK_REG && A.g_mask) ? A.g_mask + (size_t)pair * (size_t)A.n_chunks : L.mask;
   const int tid = threadIdx.x;
-  const int lane = tid & (WAVE - 1);
+  // (opaque per call: what is derived from the lane is the same for every pair and level, and hoisted out of the fused
+  // kernel's pair and level loops it was spilled to scratch there; three integer instructions per pair and level instead)
+  int lane_of_call = tid & (WAVE - 1);
+  asm volatile("" : "+v"(lane_of_call));
+  const int lane = lane_of_call;
   // wave-uniform by construction; saying so lets the chunk loops run on the scalar unit (s_cmp / s_cbranch)
   // instead of exec-masked vector compares
   const int wave = __builtin_amdgcn_readfirstlane(tid / WAVE);
@@ -125,8 +129,12 @@ __device__ __forceinline__ void level_body(const GNLevelArgs &A, const LevelLds 
     double st[6];
 #pragma unroll
     for (int j = 0; j < 6; j++) st[j] = state_in_lds ? s_state[j] : A.states[(size_t)pair * 6 + j];
-    write_pose_constants(st[0], st[1], st[2], st[3], st[4], st[5], s_cst, lane);
+    write_pass_constants(st[0], st[1], st[2], st[3], st[4], st[5], A.fx, A.fy, s_cst, lane);
     if (lane == 0) {
+      // px = (c - ox) * pz * ifx (:282) as fma(c + 0.5, ifx, -(ox + 0.5) * ifx) * pz: one fma and one product; the two
+      // constants of that form belong to the level and stay in the block for all of its iterations
+      s_cst[P_OXI] = -(A.ox + 0.5) * A.ifx;
+      s_cst[P_OYI] = -A.oy * A.ify;
 #pragma unroll
       for (int j = 0; j < 6; j++) s_state[j] = st[j];
       s_ctl[CTL_DONE] = 0;
@@ -138,8 +146,6 @@ __device__ __forceinline__ void level_body(const GNLevelArgs &A, const LevelLds 
   const double fx = A.fx, fy = A.fy, ox = A.ox, oy = A.oy, ifx = A.ifx, ify = A.ify;
   const double min_d = A.min_depth, max_d = A.max_depth;
   const double dW = (double)W;
-  // px = (c - ox) * pz * ifx (:282) as fma(c + 0.5, ifx, -(ox + 0.5) * ifx) * pz: one fma and one product
-  const double oxi = uniform_f64(-(ox + 0.5) * ifx), oyi = uniform_f64(-oy * ify);
   const double huber_delta = A.huber_delta;
   const bool huber_on = huber_delta > 0.0;
 
@@ -174,16 +180,24 @@ __device__ __forceinline__ void level_body(const GNLevelArgs &A, const LevelLds 
 #ifdef PHOVO_PHASE_STAMPS
     stamp_last = wall_clock64();
 #endif
-    // ---- constants of this iteration (uniform -> SGPRs) -----------------------------------
-    const double cx = uniform_f64(s_cst[C_X]), cyy = uniform_f64(s_cst[C_Y]), cz = uniform_f64(s_cst[C_Z]);
-    const double r01 = uniform_f64(s_cst[C_R01]), r02 = uniform_f64(s_cst[C_R02]);
-    const double r11 = uniform_f64(s_cst[C_R11]), r12 = uniform_f64(s_cst[C_R12]);
-    // the two projected rows of Rt already multiplied by the focal lengths (pass 1 only): (X*fx)*iz + ox (:295) becomes
-    // one fma on X*fx built directly -- eight products per iteration and wave instead of two per pixel
-    const double fr00 = uniform_f64(uniform_f64(s_cst[C_T15]) * fx), fr01 = uniform_f64(r01 * fx), fr02 = uniform_f64(r02 * fx);
-    const double fr10 = uniform_f64(uniform_f64(s_cst[C_T14]) * fy), fr11 = uniform_f64(r11 * fy), fr12 = uniform_f64(r12 * fy);
-    const double t1 = uniform_f64(s_cst[C_T1]), t2 = uniform_f64(s_cst[C_T2]), t3 = uniform_f64(s_cst[C_T3]);
-    const double t14 = uniform_f64(s_cst[C_T14]);
+    // The wave index, opaque per iteration: the run bounds and branch conditions of both passes derive from it on the scalar
+    // unit in a handful of instructions.  As loop invariants they did not fit the scalar file and came back from spill
+    // lanes in front of both passes, a v_readlane_b32 each (a condition is a 64-bit mask: two), and from scratch.
+    // (One wave per pair: the index is 0, the bounds depend on the level alone and stay where they are.)
+    int wv = wave;
+    if constexpr (NW > 1) asm volatile("" : "+s"(wv));
+    // ---- constants of pass 1, as wave 0 left them in the block (write_pass_constants) --------------------------
+    // The two projected rows of Rt come multiplied by the focal lengths -- (X*fx)*iz + ox (:295) is one fma on X*fx built
+    // directly -- and are scalars: each meets two vector operands in its fma.  (As vector operands they cost more than the
+    // twelve v_readfirstlane_b32 they save: profiles/r08_runs/pass_constants_ab.txt.)  Rt's third row serves both passes.
+    const double fr00 = uniform_f64(s_cst[P_FR00]), fr01 = uniform_f64(s_cst[P_FR01]), fr02 = uniform_f64(s_cst[P_FR02]);
+    const double fr10 = uniform_f64(s_cst[P_FR10]), fr11 = uniform_f64(s_cst[P_FR11]), fr12 = uniform_f64(s_cst[P_FR12]);
+    const double t1 = uniform_f64(s_cst[P_T1]), t2 = uniform_f64(s_cst[P_T2]), t3 = uniform_f64(s_cst[P_T3]);
+    // The translation (times fx, fy) and the two unprojection offsets each meet a scalar inside one fma, and an instruction
+    // reads one scalar operand: lane-uniform values in vector registers, straight from the block (pass 1 has registers to
+    // spare; through the scalar file and back they were two v_readfirstlane_b32 and a v_mov_b64 each)
+    const double cxv = s_cst[P_XF], cyv = s_cst[P_YF], czv = s_cst[P_Z];
+    const double oxv = s_cst[P_OXI], oyv = s_cst[P_OYI];
 
     // Owner map in HBM: this iteration's tag (1..OWNER_TAG_PERIOD); when the tags start over the map is wiped.
     int owner_tag = 0;
@@ -209,12 +223,8 @@ __device__ __forceinline__ void level_body(const GNLevelArgs &A, const LevelLds 
       // every wave keeps a load in flight while it computes (the passes are bound by bytes in flight per CU)
       // (PARK, after the first trip: a wave whose first chunk is parked finds that depth in the park block)
       double pz_next;
-      if (PARK && OWNER_LDS && !first_trip && wave < depth_chunks) pz_next = s_i0[k];      // wave-uniform
+      if (PARK && OWNER_LDS && !first_trip && wv < depth_chunks) pz_next = s_i0[k];      // wave-uniform
       else pz_next = plane_load<TD>(rS, k, oD);
-      // the translation sits in vector registers during this pass (pass 1 has registers to spare): an fma takes one
-      // scalar operand, and the rotation entry already is one
-      double cxv = cx * fx, cyv = cyy * fy, czv = cz, oxv = oxi, oyv = oyi;
-      asm volatile("" : "+v"(cxv), "+v"(cyv), "+v"(czv), "+v"(oxv), "+v"(oyv));
       // warp of one 64-pixel chunk: ballot of "valid and landed in bounds" and the target index of every lane
       auto warp_chunk = [&](const double pz, const int chunk, unsigned long long &m_out, int &t_out) {
         // No branch around the arithmetic: a lane that fails the depth gate computes on whatever it loaded and is
@@ -285,7 +295,7 @@ __device__ __forceinline__ void level_body(const GNLevelArgs &A, const LevelLds 
         if (!PARK || first_trip) {
           // two chunks per trip, written out by hand: the ballot / lane accesses are convergent operations, which the
           // compiler will not duplicate for a run-time trip count (#pragma unroll is refused); the bounds are wave-uniform
-          int chunk = wave;
+          int chunk = wv;
           for (; chunk + NW < A.n_chunks; chunk += 2 * NW) {
             chunk_body(chunk, std::false_type{}, std::bool_constant<PARK>{});
             chunk_body(chunk + NW, std::false_type{}, std::bool_constant<PARK>{});
@@ -298,21 +308,21 @@ __device__ __forceinline__ void level_body(const GNLevelArgs &A, const LevelLds 
           // the pixel loop (a select inside it cost 4 % twice: DESIGN.md 3.1): positions 0 .. parked - 2 of this wave's
           // chunks request their successor from LDS, position parked - 1 (its own depth came from LDS) is the first to
           // request from memory, and the positions behind it are the first trip's loop without the store.
-          const int my_chunks = wave < A.n_chunks ? (A.n_chunks - 1 - wave) / NW + 1 : 0;       // wave-uniform
-          const int parked = depth_chunks > wave ? min(my_chunks, (depth_chunks - 1 - wave) / NW + 1) : 0;
+          const int my_chunks = wv < A.n_chunks ? (A.n_chunks - 1 - wv) / NW + 1 : 0;       // wave-uniform
+          const int parked = depth_chunks > wv ? min(my_chunks, (depth_chunks - 1 - wv) / NW + 1) : 0;
           // positions c_lo .. c_end - 1, upwards, two per trip by hand as above (the loop is left at its head only: the
           // depth in flight alternates between two registers, and an exit between the two bodies would cost a copy)
           auto run = [&](int c_lo, int c_end, auto tag) {
             int c = c_lo;
             for (; c + 1 < c_end; c += 2) {
-              chunk_body(wave + c * NW, tag, std::false_type{});
-              chunk_body(wave + (c + 1) * NW, tag, std::false_type{});
+              chunk_body(wv + c * NW, tag, std::false_type{});
+              chunk_body(wv + (c + 1) * NW, tag, std::false_type{});
             }
-            if (c < c_end) chunk_body(wave + c * NW, tag, std::false_type{});
+            if (c < c_end) chunk_body(wv + c * NW, tag, std::false_type{});
           };
           if (parked > 0) {
             run(0, parked - 1, std::true_type{});
-            chunk_body(wave + (parked - 1) * NW, std::false_type{}, std::false_type{});
+            chunk_body(wv + (parked - 1) * NW, std::false_type{}, std::false_type{});
           }
           run(parked, my_chunks, std::false_type{});
         }
@@ -329,7 +339,7 @@ __device__ __forceinline__ void level_body(const GNLevelArgs &A, const LevelLds 
         pzg[0] = pz_next;
 #pragma unroll
         for (int g = 1; g < G; g++) pzg[g] = plane_load<TD>(rS, k + g * NW * WAVE, oD);
-        int chunk = wave;
+        int chunk = wv;
         while (chunk < A.n_chunks) {
 #pragma unroll
           for (int g = 0; g < G; g++) pzn[g] = plane_load<TD>(rS, k + (G + g) * NW * WAVE, oD);     // (past the plane: masked out)
@@ -366,10 +376,12 @@ __device__ __forceinline__ void level_body(const GNLevelArgs &A, const LevelLds 
     PHOVO_STAMP(1)
 
     // ---- pass 2: residual, Jacobian row, normal-equation accumulation ---------------------
-    const double t4 = uniform_f64(s_cst[C_T4]), t5 = uniform_f64(s_cst[C_T5]), t6 = uniform_f64(s_cst[C_T6]);
-    const double t8 = uniform_f64(s_cst[C_T8]), t11 = uniform_f64(s_cst[C_T11]);
-    const double t16 = uniform_f64(s_cst[C_T16]), t17 = uniform_f64(s_cst[C_T17]), t24 = uniform_f64(s_cst[C_T24]);
-    const double cosy = uniform_f64(s_cst[C_CY]), siny = uniform_f64(s_cst[C_SY]);
+    // (its constants are scalars -- the pass sits at the register cap -- read here, behind pass 1, which needs none of them)
+    const double cz = uniform_f64(s_cst[P_Z]), cx = uniform_f64(s_cst[P_X]);
+    const double t4 = uniform_f64(s_cst[P_T4]), t5 = uniform_f64(s_cst[P_T5]), t6 = uniform_f64(s_cst[P_T6]);
+    const double t8 = uniform_f64(s_cst[P_T8]), t11 = uniform_f64(s_cst[P_T11]), t14 = uniform_f64(s_cst[P_T14]);
+    const double t16 = uniform_f64(s_cst[P_T16]), t17 = uniform_f64(s_cst[P_T17]), t24 = uniform_f64(s_cst[P_T24]);
+    const double cosy = uniform_f64(s_cst[P_CY]), siny = uniform_f64(s_cst[P_SY]);
     const double t7 = -t6, t9 = -t8, t21 = -t5;
 
     double acc[NRED];
@@ -386,7 +398,7 @@ __device__ __forceinline__ void level_body(const GNLevelArgs &A, const LevelLds 
       // the pass before / keeps for the pass after.  The kernel is bound by bytes at the fabric; the
       // second read of the depth plane is the only plane traffic that is not algorithmic.
       constexpr bool REV = OWNER_LDS;
-      const int my_chunks = wave < A.n_chunks ? (A.n_chunks - 1 - wave) / NW + 1 : 0;       // wave-uniform
+      const int my_chunks = wv < A.n_chunks ? (A.n_chunks - 1 - wv) / NW + 1 : 0;       // wave-uniform
       const int first = REV ? my_chunks - 1 : 0;                                            // position of the first chunk taken
       const int k_step = REV ? -NW * WAVE : NW * WAVE;
       int k = k0 + first * (NW * WAVE), j = first;
@@ -396,9 +408,8 @@ __device__ __forceinline__ void level_body(const GNLevelArgs &A, const LevelLds 
       int o_n = -1;
       double pz_n = 0.0, gx_n = 0.0, gy_n = 0.0, i1_n = 0.0, i0_n = 0.0;
       // three constants that meet another scalar inside one fma sit in vector registers (an instruction reads one scalar
-      // operand; the compiler otherwise copies them in front of every use: three v_mov_b64 per chunk)
-      double oxv2 = oxi, oyv2 = oyi, cyv2 = cyy;
-      asm volatile("" : "+v"(oxv2), "+v"(oyv2), "+v"(cyv2));
+      // operand; the compiler otherwise copies them in front of every use: three v_mov_b64 per chunk), read as such
+      const double oxv2 = s_cst[P_OXI], oyv2 = s_cst[P_OYI], cyv2 = s_cst[P_Y];
       // Owner map in HBM: the entry is requested TWO chunks ahead (o_raw), so that the gather of the source
       // intensity one chunk ahead starts from an index that has already arrived instead of stalling on it; entries
       // of earlier iterations fail the tag comparison, so nothing is written back (a store per chunk would hold up
@@ -443,7 +454,7 @@ __device__ __forceinline__ void level_body(const GNLevelArgs &A, const LevelLds 
         o_ahead = s_owner[k];
         s_owner[k] = -1;
       }
-      if (PARK && wave + first * NW < depth_chunks) fetch(k, std::true_type{}, my_chunks >= 2);
+      if (PARK && wv + first * NW < depth_chunks) fetch(k, std::true_type{}, my_chunks >= 2);
       else fetch(k, std::false_type{}, my_chunks >= 2);
       // `behind`: chunks of this wave that follow the one the body's fetch is for (wave-uniform)
       auto chunk_body = [&](const int chunk, auto next_parked_tag, const int behind) {
@@ -483,7 +494,7 @@ __device__ __forceinline__ void level_body(const GNLevelArgs &A, const LevelLds 
           J[0] = (gxi * fx) * t25;                                        // :317
           J[1] = (gyi * fy) * t25;                                        // :322
           J[2] = -(J[0] * Au + J[1] * Bv) * t25;                          // :325-326
-          J[3] = J[0] * (cyy - Bv) + J[1] * (Au - px * cx);               // :329-330
+          J[3] = J[0] * (cyv2 - Bv) + J[1] * (Au - px * cx);               // :329-330
           J[4] = (J[0] * cosy + J[1] * siny) * Zr + Cm * J[2];            // :333-336
           J[5] = J[0] * (py * t4 + pz * t21) + J[1] * (pz * t7 + py * t9) + Dm * J[2];                   // :339-342
 
@@ -517,22 +528,22 @@ __device__ __forceinline__ void level_body(const GNLevelArgs &A, const LevelLds 
         // positions c_hi .. c_lo of this wave's chunks, downwards; `tag`: is the chunk BEHIND each of them parked?
         auto run = [&](int c_hi, int c_lo, auto tag) {
           for (int c = c_hi; c >= c_lo; c -= 2) {
-            chunk_body(wave + c * NW, tag, c - 1);           // (its fetch is for position c - 1: c - 1 positions follow that)
-            if (c > c_lo) chunk_body(wave + (c - 1) * NW, tag, c - 2);
+            chunk_body(wv + c * NW, tag, c - 1);           // (its fetch is for position c - 1: c - 1 positions follow that)
+            if (c > c_lo) chunk_body(wv + (c - 1) * NW, tag, c - 2);
           }
         };
         if (PARK) {
           // position c's successor is chunk wave + (c - 1) * NW: parked iff that is below depth_chunks (position 0's lies
           // in front of the image: read from the parked block too, clamped, unused)
           // (no chunk of this wave parked: -1, everything in the first run)
-          const int c_split = depth_chunks > wave ? min(my_chunks - 1, (depth_chunks - 1 - wave) / NW + 1) : -1;
+          const int c_split = depth_chunks > wv ? min(my_chunks - 1, (depth_chunks - 1 - wv) / NW + 1) : -1;
           run(my_chunks - 1, c_split + 1, std::false_type{});
           run(min(my_chunks - 1, c_split), 0, std::true_type{});
         } else {
           run(my_chunks - 1, 0, std::false_type{});
         }
       } else {
-        for (int chunk = wave; chunk < A.n_chunks; chunk += 2 * NW) {
+        for (int chunk = wv; chunk < A.n_chunks; chunk += 2 * NW) {
           chunk_body(chunk, std::false_type{}, 0);
           if (chunk + NW < A.n_chunks) chunk_body(chunk + NW, std::false_type{}, 0);
         }
@@ -564,8 +575,12 @@ __device__ __forceinline__ void level_body(const GNLevelArgs &A, const LevelLds 
     // ---- wave 0: cross-wave sum (fixed order), solve, update, terminate ------------------------
     if (wave == 0) {
       // lane l sums value (l & 31) over half of the waves, the halves meet in one exchange (sum_rows_broadcast)
+      // (the lane is opaque here for the reason it is in front of the row store above: the addresses of this section are
+      // loop-invariant, and one hoisted out of the iteration loop came back as a scratch reload inside the section)
+      int ln0 = lane;
+      asm volatile("" : "+v"(ln0));
       double h[21], g[6];
-      sum_rows_broadcast<NW>(lane, s_red, h, g, last_valid);
+      sum_rows_broadcast<NW>(ln0, s_red, h, g, last_valid);
 #ifdef PHOVO_PHASE_STAMPS
       asm volatile("" :: "v"(h[0]), "v"(g[5]));
       const unsigned long long solve_t0 = wall_clock64();
@@ -599,7 +614,7 @@ __device__ __forceinline__ void level_body(const GNLevelArgs &A, const LevelLds 
       const unsigned long long solve_t2 = wall_clock64();
       solve_sum[2] += solve_t2 - solve_t1;         // update, norm, termination
 #endif
-      if (!done) write_pose_constants(st[0], st[1], st[2], st[3], st[4], st[5], s_cst, lane);   // wave-uniform branch
+      if (!done) write_pass_constants(st[0], st[1], st[2], st[3], st[4], st[5], fx, fy, s_cst, lane);   // wave-uniform branch
 #ifdef PHOVO_PHASE_STAMPS
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       solve_sum[3] += wall_clock64() - solve_t2;   // sincos and pose constants
