@@ -50,8 +50,10 @@ typedef enum phovo_status {
                                     library, but it says so here.                                 */
 #define PHOVO_PAIR_WINDOW_FALLBACK 2u  /* informational: on a level whose owner map exceeds LDS this pair's warp left
                                     the sliding window of the fast kernel (a displacement of more than about 20 rows of
-                                    the level -- 13 800 pixels in linear index at 640x480, 7 700 at 320x240 -- e.g. a
-                                    large in-plane rotation) and the exact kernel with the map in HBM finished it.  The
+                                    the level, e.g. a large in-plane rotation) and the exact kernel with the map in HBM
+                                    finished it.  In linear index a uniform displacement D stays inside iff
+                                    -(m - 1) * 1536 <= D <= m * 1536, m the level's reach in bands: forward 15 360 pixels
+                                    at 640x480 (m = 10) and 9 216 at 320x240 (m = 6), backward 13 824 and 7 680.  The
                                     result is the same; only the time differs.                                   */
 #define PHOVO_PAIR_RANK_DEFICIENT 4u  /* fewer than six Jacobian rows were filled in SOME iteration of some level (the
                                     flag is sticky; phovo_pair_report.valid_pixels holds the count of each level's last

@@ -331,7 +331,7 @@ def _cond(hessians):
 
 class PhotoRef:
     """The oracle's result of one photometric case on the given plane lists: state, iteration counts, valid pixels of each
-    level's last iteration, last gradient norm, the largest cond(J^T J) of its trace and the gradient norm of every
+    level's last iteration, last gradient norm, the trace, the largest cond(J^T J) of it and the gradient norm of every
     iteration; nudged(): the same run with fx one ulp larger."""
 
     def __init__(self, ocfg, K, planes, init=None, huber=None):
@@ -339,6 +339,7 @@ class PhotoRef:
         self.K = K
         self.nl = ocfg.num_levels
         self.state, self.its, tr = self._run(K, True)
+        self.trace = tr
         self.valid = oracle.valid_pixels_per_level(tr, self.nl)
         self.gnorm = float(np.linalg.norm(tr[-1]["gradient"]))
         self.gnorms = [(e["level"], float(np.linalg.norm(e["gradient"]))) for e in tr]
