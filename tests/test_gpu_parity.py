@@ -702,7 +702,7 @@ def test_every_kernel_variant_matches_oracle(size, expect):
     ((200, 152), 2, [6, 9], [0.0, 0.0]),                  # odd sizes, partial last chunk
 ])
 def test_wide_form_equals_persistent_form_and_oracle(size, levels, max_iter, min_grad):
-    """The many-workgroups-per-pair form (three launches per iteration) against the one-workgroup-per-pair form
+    """The many-workgroups-per-pair form (two launches per iteration) against the one-workgroup-per-pair form
     and the oracle: identical iteration counts, poses within the bar, pairs that stop at different iterations."""
     w, h = size
     pairs = [synthetic.make_pair(40 + i, w, h, holes=0.02, trans=0.004 * (i + 1), rot=0.002 * (i + 1)) for i in range(3)]
