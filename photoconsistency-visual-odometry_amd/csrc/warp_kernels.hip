@@ -77,8 +77,10 @@ struct DeviceBuffers {      // freed on every exit path
 #define PHOVO_WARP_CHECK(expr)                                                                  \
   do {                                                                                          \
     hipError_t _e = (expr);                                                                     \
-    if (_e != hipSuccess)                                                                       \
+    if (_e != hipSuccess) {                                                                     \
+      (void)hipGetLastError(); /* reported here: not left behind for a later launch check */    \
       return fail(PHOVO_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));              \
+    }                                                                                           \
   } while (0)
 
 }  // namespace
@@ -128,6 +130,9 @@ extern "C" int phovo_warp_image(int device, const uint8_t *intensity, size_t int
                                     (size_t)w * sizeof(double), (size_t)h, hipMemcpyHostToDevice, b.stream));
   PHOVO_WARP_CHECK(hipMemsetAsync(b.p[2], 0xFF, n * sizeof(int), b.stream));      // every owner = -1
   const unsigned blocks = (unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
+  // hipGetLastError returns the thread's last recorded error, whoever made it (a refused hipSetDevice of an earlier
+  // call, another library): drop it, so that the checks below speak of these launches only
+  (void)hipGetLastError();
   hipLaunchKernelGGL(k_warp_scatter, dim3(blocks), dim3(256), 0, b.stream, a);
   PHOVO_WARP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(k_warp_gather, dim3(blocks), dim3(256), 0, b.stream, a);
