@@ -3,7 +3,7 @@
 //
 //   ./PhotoconsistencyVisualOdometry <config_file.yml> <rgbd_dataset_directory> <output_trajectory_file> [--batch [--gpus N] [--rccl]]
 //                                    [--method analytic|ceres|biobjective|affine|geometric] [--information <file>] [--system <file>]
-//                                    [--geometric-system <file>]
+//                                    [--geometric-system <file>] [--objective-system <file>]
 // --method picks the aligner as the reference's USE_PHOTOCONSISTENCY_ODOMETRY_METHOD does (0 = analytic, the default;
 // 1 = ceres: Levenberg-Marquardt on bilinear samples, CPhotoconsistencyOdometryCeres, which reads config_*_ceres.yml
 // files; 2 = bi-objective: photometric and depth error together, CPhotoconsistencyOdometryBiObjective), in every mode;
@@ -28,6 +28,12 @@
 // sum J_I J_I^T and the 21 of the depth block sum J_D J_D^T (phovo_geometric_system_format; the system the aligner solves is
 // their entry-by-entry sum).  The loop takes it from the class surface (GetGeometricSystem), --batch from
 // phovo_engine_evaluate_geometric_pairs; both write the same bytes, the trajectory file is the same with and without the
+// flag, and the printed times do not include the evaluation.
+// --objective-system <file> (not in the reference; --method ceres or biobjective, one device): the same for the reference's
+// methods 1 and 2 -- one line per pair, `timestamp rows cost` and the 21 upper-triangle entries of J^T J
+// (phovo_pair_system_format) at the pair's optimal state on the finest optimised level; under ceres cost is r^T r, twice
+// the solver's final cost.  The loop takes it from the class surface (GetObjectiveSystem), --batch from
+// phovo_engine_evaluate_objective_pairs; both write the same bytes, the trajectory file is the same with and without the
 // flag, and the printed times do not include the evaluation.
 //
 // Behaviour kept from the reference's app (apps/PhotoconsistencyVisualOdometry/PhotoconsistencyVisualOdometry.cpp):
@@ -169,11 +175,23 @@ static phovo_geometric_system geometricSystemOf(Odometry &, long)
   throw std::runtime_error("--geometric-system needs --method geometric");
 }
 
+// GetObjectiveSystem() of the classes that have one, in the same way.
+template <class Odometry>
+static auto objectiveSystemOf(Odometry &odometry, int) -> decltype(odometry.GetObjectiveSystem())
+{
+  return odometry.GetObjectiveSystem();
+}
+template <class Odometry>
+static phovo_pair_system objectiveSystemOf(Odometry &, long)
+{
+  throw std::runtime_error("--objective-system needs --method ceres or --method biobjective");
+}
+
 static void printHelp()
 {
   std::cout << "./PhotoconsistencyVisualOdometry <config_file.yml> <rgbd_dataset_directory> "
                "<output_trajectory_file> [--batch [--gpus N] [--rccl]] [--method analytic|ceres|biobjective|affine|geometric] "
-               "[--information <file>] [--system <file>] [--geometric-system <file>]" << std::endl;
+               "[--information <file>] [--system <file>] [--geometric-system <file>] [--objective-system <file>]" << std::endl;
 }
 
 #define PHOVO_OK_OR_FAIL(call)                                                              \
@@ -190,6 +208,7 @@ int main(int argc, char *argv[])
   std::string informationPath;                        // --information <file>: the pairs' systems at their optimal states
   std::string systemPath;                             // --system <file>: the same for the sampled aligners
   std::string geometricSystemPath;                    // --geometric-system <file>: the same for --method geometric
+  std::string objectiveSystemPath;                    // --objective-system <file>: the same for --method ceres | biobjective
   for (int i = 4; i < argc; i++) {
     const std::string a(argv[i]);
     if (a == "--batch") batch = true;
@@ -207,6 +226,7 @@ int main(int argc, char *argv[])
     else if (a == "--information" && i + 1 < argc) informationPath = argv[++i];
     else if (a == "--system" && i + 1 < argc) systemPath = argv[++i];
     else if (a == "--geometric-system" && i + 1 < argc) geometricSystemPath = argv[++i];
+    else if (a == "--objective-system" && i + 1 < argc) objectiveSystemPath = argv[++i];
     else { printHelp(); return EXIT_FAILURE; }
   }
   if (nGpus < 1 || (nGpus > 1 && !batch)) { std::cerr << "--gpus N needs --batch and N >= 1" << std::endl; return EXIT_FAILURE; }
@@ -217,7 +237,8 @@ int main(int argc, char *argv[])
     return EXIT_FAILURE;
   }
   if (information && objective != PHOVO_OBJECTIVE_PHOTOMETRIC) {
-    std::cerr << "--information needs --method analytic (the bi-objective and the Ceres method have no pair system)" << std::endl;
+    std::cerr << "--information needs --method analytic (the bi-objective and the Ceres method have no pair system there: "
+                 "--objective-system writes theirs)" << std::endl;
     return EXIT_FAILURE;
   }
   const bool sampled = !systemPath.empty();
@@ -236,6 +257,15 @@ int main(int argc, char *argv[])
   }
   if (geometricSystem && objective != PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC) {
     std::cerr << "--geometric-system needs --method geometric" << std::endl;
+    return EXIT_FAILURE;
+  }
+  const bool objectiveSystem = !objectiveSystemPath.empty();
+  if (objectiveSystem && (nGpus > 1 || rccl)) {
+    std::cerr << "--objective-system runs on one device: it cannot be combined with --gpus N > 1 or --rccl" << std::endl;
+    return EXIT_FAILURE;
+  }
+  if (objectiveSystem && objective != PHOVO_OBJECTIVE_TRUST_REGION && objective != PHOVO_OBJECTIVE_BIOBJECTIVE) {
+    std::cerr << "--objective-system needs --method ceres or --method biobjective" << std::endl;
     return EXIT_FAILURE;
   }
   if (!fileExists(configFile)) { std::cerr << "Input config file " << configFile << " does not exist" << std::endl; return EXIT_FAILURE; }
@@ -298,6 +328,11 @@ int main(int argc, char *argv[])
     geometricSystemFile.open(geometricSystemPath.c_str());
     if (!geometricSystemFile.is_open()) { std::cerr << "Cannot open output geometric system file " << geometricSystemPath << std::endl; return EXIT_FAILURE; }
   }
+  std::ofstream objectiveSystemFile;
+  if (objectiveSystem) {
+    objectiveSystemFile.open(objectiveSystemPath.c_str());
+    if (!objectiveSystemFile.is_open()) { std::cerr << "Cannot open output objective system file " << objectiveSystemPath << std::endl; return EXIT_FAILURE; }
+  }
   if (nFrames < 2) return EXIT_SUCCESS;
 
   Matrix44Type pose = Matrix44Type::Identity();
@@ -332,6 +367,7 @@ int main(int argc, char *argv[])
         if (information && !writeSystem(informationFile, rgb[t].timestamp, odometry.GetPairSystem())) return EXIT_FAILURE;
         if (sampled && !writeSystem(systemFile, rgb[t].timestamp, odometry.GetSampledSystem())) return EXIT_FAILURE;
         if (geometricSystem && !writeSystem(geometricSystemFile, rgb[t].timestamp, geometricSystemOf(odometry, 0))) return EXIT_FAILURE;
+        if (objectiveSystem && !writeSystem(objectiveSystemFile, rgb[t].timestamp, objectiveSystemOf(odometry, 0))) return EXIT_FAILURE;
         std::cout << "Rt:" << std::endl << Rt << std::endl;
         prevGray = curGray.clone();
         prevDepth = curDepth.clone();
@@ -434,6 +470,8 @@ int main(int argc, char *argv[])
       if (information && finestLevel < 0) { std::cerr << "--information: the configuration optimises no level" << std::endl; return EXIT_FAILURE; }
       if (sampled && finestLevel < 0) { std::cerr << "--system: the configuration optimises no level" << std::endl; return EXIT_FAILURE; }
       if (geometricSystem && finestLevel < 0) { std::cerr << "--geometric-system: the configuration optimises no level" << std::endl; return EXIT_FAILURE; }
+      if (objectiveSystem && finestLevel < 0) { std::cerr << "--objective-system: the configuration optimises no level" << std::endl; return EXIT_FAILURE; }
+      std::vector<phovo_pair_system> objectiveSystems(objectiveSystem ? (size_t)nPairs : 0);
       std::vector<phovo_geometric_system> geometricSystems(geometricSystem ? (size_t)nPairs : 0);
       const int systemDim = objective == PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE ? 8 : 6;
       std::vector<phovo_sampled_system> sampledSystems(sampled ? (size_t)nPairs : 0);
@@ -489,7 +527,10 @@ int main(int argc, char *argv[])
           if (!rccl) {
             if (phovo_engine_align_pairs(engine, b - a, src.data(), tgt.data(), nullptr, states.data() + (size_t)a * 6, nullptr) != PHOVO_OK)
               return fail("phovo_engine_align_pairs");
-            if (information || sampled || geometricSystem) tAligned = std::chrono::steady_clock::now();      // (the evaluation is not part of the timed run)
+            if (information || sampled || geometricSystem || objectiveSystem) tAligned = std::chrono::steady_clock::now();      // (the evaluation is not part of the timed run)
+            if (objectiveSystem && phovo_engine_evaluate_objective_pairs(engine, b - a, src.data(), tgt.data(), states.data() + (size_t)a * 6,
+                                                                         finestLevel, objectiveSystems.data() + a) != PHOVO_OK)
+              return fail("phovo_engine_evaluate_objective_pairs");
             if (geometricSystem && phovo_engine_evaluate_geometric_pairs(engine, b - a, src.data(), tgt.data(), states.data() + (size_t)a * 6,
                                                                          finestLevel, geometricSystems.data() + a) != PHOVO_OK)
               return fail("phovo_engine_evaluate_geometric_pairs");
@@ -542,7 +583,7 @@ int main(int argc, char *argv[])
           std::copy(group.gathered(g), group.gathered(g) + (size_t)(b - a) * 6, states.begin() + (size_t)a * 6);
         }
       }
-      const auto t1 = (information || sampled || geometricSystem) ? tAligned : std::chrono::steady_clock::now();
+      const auto t1 = (information || sampled || geometricSystem || objectiveSystem) ? tAligned : std::chrono::steady_clock::now();
       std::cout << "Time = " << std::chrono::duration<double>(t1 - t0).count() << " sec. (" << nPairs << " pairs on " << nGpus
                 << " device(s), upload and pyramids included)" << std::endl;
       std::vector<double> poses((size_t)nPairs * 16);
@@ -554,6 +595,7 @@ int main(int argc, char *argv[])
         if (information && !writeSystem(informationFile, rgb[(size_t)p + 1].timestamp, systems[(size_t)p])) return EXIT_FAILURE;
         if (sampled && !writeSystem(systemFile, rgb[(size_t)p + 1].timestamp, sampledSystems[(size_t)p])) return EXIT_FAILURE;
         if (geometricSystem && !writeSystem(geometricSystemFile, rgb[(size_t)p + 1].timestamp, geometricSystems[(size_t)p])) return EXIT_FAILURE;
+        if (objectiveSystem && !writeSystem(objectiveSystemFile, rgb[(size_t)p + 1].timestamp, objectiveSystems[(size_t)p])) return EXIT_FAILURE;
       }
     }
   } catch (const std::exception &e) {
@@ -564,5 +606,6 @@ int main(int argc, char *argv[])
   if (information) informationFile.close();
   if (sampled) systemFile.close();
   if (geometricSystem) geometricSystemFile.close();
+  if (objectiveSystem) objectiveSystemFile.close();
   return EXIT_SUCCESS;
 }

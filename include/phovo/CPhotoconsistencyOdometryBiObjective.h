@@ -8,7 +8,8 @@
 // The types come from the same place as CPhotoconsistencyOdometryAnalytic.h's (PHOVO_HIP_USE_REFERENCE_TYPES or
 // phovo/compat/).  It differs from that class in one method only: SetTargetFrame keeps the target's depth (reference
 // :566-578), so the depth image must be valid.  Plane storage, sampling and Huber extensions other than the reference's
-// are refused (std::runtime_error, PHOVO_E_UNSUPPORTED), and so is the inherited GetPairSystem().
+// are refused (std::runtime_error, PHOVO_E_UNSUPPORTED), and so is the inherited GetPairSystem(); this objective's system
+// is GetObjectiveSystem().
 #ifndef PHOVO_HIP_CPHOTOCONSISTENCY_ODOMETRY_BIOBJECTIVE_H
 #define PHOVO_HIP_CPHOTOCONSISTENCY_ODOMETRY_BIOBJECTIVE_H
 
@@ -43,6 +44,16 @@ class CPhotoconsistencyOdometryBiObjective : public CPhotoconsistencyOdometryAna
                                                 reinterpret_cast<const double *>(depthImage.data),
                                                 static_cast<size_t>(depthImage.step), intensityImage.cols,
                                                 intensityImage.rows), "SetTargetFrame");
+  }
+
+  // Not in the reference: J^T J and J^T r of the 2N-row system, r^T r over all 2N residuals and the contributing pixels at
+  // the optimal state on the finest level the configuration optimises.  Evaluated on demand; std::runtime_error
+  // (PHOVO_E_NOT_READY) before Optimize() and after a Set*Frame since.
+  phovo_pair_system GetObjectiveSystem() const
+  {
+    phovo_pair_system s;
+    Base::Check(phovo_odometry_get_objective_system(Base::Handle(), &s), "GetObjectiveSystem");
+    return s;
   }
 };
 

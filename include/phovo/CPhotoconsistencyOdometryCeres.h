@@ -10,7 +10,7 @@
 // phovo/compat/).  ReadConfigurationFile reads the config_*_ceres.yml keys (reference :526-576), and Optimize() prints one
 // "Ceres Solver Report" line per optimised level to stdout, as the reference does after each solve (:494).  Extensions
 // other than the reference's are refused (std::runtime_error, PHOVO_E_UNSUPPORTED), and so is the inherited
-// GetPairSystem().
+// GetPairSystem(); this objective's system is GetObjectiveSystem().
 #ifndef PHOVO_HIP_CPHOTOCONSISTENCY_ODOMETRY_CERES_H
 #define PHOVO_HIP_CPHOTOCONSISTENCY_ODOMETRY_CERES_H
 
@@ -59,6 +59,16 @@ class CPhotoconsistencyOdometryCeres : public phovo::Analytic::CPhotoconsistency
     phovo_trust_region_report r;
     Base::Check(phovo_odometry_get_trust_region_report(Base::Handle(), &r), "GetSolverReport");
     return r;
+  }
+
+  // Not in the reference: J^T J, J^T r, r^T r and the row count at the optimal state on the finest level the configuration
+  // optimises -- what ceres::Covariance works from.  cost is r^T r: TWICE Ceres's cost and twice GetSolverReport()'s
+  // final_cost.  Evaluated on demand; std::runtime_error (PHOVO_E_NOT_READY) before Optimize() and after a Set*Frame since.
+  phovo_pair_system GetObjectiveSystem() const
+  {
+    phovo_pair_system s;
+    Base::Check(phovo_odometry_get_objective_system(Base::Handle(), &s), "GetObjectiveSystem");
+    return s;
   }
 
   // Not in the reference: the solver options, per level (ReadConfigurationFile sets them from the file).

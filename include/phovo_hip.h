@@ -196,7 +196,8 @@ typedef struct phovo_extensions {
  *                                photometric objective's: switching between the two keeps the frame pool.
  *                                Reference-exact only: fp64 planes, nearest / scatter sampling setting, no Huber
  *                                weights, jacobian_corrected 0 -- anything else is PHOVO_E_UNSUPPORTED, whichever setter
- *                                comes second; phovo_engine_evaluate_pairs is PHOVO_E_UNSUPPORTED too.  Fusion,
+ *                                comes second; phovo_engine_evaluate_pairs is PHOVO_E_UNSUPPORTED too (this objective's
+ *                                system is phovo_engine_evaluate_objective_pairs).  Fusion,
  *                                sliding-window, wide and latency-form settings are accepted and have no effect.
  *                                phovo_pair_report: iterations[L] = LM steps (iteration 0 not counted), valid_pixels[L] =
  *                                owned targets at the final point, gradient_norm = ||J^T r||_2 there (of the last level
@@ -483,6 +484,11 @@ int phovo_odometry_get_sampled_system(const phovo_odometry *o, phovo_sampled_sys
  * on the finest level the configuration optimises, evaluated on demand.  PHOVO_E_NOT_READY before a successful Optimize()
  * and after a Set*Frame since; PHOVO_E_UNSUPPORTED under another objective. */
 int phovo_odometry_get_geometric_system(const phovo_odometry *o, phovo_geometric_system *out);
+/* not in the reference: the system (phovo_pair_system) of the trust-region and of the bi-objective objective at the
+ * optimal state on the finest level the configuration optimises, evaluated on demand
+ * (phovo_engine_evaluate_objective_pairs).  PHOVO_E_UNSUPPORTED under any other objective; PHOVO_E_NOT_READY before a
+ * successful Optimize() and after a Set*Frame since. */
+int phovo_odometry_get_objective_system(const phovo_odometry *o, phovo_pair_system *out);
 /* Device time of the last Optimize() in milliseconds (HIP events; the reference wraps the same
  * call in cv::TickMeter, apps/PhotoconsistencyFrameAlignment/PhotoconsistencyFrameAlignment.cpp:99-102). */
 int phovo_odometry_last_optimize_ms(const phovo_odometry *o, double *ms);
@@ -778,6 +784,35 @@ int phovo_engine_evaluate_sampled_pairs(phovo_engine *e, int n_pairs, const int 
  * large batches run in groups whose tile sums take at most 64 MB together (436 pairs at 640x480). */
 int phovo_engine_evaluate_geometric_pairs(phovo_engine *e, int n_pairs, const int *src, const int *tgt,
                                           const double *states /* [n_pairs][6] */, int level, phovo_geometric_system *out);
+
+/* The system (phovo_pair_system) of the two objectives that are the reference's own other methods, at the states
+ * [n_pairs][6] on one level; the call dispatches on the engine's objective.  Synchronous; ordered behind every enqueue in
+ * flight, and it changes nothing that phovo_engine_fetch / fetch_results / fetch_trust_region_reports return.
+ *   PHOVO_OBJECTIVE_TRUST_REGION  the rows the Levenberg-Marquardt aligner fills at that state: depth gate
+ *       min_d < d < max_d, projection with true divisions, a pixel lands iff 0 <= u < W and 0 <= v < H on the real
+ *       values, target W trunc(v) + trunc(u) owned by the largest source index landing there, r = I1(u, v) - I0 and the
+ *       row from SampleLinear's taps with the exact warp Jacobian.  information = J^T J, gradient = J^T r, rows = owned
+ *       targets, cost = r^T r: TWICE Ceres's cost (1/2 sum r^2) and twice phovo_trust_region_level.final_cost.
+ *   PHOVO_OBJECTIVE_BIOBJECTIVE   the 2N-row system of the bi-objective aligner with the reference's row
+ *       collisions: row m carries Jint(m) if m < N, m > 0 and pixel m contributes, else Jdep(m/2) if m is even and pixel
+ *       m/2 contributes; its residual is that of the larger of owner[m] (m < N) and owner[m/2] (m even), a tie (m = 0)
+ *       going to depth.  The gain and the depth-gradient planes are the ones resident for the target frame (made with the
+ *       max depth in force at upload); the gate uses the depth range in force at the call.  information = J^T J and
+ *       gradient = J^T r over all 2N rows, cost = r^T r over the whole 2N residual vector (entries whose Jacobian row is
+ *       empty count), rows = contributing source pixels (what valid_pixels reports under this objective).
+ * information is exactly symmetric (filled from the upper triangle).  flags: PHOVO_PAIR_RANK_DEFICIENT if rows < 6,
+ * PHOVO_PAIR_NONFINITE if any sum is inf or NaN.  A pair's record is the same bit for bit whatever the batch, its position
+ * in it, or any setting of the engine.
+ *   PHOVO_E_UNSUPPORTED       the photometric objective (phovo_engine_evaluate_pairs or _evaluate_sampled_pairs serves
+ *                             it), the affine-illumination objective (phovo_engine_evaluate_sampled_pairs), the
+ *                             photometric-geometric objective (phovo_engine_evaluate_geometric_pairs)
+ *   PHOVO_E_INVALID_ARGUMENT  NULL pointers (with n_pairs > 0), n_pairs < 0, a frame index or level out of range
+ *   PHOVO_E_NOT_READY         as phovo_engine_evaluate_pairs
+ * n_pairs == 0 is OK.  Device memory: the evaluate workspace (shared with the other evaluate calls, kept until the engine
+ * is destroyed) -- per pair of a group 4 bytes of owner map per pixel, 1 bit of ballots per pixel and 256 bytes of tile
+ * sums per 1024 pixels; large batches run in groups whose owner maps take at most 256 MB (218 pairs at 640x480). */
+int phovo_engine_evaluate_objective_pairs(phovo_engine *e, int n_pairs, const int *src, const int *tgt,
+                                          const double *states /* [n_pairs][6] */, int level, phovo_pair_system *out);
 
 /* Pipelining.  Pairs are independent, and with data-dependent termination a batch ends with a few long pairs on an
  * otherwise idle chip.  The engine therefore keeps PHOVO_ENQUEUE_DEPTH enqueues in flight, each with its own stream, pair

@@ -1,5 +1,5 @@
 // The Gauss-Newton systems at given poses behind the C ABI (include/phovo_hip.h): phovo_engine_evaluate_pairs,
-// _evaluate_sampled_pairs and _evaluate_geometric_pairs.  Each entry point keeps what is its own -- the objectives and
+// _evaluate_sampled_pairs, _evaluate_geometric_pairs and _evaluate_objective_pairs.  Each entry point keeps what is its own -- the objectives and
 // samplings it refuses, its state width, its workspace regions, the extras of its args and its launch -- and shares the
 // rest: the refusals about the call, the one workspace, and the loop over groups of pairs.
 
@@ -241,6 +241,59 @@ int phovo_engine_evaluate_geometric_pairs(phovo_engine *e, int n_pairs, const in
   return eval_run(e, c, group, at + 2, d_out, [&](int pairs) {
     return gn_eval_geometric_pairs(b, pairs, d_part_sampled, d_sampled, d_part_depth, d_out, e->stream);
   });
+}
+
+int phovo_engine_evaluate_objective_pairs(phovo_engine *e, int n_pairs, const int *src, const int *tgt, const double *states,
+                                          int level, phovo_pair_system *out)
+{
+  if (!e) return fail(PHOVO_E_INVALID_ARGUMENT, "evaluate_objective_pairs: null engine");
+  switch (e->objective) {
+    case PHOVO_OBJECTIVE_TRUST_REGION:
+    case PHOVO_OBJECTIVE_BIOBJECTIVE:
+      break;
+    case PHOVO_OBJECTIVE_PHOTOMETRIC:
+      return fail(PHOVO_E_UNSUPPORTED, "evaluate_objective_pairs: the photometric objective has its system in "
+                                       "phovo_engine_evaluate_pairs (nearest / scatter sampling) or "
+                                       "phovo_engine_evaluate_sampled_pairs (bilinear sampling)");
+    case PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE:
+      return fail(PHOVO_E_UNSUPPORTED, "evaluate_objective_pairs: the affine-illumination objective has its system in "
+                                       "phovo_engine_evaluate_sampled_pairs");
+    default:
+      return fail(PHOVO_E_UNSUPPORTED, "evaluate_objective_pairs: the photometric-geometric objective has its system in "
+                                       "phovo_engine_evaluate_geometric_pairs");
+  }
+  // (set_objective / set_extensions hold both objectives to fp64 planes, nearest / scatter sampling, no Huber weights; under
+  // the bi-objective a target upload carries its depth, so PHOVO_ROLE_TARGET covers the planes the rows read)
+  const EvalCall c{"evaluate_objective_pairs", n_pairs, src, tgt, states, 6, level, out, sizeof(*out)};
+  int st = eval_check(e, c, false);
+  if (st != PHOVO_OK || n_pairs == 0) return st;
+
+  // Workspace for a group of G pairs, as phovo_engine_evaluate_pairs: owner maps first (kept at -1 between calls), then
+  // ballots, tile sums, states, pair indices and the results.
+  const LevelPool &lv = e->levels[level];
+  const size_t n = (size_t)lv.n, n_chunks = (n + 63) / 64;
+  const int group = eval_group(n_pairs, EVAL_OWNER_CAP_BYTES, n * sizeof(int));
+  const size_t G = (size_t)group;
+  const size_t bytes[] = {G * n * sizeof(int), G * n_chunks * sizeof(unsigned long long),
+                          G * gn_eval_slab_doubles_per_pair(lv.n) * sizeof(double),
+                          G * 6 * sizeof(double), G * sizeof(int), G * sizeof(int), G * sizeof(phovo_pair_system)};
+  unsigned char *at[7];
+  st = eval_workspace(e, bytes, at, G * n);
+  if (st != PHOVO_OK) return st;
+
+  GNObjectiveEvalArgs a{};
+  eval_args(a, e, level, at + 3);
+  a.dgx_off = lv.dgx_off; a.dgy_off = lv.dgy_off; a.gain_off = lv.gain_off;
+  auto *d_owner = reinterpret_cast<int *>(at[0]);
+  auto *d_mask = reinterpret_cast<unsigned long long *>(at[1]);
+  auto *d_part = reinterpret_cast<double *>(at[2]);
+  auto *d_out = reinterpret_cast<phovo_pair_system *>(at[6]);
+  st = eval_run(e, c, group, at + 3, d_out, [&](int pairs) {
+    return gn_eval_objective_pairs(a, e->objective, pairs, d_owner, d_mask, d_part, d_out, e->stream);
+  });
+  // the trust region's pass 2 and the bi-objective's fill have put every owner map of every group back to -1
+  if (st == PHOVO_OK) e->eval_owner_clean = G * n;
+  return st;
 }
 
 }  // extern "C"

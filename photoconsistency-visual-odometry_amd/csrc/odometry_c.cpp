@@ -475,6 +475,22 @@ int phovo_odometry_get_geometric_system(const phovo_odometry *o, phovo_geometric
   return phovo_engine_evaluate_geometric_pairs(o->engine, 1, &src, &tgt, o->state, finest, out);
 }
 
+int phovo_odometry_get_objective_system(const phovo_odometry *o, phovo_pair_system *out)
+{
+  if (!o || !out) return fail(PHOVO_E_INVALID_ARGUMENT, "get_objective_system: null");
+  const phovo_engine *e = o->engine;
+  if (e->objective != PHOVO_OBJECTIVE_TRUST_REGION && e->objective != PHOVO_OBJECTIVE_BIOBJECTIVE)
+    return fail(PHOVO_E_UNSUPPORTED, "get_objective_system: the trust-region and the bi-objective objective only (the others "
+                                     "have phovo_odometry_get_pair_system, _get_sampled_system and _get_geometric_system)");
+  if (!o->optimized) return fail(PHOVO_E_NOT_READY, "get_objective_system: Optimize has not run since the frames were set");
+  int finest = -1;                                        // the lowest level Optimize() iterates on
+  for (int l = e->cfg.num_levels - 1; l >= 0; l--)
+    if (e->cfg.max_num_iterations[l] > 0) finest = l;
+  if (finest < 0) return fail(PHOVO_E_NOT_READY, "get_objective_system: the configuration optimises no level");
+  const int src = 0, tgt = 1;
+  return phovo_engine_evaluate_objective_pairs(o->engine, 1, &src, &tgt, o->state, finest, out);
+}
+
 int phovo_odometry_last_optimize_ms(const phovo_odometry *o, double *ms)
 {
   if (!o || !ms) return fail(PHOVO_E_INVALID_ARGUMENT, "last_optimize_ms: null");

@@ -175,6 +175,24 @@ bool gn_plan_level_trust_region(int n, GNLaunchPlan *plan);
 hipError_t gn_prepare_trust_region_kernels();
 hipError_t gn_launch_level_trust_region(const GNTrustRegionArgs &args, const GNLaunchPlan &plan, int cu_count,
                                         hipStream_t stream);
+// Evaluation of the trust-region and the bi-objective system at given states (gn_evaluate_objective_kernels.hip,
+// phovo_engine_evaluate_objective_pairs): fp64 planes, the tile form of gn_eval_pairs, gn_eval_tiles(n) tiles per pair.
+struct GNObjectiveEvalArgs {
+  int w, h, n, n_chunks;
+  double fx, fy, ox, oy, ifx, ify;   // level-scaled intrinsics, as GNLevelArgs
+  double min_depth, max_depth;       // the depth range in force at the call
+  const unsigned char *planes;       // pool of the level (GNLevelArgs)
+  size_t frame_bytes;
+  size_t plane_off[PLANES_PER_FRAME];
+  size_t dgx_off, dgy_off, gain_off; // bi-objective: the target's depth gradients and gain (GNBiObjectiveArgs)
+  const int *src, *tgt;              // [pairs of the group]
+  const double *states;              // [pairs of the group][6]
+};
+// objective: PHOVO_OBJECTIVE_TRUST_REGION or PHOVO_OBJECTIVE_BIOBJECTIVE.  g_owner: [n_pairs][n] int32 holding -1
+// everywhere (and again when the launches have run); g_mask: [n_pairs][n_chunks]; g_part: [n_pairs]
+// [gn_eval_slab_doubles_per_pair(n)]; out: [n_pairs] on the device.
+hipError_t gn_eval_objective_pairs(const GNObjectiveEvalArgs &a, int objective, int n_pairs, int *g_owner,
+                                   unsigned long long *g_mask, double *g_part, phovo_pair_system *out, hipStream_t stream);
 // Affine-illumination form (gn_affine_kernel.hip, PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE): fp64 planes, the photometric
 // objective's frames; the bilinear extension's rows with the true warp Jacobian, the residual I1 - (1 + alpha) I0 - beta and
 // an 8 x 8 system per iteration.  No owner map, any level size, 256 threads.

@@ -314,6 +314,13 @@ class CPhotoconsistencyOdometryBiObjective(CPhotoconsistencyOdometryAnalytic):
             raise ValueError("the bi-objective needs the target's depth")
         super().SetTargetFrameDevice(intensityImage, depthImage, depth_scale, channel_order, stream)
 
+    def GetObjectiveSystem(self):
+        """native.PairSystem of the 2N-row system at the optimal state on the finest level the configuration optimises
+        (rows: contributing source pixels; cost: r^T r over all 2N residuals); evaluated on demand after Optimize()."""
+        ps = native.PairSystem()
+        check(self._lib.phovo_odometry_get_objective_system(self._h, C.byref(ps)), "GetObjectiveSystem")
+        return ps
+
 
 class CPhotoconsistencyOdometryCeres(CPhotoconsistencyOdometryAnalytic):
     """One frame pair at a time; 1:1 with the reference's phovo::Ceres::CPhotoconsistencyOdometryCeres (bilinear samples,
@@ -337,6 +344,14 @@ class CPhotoconsistencyOdometryCeres(CPhotoconsistencyOdometryAnalytic):
         rep = native.TrustRegionReport()
         check(self._lib.phovo_odometry_get_trust_region_report(self._h, C.byref(rep)), "GetSolverReport")
         return rep
+
+    def GetObjectiveSystem(self):
+        """native.PairSystem at the optimal state on the finest level the configuration optimises: J^T J, J^T r, rows (owned
+        targets) and cost = r^T r, which is twice Ceres's cost and twice the solver report's final_cost; evaluated on demand
+        after Optimize()."""
+        ps = native.PairSystem()
+        check(self._lib.phovo_odometry_get_objective_system(self._h, C.byref(ps)), "GetObjectiveSystem")
+        return ps
 
 
 class CPhotoconsistencyOdometryAffine(CPhotoconsistencyOdometryAnalytic):
@@ -742,6 +757,26 @@ class AlignmentEngine:
         ip = C.POINTER(C.c_int)
         check(self._lib.phovo_engine_evaluate_pairs(self._h, n, s.ctypes.data_as(ip), t.ctypes.data_as(ip), st.ctypes.data,
                                                     int(level), out.ctypes.data), "phovo_engine_evaluate_pairs")
+        out = out[:n]
+        res = dict(information=out["information"].reshape(n, 6, 6).copy(), gradient=out["gradient"].copy(),
+                   cost=out["cost"].copy(), rows=out["rows"].astype(np.int64), flags=out["flags"].astype(np.int64))
+        if want_structs:
+            res["structs"] = list((native.PairSystem * n).from_buffer_copy(out.tobytes()))
+        return res
+
+    def evaluate_objective_pairs(self, src, tgt, states, level, want_structs=False):
+        """The system of each (source, target) pair under the trust-region or the bi-objective objective, whichever the
+        engine runs, at states [n, 6] on `level` (phovo_engine_evaluate_objective_pairs).  Returns what evaluate_pairs
+        returns: information [n, 6, 6], gradient [n, 6], cost [n] (r^T r: twice the trust region's final_cost), rows [n],
+        flags [n] (with want_structs, also the native.PairSystem records under "structs")."""
+        s, t = self._pairs(src, tgt)
+        n = s.size
+        st = np.ascontiguousarray(states, dtype=np.float64).reshape(n, 6)
+        out = np.zeros(max(n, 1), dtype=PAIR_SYSTEM_DTYPE)         # the C records, written in place
+        ip = C.POINTER(C.c_int)
+        check(self._lib.phovo_engine_evaluate_objective_pairs(self._h, n, s.ctypes.data_as(ip), t.ctypes.data_as(ip),
+                                                              st.ctypes.data, int(level), out.ctypes.data),
+              "phovo_engine_evaluate_objective_pairs")
         out = out[:n]
         res = dict(information=out["information"].reshape(n, 6, 6).copy(), gradient=out["gradient"].copy(),
                    cost=out["cost"].copy(), rows=out["rows"].astype(np.int64), flags=out["flags"].astype(np.int64))
