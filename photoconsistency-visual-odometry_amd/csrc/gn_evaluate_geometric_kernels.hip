@@ -4,33 +4,23 @@
 // exactly the rows gn_level_kernel_geometric (gn_geometric_kernel.hip) fills at that state on one level.
 // The photometric block is not computed here: it is k_eval_sampled's ROWS_CORRECTED system on fp64 planes without Huber
 // weights (gn_eval_sampled_pairs, gn_evaluate_sampled_kernels.hip), run into its own slab and record.  This file adds the
-// depth block, in that file's form: a pair is cut into tiles of 16 64-pixel chunks, one 256-thread workgroup per tile, and
-// the kernel boundary is the only synchronisation (no atomics, no grid barrier):
-//   k_eval_geometric_depth   pose constants of the pair's state into LDS (write_pose_constants), warp, the four clamped taps
-//                            of the TARGET's depth per pixel, the tap gate, the residual gate, the depth row's sums; per
-//                            tile one block of 32 sums (21 + 6 + depth rows + depth cost).  It reads D0 and D1 only: 16
-//                            algorithmic bytes per pixel.
+// depth block, in that file's form (the tile form of gn_evaluate_device.hpp: tiles, slabs, fixed summation orders; no atomics):
+//   k_eval_geometric_depth   pose constants, warp, the four clamped taps of the TARGET's depth per pixel, the tap gate, the
+//                            residual gate, the depth row's sums; per tile one block of 32 sums (21 + 6 + depth rows +
+//                            depth cost).  It reads D0 and D1 only: 16 algorithmic bytes per pixel.
 //   k_eval_geometric_finish  fixed-order sum of the tile slabs, the sampled record beside it, information = photometric +
 //                            depth with one add per entry, into phovo_geometric_system; one workgroup per pair
-// The tile count and every summation order depend on the level size only: a pair's result is the same bit for bit
-// whatever the batch, its position in it, or any setting of the engine.
 #include <hip/hip_runtime.h>
 
-#include "gn_device.hpp"
-#include "phovo_internal.hpp"
+#include "gn_evaluate_device.hpp"
 
 namespace phovo_hip {
 
 namespace {
 
-constexpr int ET = 256;                 // threads per tile workgroup
-constexpr int E_TILE_CHUNKS = 16;       // 64-pixel chunks per tile (1024 pixels), 4 per wave
-constexpr int ENW = ET / WAVE;
-constexpr int ECPW = E_TILE_CHUNKS / ENW;       // chunks per wave
-// slots of the block behind the 21 + 6 sums: the depth rows stand where the other kernels keep their row count
-constexpr int RED_DEPTH_ROWS = RED_VALID;
-constexpr int RED_DEPTH_COST = 28;      // sum r_D^2
-static_assert(RED_DEPTH_COST < NRED, "one block of NRED carries every sum");
+// slots of the block behind the 21 + 6 sums: the depth rows and sum r_D^2 stand where the other kernels keep their row
+// count and cost
+constexpr int RED_DEPTH_ROWS = RED_VALID, RED_DEPTH_COST = RED_COST;
 
 // grid (tiles, pairs of the group).  fp64 planes.
 // TWIN: the warp, the bounds test, the taps, both gates and the depth row are gn_level_kernel_geometric's (its `warp`,
@@ -46,18 +36,8 @@ __global__ __launch_bounds__(ET) void k_eval_geometric_depth(const GNGeometricEv
   const int wave = __builtin_amdgcn_readfirstlane(tid / WAVE);
   const int n = A.n, W = A.w, H = A.h;
   const double *st = A.states + (size_t)pair * 6;
-  if (tid < WAVE) write_pose_constants(st[0], st[1], st[2], st[3], st[4], st[5], s_cst, tid);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __syncthreads();
-  const double cx = uniform_f64(s_cst[C_X]), cyy = uniform_f64(s_cst[C_Y]), cz = uniform_f64(s_cst[C_Z]);
-  const double r01 = uniform_f64(s_cst[C_R01]), r02 = uniform_f64(s_cst[C_R02]);
-  const double r11 = uniform_f64(s_cst[C_R11]), r12 = uniform_f64(s_cst[C_R12]);
-  const double t1 = uniform_f64(s_cst[C_T1]), t2 = uniform_f64(s_cst[C_T2]), t3 = uniform_f64(s_cst[C_T3]);
-  const double t4 = uniform_f64(s_cst[C_T4]), t5 = uniform_f64(s_cst[C_T5]), t6 = uniform_f64(s_cst[C_T6]);
-  const double t8 = uniform_f64(s_cst[C_T8]), t14 = uniform_f64(s_cst[C_T14]), t15 = uniform_f64(s_cst[C_T15]);
-  const double t16 = uniform_f64(s_cst[C_T16]), t17 = uniform_f64(s_cst[C_T17]), t24 = uniform_f64(s_cst[C_T24]);
-  const double cosy = uniform_f64(s_cst[C_CY]), siny = uniform_f64(s_cst[C_SY]);
-  const double t7 = -t6, t9 = -t8, t21 = -t5;
+  eval_pose_to_lds(st, s_cst);
+  const SampledPose P = sampled_pose(s_cst);
 
   const unsigned char *src_frame = A.planes + (size_t)A.src[pair] * A.frame_bytes;
   const unsigned char *tgt_frame = A.planes + (size_t)A.tgt[pair] * A.frame_bytes;
@@ -65,8 +45,7 @@ __global__ __launch_bounds__(ET) void k_eval_geometric_depth(const GNGeometricEv
   // one descriptor for the target frame; its depth plane is chosen by the load's scalar offset
   const __amdgpu_buffer_rsrc_t rT = frame_rsrc(tgt_frame, A.frame_bytes);
   const int o_d = (int)A.plane_off[PLANE_D];
-  const double fx = A.fx, fy = A.fy, ox = A.ox, oy = A.oy, ifx = A.ifx, ify = A.ify;
-  const double min_d = A.min_depth, max_d = A.max_depth;
+  const double fx = A.fx, fy = A.fy, min_d = A.min_depth, max_d = A.max_depth;
   const double sigma = B.depth_weight, gate = B.max_depth_residual;
   const bool gate_on = gate > 0.0;
   const double wlim = (double)W - 0.5, hlim = (double)H - 0.5;
@@ -85,45 +64,13 @@ __global__ __launch_bounds__(ET) void k_eval_geometric_depth(const GNGeometricEv
     pzs[j] = plane_load<double>(rD0, k);
   }
 
-  struct Warped {
-    double px, py, pz, Zr, t25, ax, ay;
-    int idx[4];                           // the clamped taps p00, p01, p10, p11: indices into a plane
-    unsigned long long m;                 // lanes that are valid and land in bounds
-  };
   struct Sampled {
     double d1, dgx, dgy;                  // the bilinear sample of D1 and the derivative of its interpolant
     bool taps_ok;                         // every D1 tap passes the depth gate
   };
   double tap[4];                          // D1 at p00, p01, p10, p11 of the chunk whose taps are in flight
   auto warp = [&](Warped &w, int j) {
-    const int k = (blockIdx.x * E_TILE_CHUNKS + j * ENW + wave) * WAVE + lane;
-    const double pz = pzs[j];
-    double cd, rd;
-    rowcol_from_index((double)k, rc_map, cd, rd);
-    const double px = (cd - ox) * pz * ifx;
-    const double py = (rd - oy) * pz * ify;
-    const double X = ((t15 * px + r01 * py) + r02 * pz) + cx;
-    const double Y = ((t14 * px + r11 * py) + r12 * pz) + cyy;
-    const double Zr = py * t1 + pz * t2 - px * t3;
-    const double t25 = fast_rcp(cz + Zr);
-    const double tc = (X * fx) * t25 + ox;
-    const double tr = (Y * fy) * t25 + oy;
-    // depth gate, and in bounds iff the NEAREST pixel is inside (NaN fails the comparisons)
-    w.m = __builtin_amdgcn_ballot_w64(k < n) & __builtin_amdgcn_ballot_w64(min_d < pz) &
-          __builtin_amdgcn_ballot_w64(pz < max_d) & __builtin_amdgcn_ballot_w64(tc > -0.5) &
-          __builtin_amdgcn_ballot_w64(tc < wlim) & __builtin_amdgcn_ballot_w64(tr > -0.5) &
-          __builtin_amdgcn_ballot_w64(tr < hlim);
-    w.px = px; w.py = py; w.pz = pz; w.Zr = Zr; w.t25 = t25;
-    const double fc = floor(tc), fr = floor(tr);
-    w.ax = tc - fc;
-    w.ay = tr - fr;
-    // (lanes outside w.m: whatever the conversions give, clamped into the plane like the others; nobody uses their taps)
-    const int ic = (int)fc, ir = (int)fr;
-    const int r0w = __mul24(min(max(ir, 0), H - 1), W), r1w = __mul24(min(max(ir + 1, 0), H - 1), W);
-    // clamp-to-edge taps (in the outer half-pixel band both taps of a row / a column are the edge pixel): every index
-    // lies in [0, n)
-    const int c0i = min(max(ic, 0), W - 1), c1i = min(max(ic + 1, 0), W - 1);
-    w.idx[0] = r0w + c0i; w.idx[1] = r0w + c1i; w.idx[2] = r1w + c0i; w.idx[3] = r1w + c1i;
+    warp_bilinear(w, (blockIdx.x * E_TILE_CHUNKS + j * ENW + wave) * WAVE + lane, pzs[j], P, A, wlim, hlim, rc_map);
   };
   auto issue = [&](const Warped &w) {
     if (__builtin_amdgcn_inverse_ballot_w64(w.m)) {
@@ -144,18 +91,18 @@ __global__ __launch_bounds__(ET) void k_eval_geometric_depth(const GNGeometricEv
   };
   auto consume = [&](const Warped &w, const Sampled &s) {
     const bool row = __builtin_amdgcn_inverse_ballot_w64(w.m);
-    const double res_d = s.d1 - (cz + w.Zr);                            // D1(u, v) - Z'
+    const double res_d = s.d1 - (P.cz + w.Zr);                          // D1(u, v) - Z'
     bool depth_row = row && s.taps_ok;
     if (gate_on) depth_row = depth_row && (fabs(res_d) <= gate);        // NaN fails
     n_depth_rows += __builtin_popcountll(__builtin_amdgcn_ballot_w64(depth_row));
     if (depth_row) {
       const double px = w.px, py = w.py, pz = w.pz, Zr = w.Zr, t25 = w.t25;
-      const double base = pz * t4 + py * t5 + px * t15;
-      const double Au = base + cx;                                      // the true warp Jacobian (CORRECTED)
-      const double Bv = py * t6 + pz * t9 + px * t14 + cyy;
-      const double Cm = -py * t16 - pz * t17 - px * t24;                // dZ'/dpitch
-      const double Dm = py * t2 - pz * t1;                              // dZ'/droll
-      const double yawu = cyy - Bv, rollu = py * t4 + pz * t21, rollv = pz * t7 + py * t9;
+      const double base = pz * P.t4 + py * P.t5 + px * P.t15;
+      const double Au = base + P.cx;                                    // the true warp Jacobian (CORRECTED)
+      const double Bv = py * P.t6 + pz * P.t9 + px * P.t14 + P.cyy;
+      const double Cm = -py * P.t16 - pz * P.t17 - px * P.t24;          // dZ'/dpitch
+      const double Dm = py * P.t2 - pz * P.t1;                          // dZ'/droll
+      const double yawu = P.cyy - Bv, rollu = py * P.t4 + pz * P.t21, rollv = pz * P.t7 + py * P.t9;
       // the photometric row's six columns with the interpolant's derivative in place of the sampled gradients; dZ'/dp is
       // (0, 0, 1, 0, Cm, Dm), and since columns 4 and 5 take Cm and Dm times column 2, the -1 goes in there once
       const double rD = sigma * res_d;
@@ -164,8 +111,10 @@ __global__ __launch_bounds__(ET) void k_eval_geometric_depth(const GNGeometricEv
       J[1] = ((sigma * s.dgy) * fy) * t25;
       J[2] = -(J[0] * Au + J[1] * Bv) * t25 - sigma;
       J[3] = J[0] * yawu + J[1] * base;
-      J[4] = (J[0] * cosy + J[1] * siny) * Zr + Cm * J[2];
+      J[4] = (J[0] * P.cosy + J[1] * P.siny) * Zr + Cm * J[2];
       J[5] = J[0] * rollu + J[1] * rollv + Dm * J[2];
+      // (add_row's sums, column by column: the products of column a, then its gradient entry -- the order this kernel was
+      // compiled with; gn_evaluate_device.hpp's order schedules it differently)
       int q = 0;
 #pragma unroll
       for (int a = 0; a < 6; a++) {
@@ -200,81 +149,54 @@ __global__ __launch_bounds__(ET) void k_eval_geometric_depth(const GNGeometricEv
     }
   }
   acc[RED_DEPTH_ROWS] = lane == 0 ? (double)n_depth_rows : 0.0;
-  // tile sums: wave butterfly, then the four waves in fixed order
-  reduce_wave_to_row(acc, lane, wave, s_red);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid < NRED) {
-    double v = 0.0;
-#pragma unroll
-    for (int w2 = 0; w2 < ENW; w2++) v += s_red[w2 * NRED + tid];
-    g_part[((size_t)pair * tiles + blockIdx.x) * NRED + tid] = v;
-  }
+  tile_sums(acc, lane, wave, s_red, g_part, pair, tiles);
 }
 
-// One workgroup per pair: thread (s, j) adds tiles s, s + 8, s + 16, ... of value j, then the eight subset sums are added in
-// subset order (k_eval_sampled_finish's order); the photometric block comes from the pair's sampled record, and every entry
-// of the record is written from the upper triangles, the sum with one add.
+// One workgroup per pair: the fixed-order sum of its depth slab (k_eval_sampled_finish's order); the photometric block
+// comes from the pair's sampled record, and every entry of the record is written from the upper triangles, the sum with
+// one add.
 __global__ __launch_bounds__(ET) void k_eval_geometric_finish(const double *g_part, int tiles, const phovo_sampled_system *sampled,
                                                               phovo_geometric_system *out)
 {
-  constexpr int SUBSETS = ET / NRED;
-  __shared__ double s_part[SUBSETS * NRED];
-  const int pair = blockIdx.x, tid = threadIdx.x;
-  {
-    const int j = tid & (NRED - 1), sub = tid / NRED;
-    const double *base = g_part + (size_t)pair * tiles * NRED + j;
-    double v = 0.0;
-#pragma unroll 4
-    for (int t = sub; t < tiles; t += SUBSETS) v += base[(size_t)t * NRED];
-    s_part[sub * NRED + j] = v;
-  }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid >= WAVE) return;
-  const int lane = tid;
-  double v = 0.0;                         // lanes 0..31: the depth block's sums
-  if (lane < NRED) {
-#pragma unroll
-    for (int sub = 0; sub < SUBSETS; sub++) v += s_part[sub * NRED + lane];
-  }
-  const phovo_sampled_system *ps = sampled + pair;
-  phovo_geometric_system *o = out + pair;
-  // lane (a, b) of the 6 x 6 records: the slot of (min, max)(a, b).  Every shuffle runs in the whole wave (its source lanes
-  // must be active).
-  const bool inside = lane < 36;
-  const int ra = inside ? lane / 6 : 0, rb = inside ? lane - ra * 6 : 0;
-  const int a = min(ra, rb), b = max(ra, rb);
-  const double hd = __shfl(v, tri(a, b), WAVE);
-  const double gd = __shfl(v, 21 + (lane < 6 ? lane : 0), WAVE);
-  const double depth_rows = __shfl(v, RED_DEPTH_ROWS, WAVE);
-  const double depth_cost = __shfl(v, RED_DEPTH_COST, WAVE);
-  const bool finite = fabs(v) <= 1.79769313486231570815e308;            // (unused slots and lanes hold 0)
-  const bool depth_finite = __ballot(!finite) == 0ull;
-  if (inside) {
-    const double hi = ps->information[a * PHOVO_SYSTEM_MAX_DIM + b];
-    o->photometric_information[lane] = hi;
-    o->depth_information[lane] = hd;
-    o->information[lane] = hi + hd;
-  }
-  if (lane < 6) {
-    const double gi = ps->gradient[lane];
-    o->photometric_gradient[lane] = gi;
-    o->depth_gradient[lane] = gd;
-    o->gradient[lane] = gi + gd;
-  }
-  if (lane == 0) {
-    const int32_t rows = ps->rows;
-    o->photometric_cost = ps->cost;
-    o->depth_cost = depth_cost;
-    o->rows = rows;
-    o->depth_rows = (int32_t)depth_rows;
-    uint32_t flags = 0;
-    if (rows < 6) flags |= PHOVO_PAIR_RANK_DEFICIENT;
-    if (!depth_finite || (ps->flags & PHOVO_PAIR_NONFINITE)) flags |= PHOVO_PAIR_NONFINITE;
-    o->flags = flags;
-    o->reserved = 0;
-  }
+  finish_slab<NRED>(g_part, tiles, [&](int pair, int lane, double v) {      // lanes 0..31: the depth block's sums
+    const phovo_sampled_system *ps = sampled + pair;
+    phovo_geometric_system *o = out + pair;
+    // lane (a, b) of the 6 x 6 records: the slot of (min, max)(a, b).  Every shuffle runs in the whole wave (its source lanes
+    // must be active).
+    const bool inside = lane < 36;
+    const int ra = inside ? lane / 6 : 0, rb = inside ? lane - ra * 6 : 0;
+    const int a = min(ra, rb), b = max(ra, rb);
+    const double hd = __shfl(v, tri(a, b), WAVE);
+    const double gd = __shfl(v, 21 + (lane < 6 ? lane : 0), WAVE);
+    const double depth_rows = __shfl(v, RED_DEPTH_ROWS, WAVE);
+    const double depth_cost = __shfl(v, RED_DEPTH_COST, WAVE);
+    const bool finite = finite_f64(v);                                  // (unused slots and lanes hold 0)
+    const bool depth_finite = __ballot(!finite) == 0ull;
+    if (inside) {
+      const double hi = ps->information[a * PHOVO_SYSTEM_MAX_DIM + b];
+      o->photometric_information[lane] = hi;
+      o->depth_information[lane] = hd;
+      o->information[lane] = hi + hd;
+    }
+    if (lane < 6) {
+      const double gi = ps->gradient[lane];
+      o->photometric_gradient[lane] = gi;
+      o->depth_gradient[lane] = gd;
+      o->gradient[lane] = gi + gd;
+    }
+    if (lane == 0) {
+      const int32_t rows = ps->rows;
+      o->photometric_cost = ps->cost;
+      o->depth_cost = depth_cost;
+      o->rows = rows;
+      o->depth_rows = (int32_t)depth_rows;
+      uint32_t flags = 0;
+      if (rows < 6) flags |= PHOVO_PAIR_RANK_DEFICIENT;
+      if (!depth_finite || (ps->flags & PHOVO_PAIR_NONFINITE)) flags |= PHOVO_PAIR_NONFINITE;
+      o->flags = flags;
+      o->reserved = 0;
+    }
+  });
 }
 
 }  // namespace

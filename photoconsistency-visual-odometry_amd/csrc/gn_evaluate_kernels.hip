@@ -6,30 +6,19 @@
 // including its temp11 slip (:253) -- the matrix the aligner inverts (:538-540).  W is the identity, or with
 // huber_delta > 0 the IRLS weights the aligner uses (1 or delta/|r|, from r at the state).
 //
-// The wide form's shape (gn_wide_kernels.hip): a pair is cut into tiles of 16 64-pixel chunks, one 256-thread workgroup
-// per tile, and the kernel boundary is the only synchronisation (no grid barrier, nothing that can hang):
-//   k_eval_pass1   pose constants of the pair's state into LDS (write_pose_constants: every sin/cos branch is the
-//                  aligner's), warp, atomicMax into the owner map in HBM, per-chunk in-bounds ballots
+// The tile form of gn_evaluate_device.hpp (tiles, slabs, fixed summation orders: there):
+//   k_eval_pass1   pose constants, warp, atomicMax into the owner map in HBM, per-chunk in-bounds ballots
 //   k_eval_pass2   residual and Jacobian rows, 21 + 6 + 1 sums and the row count per tile into a slab; the owner slots
 //                  are put back to -1.  No float atomics.
 //   k_eval_finish  fixed-order sum of the tile slabs into phovo_pair_system, one workgroup per pair
-// The tile count and every summation order depend on the level size only: a pair's result is the same bit for bit
-// whatever the batch, its position in it, or any setting of the engine.
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 
-#include "gn_device.hpp"
-#include "phovo_internal.hpp"
+#include "gn_evaluate_device.hpp"
 
 namespace phovo_hip {
 
 namespace {
-
-constexpr int ET = 256;                 // threads per tile workgroup
-constexpr int E_TILE_CHUNKS = 16;       // 64-pixel chunks per tile (1024 pixels), 4 per wave
-constexpr int ENW = ET / WAVE;
-constexpr int ECPW = E_TILE_CHUNKS / ENW;       // chunks per wave
-constexpr int RED_COST = 28;            // slot behind the row count: r^T W r
 
 struct EvalPose {
   double cx, cyy, cz, r01, r02, r11, r12, t1, t2, t3, t4, t5, t6, t8, t11, t14, t15, t16, t17, t24, cosy, siny;
@@ -38,10 +27,7 @@ struct EvalPose {
 // Wave 0 writes the pose constants of the pair's state into s_cst; every thread reads them back behind the barrier.
 __device__ __forceinline__ EvalPose eval_pose(const double *st, double *s_cst)
 {
-  const int tid = threadIdx.x;
-  if (tid < WAVE) write_pose_constants(st[0], st[1], st[2], st[3], st[4], st[5], s_cst, tid);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __syncthreads();
+  eval_pose_to_lds(st, s_cst);
   const double *c = s_cst;
   EvalPose p;
   p.cx = c[C_X]; p.cyy = c[C_Y]; p.cz = c[C_Z];
@@ -204,78 +190,18 @@ __global__ __launch_bounds__(ET) void k_eval_pass2(const GNEvalArgs A, int *g_ow
       double Jw[6];
 #pragma unroll
       for (int a = 0; a < 6; a++) Jw[a] = HUBER ? J[a] * wgt : J[a];
-      int q = 0;
-#pragma unroll
-      for (int a = 0; a < 6; a++) {
-#pragma unroll
-        for (int b = a; b < 6; b++) {
-          acc[q] = fma(Jw[a], J[b], acc[q]);                              // J^T W J  :540
-          q++;
-        }
-      }
-#pragma unroll
-      for (int a = 0; a < 6; a++) acc[21 + a] = fma(Jw[a], res, acc[21 + a]);      // J^T W r  :538
+      add_row(acc, Jw, J, res);                                           // J^T W J  :540, J^T W r  :538
     }
   };
   if (huber_delta > 0.0) rows(std::true_type{}); else rows(std::false_type{});
   acc[RED_VALID] = lane == 0 ? (double)n_rows : 0.0;
-  // tile sums: wave butterfly, then the four waves in fixed order
-  reduce_wave_to_row(acc, lane, wave, s_red);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid < NRED) {
-    double v = 0.0;
-#pragma unroll
-    for (int w2 = 0; w2 < ENW; w2++) v += s_red[w2 * NRED + tid];
-    g_part[((size_t)pair * tiles + blockIdx.x) * NRED + tid] = v;
-  }
+  tile_sums(acc, lane, wave, s_red, g_part, pair, tiles);
 }
 
-// One workgroup per pair: thread (s, j) adds tiles s, s + 8, s + 16, ... of value j, then the 8 subset sums are added in
-// subset order; the system is written from the upper triangle.
-constexpr int FIN_SUBSETS = ET / NRED;
+// One workgroup per pair: the fixed-order sum of its slab, the system written from the upper triangle.
 __global__ __launch_bounds__(ET) void k_eval_finish(const double *g_part, int tiles, phovo_pair_system *out)
 {
-  __shared__ double s_part[FIN_SUBSETS * NRED];
-  const int pair = blockIdx.x, tid = threadIdx.x;
-  {
-    const int j = tid & (NRED - 1), sub = tid / NRED;
-    const double *base = g_part + (size_t)pair * tiles * NRED + j;
-    double v = 0.0;
-#pragma unroll 4
-    for (int t = sub; t < tiles; t += FIN_SUBSETS) v += base[(size_t)t * NRED];
-    s_part[sub * NRED + j] = v;
-  }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid >= WAVE) return;
-  const int lane = tid;
-  double v = 0.0;
-  if (lane < NRED) {
-#pragma unroll
-    for (int sub = 0; sub < FIN_SUBSETS; sub++) v += s_part[sub * NRED + lane];
-  }
-  phovo_pair_system *o = out + pair;
-  // lane (a, b) of the 6x6 matrix, 36 lanes: the upper-triangle slot of (min, max)(a, b).  Every shuffle runs in the
-  // whole wave (its source lanes must be active).
-  const int a = lane / 6, b = lane % 6;
-  const int q = lane >= 36 ? 0 : (a <= b ? tri(a, b) : tri(b, a));
-  const double h = __shfl(v, q, WAVE);
-  if (lane < 36) o->information[lane] = h;
-  const double g = __shfl(v, lane < 6 ? 21 + lane : 0, WAVE);
-  if (lane < 6) o->gradient[lane] = g;
-  const double rows = __shfl(v, RED_VALID, WAVE);
-  const double cost = __shfl(v, RED_COST, WAVE);
-  const bool finite = lane >= RED_VALID || fabs(v) <= 1.79769313486231570815e308;
-  const bool all_finite = __ballot(!finite) == 0ull && fabs(cost) <= 1.79769313486231570815e308;
-  if (lane == 0) {
-    o->cost = cost;
-    o->rows = (int32_t)rows;
-    uint32_t flags = 0;
-    if (rows < 6.0) flags |= PHOVO_PAIR_RANK_DEFICIENT;
-    if (!all_finite) flags |= PHOVO_PAIR_NONFINITE;
-    o->flags = flags;
-  }
+  finish_slab<NRED>(g_part, tiles, [&](int pair, int lane, double v) { write_pair_system(out + pair, lane, v); });
 }
 
 template <typename TI, typename TD>
@@ -291,11 +217,7 @@ hipError_t eval_launch(const GNEvalArgs &a, int n_pairs, int tiles, int *g_owner
 
 }  // namespace
 
-int gn_eval_tiles(int n)
-{
-  const int n_chunks = (n + WAVE - 1) / WAVE;
-  return (n_chunks + E_TILE_CHUNKS - 1) / E_TILE_CHUNKS;
-}
+int gn_eval_tiles(int n) { return eval_tiles(n); }
 
 size_t gn_eval_slab_doubles_per_pair(int n) { return (size_t)gn_eval_tiles(n) * NRED; }
 
@@ -304,12 +226,9 @@ hipError_t gn_eval_pairs(const GNEvalArgs &a, int n_pairs, int storage, int *g_o
 {
   if (n_pairs <= 0) return hipSuccess;
   const int tiles = gn_eval_tiles(a.n);
-  switch (storage) {
-    case PHOVO_STORAGE_F64: return eval_launch<double, double>(a, n_pairs, tiles, g_owner, g_mask, g_part, out, stream);
-    case PHOVO_STORAGE_F32: return eval_launch<float, float>(a, n_pairs, tiles, g_owner, g_mask, g_part, out, stream);
-    case PHOVO_STORAGE_F16: return eval_launch<__half, float>(a, n_pairs, tiles, g_owner, g_mask, g_part, out, stream);
-    default: return hipErrorInvalidValue;
-  }
+  return with_storage_types(storage, [&](auto ti, auto td) {
+    return eval_launch<decltype(ti), decltype(td)>(a, n_pairs, tiles, g_owner, g_mask, g_part, out, stream);
+  });
 }
 
 }  // namespace phovo_hip

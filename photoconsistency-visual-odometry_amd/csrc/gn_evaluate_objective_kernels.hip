@@ -10,14 +10,12 @@
 //                  reference's row collisions resolved as there; rows = contributing source pixels; cost = r^T r over the
 //                  whole 2N residual vector, entries whose Jacobian row is empty included.
 //
-// The form is gn_evaluate_kernels.hip's: a pair is cut into tiles of 16 64-pixel chunks, one 256-thread workgroup per
-// tile, and the kernel boundary is the only synchronisation:
-//   k_obj_pass1_*   pose constants of the pair's state into LDS (write_pose_constants), warp, atomicMax of the source index
-//                   into the owner map in HBM, per-chunk ballots ("lands" / "contributes")
+// The tile form of gn_evaluate_device.hpp (tiles, slabs, fixed summation orders: there), with gn_evaluate_kernels.hip's
+// three kernels:
+//   k_obj_pass1_*   pose constants, warp, atomicMax of the source index into the owner map in HBM, per-chunk ballots
+//                   ("lands" / "contributes")
 //   k_obj_pass2_*   residuals and rows, 21 + 6 sums, r^2 and the row count per tile into a slab.  No float atomics.
 //   k_obj_finish    fixed-order sum of the tile slabs into phovo_pair_system, one workgroup per pair
-// The tile count and every summation order depend on the level size only: a pair's record is the same bit for bit
-// whatever the batch, its position in it, the group split, or any setting of the engine.
 //
 // The owner maps hold -1 between calls.  Who puts them back differs:
 //   trust region   pass 2.  Slot t is read by the landing pixels whose target is t -- possibly from several workgroups --
@@ -30,62 +28,16 @@
 #include <hip/hip_runtime.h>
 
 // As gn_trust_region_kernel.hip: the warps are computed exactly as written, without contracting products into FMAs, so that
-// the trust-region warp is the aligner's and the CPU checker's bit for bit.  The sums use explicit fma().
+// the trust-region warp is the aligner's and the CPU checker's bit for bit.  The sums use explicit fma(), and so does
+// everything this file takes from gn_evaluate_device.hpp (not its bilinear warp).
 #pragma clang fp contract(off)
 
-#include "gn_device.hpp"
+#include "gn_evaluate_device.hpp"
 #include "gn_trust_region_device.hpp"
-#include "phovo_internal.hpp"
 
 namespace phovo_hip {
 
 namespace {
-
-constexpr int ET = 256;                 // threads per tile workgroup
-constexpr int E_TILE_CHUNKS = 16;       // 64-pixel chunks per tile (1024 pixels), 4 per wave
-constexpr int ENW = ET / WAVE;
-constexpr int ECPW = E_TILE_CHUNKS / ENW;       // chunks per wave
-constexpr int RED_COST = 28;            // slot behind the row count: r^T r
-
-// Wave 0 writes the pose constants of the pair's state into s_cst; every thread reads them behind the barrier.
-__device__ __forceinline__ void obj_pose(const double *st, double *s_cst)
-{
-  const int tid = threadIdx.x;
-  if (tid < WAVE) write_pose_constants(st[0], st[1], st[2], st[3], st[4], st[5], s_cst, tid);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __syncthreads();
-}
-
-// The tile's sums: wave butterfly, then the four waves in fixed order, into the pair's slab.
-__device__ __forceinline__ void obj_tile_sums(double (&acc)[NRED], int lane, int wave, double *s_red, double *g_part,
-                                              int pair, int tiles)
-{
-  reduce_wave_to_row(acc, lane, wave, s_red);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __syncthreads();
-  const int tid = threadIdx.x;
-  if (tid < NRED) {
-    double v = 0.0;
-#pragma unroll
-    for (int w2 = 0; w2 < ENW; w2++) v += s_red[w2 * NRED + tid];
-    g_part[((size_t)pair * tiles + blockIdx.x) * NRED + tid] = v;
-  }
-}
-
-__device__ __forceinline__ void obj_add_row(double (&acc)[NRED], const double (&J)[6], const double res)
-{
-  int q = 0;
-#pragma unroll
-  for (int a = 0; a < 6; a++) {
-#pragma unroll
-    for (int b = a; b < 6; b++) {
-      acc[q] = fma(J[a], J[b], acc[q]);
-      q++;
-    }
-  }
-#pragma unroll
-  for (int a = 0; a < 6; a++) acc[21 + a] = fma(J[a], res, acc[21 + a]);
-}
 
 // ---- trust region ---------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void tr_pose(const double *s_cst, double (&R)[9], double (&tv)[3])
@@ -105,7 +57,7 @@ __global__ __launch_bounds__(ET) void k_obj_pass1_tr(const GNObjectiveEvalArgs A
   const int tid = threadIdx.x, lane = tid & (WAVE - 1);
   const int wave = __builtin_amdgcn_readfirstlane(tid / WAVE);
   const int n = A.n, W = A.w;
-  obj_pose(A.states + (size_t)pair * 6, s_cst);
+  eval_pose_to_lds(A.states + (size_t)pair * 6, s_cst);
   double R[9], tv[3];
   tr_pose(s_cst, R, tv);
   const unsigned char *src_frame = A.planes + (size_t)A.src[pair] * A.frame_bytes;
@@ -137,7 +89,7 @@ __global__ __launch_bounds__(ET) void k_obj_pass2_tr(const GNObjectiveEvalArgs A
   const int tid = threadIdx.x, lane = tid & (WAVE - 1);
   const int wave = __builtin_amdgcn_readfirstlane(tid / WAVE);
   const int n = A.n, W = A.w, H = A.h;
-  obj_pose(A.states + (size_t)pair * 6, s_cst);
+  eval_pose_to_lds(A.states + (size_t)pair * 6, s_cst);
   double R[9], tv[3];
   tr_pose(s_cst, R, tv);
   const double cy = uniform_f64(s_cst[C_CY]), sy = uniform_f64(s_cst[C_SY]);
@@ -188,11 +140,11 @@ __global__ __launch_bounds__(ET) void k_obj_pass2_tr(const GNObjectiveEvalArgs A
     const double dq2_roll = cr_cp * w.py - sr_cp * w.pz;
     const double J[6] = {ju, jv, jw, jv * w.a0 - ju * w.a1, (ju * cy + jv * sy) * w.a2 + jw * dq2_pitch,
                          ju * dq0_roll + jv * dq1_roll + jw * dq2_roll};
-    obj_add_row(acc, J, res);
+    add_row(acc, J, res);
     acc[RED_VALID] += 1.0;
     acc[RED_COST] = fma(res, res, acc[RED_COST]);
   }
-  obj_tile_sums(acc, lane, wave, s_red, g_part, pair, tiles);
+  tile_sums(acc, lane, wave, s_red, g_part, pair, tiles);
 }
 
 // ---- bi-objective ---------------------------------------------------------------------------------------------------
@@ -218,7 +170,7 @@ __global__ __launch_bounds__(ET) void k_obj_pass1_bi(const GNObjectiveEvalArgs A
   const int tid = threadIdx.x, lane = tid & (WAVE - 1);
   const int wave = __builtin_amdgcn_readfirstlane(tid / WAVE);
   const int n = A.n, W = A.w, H = A.h;
-  obj_pose(A.states + (size_t)pair * 6, s_cst);
+  eval_pose_to_lds(A.states + (size_t)pair * 6, s_cst);
   const BiPose P = bi_pose(s_cst);
   const unsigned char *src_frame = A.planes + (size_t)A.src[pair] * A.frame_bytes;
   const __amdgpu_buffer_rsrc_t rS = frame_rsrc(src_frame, A.frame_bytes);
@@ -269,7 +221,7 @@ __global__ __launch_bounds__(ET) void k_obj_pass2_bi(const GNObjectiveEvalArgs A
   const int tid = threadIdx.x, lane = tid & (WAVE - 1);
   const int wave = __builtin_amdgcn_readfirstlane(tid / WAVE);
   const int n = A.n, W = A.w;
-  obj_pose(A.states + (size_t)pair * 6, s_cst);
+  eval_pose_to_lds(A.states + (size_t)pair * 6, s_cst);
   const BiPose P = bi_pose(s_cst);
   const double t1 = P.r21, t2 = P.r22, t3 = -P.r20;
   // (the constants only the Jacobians use stay in vector registers: the kernel has them to spare and no scalar one spills)
@@ -351,60 +303,19 @@ __global__ __launch_bounds__(ET) void k_obj_pass2_bi(const GNObjectiveEvalArgs A
       const double u = ga * p00, v = gb * p11, w = ga * p02 + gb * p12;
       const double J[6] = {gn * u, gn * v, gn * (w - sub), gn * (u * a3 + v * b3),
                            gn * (u * a4 + v * b4 + w * c4 - sub * c4), gn * (u * a5 + v * b5 + w * c5 - sub * c5)};
-      obj_add_row(acc, J, dep ? res_i2 : res_i);
+      add_row(acc, J, dep ? res_i2 : res_i);
     }
   }
   // contributing pixels ride through the reduction in the spare slot (lane 0 of every wave)
   acc[RED_VALID] = lane == 0 ? (double)n_contrib : 0.0;
-  obj_tile_sums(acc, lane, wave, s_red, g_part, pair, tiles);
+  tile_sums(acc, lane, wave, s_red, g_part, pair, tiles);
 }
 
 // ---- finish -----------------------------------------------------------------------------------------------------------
-// One workgroup per pair, as k_eval_finish: thread (s, j) adds tiles s, s + 8, s + 16, ... of value j, then the 8 subset
-// sums are added in subset order; the system is written from the upper triangle.
-constexpr int FIN_SUBSETS = ET / NRED;
+// One workgroup per pair, k_eval_finish's body: the fixed-order sum of its slab, the system written from the upper triangle.
 __global__ __launch_bounds__(ET) void k_obj_finish(const double *g_part, int tiles, phovo_pair_system *out)
 {
-  __shared__ double s_part[FIN_SUBSETS * NRED];
-  const int pair = blockIdx.x, tid = threadIdx.x;
-  {
-    const int j = tid & (NRED - 1), sub = tid / NRED;
-    const double *base = g_part + (size_t)pair * tiles * NRED + j;
-    double v = 0.0;
-#pragma unroll 4
-    for (int t = sub; t < tiles; t += FIN_SUBSETS) v += base[(size_t)t * NRED];
-    s_part[sub * NRED + j] = v;
-  }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid >= WAVE) return;
-  const int lane = tid;
-  double v = 0.0;
-  if (lane < NRED) {
-#pragma unroll
-    for (int sub = 0; sub < FIN_SUBSETS; sub++) v += s_part[sub * NRED + lane];
-  }
-  phovo_pair_system *o = out + pair;
-  // lane (a, b) of the 6x6 matrix, 36 lanes: the upper-triangle slot of (min, max)(a, b).  Every shuffle runs in the
-  // whole wave (its source lanes must be active).
-  const int a = lane / 6, b = lane % 6;
-  const int q = lane >= 36 ? 0 : (a <= b ? tri(a, b) : tri(b, a));
-  const double h = __shfl(v, q, WAVE);
-  if (lane < 36) o->information[lane] = h;
-  const double g = __shfl(v, lane < 6 ? 21 + lane : 0, WAVE);
-  if (lane < 6) o->gradient[lane] = g;
-  const double rows = __shfl(v, RED_VALID, WAVE);
-  const double cost = __shfl(v, RED_COST, WAVE);
-  const bool finite = lane >= RED_VALID || finite_f64(v);
-  const bool all_finite = __ballot(!finite) == 0ull && finite_f64(cost);
-  if (lane == 0) {
-    o->cost = cost;
-    o->rows = (int32_t)rows;
-    uint32_t flags = 0;
-    if (rows < 6.0) flags |= PHOVO_PAIR_RANK_DEFICIENT;
-    if (!all_finite) flags |= PHOVO_PAIR_NONFINITE;
-    o->flags = flags;
-  }
+  finish_slab<NRED>(g_part, tiles, [&](int pair, int lane, double v) { write_pair_system(out + pair, lane, v); });
 }
 
 }  // namespace

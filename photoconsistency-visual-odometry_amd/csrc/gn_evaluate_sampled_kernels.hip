@@ -11,30 +11,21 @@
 //   ROWS_AFFINE     the corrected six, dr/dalpha = -I0, dr/dbeta = -1, residual I1(u, v) - (1 + alpha) I0 - beta
 // W is the identity, or on the six-column kinds with huber_delta > 0 the aligner's IRLS weights (1 or delta/|r|).
 //
-// The form is gn_evaluate_kernels.hip's without its first pass: a pair is cut into tiles of 16 64-pixel chunks, one 256-thread
-// workgroup per tile, and the kernel boundary is the only synchronisation (no atomics, no grid barrier):
-//   k_eval_sampled         pose constants of the pair's state into LDS (write_pose_constants: every sin/cos branch is the
-//                          aligners'), warp, twelve clamped taps per pixel gathered from the planes, the row's sums; per
-//                          tile one block of 32 sums (21 + 6 + rows + cost) or, with eight columns, two (the affine
+// The tile form of gn_evaluate_device.hpp (tiles, slabs, fixed summation orders: there) without gn_evaluate_kernels.hip's
+// first pass (no atomics):
+//   k_eval_sampled         pose constants, warp, twelve clamped taps per pixel gathered from the planes, the row's sums;
+//                          per tile one block of 32 sums (21 + 6 + rows + cost) or, with eight columns, two (the affine
 //                          kernel's second block: sum J_j I0, sum J_j, sum I0^2, sum I0, sum r I0, sum r)
 //   k_eval_sampled_finish  fixed-order sum of the tile slabs into phovo_sampled_system, one workgroup per pair
-// The tile count and every summation order depend on the level size only: a pair's result is the same bit for bit
-// whatever the batch, its position in it, or any setting of the engine.
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 
-#include "gn_device.hpp"
-#include "phovo_internal.hpp"
+#include "gn_evaluate_device.hpp"
 
 namespace phovo_hip {
 
 namespace {
 
-constexpr int ET = 256;                 // threads per tile workgroup
-constexpr int E_TILE_CHUNKS = 16;       // 64-pixel chunks per tile (1024 pixels), 4 per wave
-constexpr int ENW = ET / WAVE;
-constexpr int ECPW = E_TILE_CHUNKS / ENW;       // chunks per wave
-constexpr int RED_COST = 28;            // slot behind the row count: r^T W r
 enum { ROWS_SLIP = 0, ROWS_CORRECTED = 1, ROWS_AFFINE = 2 };
 // second block of sums (eight columns): the affine kernel's
 enum { X_JI0 = 0, X_J = 6, X_I0I0 = 12, X_I0 = 13, X_RI0 = 14, X_R = 15 };
@@ -56,18 +47,8 @@ __global__ __launch_bounds__(ET) void k_eval_sampled(const GNSampledEvalArgs A, 
   const int wave = __builtin_amdgcn_readfirstlane(tid / WAVE);
   const int n = A.n, W = A.w, H = A.h;
   const double *st = A.states + (size_t)pair * A.state_dim;
-  if (tid < WAVE) write_pose_constants(st[0], st[1], st[2], st[3], st[4], st[5], s_cst, tid);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __syncthreads();
-  const double cx = uniform_f64(s_cst[C_X]), cyy = uniform_f64(s_cst[C_Y]), cz = uniform_f64(s_cst[C_Z]);
-  const double r01 = uniform_f64(s_cst[C_R01]), r02 = uniform_f64(s_cst[C_R02]);
-  const double r11 = uniform_f64(s_cst[C_R11]), r12 = uniform_f64(s_cst[C_R12]);
-  const double t1 = uniform_f64(s_cst[C_T1]), t2 = uniform_f64(s_cst[C_T2]), t3 = uniform_f64(s_cst[C_T3]);
-  const double t4 = uniform_f64(s_cst[C_T4]), t5 = uniform_f64(s_cst[C_T5]), t6 = uniform_f64(s_cst[C_T6]);
-  const double t8 = uniform_f64(s_cst[C_T8]), t14 = uniform_f64(s_cst[C_T14]), t15 = uniform_f64(s_cst[C_T15]);
-  const double t16 = uniform_f64(s_cst[C_T16]), t17 = uniform_f64(s_cst[C_T17]), t24 = uniform_f64(s_cst[C_T24]);
-  const double cosy = uniform_f64(s_cst[C_CY]), siny = uniform_f64(s_cst[C_SY]);
-  const double t7 = -t6, t9 = -t8, t21 = -t5;
+  eval_pose_to_lds(st, s_cst);
+  const SampledPose P = sampled_pose(s_cst);
   const double gain = AFFINE ? 1.0 + st[6] : 1.0, beta = AFFINE ? st[7] : 0.0;
 
   const unsigned char *src_frame = A.planes + (size_t)A.src[pair] * A.frame_bytes;
@@ -77,8 +58,7 @@ __global__ __launch_bounds__(ET) void k_eval_sampled(const GNSampledEvalArgs A, 
   // one descriptor for the target frame; a plane is chosen by the load's scalar offset
   const __amdgpu_buffer_rsrc_t rT = frame_rsrc(tgt_frame, A.frame_bytes);
   const int o_i = (int)A.plane_off[PLANE_I], o_gx = (int)A.plane_off[PLANE_GX], o_gy = (int)A.plane_off[PLANE_GY];
-  const double fx = A.fx, fy = A.fy, ox = A.ox, oy = A.oy, ifx = A.ifx, ify = A.ify;
-  const double min_d = A.min_depth, max_d = A.max_depth;
+  const double fx = A.fx, fy = A.fy;
   const double wlim = (double)W - 0.5, hlim = (double)H - 0.5;
   const double huber_delta = A.huber_delta;
   const RowColFromIndex rc_map = make_rowcol_from_index(W);
@@ -97,41 +77,9 @@ __global__ __launch_bounds__(ET) void k_eval_sampled(const GNSampledEvalArgs A, 
     i0s[j] = plane_load<TI>(rI0, k);
   }
 
-  struct Warped {
-    double px, py, pz, Zr, t25, ax, ay;
-    int idx[4];                           // the clamped taps p00, p01, p10, p11: indices into a plane
-    unsigned long long m;                 // lanes that are valid and land in bounds
-  };
   double tap[12];                         // I1, GX1, GY1 at p00, p01, p10, p11 of the chunk whose taps are in flight
   auto warp = [&](Warped &w, int j) {
-    const int k = (blockIdx.x * E_TILE_CHUNKS + j * ENW + wave) * WAVE + lane;
-    const double pz = pzs[j];
-    double cd, rd;
-    rowcol_from_index((double)k, rc_map, cd, rd);
-    const double px = (cd - ox) * pz * ifx;                               // :282
-    const double py = (rd - oy) * pz * ify;                               // :283
-    const double X = ((t15 * px + r01 * py) + r02 * pz) + cx;             // :291
-    const double Y = ((t14 * px + r11 * py) + r12 * pz) + cyy;
-    const double Zr = py * t1 + pz * t2 - px * t3;
-    const double t25 = fast_rcp(cz + Zr);                                 // :294 and :313 are the same quantity
-    const double tc = (X * fx) * t25 + ox;                                // :295
-    const double tr = (Y * fy) * t25 + oy;                                // :296
-    // depth gate, and in bounds iff the NEAREST pixel is inside (NaN fails the comparisons)
-    w.m = __builtin_amdgcn_ballot_w64(k < n) & __builtin_amdgcn_ballot_w64(min_d < pz) &
-          __builtin_amdgcn_ballot_w64(pz < max_d) & __builtin_amdgcn_ballot_w64(tc > -0.5) &
-          __builtin_amdgcn_ballot_w64(tc < wlim) & __builtin_amdgcn_ballot_w64(tr > -0.5) &
-          __builtin_amdgcn_ballot_w64(tr < hlim);
-    w.px = px; w.py = py; w.pz = pz; w.Zr = Zr; w.t25 = t25;
-    const double fc = floor(tc), fr = floor(tr);
-    w.ax = tc - fc;
-    w.ay = tr - fr;
-    // (lanes outside w.m: whatever the conversions give, clamped into the plane like the others; nobody uses their taps)
-    const int ic = (int)fc, ir = (int)fr;
-    const int r0w = __mul24(min(max(ir, 0), H - 1), W), r1w = __mul24(min(max(ir + 1, 0), H - 1), W);
-    // clamp-to-edge taps (in the outer half-pixel band both taps of a row / a column are the edge pixel): every index
-    // lies in [0, n)
-    const int c0i = min(max(ic, 0), W - 1), c1i = min(max(ic + 1, 0), W - 1);
-    w.idx[0] = r0w + c0i; w.idx[1] = r0w + c1i; w.idx[2] = r1w + c0i; w.idx[3] = r1w + c1i;
+    warp_bilinear(w, (blockIdx.x * E_TILE_CHUNKS + j * ENW + wave) * WAVE + lane, pzs[j], P, A, wlim, hlim, rc_map);
   };
   auto issue = [&](const Warped &w) {
     if (__builtin_amdgcn_inverse_ballot_w64(w.m)) {
@@ -160,24 +108,25 @@ __global__ __launch_bounds__(ET) void k_eval_sampled(const GNSampledEvalArgs A, 
         const double px = w.px, py = w.py, pz = w.pz, Zr = w.Zr, t25 = w.t25;
         const double res = AFFINE ? (smp[0] - gain * i0) - beta : smp[0] - i0;
         const double gxi = smp[1], gyi = smp[2];
-        const double base = pz * t4 + py * t5 + px * t15;                 // (pz*temp4+py*temp5+px*temp15) = X - x
-        const double Au = KIND != ROWS_SLIP ? base + cx : base + px * cx; // reference: px*(temp15 + x)  (:253)
-        const double Bv = py * t6 + pz * t9 + px * t14 + cyy;
-        const double Cm = -py * t16 - pz * t17 - px * t24;
-        const double Dm = py * t2 - pz * t1;
+        const double base = pz * P.t4 + py * P.t5 + px * P.t15;           // (pz*temp4+py*temp5+px*temp15) = X - x
+        const double Au = KIND != ROWS_SLIP ? base + P.cx : base + px * P.cx;     // reference: px*(temp15 + x)  (:253)
+        const double Bv = py * P.t6 + pz * P.t9 + px * P.t14 + P.cyy;
+        const double Cm = -py * P.t16 - pz * P.t17 - px * P.t24;
+        const double Dm = py * P.t2 - pz * P.t1;
         double J[6];
         J[0] = (gxi * fx) * t25;
         J[1] = (gyi * fy) * t25;
         J[2] = -(J[0] * Au + J[1] * Bv) * t25;
-        J[3] = J[0] * (cyy - Bv) + J[1] * base;
-        J[4] = (J[0] * cosy + J[1] * siny) * Zr + Cm * J[2];
-        J[5] = J[0] * (py * t4 + pz * t21) + J[1] * (pz * t7 + py * t9) + Dm * J[2];
+        J[3] = J[0] * (P.cyy - Bv) + J[1] * base;
+        J[4] = (J[0] * P.cosy + J[1] * P.siny) * Zr + Cm * J[2];
+        J[5] = J[0] * (py * P.t4 + pz * P.t21) + J[1] * (pz * P.t7 + py * P.t9) + Dm * J[2];
         double wgt = 1.0;
         if (HUBER) {                                // the aligner's IRLS weight
           const double ar = fabs(res);
           wgt = ar <= huber_delta ? 1.0 : huber_delta / ar;
         }
         acc[RED_COST] = fma(HUBER ? res * wgt : res, res, acc[RED_COST]); // r^T W r
+        // (add_row's sums column by column, with the second block's between them: the order this kernel was compiled with)
         int q = 0;
 #pragma unroll
         for (int a = 0; a < 6; a++) {
@@ -220,7 +169,7 @@ __global__ __launch_bounds__(ET) void k_eval_sampled(const GNSampledEvalArgs A, 
   };
   if (!AFFINE && huber_delta > 0.0) rows(std::true_type{}); else rows(std::false_type{});
   acc[RED_VALID] = lane == 0 ? (double)n_rows : 0.0;
-  // tile sums: wave butterfly, then the four waves in fixed order
+  // tile_sums() for NB blocks: wave butterfly, then the four waves in fixed order, slab [pairs][tiles][NB][NRED]
   reduce_wave_to_row(acc, lane, wave, s_red);
   if (AFFINE) reduce_wave_to_row(acc2, lane, ENW + wave, s_red);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -234,67 +183,48 @@ __global__ __launch_bounds__(ET) void k_eval_sampled(const GNSampledEvalArgs A, 
   }
 }
 
-// One workgroup per pair: thread (s, j) adds tiles s, s + S, s + 2 S, ... of value j (S = 8 subsets of one block of sums,
-// 4 of two blocks), then the subset sums are added in subset order; the system is written from the upper triangle, with
-// the signs of the affine columns applied here (exact).
+// One workgroup per pair: the fixed-order sum of its slab (finish_slab: 8 subsets of one block of sums, 4 of two blocks);
+// the system is written from the upper triangle, with the signs of the affine columns applied here (exact).
 template <int NB>
 __global__ __launch_bounds__(ET) void k_eval_sampled_finish(const double *g_part, int tiles, phovo_sampled_system *out)
 {
-  constexpr int NV = NB * NRED;           // values per tile
-  constexpr int SUBSETS = ET / NV;
   constexpr int DIM = NB == 2 ? 8 : 6;
-  __shared__ double s_part[SUBSETS * NV];
-  const int pair = blockIdx.x, tid = threadIdx.x;
-  {
-    const int j = tid & (NV - 1), sub = tid / NV;
-    const double *base = g_part + (size_t)pair * tiles * NV + j;
-    double v = 0.0;
-#pragma unroll 4
-    for (int t = sub; t < tiles; t += SUBSETS) v += base[(size_t)t * NV];
-    s_part[sub * NV + j] = v;
-  }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid >= WAVE) return;
-  const int lane = tid;
-  double v = 0.0;                         // lanes 0..31: the first block of sums; 32..63: the second (eight columns)
-  if (lane < NV) {
-#pragma unroll
-    for (int sub = 0; sub < SUBSETS; sub++) v += s_part[sub * NV + lane];
-  }
-  phovo_sampled_system *o = out + pair;
-  // lane (a, b) of the 8 x 8 record: the slot of (min, max)(a, b); rows and columns >= DIM are 0.  Every shuffle runs in
-  // the whole wave (its source lanes must be active).
-  const int a = min(lane >> 3, lane & 7), b = max(lane >> 3, lane & 7);
-  int q = 0;
-  bool negate = false, inside = b < DIM;
-  if (b < 6) q = tri(a, b);
-  else if (NB == 2) {
-    if (a < 6) { q = NRED + (b == 6 ? X_JI0 : X_J) + a; negate = true; }
-    else if (b == 6) q = NRED + X_I0I0;
-    else q = a == 6 ? NRED + X_I0 : RED_VALID;
-  }
-  const double hs = __shfl(v, inside ? q : 0, WAVE);
-  o->information[lane] = !inside ? 0.0 : (negate ? 0.0 - hs : hs);
-  int qg = 0;
-  if (lane < 6) qg = 21 + lane;
-  else if (NB == 2 && lane < 8) qg = NRED + (lane == 6 ? X_RI0 : X_R);
-  const double gs = __shfl(v, qg, WAVE);
-  if (lane < 8) o->gradient[lane] = lane < 6 ? gs : (lane < DIM ? 0.0 - gs : 0.0);
-  const double rows = __shfl(v, RED_VALID, WAVE);
-  const double cost = __shfl(v, RED_COST, WAVE);
-  const bool finite = fabs(v) <= 1.79769313486231570815e308;            // (unused slots and lanes hold 0)
-  const bool all_finite = __ballot(!finite) == 0ull;
-  if (lane == 0) {
-    o->cost = cost;
-    o->rows = (int32_t)rows;
-    uint32_t flags = 0;
-    if (rows < (double)DIM) flags |= PHOVO_PAIR_RANK_DEFICIENT;
-    if (!all_finite) flags |= PHOVO_PAIR_NONFINITE;
-    o->flags = flags;
-    o->dim = DIM;
-    o->reserved = 0;
-  }
+  // lanes 0..31: the first block of sums; 32..63: the second (eight columns)
+  finish_slab<NB * NRED>(g_part, tiles, [&](int pair, int lane, double v) {
+    phovo_sampled_system *o = out + pair;
+    // lane (a, b) of the 8 x 8 record: the slot of (min, max)(a, b); rows and columns >= DIM are 0.  Every shuffle runs in
+    // the whole wave (its source lanes must be active).
+    const int a = min(lane >> 3, lane & 7), b = max(lane >> 3, lane & 7);
+    int q = 0;
+    bool negate = false, inside = b < DIM;
+    if (b < 6) q = tri(a, b);
+    else if (NB == 2) {
+      if (a < 6) { q = NRED + (b == 6 ? X_JI0 : X_J) + a; negate = true; }
+      else if (b == 6) q = NRED + X_I0I0;
+      else q = a == 6 ? NRED + X_I0 : RED_VALID;
+    }
+    const double hs = __shfl(v, inside ? q : 0, WAVE);
+    o->information[lane] = !inside ? 0.0 : (negate ? 0.0 - hs : hs);
+    int qg = 0;
+    if (lane < 6) qg = 21 + lane;
+    else if (NB == 2 && lane < 8) qg = NRED + (lane == 6 ? X_RI0 : X_R);
+    const double gs = __shfl(v, qg, WAVE);
+    if (lane < 8) o->gradient[lane] = lane < 6 ? gs : (lane < DIM ? 0.0 - gs : 0.0);
+    const double rows = __shfl(v, RED_VALID, WAVE);
+    const double cost = __shfl(v, RED_COST, WAVE);
+    const bool finite = finite_f64(v);                                  // (unused slots and lanes hold 0)
+    const bool all_finite = __ballot(!finite) == 0ull;
+    if (lane == 0) {
+      o->cost = cost;
+      o->rows = (int32_t)rows;
+      uint32_t flags = 0;
+      if (rows < (double)DIM) flags |= PHOVO_PAIR_RANK_DEFICIENT;
+      if (!all_finite) flags |= PHOVO_PAIR_NONFINITE;
+      o->flags = flags;
+      o->dim = DIM;
+      o->reserved = 0;
+    }
+  });
 }
 
 template <typename TI, typename TD>
@@ -328,12 +258,9 @@ hipError_t gn_eval_sampled_pairs(const GNSampledEvalArgs &a, int n_pairs, int st
   }
   if (a.state_dim != 6) return hipErrorInvalidValue;
   const int kind = corrected ? ROWS_CORRECTED : ROWS_SLIP;
-  switch (storage) {
-    case PHOVO_STORAGE_F64: return sampled_launch<double, double>(a, n_pairs, kind, tiles, g_part, out, stream);
-    case PHOVO_STORAGE_F32: return sampled_launch<float, float>(a, n_pairs, kind, tiles, g_part, out, stream);
-    case PHOVO_STORAGE_F16: return sampled_launch<__half, float>(a, n_pairs, kind, tiles, g_part, out, stream);
-    default: return hipErrorInvalidValue;
-  }
+  return with_storage_types(storage, [&](auto ti, auto td) {
+    return sampled_launch<decltype(ti), decltype(td)>(a, n_pairs, kind, tiles, g_part, out, stream);
+  });
 }
 
 }  // namespace phovo_hip
