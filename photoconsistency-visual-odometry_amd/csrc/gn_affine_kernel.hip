@@ -14,8 +14,7 @@
 // summation order depends on the level size only.
 #include <hip/hip_runtime.h>
 
-#include "gn_device.hpp"
-#include "phovo_internal.hpp"
+#include "gn_sampled_device.hpp"
 
 namespace phovo_hip {
 
@@ -67,30 +66,8 @@ __device__ __forceinline__ void affine_solve_update(int lane, const double *s_re
   last_valid = (int)rows;
   double step[NP];
   solve8_ldlt(h, g, step);
-  double st[NP];
-  bool finite = true;
-#pragma unroll
-  for (int i = 0; i < NP; i++) {
-    st[i] = s_state[i] - lambda * step[i];
-    finite = finite && (fabs(st[i]) <= 1.79769313486231570815e308);
-  }
-  double gn2 = 0.0;
-#pragma unroll
-  for (int i = 0; i < NP; i++) gn2 += g[i] * g[i];
-  const double gnorm = sqrt(gn2);
-  bool done = false;
-  if (iteration + 1 >= max_iter) done = true;
-  else if (gnorm < min_grad_norm) done = true;
-  if (!finite) done = true;
-  if (!done) write_pose_constants(st[0], st[1], st[2], st[3], st[4], st[5], s_cst, lane);
-  if (lane == 0) {
-#pragma unroll
-    for (int i = 0; i < NP; i++) s_state[i] = st[i];
-    s_ctl[CTL_DONE] = done ? 1 : 0;
-    if (!finite) s_ctl[CTL_FLAGS] |= (int)PHOVO_PAIR_NONFINITE;
-    if (last_valid < NP) s_ctl[CTL_FLAGS] |= (int)PHOVO_PAIR_RANK_DEFICIENT;
-  }
-  last_gnorm = gnorm;
+  update_and_terminate<NP>(lane, step, g, s_state, s_cst, s_ctl, lambda, max_iter, min_grad_norm, iteration, last_valid,
+                           last_gnorm);
 }
 
 template <int T, int WPS>
@@ -99,20 +76,15 @@ __global__ __launch_bounds__(T, WPS) void gn_level_kernel_affine(const GNAffineA
   const GNLevelArgs &A = B.lv;
   constexpr int NW = T / WAVE;
   extern __shared__ __align__(16) unsigned char lds_raw[];
-  double *s_cst = reinterpret_cast<double *>(lds_raw);                 // [32]
-  double *s_state = s_cst + 32;                                        // [8]: the pose, alpha, beta
-  double *s_red = s_state + 8;                                         // [2][NW][NRED]
-  int *s_ctl = reinterpret_cast<int *>(s_red + 2 * NW * NRED);         // [CTL_COUNT]
+  const PairLds L = pair_lds<NW, 2>(lds_raw);                          // state: the pose, alpha, beta; two blocks of sums
 
   const int tid = threadIdx.x;
   const int lane = tid & (WAVE - 1);
   const int wave = __builtin_amdgcn_readfirstlane(tid / WAVE);
   const int n = A.n, W = A.w, H = A.h;
-  if (tid == 0) s_ctl[CTL_PAIR] = draw_pair(A.work_counter, A.n_queues, A.n_pairs);
+  if (tid == 0) L.ctl[CTL_PAIR] = draw_pair(A.work_counter, A.n_queues, A.n_pairs);
   for (;;) {                                // work queue, as in gn_level_kernel
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // see gn_level_kernel
-  __syncthreads();
-  const int pair = __builtin_amdgcn_readfirstlane(s_ctl[CTL_PAIR]);
+  const int pair = pair_drawn(L);
   if (pair >= A.n_pairs) break;
   const unsigned char *src_frame = A.planes + (size_t)A.src[pair] * A.frame_bytes;
   const unsigned char *tgt_frame = A.planes + (size_t)A.tgt[pair] * A.frame_bytes;
@@ -122,45 +94,20 @@ __global__ __launch_bounds__(T, WPS) void gn_level_kernel_affine(const GNAffineA
   const __amdgpu_buffer_rsrc_t rT = frame_rsrc(tgt_frame, A.frame_bytes);
   const int o_i = (int)A.plane_off[PLANE_I], o_gx = (int)A.plane_off[PLANE_GX], o_gy = (int)A.plane_off[PLANE_GY];
 
-  if (wave == 0) {
-    double st[6];
-#pragma unroll
-    for (int j = 0; j < 6; j++) st[j] = A.states[(size_t)pair * 6 + j];
-    write_pose_constants(st[0], st[1], st[2], st[3], st[4], st[5], s_cst, lane);
-    if (lane == 0) {
-#pragma unroll
-      for (int j = 0; j < 6; j++) s_state[j] = st[j];
-      s_state[6] = B.illum[(size_t)pair * 2];
-      s_state[7] = B.illum[(size_t)pair * 2 + 1];
-      s_ctl[CTL_DONE] = 0;
-      s_ctl[CTL_FLAGS] = 0;
-    }
-  }
-  __syncthreads();
+  pair_begin(A, pair, wave, lane, L, [L, &B, pair] {
+    L.state[6] = B.illum[(size_t)pair * 2];
+    L.state[7] = B.illum[(size_t)pair * 2 + 1];
+  });
 
-  const double fx = A.fx, fy = A.fy, ox = A.ox, oy = A.oy, ifx = A.ifx, ify = A.ify;
-  const double min_d = A.min_depth, max_d = A.max_depth;
-  const double wlim = (double)W - 0.5, hlim = (double)H - 0.5;
-  const int k0 = wave * WAVE + lane;
-  const int r0 = k0 / W, c0 = k0 - r0 * W;
-  const int step_r = (NW * WAVE) / W, step_c = (NW * WAVE) - step_r * W;
-  const RowColStep rc_step = make_rowcol_step(step_r, step_c, W);
-  const double cd0 = (double)c0, rd0 = (double)r0;
+  const WarpFrame F = warp_frame(A);
+  const LaneWalk lw = lane_walk<NW>(wave, lane, W);
 
   int iteration = 0;
   double last_gnorm = 0.0;
   int last_valid = 0;
   while (true) {
-    const double cx = uniform_f64(s_cst[C_X]), cyy = uniform_f64(s_cst[C_Y]), cz = uniform_f64(s_cst[C_Z]);
-    const double r01 = uniform_f64(s_cst[C_R01]), r02 = uniform_f64(s_cst[C_R02]);
-    const double r11 = uniform_f64(s_cst[C_R11]), r12 = uniform_f64(s_cst[C_R12]);
-    const double t1 = uniform_f64(s_cst[C_T1]), t2 = uniform_f64(s_cst[C_T2]), t3 = uniform_f64(s_cst[C_T3]);
-    const double t4 = uniform_f64(s_cst[C_T4]), t5 = uniform_f64(s_cst[C_T5]), t6 = uniform_f64(s_cst[C_T6]);
-    const double t8 = uniform_f64(s_cst[C_T8]), t14 = uniform_f64(s_cst[C_T14]), t15 = uniform_f64(s_cst[C_T15]);
-    const double t16 = uniform_f64(s_cst[C_T16]), t17 = uniform_f64(s_cst[C_T17]), t24 = uniform_f64(s_cst[C_T24]);
-    const double cosy = uniform_f64(s_cst[C_CY]), siny = uniform_f64(s_cst[C_SY]);
-    const double t7 = -t6, t9 = -t8, t21 = -t5;
-    const double gain = 1.0 + uniform_f64(s_state[6]), beta = uniform_f64(s_state[7]);
+    const SampledPose P = sampled_pose(L.cst);
+    const double gain = 1.0 + uniform_f64(L.state[6]), beta = uniform_f64(L.state[7]);
 
     double acc[NRED], acc2[NRED];
 #pragma unroll
@@ -178,8 +125,8 @@ __global__ __launch_bounds__(T, WPS) void gn_level_kernel_affine(const GNAffineA
       unsigned long long m;                 // lanes that are valid and land in bounds
     };
     double tap[12];                         // I1, GX1, GY1 at p00, p01, p10, p11 of the chunk whose taps are in flight
-    int k = k0;
-    double cd = cd0, rd = rd0;
+    int k = lw.k0;
+    double cd = lw.cd0, rd = lw.rd0;
     double pz_next = plane_load<double>(rD0, k);                          // past the plane: 0
     double i0_next = plane_load<double>(rI0, k);
     auto warp = [&](Warped &w) {
@@ -187,32 +134,9 @@ __global__ __launch_bounds__(T, WPS) void gn_level_kernel_affine(const GNAffineA
       w.i0 = i0_next;
       pz_next = plane_load<double>(rD0, k + NW * WAVE);
       i0_next = plane_load<double>(rI0, k + NW * WAVE);
-      const double px = (cd - ox) * pz * ifx;
-      const double py = (rd - oy) * pz * ify;
-      const double X = ((t15 * px + r01 * py) + r02 * pz) + cx;
-      const double Y = ((t14 * px + r11 * py) + r12 * pz) + cyy;
-      const double Zr = py * t1 + pz * t2 - px * t3;
-      const double t25 = fast_rcp(cz + Zr);
-      const double tc = (X * fx) * t25 + ox;
-      const double tr = (Y * fy) * t25 + oy;
-      // depth gate, and in bounds iff the NEAREST pixel is inside (NaN fails the comparisons)
-      w.m = __builtin_amdgcn_ballot_w64(k < n) & __builtin_amdgcn_ballot_w64(min_d < pz) &
-            __builtin_amdgcn_ballot_w64(pz < max_d) & __builtin_amdgcn_ballot_w64(tc > -0.5) &
-            __builtin_amdgcn_ballot_w64(tc < wlim) & __builtin_amdgcn_ballot_w64(tr > -0.5) &
-            __builtin_amdgcn_ballot_w64(tr < hlim);
-      w.px = px; w.py = py; w.pz = pz; w.Zr = Zr; w.t25 = t25;
-      const double fc = floor(tc), fr = floor(tr);
-      w.ax = tc - fc;
-      w.ay = tr - fr;
-      // (lanes outside w.m: whatever the conversions give, clamped into the plane like the others; nobody uses their taps)
-      const int ic = (int)fc, ir = (int)fr;
-      const int r0w = __mul24(min(max(ir, 0), H - 1), W), r1w = __mul24(min(max(ir + 1, 0), H - 1), W);
-      // clamp-to-edge taps (in the outer half-pixel band both taps of a row / a column are the edge pixel): every index
-      // lies in [0, n)
-      const int c0i = min(max(ic, 0), W - 1), c1i = min(max(ic + 1, 0), W - 1);
-      w.idx[0] = r0w + c0i; w.idx[1] = r0w + c1i; w.idx[2] = r1w + c0i; w.idx[3] = r1w + c1i;
+      clamped_taps(w.idx, warp_cell(w, warp_project(w, k, cd, rd, pz, P, F)), W, H);
       k += NW * WAVE;
-      rowcol_advance(cd, rd, rc_step);
+      rowcol_advance(cd, rd, lw.step);
     };
     auto issue = [&](const Warped &w) {
       if (__builtin_amdgcn_inverse_ballot_w64(w.m)) {
@@ -225,40 +149,20 @@ __global__ __launch_bounds__(T, WPS) void gn_level_kernel_affine(const GNAffineA
       }
     };
     auto sample3 = [&](const Warped &w, double (&smp)[3]) {               // -> the bilinear samples I1, GX1, GY1
-      const double ax = w.ax, ay = w.ay;
 #pragma unroll
-      for (int c = 0; c < 3; c++)
-        smp[c] = (1.0 - ay) * ((1.0 - ax) * tap[4 * c] + ax * tap[4 * c + 1]) + ay * ((1.0 - ax) * tap[4 * c + 2] + ax * tap[4 * c + 3]);
+      for (int c = 0; c < 3; c++) smp[c] = bilerp(w.ax, w.ay, tap[4 * c], tap[4 * c + 1], tap[4 * c + 2], tap[4 * c + 3]);
     };
     int n_rows = 0;
     auto consume = [&](const Warped &w, const double (&smp)[3]) {
       n_rows += __builtin_popcountll(w.m);
       if (__builtin_amdgcn_inverse_ballot_w64(w.m)) {
-        const double px = w.px, py = w.py, pz = w.pz, Zr = w.Zr, t25 = w.t25, i0 = w.i0;
+        const double i0 = w.i0;
         const double res = (smp[0] - gain * i0) - beta;
-        const double gxi = smp[1], gyi = smp[2];
-
-        const double base = pz * t4 + py * t5 + px * t15;
-        const double Au = base + cx;                                      // the true warp Jacobian (CORRECTED)
-        const double Bv = py * t6 + pz * t9 + px * t14 + cyy;
-        const double Cm = -py * t16 - pz * t17 - px * t24;
-        const double Dm = py * t2 - pz * t1;
         double J[6];
-        J[0] = (gxi * fx) * t25;
-        J[1] = (gyi * fy) * t25;
-        J[2] = -(J[0] * Au + J[1] * Bv) * t25;
-        J[3] = J[0] * (cyy - Bv) + J[1] * base;
-        J[4] = (J[0] * cosy + J[1] * siny) * Zr + Cm * J[2];
-        J[5] = J[0] * (py * t4 + pz * t21) + J[1] * (pz * t7 + py * t9) + Dm * J[2];
-        int q = 0;
+        pose_columns<true>(J, smp[1], smp[2], w, P, F.fx, F.fy);
+        add_row(acc, J, res);
 #pragma unroll
         for (int a = 0; a < 6; a++) {
-#pragma unroll
-          for (int b = a; b < 6; b++) {
-            acc[q] = fma(J[a], J[b], acc[q]);
-            q++;
-          }
-          acc[21 + a] = fma(J[a], res, acc[21 + a]);
           acc2[X_JI0 + a] = fma(J[a], i0, acc2[X_JI0 + a]);
           acc2[X_J + a] += J[a];
         }
@@ -294,28 +198,22 @@ __global__ __launch_bounds__(T, WPS) void gn_level_kernel_affine(const GNAffineA
       }
     }
     acc[RED_VALID] = lane == 0 ? (double)n_rows : 0.0;
-    reduce_wave_to_row(acc, lane, wave, s_red);
-    reduce_wave_to_row(acc2, lane, NW + wave, s_red);
+    reduce_wave_to_row(acc, lane, wave, L.red);
+    reduce_wave_to_row(acc2, lane, NW + wave, L.red);
     __syncthreads();
     if (wave == 0)
-      affine_solve_update<NW>(lane, s_red, s_state, s_cst, s_ctl, A.lambda, A.max_iter, A.min_grad_norm, iteration,
+      affine_solve_update<NW>(lane, L.red, L.state, L.cst, L.ctl, A.lambda, A.max_iter, A.min_grad_norm, iteration,
                               last_gnorm, last_valid);
     __syncthreads();
     iteration++;
-    if (s_ctl[CTL_DONE]) break;
+    if (L.ctl[CTL_DONE]) break;
   }
   if (tid == 0) {
-#pragma unroll
-    for (int j = 0; j < 6; j++) A.states[(size_t)pair * 6 + j] = s_state[j];
-    B.illum[(size_t)pair * 2] = s_state[6];
-    B.illum[(size_t)pair * 2 + 1] = s_state[7];
-    if (A.reports) {
-      A.reports[pair].iterations[A.level] = iteration;
-      A.reports[pair].gradient_norm = last_gnorm;
-      A.reports[pair].valid_pixels[A.level] = last_valid;
-      A.reports[pair].flags |= (uint32_t)s_ctl[CTL_FLAGS];
-    }
-    s_ctl[CTL_PAIR] = draw_pair(A.work_counter, A.n_queues, A.n_pairs);
+    pair_report(A, pair, L, iteration, last_gnorm, last_valid, [L, &B, pair] {
+      B.illum[(size_t)pair * 2] = L.state[6];
+      B.illum[(size_t)pair * 2 + 1] = L.state[7];
+    });
+    L.ctl[CTL_PAIR] = draw_pair(A.work_counter, A.n_queues, A.n_pairs);
   }
   }   // next pair
 }
@@ -333,10 +231,8 @@ hipError_t gn_launch_level_affine(const GNAffineArgs &b, int cu_count, hipStream
 {
   if (b.lv.n_pairs <= 0) return hipSuccess;
   if (!b.illum) return hipErrorInvalidValue;
-  const int resident = cu_count * AFFINE_WPS;                        // persistent grid: as many workgroups as stay resident
-  const dim3 grid((unsigned)(b.lv.n_pairs < resident ? b.lv.n_pairs : resident)), block(256);
-  hipLaunchKernelGGL((gn_level_kernel_affine<256, AFFINE_WPS>), grid, block, affine_lds_bytes(256), stream, b);
-  return hipGetLastError();
+  return launch_persistent(gn_level_kernel_affine<256, AFFINE_WPS>, b.lv.n_pairs, cu_count, AFFINE_WPS, 256,
+                           affine_lds_bytes(256), stream, b);
 }
 
 }  // namespace phovo_hip

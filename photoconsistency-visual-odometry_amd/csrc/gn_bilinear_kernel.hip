@@ -21,8 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 
-#include "gn_device.hpp"
-#include "phovo_internal.hpp"
+#include "gn_sampled_device.hpp"
 
 namespace phovo_hip {
 
@@ -52,10 +51,11 @@ __global__ __launch_bounds__(T, WPS) void gn_level_kernel_bilinear(const GNLevel
 {
   constexpr int NW = T / WAVE;
   extern __shared__ __align__(16) unsigned char lds_raw[];
-  double *s_cst = reinterpret_cast<double *>(lds_raw);                 // [32]
-  double *s_state = s_cst + 32;                                        // [8]
-  double *s_red = s_state + 8;                                         // [NW][NRED]
-  int *s_ctl = reinterpret_cast<int *>(s_red + NW * NRED);             // [CTL_COUNT]
+  const PairLds L = pair_lds<NW>(lds_raw);
+  // (copies for the kernel's own accesses: through L, which the lambdas below would capture by reference, the compiler
+  // forms the LDS addresses anew -- other address instructions in both forms, one more scratch store and load in the fp32 dma form)
+  double *const s_cst = L.cst, *const s_state = L.state, *const s_red = L.red;
+  int *const s_ctl = L.ctl;
 
   const int tid = threadIdx.x;
   const int lane = tid & (WAVE - 1);
@@ -63,9 +63,7 @@ __global__ __launch_bounds__(T, WPS) void gn_level_kernel_bilinear(const GNLevel
   const int n = A.n, W = A.w, H = A.h;
   if (tid == 0) s_ctl[CTL_PAIR] = draw_pair(A.work_counter, A.n_queues, A.n_pairs);
   for (;;) {                                // work queue, as in gn_level_kernel
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // see gn_level_kernel
-  __syncthreads();
-  const int pair = __builtin_amdgcn_readfirstlane(s_ctl[CTL_PAIR]);
+  const int pair = pair_drawn(L);
   if (pair >= A.n_pairs) break;
   const unsigned char *src_frame = A.planes + (size_t)A.src[pair] * A.frame_bytes;
   const unsigned char *tgt_frame = A.planes + (size_t)A.tgt[pair] * A.frame_bytes;
@@ -74,44 +72,18 @@ __global__ __launch_bounds__(T, WPS) void gn_level_kernel_bilinear(const GNLevel
   static_assert(sizeof(TI) == 2, "the record form serves fp16 planes (fp64 / fp32: gn_level_kernel_bilinear_dma)");
   const __amdgpu_buffer_rsrc_t rRec = plane_rsrc<TI>(tgt_frame + A.rec_off, 4 * n);      // the target's tap records {I, GX, GY, pad}
 
-  if (wave == 0) {
-    double st[6];
-#pragma unroll
-    for (int j = 0; j < 6; j++) st[j] = A.states[(size_t)pair * 6 + j];
-    write_pose_constants(st[0], st[1], st[2], st[3], st[4], st[5], s_cst, lane);
-    if (lane == 0) {
-#pragma unroll
-      for (int j = 0; j < 6; j++) s_state[j] = st[j];
-      s_ctl[CTL_DONE] = 0;
-      s_ctl[CTL_FLAGS] = 0;
-    }
-  }
-  __syncthreads();
+  pair_begin(A, pair, wave, lane, L);
 
-  const double fx = A.fx, fy = A.fy, ox = A.ox, oy = A.oy, ifx = A.ifx, ify = A.ify;
-  const double min_d = A.min_depth, max_d = A.max_depth;
-  const double wlim = (double)W - 0.5, hlim = (double)H - 0.5;
+  const WarpFrame F = warp_frame(A);
   const double huber_delta = A.huber_delta;
   const bool huber_on = huber_delta > 0.0;
-  const int k0 = wave * WAVE + lane;
-  const int r0 = k0 / W, c0 = k0 - r0 * W;
-  const int step_r = (NW * WAVE) / W, step_c = (NW * WAVE) - step_r * W;
-  const RowColStep rc_step = make_rowcol_step(step_r, step_c, W);
-  const double cd0 = (double)c0, rd0 = (double)r0;
+  const LaneWalk lw = lane_walk<NW>(wave, lane, W);
 
   int iteration = 0;
   double last_gnorm = 0.0;
   int last_valid = 0;
   while (true) {
-    const double cx = uniform_f64(s_cst[C_X]), cyy = uniform_f64(s_cst[C_Y]), cz = uniform_f64(s_cst[C_Z]);
-    const double r01 = uniform_f64(s_cst[C_R01]), r02 = uniform_f64(s_cst[C_R02]);
-    const double r11 = uniform_f64(s_cst[C_R11]), r12 = uniform_f64(s_cst[C_R12]);
-    const double t1 = uniform_f64(s_cst[C_T1]), t2 = uniform_f64(s_cst[C_T2]), t3 = uniform_f64(s_cst[C_T3]);
-    const double t4 = uniform_f64(s_cst[C_T4]), t5 = uniform_f64(s_cst[C_T5]), t6 = uniform_f64(s_cst[C_T6]);
-    const double t8 = uniform_f64(s_cst[C_T8]), t14 = uniform_f64(s_cst[C_T14]), t15 = uniform_f64(s_cst[C_T15]);
-    const double t16 = uniform_f64(s_cst[C_T16]), t17 = uniform_f64(s_cst[C_T17]), t24 = uniform_f64(s_cst[C_T24]);
-    const double cosy = uniform_f64(s_cst[C_CY]), siny = uniform_f64(s_cst[C_SY]);
-    const double t7 = -t6, t9 = -t8, t21 = -t5;
+    const SampledPose P = sampled_pose(s_cst);
 
     double acc[NRED];
 #pragma unroll
@@ -128,8 +100,8 @@ __global__ __launch_bounds__(T, WPS) void gn_level_kernel_bilinear(const GNLevel
       tap_rec<TI> rec[4];                   // the records at p00, p01, p10, p11
       unsigned long long m;                 // lanes that are valid and land in bounds
     };
-    int k = k0;
-    double cd = cd0, rd = rd0;
+    int k = lw.k0;
+    double cd = lw.cd0, rd = lw.rd0;
     double pz_next = plane_load<TD>(rD0, k);                              // past the plane: 0
     double i0_next = plane_load<TI>(rI0, k);
     auto warp = [&](Warped &w) {
@@ -137,28 +109,11 @@ __global__ __launch_bounds__(T, WPS) void gn_level_kernel_bilinear(const GNLevel
       w.i0 = i0_next;
       pz_next = plane_load<TD>(rD0, k + NW * WAVE);
       i0_next = plane_load<TI>(rI0, k + NW * WAVE);
-      const double px = (cd - ox) * pz * ifx;                             // :282
-      const double py = (rd - oy) * pz * ify;                             // :283
-      const double X = ((t15 * px + r01 * py) + r02 * pz) + cx;           // :291
-      const double Y = ((t14 * px + r11 * py) + r12 * pz) + cyy;
-      const double Zr = py * t1 + pz * t2 - px * t3;
-      const double t25 = fast_rcp(cz + Zr);                               // :294 and :313 are the same quantity
-      const double tc = (X * fx) * t25 + ox;                              // :295
-      const double tr = (Y * fy) * t25 + oy;                              // :296
-      // depth gate (:280), and in bounds iff the NEAREST pixel is inside -- the same region as the reference's
-      // round() test (:297-303), so a zero-motion start never sits on the boundary; in the outer half-pixel band the
-      // taps are clamped to the edge row / column (NaN fails the comparisons).  One ballot per comparison, ANDed on
-      // the scalar unit.
-      w.m = __builtin_amdgcn_ballot_w64(k < n) & __builtin_amdgcn_ballot_w64(min_d < pz) &
-            __builtin_amdgcn_ballot_w64(pz < max_d) & __builtin_amdgcn_ballot_w64(tc > -0.5) &
-            __builtin_amdgcn_ballot_w64(tc < wlim) & __builtin_amdgcn_ballot_w64(tr > -0.5) &
-            __builtin_amdgcn_ballot_w64(tr < hlim);
-      w.px = px; w.py = py; w.pz = pz; w.Zr = Zr; w.t25 = t25;
+      const WarpTarget t = warp_project(w, k, cd, rd, pz, P, F);
+      // the taps under the row mask, so one-sided clamps do (in the outer half-pixel band the taps are the edge row / column)
       if (__builtin_amdgcn_inverse_ballot_w64(w.m)) {
-        const double fc = floor(tc), fr = floor(tr);
-        w.ax = tc - fc;
-        w.ay = tr - fr;
-        const int ic = (int)fc, ir = (int)fr;
+        const WarpCell c = warp_cell(w, t);
+        const int ic = c.ic, ir = c.ir;
         const int r0w = __mul24(max(ir, 0), W), r1w = __mul24(min(ir + 1, H - 1), W);
         // clamp-to-edge taps (in the outer half-pixel band both taps of a row / a column are the edge pixel)
         const int c0i = max(ic, 0), c1i = min(ic + 1, W - 1);
@@ -166,37 +121,27 @@ __global__ __launch_bounds__(T, WPS) void gn_level_kernel_bilinear(const GNLevel
         w.rec[2].load(rRec, r1w + c0i); w.rec[3].load(rRec, r1w + c1i);
       }
       k += NW * WAVE;
-      rowcol_advance(cd, rd, rc_step);
+      rowcol_advance(cd, rd, lw.step);
     };
     int n_rows = 0;
     auto consume = [&](const Warped &w) {
       n_rows += __builtin_popcountll(w.m);
       if (__builtin_amdgcn_inverse_ballot_w64(w.m)) {
-        const double px = w.px, py = w.py, pz = w.pz, Zr = w.Zr, t25 = w.t25, ax = w.ax, ay = w.ay;
-        auto sample = [&](double p00, double p01, double p10, double p11) {
-          return (1.0 - ay) * ((1.0 - ax) * p00 + ax * p01) + ay * ((1.0 - ax) * p10 + ax * p11);
-        };
+        const double ax = w.ax, ay = w.ay;
+        auto sample = [&](double p00, double p01, double p10, double p11) { return bilerp(ax, ay, p00, p01, p10, p11); };
         const double res = sample(w.rec[0].i(), w.rec[1].i(), w.rec[2].i(), w.rec[3].i()) - w.i0;
         const double gxi = sample(w.rec[0].gx(), w.rec[1].gx(), w.rec[2].gx(), w.rec[3].gx());
         const double gyi = sample(w.rec[0].gy(), w.rec[1].gy(), w.rec[2].gy(), w.rec[3].gy());
 
-        const double base = pz * t4 + py * t5 + px * t15;                 // (pz*temp4+py*temp5+px*temp15) = X - x
-        const double Au = CORRECTED ? base + cx : base + px * cx;         // reference: px*(temp15 + x)  (:253)
-        const double Bv = py * t6 + pz * t9 + px * t14 + cyy;
-        const double Cm = -py * t16 - pz * t17 - px * t24;
-        const double Dm = py * t2 - pz * t1;
         double J[6];
-        J[0] = (gxi * fx) * t25;
-        J[1] = (gyi * fy) * t25;
-        J[2] = -(J[0] * Au + J[1] * Bv) * t25;
-        J[3] = J[0] * (cyy - Bv) + J[1] * base;
-        J[4] = (J[0] * cosy + J[1] * siny) * Zr + Cm * J[2];
-        J[5] = J[0] * (py * t4 + pz * t21) + J[1] * (pz * t7 + py * t9) + Dm * J[2];
+        pose_columns<CORRECTED>(J, gxi, gyi, w, P, F.fx, F.fy);
         double wgt = 1.0;
         if (huber_on) {
           const double ar = fabs(res);
           wgt = ar <= huber_delta ? 1.0 : huber_delta / ar;
         }
+        // add_row's sums, kept local: with the six weighted columns formed first (add_row(acc, Jw, J, res), as the dma form
+        // has it) this kernel takes 197 VGPRs instead of 191
         int q = 0;
 #pragma unroll
         for (int a = 0; a < 6; a++) {
@@ -236,14 +181,7 @@ __global__ __launch_bounds__(T, WPS) void gn_level_kernel_bilinear(const GNLevel
     if (s_ctl[CTL_DONE]) break;
   }
   if (tid == 0) {
-#pragma unroll
-    for (int j = 0; j < 6; j++) A.states[(size_t)pair * 6 + j] = s_state[j];
-    if (A.reports) {
-      A.reports[pair].iterations[A.level] = iteration;
-      A.reports[pair].gradient_norm = last_gnorm;
-      A.reports[pair].valid_pixels[A.level] = last_valid;
-      A.reports[pair].flags |= (uint32_t)s_ctl[CTL_FLAGS];
-    }
+    pair_report(A, pair, L, iteration, last_gnorm, last_valid);
     s_ctl[CTL_PAIR] = draw_pair(A.work_counter, A.n_queues, A.n_pairs);
   }
   }   // next pair
@@ -272,10 +210,11 @@ __global__ __launch_bounds__(T, WPS) void gn_level_kernel_bilinear_dma(const GNL
   constexpr bool PAIRS = sizeof(TI) == 8;                                // fp64: a row's two taps are one 16-byte load
   constexpr int SLOT_BYTES = 12 * (int)sizeof(TI) * WAVE;                // a chunk's taps: I1, GX, GY x (p00, p01, p10, p11), all 64 lanes
   extern __shared__ __align__(16) unsigned char lds_raw[];
-  double *s_cst = reinterpret_cast<double *>(lds_raw);                 // [32]
-  double *s_state = s_cst + 32;                                        // [8]
-  double *s_red = s_state + 8;                                         // [NW][NRED]
-  int *s_ctl = reinterpret_cast<int *>(s_red + NW * NRED);             // [CTL_COUNT]
+  const PairLds L = pair_lds<NW>(lds_raw);
+  // (copies for the kernel's own accesses: through L, which the lambdas below would capture by reference, the compiler
+  // forms the LDS addresses anew -- other address instructions in both forms, one more scratch store and load in the fp32 dma form)
+  double *const s_cst = L.cst, *const s_state = L.state, *const s_red = L.red;
+  int *const s_ctl = L.ctl;
   unsigned char *s_taps = lds_raw + ((lds_fixed_bytes(T) + 15) & ~(size_t)15);      // [NW][2][SLOT_BYTES]
 
   const int tid = threadIdx.x;
@@ -292,9 +231,7 @@ __global__ __launch_bounds__(T, WPS) void gn_level_kernel_bilinear_dma(const GNL
     s_ctl[CTL_PAIR] = draw_pair(A.work_counter, A.n_queues, A.n_pairs);
   }
   for (;;) {                                // work queue, as in gn_level_kernel
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // see gn_level_kernel
-  __syncthreads();
-  const int pair = __builtin_amdgcn_readfirstlane(s_ctl[CTL_PAIR]);
+  const int pair = pair_drawn(L);
   if (pair >= A.n_pairs) break;
   const unsigned char *src_frame = A.planes + (size_t)A.src[pair] * A.frame_bytes;
   const unsigned char *tgt_frame = A.planes + (size_t)A.tgt[pair] * A.frame_bytes;
@@ -304,38 +241,18 @@ __global__ __launch_bounds__(T, WPS) void gn_level_kernel_bilinear_dma(const GNL
   const __amdgpu_buffer_rsrc_t rT = frame_rsrc(tgt_frame, A.frame_bytes);
   const int o_plane[3] = {(int)A.plane_off[PLANE_I], (int)A.plane_off[PLANE_GX], (int)A.plane_off[PLANE_GY]};
 
-  if (wave == 0) {
-    double st[6];
-#pragma unroll
-    for (int j = 0; j < 6; j++) st[j] = A.states[(size_t)pair * 6 + j];
-    write_pose_constants(st[0], st[1], st[2], st[3], st[4], st[5], s_cst, lane);
-    if (lane == 0) {
-#pragma unroll
-      for (int j = 0; j < 6; j++) s_state[j] = st[j];
-      s_ctl[CTL_DONE] = 0;
-      s_ctl[CTL_FLAGS] = 0;
-    }
-  }
-  __syncthreads();
+  pair_begin(A, pair, wave, lane, L);
 
-  const double fx = A.fx, fy = A.fy, ox = A.ox, oy = A.oy, ifx = A.ifx, ify = A.ify;
+  const WarpFrame F = warp_frame(A);                                    // (its bounds are read from LDS per chunk: warp())
   const double huber_delta = A.huber_delta;
   const bool huber_on = huber_delta > 0.0;
-  const int k0 = wave * WAVE + lane;
-  const int r0 = k0 / W, c0 = k0 - r0 * W;
-  const int step_r = (NW * WAVE) / W, step_c = (NW * WAVE) - step_r * W;
-  const RowColStep rc_step = make_rowcol_step(step_r, step_c, W);
-  const double cd0 = (double)c0, rd0 = (double)r0;
+  const LaneWalk lw = lane_walk<NW>(wave, lane, W);
 
   int iteration = 0;
   double last_gnorm = 0.0;
   int last_valid = 0;
   while (true) {
-    const double cx = uniform_f64(s_cst[C_X]), cyy = uniform_f64(s_cst[C_Y]), cz = uniform_f64(s_cst[C_Z]);
-    const double r01 = uniform_f64(s_cst[C_R01]), r02 = uniform_f64(s_cst[C_R02]);
-    const double r11 = uniform_f64(s_cst[C_R11]), r12 = uniform_f64(s_cst[C_R12]);
-    const double t1 = uniform_f64(s_cst[C_T1]), t2 = uniform_f64(s_cst[C_T2]), t3 = uniform_f64(s_cst[C_T3]);
-    const double t14 = uniform_f64(s_cst[C_T14]), t15 = uniform_f64(s_cst[C_T15]);
+    const SampledPose P = sampled_pose(s_cst);                           // (the row's nine are not used from here: consume())
 
     double acc[NRED];
 #pragma unroll
@@ -346,8 +263,8 @@ __global__ __launch_bounds__(T, WPS) void gn_level_kernel_bilinear_dma(const GNL
       int off[4];                           // byte offsets in a plane: fp32 the taps p00, p01, p10, p11; fp64 [0], [1]: the two PAIRS
       unsigned long long m;                 // lanes that are valid and land in bounds
     };
-    int k = k0;
-    double cd = cd0, rd = rd0;
+    int k = lw.k0;
+    double cd = lw.cd0, rd = lw.rd0;
     double pz_next = plane_load<TD>(rD0, k);                              // past the plane: 0
     double i0_next = plane_load<TI>(rI0, k);
     // (the depth and source intensity of the chunk after the one warp() has just worked on: requested by prefetch(), which the
@@ -359,26 +276,11 @@ __global__ __launch_bounds__(T, WPS) void gn_level_kernel_bilinear_dma(const GNL
     auto warp = [&](Warped &w) {            // geometry of the wave's next chunk; the taps are requested by issue()
       const double pz = pz_next;
       w.i0 = i0_next;
-      const double min_d = lds_cst(s_cst)[C_MIN_D], max_d = lds_cst(s_cst)[C_MAX_D];
-      const double wlim = lds_cst(s_cst)[C_WLIM], hlim = lds_cst(s_cst)[C_HLIM];
-      const double px = (cd - ox) * pz * ifx;                             // :282
-      const double py = (rd - oy) * pz * ify;                             // :283
-      const double X = ((t15 * px + r01 * py) + r02 * pz) + cx;           // :291
-      const double Y = ((t14 * px + r11 * py) + r12 * pz) + cyy;
-      const double Zr = py * t1 + pz * t2 - px * t3;
-      const double t25 = fast_rcp(cz + Zr);                               // :294 and :313 are the same quantity
-      const double tc = (X * fx) * t25 + ox;                              // :295
-      const double tr = (Y * fy) * t25 + oy;                              // :296
-      w.m = __builtin_amdgcn_ballot_w64(k < n) & __builtin_amdgcn_ballot_w64(min_d < pz) &
-            __builtin_amdgcn_ballot_w64(pz < max_d) & __builtin_amdgcn_ballot_w64(tc > -0.5) &
-            __builtin_amdgcn_ballot_w64(tc < wlim) & __builtin_amdgcn_ballot_w64(tr > -0.5) &
-            __builtin_amdgcn_ballot_w64(tr < hlim);
-      w.px = px; w.py = py; w.pz = pz; w.Zr = Zr; w.t25 = t25;
-      const double fc = floor(tc), fr = floor(tr);
-      w.ay = tr - fr;
+      WarpFrame Fw = F;
+      Fw.min_d = lds_cst(s_cst)[C_MIN_D]; Fw.max_d = lds_cst(s_cst)[C_MAX_D];
+      Fw.wlim = lds_cst(s_cst)[C_WLIM]; Fw.hlim = lds_cst(s_cst)[C_HLIM];
       // (lanes outside w.m: whatever the conversions give; their taps are range-checked reads nobody uses)
-      const int ic = (int)fc, ir = (int)fr;
-      const int r0w = __mul24(min(max(ir, 0), H - 1), W), r1w = __mul24(min(max(ir + 1, 0), H - 1), W);
+      const WarpCell c = warp_cell(w, warp_project(w, k, cd, rd, pz, P, Fw));
       if (PAIRS) {
         // fp64 planes: the two horizontal taps of a row are neighbours in memory and travel as ONE 16-byte load (24 dword loads
         // per chunk made this form a third SLOWER than the gathers: a CU has one address path).  In the outer half-pixel band
@@ -389,17 +291,19 @@ __global__ __launch_bounds__(T, WPS) void gn_level_kernel_bilinear_dma(const GNL
         // 93 % busy (profiles/r05_bilinear_pmc_sq.json).  x is a pixel of the plane, finite whenever the plane is -- except on
         // a level one column wide, where x is the first double of the next row, and behind a plane's last row of the next
         // plane (the target's depth behind its intensity): phovo_hip.h asks for finite target planes there.
+        const int ic = c.ic, ir = c.ir;
+        const int r0w = __mul24(min(max(ir, 0), H - 1), W), r1w = __mul24(min(max(ir + 1, 0), H - 1), W);
         const int cb = min(max(ic, 0), max(W - 2, 0));
         w.off[0] = (r0w + cb) * 8; w.off[1] = (r1w + cb) * 8; w.off[2] = w.off[3] = 0;
-        w.ax = (ic < 0 || W < 2) ? 0.0 : (ic > W - 2 ? 1.0 : tc - fc);       // (a one-column image: both taps are that column)
+        const double ax = w.ax;             // (read before the store below: written as one select on w.ax, three compares change)
+        w.ax = (ic < 0 || W < 2) ? 0.0 : (ic > W - 2 ? 1.0 : ax);       // (a one-column image: both taps are that column)
       } else {
-        const int c0i = min(max(ic, 0), W - 1), c1i = min(max(ic + 1, 0), W - 1);      // clamp-to-edge taps
-        w.off[0] = (r0w + c0i) * (int)sizeof(TI); w.off[1] = (r0w + c1i) * (int)sizeof(TI);
-        w.off[2] = (r1w + c0i) * (int)sizeof(TI); w.off[3] = (r1w + c1i) * (int)sizeof(TI);
-        w.ax = tc - fc;
+        clamped_taps(w.off, c, W, H);
+#pragma unroll
+        for (int t = 0; t < 4; t++) w.off[t] *= (int)sizeof(TI);
       }
       k += NW * WAVE;
-      rowcol_advance(cd, rd, rc_step);
+      rowcol_advance(cd, rd, lw.step);
     };
     typedef __attribute__((address_space(3))) void *lds_ptr;
     auto issue = [&](const Warped &w, int slot) {                         // the chunk's twelve taps, straight to LDS
@@ -443,13 +347,12 @@ __global__ __launch_bounds__(T, WPS) void gn_level_kernel_bilinear_dma(const GNL
           p00 = (double)__uint_as_float(words[(4 * c) * 64]); p01 = (double)__uint_as_float(words[(4 * c + 1) * 64]);
           p10 = (double)__uint_as_float(words[(4 * c + 2) * 64]); p11 = (double)__uint_as_float(words[(4 * c + 3) * 64]);
         }
-        smp[c] = (1.0 - ay) * ((1.0 - ax) * p00 + ax * p01) + ay * ((1.0 - ax) * p10 + ax * p11);
+        smp[c] = bilerp(ax, ay, p00, p01, p10, p11);
       }
     };
     auto consume = [&](const Warped &w, const double (&smp)[3]) {
       n_rows += __builtin_popcountll(w.m);
       if (__builtin_amdgcn_inverse_ballot_w64(w.m)) {
-        const double px = w.px, py = w.py, pz = w.pz, Zr = w.Zr, t25 = w.t25;
         const double res = smp[0] - w.i0;
         const double gxi = smp[1], gyi = smp[2];
         // The pose constants only this block uses come out of LDS each time (a broadcast read, the LDS pipe has room), not out
@@ -457,38 +360,21 @@ __global__ __launch_bounds__(T, WPS) void gn_level_kernel_bilinear_dma(const GNL
         // then parks in lanes of a vector register comes back through v_readlane -- 30 of them per chunk, on vector units
         // that are the kernel's bound.
         const lds_cst_ptr vc = lds_cst(s_cst);
-        const double t4 = vc[C_T4], t5 = vc[C_T5], t6 = vc[C_T6], t8 = vc[C_T8];
-        const double t16 = vc[C_T16], t17 = vc[C_T17], t24 = vc[C_T24], cosy = vc[C_CY], siny = vc[C_SY];
-        const double t7 = -t6, t9 = -t8, t21 = -t5;
-
-        const double base = pz * t4 + py * t5 + px * t15;                 // (pz*temp4+py*temp5+px*temp15) = X - x
-        const double Au = CORRECTED ? base + cx : base + px * cx;         // reference: px*(temp15 + x)  (:253)
-        const double Bv = py * t6 + pz * t9 + px * t14 + cyy;
-        const double Cm = -py * t16 - pz * t17 - px * t24;
-        const double Dm = py * t2 - pz * t1;
+        SampledPose R = P;
+        R.t4 = vc[C_T4]; R.t5 = vc[C_T5]; R.t6 = vc[C_T6]; R.t8 = vc[C_T8];
+        R.t16 = vc[C_T16]; R.t17 = vc[C_T17]; R.t24 = vc[C_T24]; R.cosy = vc[C_CY]; R.siny = vc[C_SY];
+        R.t7 = -R.t6; R.t9 = -R.t8; R.t21 = -R.t5;
         double J[6];
-        J[0] = (gxi * fx) * t25;
-        J[1] = (gyi * fy) * t25;
-        J[2] = -(J[0] * Au + J[1] * Bv) * t25;
-        J[3] = J[0] * (cyy - Bv) + J[1] * base;
-        J[4] = (J[0] * cosy + J[1] * siny) * Zr + Cm * J[2];
-        J[5] = J[0] * (py * t4 + pz * t21) + J[1] * (pz * t7 + py * t9) + Dm * J[2];
+        pose_columns<CORRECTED>(J, gxi, gyi, w, R, F.fx, F.fy);
         double wgt = 1.0;
         if (huber_on) {
           const double ar = fabs(res);
           wgt = ar <= huber_delta ? 1.0 : huber_delta / ar;
         }
-        int q = 0;
+        double Jw[6];
 #pragma unroll
-        for (int a = 0; a < 6; a++) {
-          const double jw = J[a] * wgt;
-#pragma unroll
-          for (int b = a; b < 6; b++) {
-            acc[q] = fma(jw, J[b], acc[q]);
-            q++;
-          }
-          acc[21 + a] = fma(jw, res, acc[21 + a]);
-        }
+        for (int a = 0; a < 6; a++) Jw[a] = J[a] * wgt;
+        add_row(acc, Jw, J, res);
       }
     };
     {
@@ -533,14 +419,7 @@ __global__ __launch_bounds__(T, WPS) void gn_level_kernel_bilinear_dma(const GNL
     if (s_ctl[CTL_DONE]) break;
   }
   if (tid == 0) {
-#pragma unroll
-    for (int j = 0; j < 6; j++) A.states[(size_t)pair * 6 + j] = s_state[j];
-    if (A.reports) {
-      A.reports[pair].iterations[A.level] = iteration;
-      A.reports[pair].gradient_norm = last_gnorm;
-      A.reports[pair].valid_pixels[A.level] = last_valid;
-      A.reports[pair].flags |= (uint32_t)s_ctl[CTL_FLAGS];
-    }
+    pair_report(A, pair, L, iteration, last_gnorm, last_valid);
     s_ctl[CTL_PAIR] = draw_pair(A.work_counter, A.n_queues, A.n_pairs);
   }
   }   // next pair
@@ -563,6 +442,7 @@ constexpr size_t bilinear_dma_lds_bytes()
 template <typename TI, typename TD>
 hipError_t launch_bilinear_dma(const GNLevelArgs &a, bool corrected, int cu_count, hipStream_t stream)
 {
+  // (not launch_persistent: this template would then be inlined away, and the library's exported symbols change)
   const int resident = cu_count * BILINEAR_DMA_WPS;
   const dim3 grid((unsigned)(a.n_pairs < resident ? a.n_pairs : resident)), block(256);
   const size_t lds = bilinear_dma_lds_bytes<TI>();

@@ -38,12 +38,6 @@ namespace phovo_hip {
 
 namespace {
 
-__device__ __forceinline__ void lds_barrier()
-{
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __syncthreads();
-}
-
 // T threads per workgroup.  OWNER_LDS: owner map in LDS (else in HBM, args.lv.g_owner + pair * n).
 template <int T, bool OWNER_LDS>
 __global__ __launch_bounds__(T, 2) void gn_level_kernel_biobjective(const GNBiObjectiveArgs B)
@@ -296,13 +290,8 @@ hipError_t gn_launch_level_biobjective(const GNBiObjectiveArgs &b, const GNLaunc
 {
   if (b.lv.n_pairs <= 0) return hipSuccess;
   if (!plan.owner_in_lds && !b.lv.g_owner) return hipErrorInvalidValue;
-  const int slots = cu_count * plan.wgs_per_cu;
-  const dim3 grid((unsigned)(b.lv.n_pairs < slots ? b.lv.n_pairs : slots)), block((unsigned)plan.threads);
-  const size_t lds = (size_t)plan.lds_bytes;
-  if (!plan.owner_in_lds) hipLaunchKernelGGL(PHOVO_KERNEL_BI_HBM, grid, block, lds, stream, b);
-  else if (plan.threads == 256) hipLaunchKernelGGL(PHOVO_KERNEL_BI_SMALL, grid, block, lds, stream, b);
-  else hipLaunchKernelGGL(PHOVO_KERNEL_BI_LARGE, grid, block, lds, stream, b);
-  return hipGetLastError();
+  const auto kernel = !plan.owner_in_lds ? PHOVO_KERNEL_BI_HBM : (plan.threads == 256 ? PHOVO_KERNEL_BI_SMALL : PHOVO_KERNEL_BI_LARGE);
+  return launch_persistent(kernel, b.lv.n_pairs, cu_count, plan.wgs_per_cu, plan.threads, (size_t)plan.lds_bytes, stream, b);
 }
 
 }  // namespace phovo_hip

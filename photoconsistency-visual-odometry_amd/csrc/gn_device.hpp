@@ -34,6 +34,13 @@ __host__ __device__ constexpr size_t lds_fixed_bytes(int threads)
   return sizeof(double) * (32 + 8 + (size_t)(threads / WAVE) * NRED) + sizeof(int) * CTL_COUNT;
 }
 
+// A workgroup barrier behind which every LDS access issued in front of it has completed.
+__device__ __forceinline__ void lds_barrier()
+{
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __syncthreads();
+}
+
 __device__ __forceinline__ double uniform_f64(double v)
 {
   // The value is identical in every lane: move it to scalar registers so that the per-pixel
@@ -661,6 +668,39 @@ __device__ __forceinline__ void sum_rows_broadcast(int lane, double *s_red, doub
   n_valid = (int)s_red[RED_VALID];
 }
 
+// The tail of a Gauss-Newton iteration on N parameters (the pose in the first six), by the one wave that solved: the state
+// minus lambda * step, the finite test, the gradient norm, termination, the next iteration's pose constants, the flags.
+template <int N>
+__device__ __forceinline__ void update_and_terminate(int lane, const double (&step)[N], const double (&g)[N], double *s_state,
+                                                     double *s_cst, int *s_ctl, double lambda, int max_iter,
+                                                     double min_grad_norm, int iteration, int last_valid, double &last_gnorm)
+{
+  double st[N];
+  bool finite = true;
+#pragma unroll
+  for (int i = 0; i < N; i++) {
+    st[i] = s_state[i] - lambda * step[i];                                            // :539
+    finite = finite && finite_f64(st[i]);
+  }
+  double gn2 = 0.0;
+#pragma unroll
+  for (int i = 0; i < N; i++) gn2 += g[i] * g[i];
+  const double gnorm = sqrt(gn2);                                                     // :380
+  bool done = false;
+  if (iteration + 1 >= max_iter) done = true;                                         // :383
+  else if (gnorm < min_grad_norm) done = true;                                        // :388
+  if (!finite) done = true;
+  if (!done) write_pose_constants(st[0], st[1], st[2], st[3], st[4], st[5], s_cst, lane);
+  if (lane == 0) {
+#pragma unroll
+    for (int i = 0; i < N; i++) s_state[i] = st[i];
+    s_ctl[CTL_DONE] = done ? 1 : 0;
+    if (!finite) s_ctl[CTL_FLAGS] |= (int)PHOVO_PAIR_NONFINITE;
+    if (last_valid < N) s_ctl[CTL_FLAGS] |= (int)PHOVO_PAIR_RANK_DEFICIENT;
+  }
+  last_gnorm = gnorm;
+}
+
 // Called by ONE wave behind the barrier that follows reduce_wave_to_row: sum of the NROWS rows, solve, update, termination
 // (as gn_level_kernel's tail); the caller closes with a barrier and reads s_ctl[CTL_DONE].
 template <int NROWS>
@@ -672,30 +712,8 @@ __device__ __forceinline__ void sum_rows_solve_update(int lane, double *s_red, d
   sum_rows_broadcast<NROWS>(lane, s_red, h, g, last_valid);
   double step[6];
   solve6_ldlt(h, g, step);
-  double st[6];
-  bool finite = true;
-#pragma unroll
-  for (int i = 0; i < 6; i++) {
-    st[i] = s_state[i] - lambda * step[i];                                            // :539
-    finite = finite && (fabs(st[i]) <= 1.79769313486231570815e308);
-  }
-  double gn2 = 0.0;
-#pragma unroll
-  for (int i = 0; i < 6; i++) gn2 += g[i] * g[i];
-  const double gnorm = sqrt(gn2);                                                     // :380
-  bool done = false;
-  if (iteration + 1 >= max_iter) done = true;                                         // :383
-  else if (gnorm < min_grad_norm) done = true;                                        // :388
-  if (!finite) done = true;
-  if (!done) write_pose_constants(st[0], st[1], st[2], st[3], st[4], st[5], s_cst, lane);
-  if (lane == 0) {
-#pragma unroll
-    for (int i = 0; i < 6; i++) s_state[i] = st[i];
-    s_ctl[CTL_DONE] = done ? 1 : 0;
-    if (!finite) s_ctl[CTL_FLAGS] |= (int)PHOVO_PAIR_NONFINITE;
-    if (last_valid < 6) s_ctl[CTL_FLAGS] |= (int)PHOVO_PAIR_RANK_DEFICIENT;
-  }
-  last_gnorm = gnorm;
+  update_and_terminate<6>(lane, step, g, s_state, s_cst, s_ctl, lambda, max_iter, min_grad_norm, iteration, last_valid,
+                          last_gnorm);
 }
 
 // Wave butterfly + cross-wave sum + solve + update + termination, as in gn_level_kernel's tail, for kernels
@@ -712,6 +730,36 @@ __device__ __forceinline__ void reduce_solve_update(double (&acc)[NRED], int lan
     sum_rows_solve_update<NW>(lane, s_red, s_state, s_cst, s_ctl, lambda, max_iter, min_grad_norm, iteration, last_gnorm,
                               last_valid);
   __syncthreads();
+}
+
+// One Jacobian row into a block of sums: the upper triangle of J^T W J (...Analytic.h:540), then J^T W r (:538); Jw = W J.
+__device__ __forceinline__ void add_row(double (&acc)[NRED], const double (&Jw)[6], const double (&J)[6], const double res)
+{
+  int q = 0;
+#pragma unroll
+  for (int a = 0; a < 6; a++) {
+#pragma unroll
+    for (int b = a; b < 6; b++) {
+      acc[q] = fma(Jw[a], J[b], acc[q]);
+      q++;
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < 6; a++) acc[21 + a] = fma(Jw[a], res, acc[21 + a]);
+}
+// W = identity: no weight and none of its instructions.
+__device__ __forceinline__ void add_row(double (&acc)[NRED], const double (&J)[6], const double res) { add_row(acc, J, J, res); }
+
+// Host: a persistent kernel (one that draws its pairs from the work queue) on as many workgroups as stay resident, or one
+// per pair if those are fewer.
+template <typename Kernel, typename Args>
+hipError_t launch_persistent(Kernel kernel, int n_pairs, int cu_count, int wgs_per_cu, int threads, size_t lds_bytes,
+                             hipStream_t stream, const Args &args)
+{
+  const int resident = cu_count * wgs_per_cu;
+  const dim3 grid((unsigned)(n_pairs < resident ? n_pairs : resident)), block((unsigned)threads);
+  hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, args);
+  return hipGetLastError();
 }
 
 }  // namespace

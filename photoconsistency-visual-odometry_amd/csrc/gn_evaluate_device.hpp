@@ -17,15 +17,14 @@
 //
 // Everything is __forceinline__ in an anonymous namespace, as in gn_device.hpp.  The first half (geometry, pose preamble,
 // row sums, tile sums, finish) holds explicit fma() and plain adds only, so it means the same under
-// `#pragma clang fp contract(off)` (gn_evaluate_objective_kernels.hip) and without; the bilinear warp at the end has products
-// feeding adds and is for the two files compiled with default contraction only.
+// `#pragma clang fp contract(off)` (gn_evaluate_objective_kernels.hip) and without; the bilinear warp at the end (and
+// gn_sampled_device.hpp behind it) has products feeding adds and is for the two files compiled with default contraction only.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 
-#include "gn_device.hpp"
-#include "phovo_internal.hpp"
+#include "gn_sampled_device.hpp"
 
 namespace phovo_hip {
 
@@ -54,25 +53,7 @@ __device__ __forceinline__ void eval_pose_to_lds(const double *st, double *s_cst
   __syncthreads();
 }
 
-// ---- row sums ---------------------------------------------------------------------------------------------------------
-// One Jacobian row into a block of sums: the upper triangle of J^T W J (...Analytic.h:540), then J^T W r (:538); Jw = W J.
-// (k_eval_sampled and k_eval_geometric_depth add the same sums column by column, in loops of their own.)
-__device__ __forceinline__ void add_row(double (&acc)[NRED], const double (&Jw)[6], const double (&J)[6], const double res)
-{
-  int q = 0;
-#pragma unroll
-  for (int a = 0; a < 6; a++) {
-#pragma unroll
-    for (int b = a; b < 6; b++) {
-      acc[q] = fma(Jw[a], J[b], acc[q]);
-      q++;
-    }
-  }
-#pragma unroll
-  for (int a = 0; a < 6; a++) acc[21 + a] = fma(Jw[a], res, acc[21 + a]);
-}
-// W = identity: no weight and none of its instructions.
-__device__ __forceinline__ void add_row(double (&acc)[NRED], const double (&J)[6], const double res) { add_row(acc, J, J, res); }
+// (the row sums: add_row of gn_device.hpp)
 
 // ---- tile sums --------------------------------------------------------------------------------------------------------
 // The tile's block of sums: wave butterfly, then the four waves in fixed order, into the tile's place in the pair's slab
@@ -163,65 +144,19 @@ hipError_t with_storage_types(int storage, Launch launch)
 }
 
 // ---- bilinear warp (default contraction only: k_eval_sampled, k_eval_geometric_depth) --------------------------------
-// The pose constants both kernels read, in scalar registers.
-struct SampledPose {
-  double cx, cyy, cz, r01, r02, r11, r12, t1, t2, t3, t4, t5, t6, t8, t14, t15, t16, t17, t24, cosy, siny;
-  double t7, t9, t21;                     // -t6, -t8, -t5
-};
-__device__ __forceinline__ SampledPose sampled_pose(const double *s_cst)
-{
-  SampledPose P;
-  P.cx = uniform_f64(s_cst[C_X]); P.cyy = uniform_f64(s_cst[C_Y]); P.cz = uniform_f64(s_cst[C_Z]);
-  P.r01 = uniform_f64(s_cst[C_R01]); P.r02 = uniform_f64(s_cst[C_R02]);
-  P.r11 = uniform_f64(s_cst[C_R11]); P.r12 = uniform_f64(s_cst[C_R12]);
-  P.t1 = uniform_f64(s_cst[C_T1]); P.t2 = uniform_f64(s_cst[C_T2]); P.t3 = uniform_f64(s_cst[C_T3]);
-  P.t4 = uniform_f64(s_cst[C_T4]); P.t5 = uniform_f64(s_cst[C_T5]); P.t6 = uniform_f64(s_cst[C_T6]);
-  P.t8 = uniform_f64(s_cst[C_T8]); P.t14 = uniform_f64(s_cst[C_T14]); P.t15 = uniform_f64(s_cst[C_T15]);
-  P.t16 = uniform_f64(s_cst[C_T16]); P.t17 = uniform_f64(s_cst[C_T17]); P.t24 = uniform_f64(s_cst[C_T24]);
-  P.cosy = uniform_f64(s_cst[C_CY]); P.siny = uniform_f64(s_cst[C_SY]);
-  P.t7 = -P.t6; P.t9 = -P.t8; P.t21 = -P.t5;
-  return P;
-}
-
 struct Warped {
   double px, py, pz, Zr, t25, ax, ay;
   int idx[4];                             // the clamped taps p00, p01, p10, p11: indices into a plane
   unsigned long long m;                   // lanes that are valid and land in bounds
 };
-// Source pixel k of depth pz through the pose: the row's geometry, the bilinear weights and the four clamped taps; wlim,
-// hlim: W - 0.5 and H - 0.5.  (Line numbers: ...Analytic.h.)
-// TWIN: the `warp` of gn_level_kernel_bilinear, gn_level_kernel_affine and gn_level_kernel_geometric; all must select the
-// same rows, so a change to the gates, the bounds test or the taps goes into those too.
-__device__ __forceinline__ void warp_bilinear(Warped &w, int k, double pz, const SampledPose &P, const GNSampledEvalArgs &A,
-                                              double wlim, double hlim, const RowColFromIndex &rc_map)
+// Source pixel k of depth pz through the pose, by the aligners' own warp (gn_sampled_device.hpp): the row's geometry, the
+// bilinear weights and the four clamped taps.
+__device__ __forceinline__ void warp_bilinear(Warped &w, int k, double pz, const SampledPose &P, const WarpFrame &F, int W, int H,
+                                              const RowColFromIndex &rc_map)
 {
-  const int n = A.n, W = A.w, H = A.h;
   double cd, rd;
   rowcol_from_index((double)k, rc_map, cd, rd);
-  const double px = (cd - A.ox) * pz * A.ifx;                             // :282
-  const double py = (rd - A.oy) * pz * A.ify;                             // :283
-  const double X = ((P.t15 * px + P.r01 * py) + P.r02 * pz) + P.cx;       // :291
-  const double Y = ((P.t14 * px + P.r11 * py) + P.r12 * pz) + P.cyy;
-  const double Zr = py * P.t1 + pz * P.t2 - px * P.t3;
-  const double t25 = fast_rcp(P.cz + Zr);                                 // :294 and :313 are the same quantity
-  const double tc = (X * A.fx) * t25 + A.ox;                              // :295
-  const double tr = (Y * A.fy) * t25 + A.oy;                              // :296
-  // depth gate, and in bounds iff the NEAREST pixel is inside (NaN fails the comparisons)
-  w.m = __builtin_amdgcn_ballot_w64(k < n) & __builtin_amdgcn_ballot_w64(A.min_depth < pz) &
-        __builtin_amdgcn_ballot_w64(pz < A.max_depth) & __builtin_amdgcn_ballot_w64(tc > -0.5) &
-        __builtin_amdgcn_ballot_w64(tc < wlim) & __builtin_amdgcn_ballot_w64(tr > -0.5) &
-        __builtin_amdgcn_ballot_w64(tr < hlim);
-  w.px = px; w.py = py; w.pz = pz; w.Zr = Zr; w.t25 = t25;
-  const double fc = floor(tc), fr = floor(tr);
-  w.ax = tc - fc;
-  w.ay = tr - fr;
-  // (lanes outside w.m: whatever the conversions give, clamped into the plane like the others; nobody uses their taps)
-  const int ic = (int)fc, ir = (int)fr;
-  const int r0w = __mul24(min(max(ir, 0), H - 1), W), r1w = __mul24(min(max(ir + 1, 0), H - 1), W);
-  // clamp-to-edge taps (in the outer half-pixel band both taps of a row / a column are the edge pixel): every index
-  // lies in [0, n)
-  const int c0i = min(max(ic, 0), W - 1), c1i = min(max(ic + 1, 0), W - 1);
-  w.idx[0] = r0w + c0i; w.idx[1] = r0w + c1i; w.idx[2] = r1w + c0i; w.idx[3] = r1w + c1i;
+  clamped_taps(w.idx, warp_cell(w, warp_project(w, k, cd, rd, pz, P, F)), W, H);
 }
 
 }  // namespace

@@ -23,9 +23,9 @@ namespace {
 constexpr int RED_DEPTH_ROWS = RED_VALID, RED_DEPTH_COST = RED_COST;
 
 // grid (tiles, pairs of the group).  fp64 planes.
-// TWIN: the warp, the bounds test, the taps, both gates and the depth row are gn_level_kernel_geometric's (its `warp`,
-// `sample` and the `if (depth_row)` block of `consume`); the two must select the same rows, so a change to those semantics
-// goes into both.
+// The warp, the bounds test, the taps, the interpolation and the six columns are the aligners' (gn_sampled_device.hpp).
+// TWIN: the tap gate, the residual gate, dgx / dgy and rD are gn_level_kernel_geometric's (its `sample` and the head of
+// `consume`); the two must select the same depth rows, so a change to those goes into both.
 __global__ __launch_bounds__(ET) void k_eval_geometric_depth(const GNGeometricEvalArgs B, double *g_part, int tiles)
 {
   const GNSampledEvalArgs &A = B.s;
@@ -45,10 +45,10 @@ __global__ __launch_bounds__(ET) void k_eval_geometric_depth(const GNGeometricEv
   // one descriptor for the target frame; its depth plane is chosen by the load's scalar offset
   const __amdgpu_buffer_rsrc_t rT = frame_rsrc(tgt_frame, A.frame_bytes);
   const int o_d = (int)A.plane_off[PLANE_D];
-  const double fx = A.fx, fy = A.fy, min_d = A.min_depth, max_d = A.max_depth;
+  const WarpFrame F = warp_frame(A);
+  const double min_d = F.min_d, max_d = F.max_d;
   const double sigma = B.depth_weight, gate = B.max_depth_residual;
   const bool gate_on = gate > 0.0;
-  const double wlim = (double)W - 0.5, hlim = (double)H - 0.5;
   const RowColFromIndex rc_map = make_rowcol_from_index(W);
 
   double acc[NRED];
@@ -70,7 +70,7 @@ __global__ __launch_bounds__(ET) void k_eval_geometric_depth(const GNGeometricEv
   };
   double tap[4];                          // D1 at p00, p01, p10, p11 of the chunk whose taps are in flight
   auto warp = [&](Warped &w, int j) {
-    warp_bilinear(w, (blockIdx.x * E_TILE_CHUNKS + j * ENW + wave) * WAVE + lane, pzs[j], P, A, wlim, hlim, rc_map);
+    warp_bilinear(w, (blockIdx.x * E_TILE_CHUNKS + j * ENW + wave) * WAVE + lane, pzs[j], P, F, W, H, rc_map);
   };
   auto issue = [&](const Warped &w) {
     if (__builtin_amdgcn_inverse_ballot_w64(w.m)) {
@@ -80,7 +80,7 @@ __global__ __launch_bounds__(ET) void k_eval_geometric_depth(const GNGeometricEv
   };
   auto sample = [&](const Warped &w, Sampled &s) {
     const double ax = w.ax, ay = w.ay;
-    s.d1 = (1.0 - ay) * ((1.0 - ax) * tap[0] + ax * tap[1]) + ay * ((1.0 - ax) * tap[2] + ax * tap[3]);
+    s.d1 = bilerp(ax, ay, tap[0], tap[1], tap[2], tap[3]);
     const double p00 = tap[0], p01 = tap[1], p10 = tap[2], p11 = tap[3];
     s.dgx = (1.0 - ay) * (p01 - p00) + ay * (p11 - p10);
     s.dgy = (1.0 - ax) * (p10 - p00) + ax * (p11 - p01);
@@ -96,23 +96,10 @@ __global__ __launch_bounds__(ET) void k_eval_geometric_depth(const GNGeometricEv
     if (gate_on) depth_row = depth_row && (fabs(res_d) <= gate);        // NaN fails
     n_depth_rows += __builtin_popcountll(__builtin_amdgcn_ballot_w64(depth_row));
     if (depth_row) {
-      const double px = w.px, py = w.py, pz = w.pz, Zr = w.Zr, t25 = w.t25;
-      const double base = pz * P.t4 + py * P.t5 + px * P.t15;
-      const double Au = base + P.cx;                                    // the true warp Jacobian (CORRECTED)
-      const double Bv = py * P.t6 + pz * P.t9 + px * P.t14 + P.cyy;
-      const double Cm = -py * P.t16 - pz * P.t17 - px * P.t24;          // dZ'/dpitch
-      const double Dm = py * P.t2 - pz * P.t1;                          // dZ'/droll
-      const double yawu = P.cyy - Bv, rollu = py * P.t4 + pz * P.t21, rollv = pz * P.t7 + py * P.t9;
-      // the photometric row's six columns with the interpolant's derivative in place of the sampled gradients; dZ'/dp is
-      // (0, 0, 1, 0, Cm, Dm), and since columns 4 and 5 take Cm and Dm times column 2, the -1 goes in there once
+      // the photometric row's six columns with the interpolant's derivative in place of the sampled gradients, and -dZ'/dp
       const double rD = sigma * res_d;
       double J[6];
-      J[0] = ((sigma * s.dgx) * fx) * t25;
-      J[1] = ((sigma * s.dgy) * fy) * t25;
-      J[2] = -(J[0] * Au + J[1] * Bv) * t25 - sigma;
-      J[3] = J[0] * yawu + J[1] * base;
-      J[4] = (J[0] * P.cosy + J[1] * P.siny) * Zr + Cm * J[2];
-      J[5] = J[0] * rollu + J[1] * rollv + Dm * J[2];
+      pose_columns<true>(J, sigma * s.dgx, sigma * s.dgy, w, P, F.fx, F.fy, sigma);
       // (add_row's sums, column by column: the products of column a, then its gradient entry -- the order this kernel was
       // compiled with; gn_evaluate_device.hpp's order schedules it differently)
       int q = 0;

@@ -33,8 +33,9 @@ enum { X_JI0 = 0, X_J = 6, X_I0I0 = 12, X_I0 = 13, X_RI0 = 14, X_R = 15 };
 constexpr int blocks_of(int kind) { return kind == ROWS_AFFINE ? 2 : 1; }
 
 // grid (tiles, pairs of the group).  TI / TD: storage type of the intensity and gradient planes / of the depth plane.
-// TWIN: the warp, the bounds test, the taps and the row arithmetic are gn_level_kernel_bilinear's / gn_level_kernel_affine's;
-// the three must select the same rows, so a change to those semantics goes into all of them.
+// The warp, the bounds test, the taps, the interpolation and the six columns are the aligners' (gn_sampled_device.hpp).
+// TWIN: clamped_taps here against the tap policies that gn_level_kernel_bilinear and the fp64 gn_level_kernel_bilinear_dma
+// keep for themselves (the header's note); they must name the same pixels wherever the row mask is set.
 template <typename TI, typename TD, int KIND>
 __global__ __launch_bounds__(ET) void k_eval_sampled(const GNSampledEvalArgs A, double *g_part, int tiles)
 {
@@ -58,8 +59,7 @@ __global__ __launch_bounds__(ET) void k_eval_sampled(const GNSampledEvalArgs A, 
   // one descriptor for the target frame; a plane is chosen by the load's scalar offset
   const __amdgpu_buffer_rsrc_t rT = frame_rsrc(tgt_frame, A.frame_bytes);
   const int o_i = (int)A.plane_off[PLANE_I], o_gx = (int)A.plane_off[PLANE_GX], o_gy = (int)A.plane_off[PLANE_GY];
-  const double fx = A.fx, fy = A.fy;
-  const double wlim = (double)W - 0.5, hlim = (double)H - 0.5;
+  const WarpFrame F = warp_frame(A);
   const double huber_delta = A.huber_delta;
   const RowColFromIndex rc_map = make_rowcol_from_index(W);
 
@@ -79,7 +79,7 @@ __global__ __launch_bounds__(ET) void k_eval_sampled(const GNSampledEvalArgs A, 
 
   double tap[12];                         // I1, GX1, GY1 at p00, p01, p10, p11 of the chunk whose taps are in flight
   auto warp = [&](Warped &w, int j) {
-    warp_bilinear(w, (blockIdx.x * E_TILE_CHUNKS + j * ENW + wave) * WAVE + lane, pzs[j], P, A, wlim, hlim, rc_map);
+    warp_bilinear(w, (blockIdx.x * E_TILE_CHUNKS + j * ENW + wave) * WAVE + lane, pzs[j], P, F, W, H, rc_map);
   };
   auto issue = [&](const Warped &w) {
     if (__builtin_amdgcn_inverse_ballot_w64(w.m)) {
@@ -92,10 +92,8 @@ __global__ __launch_bounds__(ET) void k_eval_sampled(const GNSampledEvalArgs A, 
     }
   };
   auto sample3 = [&](const Warped &w, double (&smp)[3]) {                 // -> the bilinear samples I1, GX1, GY1
-    const double ax = w.ax, ay = w.ay;
 #pragma unroll
-    for (int c = 0; c < 3; c++)
-      smp[c] = (1.0 - ay) * ((1.0 - ax) * tap[4 * c] + ax * tap[4 * c + 1]) + ay * ((1.0 - ax) * tap[4 * c + 2] + ax * tap[4 * c + 3]);
+    for (int c = 0; c < 3; c++) smp[c] = bilerp(w.ax, w.ay, tap[4 * c], tap[4 * c + 1], tap[4 * c + 2], tap[4 * c + 3]);
   };
   // Two compiled copies of the row loop behind a wave-uniform branch: without Huber weights none of the extension's
   // instructions run.  Order per chunk as in gn_level_kernel_affine: geometry of chunk j + 1, the three samples of chunk j
@@ -105,21 +103,9 @@ __global__ __launch_bounds__(ET) void k_eval_sampled(const GNSampledEvalArgs A, 
     auto consume = [&](const Warped &w, const double (&smp)[3], double i0) {
       n_rows += __builtin_popcountll(w.m);
       if (__builtin_amdgcn_inverse_ballot_w64(w.m)) {
-        const double px = w.px, py = w.py, pz = w.pz, Zr = w.Zr, t25 = w.t25;
         const double res = AFFINE ? (smp[0] - gain * i0) - beta : smp[0] - i0;
-        const double gxi = smp[1], gyi = smp[2];
-        const double base = pz * P.t4 + py * P.t5 + px * P.t15;           // (pz*temp4+py*temp5+px*temp15) = X - x
-        const double Au = KIND != ROWS_SLIP ? base + P.cx : base + px * P.cx;     // reference: px*(temp15 + x)  (:253)
-        const double Bv = py * P.t6 + pz * P.t9 + px * P.t14 + P.cyy;
-        const double Cm = -py * P.t16 - pz * P.t17 - px * P.t24;
-        const double Dm = py * P.t2 - pz * P.t1;
         double J[6];
-        J[0] = (gxi * fx) * t25;
-        J[1] = (gyi * fy) * t25;
-        J[2] = -(J[0] * Au + J[1] * Bv) * t25;
-        J[3] = J[0] * (P.cyy - Bv) + J[1] * base;
-        J[4] = (J[0] * P.cosy + J[1] * P.siny) * Zr + Cm * J[2];
-        J[5] = J[0] * (py * P.t4 + pz * P.t21) + J[1] * (pz * P.t7 + py * P.t9) + Dm * J[2];
+        pose_columns<KIND != ROWS_SLIP>(J, smp[1], smp[2], w, P, F.fx, F.fy);
         double wgt = 1.0;
         if (HUBER) {                                // the aligner's IRLS weight
           const double ar = fabs(res);

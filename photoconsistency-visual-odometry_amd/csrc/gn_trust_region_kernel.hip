@@ -41,12 +41,6 @@ namespace phovo_hip {
 
 namespace {
 
-__device__ __forceinline__ void lds_barrier()
-{
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __syncthreads();
-}
-
 // Trust-region state in LDS (doubles), written by lane 0 of wave 0 only
 enum {
   TR_X = 0,            // [6] the current point x
@@ -444,13 +438,8 @@ hipError_t gn_launch_level_trust_region(const GNTrustRegionArgs &b, const GNLaun
 {
   if (b.lv.n_pairs <= 0) return hipSuccess;
   if (!plan.owner_in_lds && !b.lv.g_owner) return hipErrorInvalidValue;
-  const int slots = cu_count * plan.wgs_per_cu;
-  const dim3 grid((unsigned)(b.lv.n_pairs < slots ? b.lv.n_pairs : slots)), block((unsigned)plan.threads);
-  const size_t lds = (size_t)plan.lds_bytes;
-  if (!plan.owner_in_lds) hipLaunchKernelGGL(PHOVO_KERNEL_TR_HBM, grid, block, lds, stream, b);
-  else if (plan.threads == 256) hipLaunchKernelGGL(PHOVO_KERNEL_TR_SMALL, grid, block, lds, stream, b);
-  else hipLaunchKernelGGL(PHOVO_KERNEL_TR_LARGE, grid, block, lds, stream, b);
-  return hipGetLastError();
+  const auto kernel = !plan.owner_in_lds ? PHOVO_KERNEL_TR_HBM : (plan.threads == 256 ? PHOVO_KERNEL_TR_SMALL : PHOVO_KERNEL_TR_LARGE);
+  return launch_persistent(kernel, b.lv.n_pairs, cu_count, plan.wgs_per_cu, plan.threads, (size_t)plan.lds_bytes, stream, b);
 }
 
 }  // namespace phovo_hip
