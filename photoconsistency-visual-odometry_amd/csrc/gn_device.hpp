@@ -122,7 +122,8 @@ __device__ __forceinline__ void pose_sincos_lane0(double yaw, double pitch, doub
 // temp23 = temp1 hold exactly in IEEE arithmetic and are not stored; Rt(0,0) = temp15,
 // Rt(1,0) = temp14, Rt(2,0) = -temp3, Rt(2,1) = temp1, Rt(2,2) = temp2 likewise.  temp10, temp12, temp13 are
 // temp1, temp2, temp3 times cos(yaw) and temp18, temp19, temp20 the same times sin(yaw): the kernel applies
-// those two factors to the sum instead (see pass 2), so only cos(yaw) and sin(yaw) are stored.
+// those two factors to the sum instead (the sampled kernels' row, gn_sampled_device.hpp; in analytic_row below they are the
+// pitch axis), so only cos(yaw) and sin(yaw) are stored.
 __device__ __forceinline__ void write_pose_constants(double x, double y, double z, double yaw, double pitch,
                                                      double roll, double *cst, int lane)
 {
@@ -163,7 +164,7 @@ __device__ __forceinline__ void write_pose_constants(double x, double y, double 
 enum {
   P_FR00 = 0, P_FR01, P_FR02, P_FR10, P_FR11, P_FR12, P_XF, P_YF,
   P_OXI, P_OYI, P_Z, P_T1, P_T2, P_T3,
-  P_T4, P_T5, P_T6, P_T8, P_T11, P_T14, P_T16, P_T17, P_T24, P_CY, P_SY, P_X, P_Y, P_COUNT
+  P_T4, P_T5, P_T6, P_T8, P_T11, P_T14, P_T15, P_CY, P_SY, P_X, P_Y, P_COUNT
 };
 static_assert(P_COUNT <= 32 && P_OXI % 2 == 0, "the block has 32 slots; pass 2's first read starts a 16-byte pair");
 
@@ -192,9 +193,7 @@ __device__ __forceinline__ void write_pass_constants(double x, double y, double 
   cst[P_T8] = sr * cy - sp * cr * sy;
   cst[P_T11] = cp * cy + x;          // the reference's bug, kept (:253)
   cst[P_T14] = t14;
-  cst[P_T16] = sp * sr;
-  cst[P_T17] = sp * cr;
-  cst[P_T24] = cp;
+  cst[P_T15] = t15;                  // Rt's first column (t15, t14, -t3) is the roll axis of the row (analytic_row)
   cst[P_CY] = cy;
   cst[P_SY] = sy;
   cst[P_X] = x; cst[P_Y] = y;
@@ -749,6 +748,51 @@ __device__ __forceinline__ void add_row(double (&acc)[NRED], const double (&Jw)[
 }
 // W = identity: no weight and none of its instructions.
 __device__ __forceinline__ void add_row(double (&acc)[NRED], const double (&J)[6], const double res) { add_row(acc, J, J, res); }
+
+// One row of the analytic Jacobian on the reference-exact (nearest-scatter) path: the 2x6 warp Jacobian (:312-342)
+// contracted with the image gradient (:348), for the source point (px, py, pz) and the target gradient (gxi, gyi).
+// With Rt the rotation of the state, Pr = Rt * p = (Xr, Yr, Zr) and Jt = (J0, J1, J2) the row's three translation columns
+//   temp25 = 1/Zd, Zd = z + Zr, Zr = py*temp1 + pz*temp2 - px*temp3,
+//   Au = pz*temp4 + py*temp5 + px*temp11      [temp11 = temp15 + x carries the reference's bug, :253]
+//   Bv = py*temp6 + pz*temp9 + px*temp14 + y
+//   J0 = gx*fx*temp25, J1 = gy*fy*temp25, J2 = -(J0*Au + J1*Bv)*temp25.
+// The three rotation columns are the derivatives of Pr by yaw, pitch and roll, each contracted with Jt.  The reference's
+// generated code writes the three derivatives out one by one (:329-342); they are w_i x Pr for three axes that do not
+// depend on the pixel -- yaw: e_z, pitch: (-sin yaw, cos yaw, 0), roll: Rt's first column (temp15, temp14, -temp3) -- and
+// Jt . (w_i x Pr) = w_i . (Pr x Jt), so ONE cross product per pixel serves all three:
+//   Xr  = Au - px*x      (Rt's first row times p: the bug term of temp11 cancels, as in the reference's own temp15 terms)
+//   nYr = y - Bv         (-Yr; py*temp7 + pz*temp8 - px*temp14 of :329, since temp7 = -temp6, temp8 = -temp9)
+//   c_z = J0*nYr + J1*Xr,  -c_x = nYr*J2 + Zr*J1,  c_y = Zr*J0 - Xr*J2
+//   J3 = c_z,  J4 = cos(yaw)*c_y - sin(yaw)*c_x,  J5 = temp15*c_x + temp14*c_y - temp3*c_z:
+// 13 fp64 instructions where the three derivatives and their contractions took 20, and neither temp16/17/24 nor
+// temp21/temp7 are needed.  Au -- with the bug -- still enters J2 and through it J4 and J5, as in the reference; the
+// identity is exact in real arithmetic and the grouping differs from the reference's by rounding only (5e-15 of |p| |Jt|).
+// The cross product's fmas are spelled out: every kernel that carries the row forms it with the same grouping whatever
+// the compiler contracts around it (the sliding-window kernel equals its exact fall-back bit for bit).  The constants
+// come as values, so a kernel hands them over from wherever it keeps them -- scalar registers, vector registers (y, which
+// meets another constant inside one fma), members of a block read from LDS; RCP_STEPS: fast_rcp's Newton steps for temp25.
+template <int RCP_STEPS>
+__device__ __forceinline__ void analytic_row(const double px, const double py, const double pz, const double gxi, const double gyi,
+                                             const double fx, const double fy, const double x, const double y, const double z,
+                                             const double t1, const double t2, const double t3, const double t4, const double t5,
+                                             const double t6, const double t9, const double t11, const double t14,
+                                             const double t15, const double cosy, const double siny, double (&J)[6], double &Zr)
+{
+  Zr = py * t1 + pz * t2 - px * t3;                                       // Zd - z
+  const double t25 = fast_rcp<RCP_STEPS>(z + Zr);                         // :313
+  const double Au = pz * t4 + py * t5 + px * t11;
+  const double Bv = fma(py, t6, fma(pz, t9, fma(px, t14, y)));
+  J[0] = (gxi * fx) * t25;                                                // :317
+  J[1] = (gyi * fy) * t25;                                                // :322
+  J[2] = -(J[0] * Au + J[1] * Bv) * t25;                                  // :325-326
+  const double Xr = fma(-px, x, Au);
+  const double nYr = y - Bv;
+  const double ncx = fma(Zr, J[1], nYr * J[2]);
+  const double cyc = fma(Zr, J[0], -(Xr * J[2]));
+  J[3] = fma(J[1], Xr, J[0] * nYr);                                       // :329-330
+  J[4] = fma(cosy, cyc, siny * ncx);                                      // :333-336
+  J[5] = fma(-t3, J[3], fma(t14, cyc, -(t15 * ncx)));                     // :339-342
+}
 
 // Host: a persistent kernel (one that draws its pairs from the work queue) on as many workgroups as stay resident, or one
 // per pair if those are fewer.

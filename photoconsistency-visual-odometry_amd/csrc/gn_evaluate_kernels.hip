@@ -21,7 +21,7 @@ namespace phovo_hip {
 namespace {
 
 struct EvalPose {
-  double cx, cyy, cz, r01, r02, r11, r12, t1, t2, t3, t4, t5, t6, t8, t11, t14, t15, t16, t17, t24, cosy, siny;
+  double cx, cyy, cz, r01, r02, r11, r12, t1, t2, t3, t4, t5, t6, t8, t11, t14, t15, cosy, siny;
 };
 
 // Wave 0 writes the pose constants of the pair's state into s_cst; every thread reads them back behind the barrier.
@@ -33,8 +33,8 @@ __device__ __forceinline__ EvalPose eval_pose(const double *st, double *s_cst)
   p.cx = c[C_X]; p.cyy = c[C_Y]; p.cz = c[C_Z];
   p.r01 = c[C_R01]; p.r02 = c[C_R02]; p.r11 = c[C_R11]; p.r12 = c[C_R12];
   p.t1 = c[C_T1]; p.t2 = c[C_T2]; p.t3 = c[C_T3]; p.t4 = c[C_T4]; p.t5 = c[C_T5]; p.t6 = c[C_T6];
-  p.t8 = c[C_T8]; p.t11 = c[C_T11]; p.t14 = c[C_T14]; p.t15 = c[C_T15]; p.t16 = c[C_T16]; p.t17 = c[C_T17];
-  p.t24 = c[C_T24]; p.cosy = c[C_CY]; p.siny = c[C_SY];
+  p.t8 = c[C_T8]; p.t11 = c[C_T11]; p.t14 = c[C_T14]; p.t15 = c[C_T15];
+  p.cosy = c[C_CY]; p.siny = c[C_SY];
   return p;
 }
 
@@ -111,7 +111,7 @@ __global__ __launch_bounds__(ET) void k_eval_pass2(const GNEvalArgs A, int *g_ow
   const __amdgpu_buffer_rsrc_t rGY = plane_rsrc<TI>(tgt_frame + A.plane_off[PLANE_GY], n);
   int *owner = g_owner + (size_t)pair * (size_t)n;
   const double fx = A.fx, fy = A.fy, ox = A.ox, oy = A.oy, ifx = A.ifx, ify = A.ify;
-  const double t7 = -P.t6, t9 = -P.t8, t21 = -P.t5;
+  const double t9 = -P.t8;
   const double huber_delta = A.huber_delta;
 
   double acc[NRED];
@@ -173,20 +173,10 @@ __global__ __launch_bounds__(ET) void k_eval_pass2(const GNEvalArgs A, int *g_ow
       rowcol_from_index((double)k, rc_map, cd, rd);
       const double px = (cd - ox) * pz * ifx;
       const double py = (rd - oy) * pz * ify;
-      // the factored Jacobian of gn_level_kernel / k_wide_pass2 (derivation in gn_kernels.hip)
-      const double Zr = py * P.t1 + pz * P.t2 - px * P.t3;
-      const double t25 = fast_rcp(P.cz + Zr);                             // :313
-      const double Au = pz * P.t4 + py * P.t5 + px * P.t11;               // temp11 = temp15 + x: the reference's slip, kept
-      const double Bv = py * P.t6 + pz * t9 + px * P.t14 + P.cyy;
-      const double Cm = -py * P.t16 - pz * P.t17 - px * P.t24;
-      const double Dm = py * P.t2 - pz * P.t1;
-      double J[6];
-      J[0] = (gxi * fx) * t25;
-      J[1] = (gyi * fy) * t25;
-      J[2] = -(J[0] * Au + J[1] * Bv) * t25;
-      J[3] = J[0] * (P.cyy - Bv) + J[1] * (Au - px * P.cx);
-      J[4] = (J[0] * P.cosy + J[1] * P.siny) * Zr + Cm * J[2];
-      J[5] = J[0] * (py * P.t4 + pz * t21) + J[1] * (pz * t7 + py * t9) + Dm * J[2];
+      // the analytic row of gn_level_kernel / k_wide_pass2 (gn_device.hpp, analytic_row), temp25 with both Newton steps
+      double J[6], Zr;
+      analytic_row<2>(px, py, pz, gxi, gyi, fx, fy, P.cx, P.cyy, P.cz, P.t1, P.t2, P.t3, P.t4, P.t5, P.t6, t9, P.t11, P.t14,
+                      P.t15, P.cosy, P.siny, J, Zr);
       double Jw[6];
 #pragma unroll
       for (int a = 0; a < 6; a++) Jw[a] = HUBER ? J[a] * wgt : J[a];

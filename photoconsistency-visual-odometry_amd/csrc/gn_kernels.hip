@@ -380,9 +380,9 @@ __device__ __forceinline__ void level_body(const GNLevelArgs &A, const LevelLds 
     const double cz = uniform_f64(s_cst[P_Z]), cx = uniform_f64(s_cst[P_X]);
     const double t4 = uniform_f64(s_cst[P_T4]), t5 = uniform_f64(s_cst[P_T5]), t6 = uniform_f64(s_cst[P_T6]);
     const double t8 = uniform_f64(s_cst[P_T8]), t11 = uniform_f64(s_cst[P_T11]), t14 = uniform_f64(s_cst[P_T14]);
-    const double t16 = uniform_f64(s_cst[P_T16]), t17 = uniform_f64(s_cst[P_T17]), t24 = uniform_f64(s_cst[P_T24]);
+    const double t15 = uniform_f64(s_cst[P_T15]);
     const double cosy = uniform_f64(s_cst[P_CY]), siny = uniform_f64(s_cst[P_SY]);
-    const double t7 = -t6, t9 = -t8, t21 = -t5;
+    const double t9 = -t8;
 
     double acc[NRED];
 #pragma unroll
@@ -471,32 +471,10 @@ __device__ __forceinline__ void level_body(const GNLevelArgs &A, const LevelLds 
           const double px = fma(cd, ifx, oxv2) * pz;
           const double py = fma(rd, ify, oyv2) * pz;
 
-          // The 2x6 warp Jacobian (:312-342) contracted with the image gradient (:348), with the common
-          // factors pulled out and the reference's temps folded by exact algebraic identities:
-          //   temp25 = 1/Zd, Zd = z+py*temp1+pz*temp2-px*temp3, temp26 = temp25^2,
-          //   Au = (pz*temp4+py*temp5+px*temp11)   [temp11 = temp15 + x carries the reference's bug, :253]
-          //   Bv = (py*temp6+pz*temp9+px*temp14+y)
-          //   Cm = (-py*temp16-pz*temp17-px*temp24), Dm = (py*temp22-pz*temp23)
-          //   (py*temp7+pz*temp8-px*temp14) = y - Bv          since temp7 = -temp6, temp8 = -temp9
-          //   (pz*temp4+py*temp5+px*temp15) = Au - px*x       since temp15 = temp11 - x
-          //   (py*temp10+pz*temp12-px*temp13) = cos(yaw)*(Zd - z), (py*temp18+pz*temp19-px*temp20) = sin(yaw)*(Zd - z)
-          //   J0 = gx*fx*temp25, J1 = gy*fy*temp25, J2 = -(J0*Au + J1*Bv)*temp25,
-          //   J3 = J0*(y - Bv) + J1*(Au - px*x),
-          //   J4 = (J0*cos(yaw) + J1*sin(yaw))*(Zd - z) + Cm*J2,
-          //   J5 = J0*(py*temp4+pz*temp21) + J1*(pz*temp7+py*temp9) + Dm*J2.
-          const double Zr = py * t1 + pz * t2 - px * t3;                  // Zd - z
-          const double t25 = fast_rcp<1>(cz + Zr);                        // :313  (one Newton step: 2^-48, a Jacobian factor)
-          const double Au = pz * t4 + py * t5 + px * t11;
-          const double Bv = fma(py, t6, fma(pz, t9, fma(px, t14, cyv2)));
-          const double Cm = -py * t16 - pz * t17 - px * t24;
-          const double Dm = py * t2 - pz * t1;
-          double J[6];
-          J[0] = (gxi * fx) * t25;                                        // :317
-          J[1] = (gyi * fy) * t25;                                        // :322
-          J[2] = -(J[0] * Au + J[1] * Bv) * t25;                          // :325-326
-          J[3] = J[0] * (cyv2 - Bv) + J[1] * (Au - px * cx);               // :329-330
-          J[4] = (J[0] * cosy + J[1] * siny) * Zr + Cm * J[2];            // :333-336
-          J[5] = J[0] * (py * t4 + pz * t21) + J[1] * (pz * t7 + py * t9) + Dm * J[2];                   // :339-342
+          // the analytic row (gn_device.hpp, analytic_row: the factored form and its derivation); temp25 with one Newton
+          // step: 2^-48, a Jacobian factor
+          double J[6], Zr;
+          analytic_row<1>(px, py, pz, gxi, gyi, fx, fy, cx, cyv2, cz, t1, t2, t3, t4, t5, t6, t9, t11, t14, t15, cosy, siny, J, Zr);
 
           double Jw[6];
 #pragma unroll

@@ -197,9 +197,9 @@ __global__ __launch_bounds__(T, T / 256) void gn_level_kernel_slide(const GNLeve
       const double t14 = uniform_f64(s_cst[C_T14]);
       const double t4 = uniform_f64(s_cst[C_T4]), t5 = uniform_f64(s_cst[C_T5]), t6 = uniform_f64(s_cst[C_T6]);
       const double t8 = uniform_f64(s_cst[C_T8]), t11 = uniform_f64(s_cst[C_T11]);
-      const double t16 = uniform_f64(s_cst[C_T16]), t17 = uniform_f64(s_cst[C_T17]), t24 = uniform_f64(s_cst[C_T24]);
+      const double t15 = uniform_f64(s_cst[C_T15]);
       const double cosy = uniform_f64(s_cst[C_CY]), siny = uniform_f64(s_cst[C_SY]);
-      const double t7 = -t6, t9 = -t8, t21 = -t5;
+      const double t9 = -t8;
       const double huber_delta = A.huber_delta;
       const bool huber_on = huber_delta > 0.0;
       constexpr int STEP = NW2 * WAVE;
@@ -258,20 +258,9 @@ __global__ __launch_bounds__(T, T / 256) void gn_level_kernel_slide(const GNLeve
               const double rd = trunc(kd2 * inv_w), cd = fma(-rd, dW, kd2);
               const double px = fma(cd, ifx, oxv2) * pz;
               const double py = fma(rd, ify, oyv2) * pz;
-              // factored Jacobian, derivation in gn_kernels.hip (pass 2)
-              const double Zr = py * t1 + pz * t2 - px * t3;
-              const double t25 = fast_rcp<1>(cz + Zr);                  // :313
-              const double Au = pz * t4 + py * t5 + px * t11;           // temp11 = temp15 + x: the reference's slip (:253), kept
-              const double Bv = fma(py, t6, fma(pz, t9, fma(px, t14, cyv2)));
-              const double Cm = -py * t16 - pz * t17 - px * t24;
-              const double Dm = py * t2 - pz * t1;
-              double J[6];
-              J[0] = (gxi * fx) * t25;                                  // :317
-              J[1] = (gyi * fy) * t25;                                  // :322
-              J[2] = -(J[0] * Au + J[1] * Bv) * t25;                    // :325-326
-              J[3] = J[0] * (cyy - Bv) + J[1] * (Au - px * cx);         // :329-330
-              J[4] = (J[0] * cosy + J[1] * siny) * Zr + Cm * J[2];      // :333-336
-              J[5] = J[0] * (py * t4 + pz * t21) + J[1] * (pz * t7 + py * t9) + Dm * J[2];     // :339-342
+              // the analytic row, as level_body forms it (gn_device.hpp, analytic_row)
+              double J[6], Zr;
+              analytic_row<1>(px, py, pz, gxi, gyi, fx, fy, cx, cyv2, cz, t1, t2, t3, t4, t5, t6, t9, t11, t14, t15, cosy, siny, J, Zr);
               double Jw[6];
 #pragma unroll
               for (int a = 0; a < 6; a++) Jw[a] = J[a];
