@@ -771,6 +771,35 @@ __device__ __forceinline__ void add_row(double (&acc)[NRED], const double (&J)[6
 // the compiler contracts around it (the sliding-window kernel equals its exact fall-back bit for bit).  The constants
 // come as values, so a kernel hands them over from wherever it keeps them -- scalar registers, vector registers (y, which
 // meets another constant inside one fma), members of a block read from LDS; RCP_STEPS: fast_rcp's Newton steps for temp25.
+//
+// The row in the TWIST basis: q = (J0, J1, J2, c_z, c_y, -c_x), everything above up to the cross product.  The state-basis
+// row is J = T q with a 6x6 matrix T of the state alone -- unit rows 0..3, row 4 = (0, 0, 0, 0, cos yaw, sin yaw), row 5 =
+// (0, 0, 0, -temp3, temp14, -temp15) -- so J^T J = T (sum q q^T) T^T and J^T r = T (sum q r): the level kernels and the
+// sliding-window kernel sum q and apply T once per iteration to the 27 totals (rotate_system below), which takes the five
+// instructions of J4 and J5 out of every pixel.  A row weight (Huber) is a scalar per row and commutes with T.
+template <int RCP_STEPS>
+__device__ __forceinline__ void analytic_twist_row(const double px, const double py, const double pz, const double gxi,
+                                                   const double gyi, const double fx, const double fy, const double x,
+                                                   const double y, const double z, const double t1, const double t2,
+                                                   const double t3, const double t4, const double t5, const double t6,
+                                                   const double t9, const double t11, const double t14, double (&q)[6],
+                                                   double &Zr)
+{
+  Zr = py * t1 + pz * t2 - px * t3;                                       // Zd - z
+  const double t25 = fast_rcp<RCP_STEPS>(z + Zr);                         // :313
+  const double Au = pz * t4 + py * t5 + px * t11;
+  const double Bv = fma(py, t6, fma(pz, t9, fma(px, t14, y)));
+  q[0] = (gxi * fx) * t25;                                                // :317
+  q[1] = (gyi * fy) * t25;                                                // :322
+  q[2] = -(q[0] * Au + q[1] * Bv) * t25;                                  // :325-326
+  const double Xr = fma(-px, x, Au);
+  const double nYr = y - Bv;
+  q[5] = fma(Zr, q[1], nYr * q[2]);                                       // -c_x
+  q[4] = fma(Zr, q[0], -(Xr * q[2]));                                     // c_y
+  q[3] = fma(q[1], Xr, q[0] * nYr);                                       // c_z  :329-330
+}
+
+// The row in the state basis (the wide form and the evaluate kernels, whose J^T J is the state basis' by contract).
 template <int RCP_STEPS>
 __device__ __forceinline__ void analytic_row(const double px, const double py, const double pz, const double gxi, const double gyi,
                                              const double fx, const double fy, const double x, const double y, const double z,
@@ -778,20 +807,44 @@ __device__ __forceinline__ void analytic_row(const double px, const double py, c
                                              const double t6, const double t9, const double t11, const double t14,
                                              const double t15, const double cosy, const double siny, double (&J)[6], double &Zr)
 {
-  Zr = py * t1 + pz * t2 - px * t3;                                       // Zd - z
-  const double t25 = fast_rcp<RCP_STEPS>(z + Zr);                         // :313
-  const double Au = pz * t4 + py * t5 + px * t11;
-  const double Bv = fma(py, t6, fma(pz, t9, fma(px, t14, y)));
-  J[0] = (gxi * fx) * t25;                                                // :317
-  J[1] = (gyi * fy) * t25;                                                // :322
-  J[2] = -(J[0] * Au + J[1] * Bv) * t25;                                  // :325-326
-  const double Xr = fma(-px, x, Au);
-  const double nYr = y - Bv;
-  const double ncx = fma(Zr, J[1], nYr * J[2]);
-  const double cyc = fma(Zr, J[0], -(Xr * J[2]));
-  J[3] = fma(J[1], Xr, J[0] * nYr);                                       // :329-330
+  analytic_twist_row<RCP_STEPS>(px, py, pz, gxi, gyi, fx, fy, x, y, z, t1, t2, t3, t4, t5, t6, t9, t11, t14, J, Zr);
+  const double cyc = J[4], ncx = J[5];
   J[4] = fma(cosy, cyc, siny * ncx);                                      // :333-336
   J[5] = fma(-t3, J[3], fma(t14, cyc, -(t15 * ncx)));                     // :339-342
+}
+
+// The normal equations of the twist basis taken to the state basis: h, g in (the 21 + 6 totals of q q^T and q r, as
+// solve6_ldlt lays them out) become the upper triangle of T h T^T and T g, T as above analytic_twist_row.  Lane-uniform
+// work of the wave that solves, between sum_rows_broadcast and solve6_ldlt; the five constants are those of the state the
+// rows were formed with.  Every product and fma is spelled out -- with the grouping of J4 and J5 in analytic_row -- so
+// that every kernel rounds alike (the sliding-window kernel and its exact fall-back):
+//   two(a, b)      = cos yaw * a + sin yaw * b                 row 4 of T on (., a, b):      2 roundings
+//   three(a, b, c) = -temp3 * a + temp14 * b - temp15 * c      row 5 of T on (a, b, c):      3 roundings
+// Entries among 0..3 are T's unit rows: copies.  Column 4 of rows 0..3 is two(), column 5 three(); the lower right 3x3
+// block B = h[3..5][3..5] goes through B u and B v (u, v: rows 4 and 5 of T on indices 3..5), whose first entries are
+// H34 and H35: H44 = u . B u, H45 = u . B v, H55 = v . B v.  42 fp64 instructions, the negations are operand modifiers.
+// (tests/test_gpu_system_rotation.py holds every entry against exact rational arithmetic, with the rounding count of
+// each entry's expression as written here.)
+__device__ __forceinline__ void rotate_system(double (&h)[21], double (&g)[6], const double cosy, const double siny,
+                                              const double t3, const double t14, const double t15)
+{
+  auto two = [&](const double a, const double b) { return fma(cosy, a, siny * b); };
+  auto three = [&](const double a, const double b, const double c) { return fma(-t3, a, fma(t14, b, -(t15 * c))); };
+  // B u and B v without their first entries (those are H34, H35 below), from the totals before any is overwritten
+  const double bu4 = two(h[tri(4, 4)], h[tri(4, 5)]), bu5 = two(h[tri(4, 5)], h[tri(5, 5)]);
+  const double bv4 = three(h[tri(3, 4)], h[tri(4, 4)], h[tri(4, 5)]), bv5 = three(h[tri(3, 5)], h[tri(4, 5)], h[tri(5, 5)]);
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const double a3 = h[tri(i, 3)], a4 = h[tri(i, 4)], a5 = h[tri(i, 5)];
+    h[tri(i, 4)] = two(a4, a5);
+    h[tri(i, 5)] = three(a3, a4, a5);
+  }
+  h[tri(4, 4)] = two(bu4, bu5);
+  h[tri(4, 5)] = two(bv4, bv5);
+  h[tri(5, 5)] = three(h[tri(3, 5)], bv4, bv5);                           // (h[3][5] is B v's first entry by now)
+  const double g3 = g[3], g4 = g[4], g5 = g[5];
+  g[4] = two(g4, g5);
+  g[5] = three(g3, g4, g5);
 }
 
 // Host: a persistent kernel (one that draws its pairs from the work queue) on as many workgroups as stay resident, or one

@@ -17,10 +17,11 @@
 //           J_k = gx1[k]*Ju + gy1[k]*Jv from pixel k's own depth (the reference reads the gradient at
 //           the SOURCE index, :346-347, and writes J at the source row, :351-356, while r is scattered,
 //           so row k of J meets residual k in J^T r, :538), then 21 + 6 FMAs into the upper triangle of
-//           J^T J and J^T r held in registers.
+//           J^T J and J^T r held in registers -- in the twist basis (gn_device.hpp, analytic_twist_row): the
+//           row's last two columns are a fixed matrix T of the state applied to it, left to the solve.
 //   reduce  per-wave transposed butterfly (32 shuffles for 32 values instead of 6 x 27), one LDS row
 //           per wave, fixed-order sum across waves -> bitwise reproducible.
-//   solve   wave 0: 6x6 LDL^T solve, state -= lambda * H^-1 g,
+//   solve   wave 0: the 27 totals to the state basis (rotate_system), 6x6 LDL^T solve, state -= lambda * H^-1 g,
 //           termination test, pose constants of the next iteration.
 // No MFMA: J^T J is a 6 x N by N x 6 contraction, a reduction, not a GEMM tile.
 //
@@ -379,9 +380,8 @@ __device__ __forceinline__ void level_body(const GNLevelArgs &A, const LevelLds 
     // (its constants are scalars -- the pass sits at the register cap -- read here, behind pass 1, which needs none of them)
     const double cz = uniform_f64(s_cst[P_Z]), cx = uniform_f64(s_cst[P_X]);
     const double t4 = uniform_f64(s_cst[P_T4]), t5 = uniform_f64(s_cst[P_T5]), t6 = uniform_f64(s_cst[P_T6]);
+    // (P_T15, P_CY, P_SY are not the pass's: the rows are summed in the twist basis and wave 0 applies those once, below)
     const double t8 = uniform_f64(s_cst[P_T8]), t11 = uniform_f64(s_cst[P_T11]), t14 = uniform_f64(s_cst[P_T14]);
-    const double t15 = uniform_f64(s_cst[P_T15]);
-    const double cosy = uniform_f64(s_cst[P_CY]), siny = uniform_f64(s_cst[P_SY]);
     const double t9 = -t8;
 
     double acc[NRED];
@@ -471,10 +471,10 @@ __device__ __forceinline__ void level_body(const GNLevelArgs &A, const LevelLds 
           const double px = fma(cd, ifx, oxv2) * pz;
           const double py = fma(rd, ify, oyv2) * pz;
 
-          // the analytic row (gn_device.hpp, analytic_row: the factored form and its derivation); temp25 with one Newton
-          // step: 2^-48, a Jacobian factor
+          // the analytic row in the twist basis (gn_device.hpp, analytic_twist_row: the factored form and its derivation);
+          // temp25 with one Newton step: 2^-48, a Jacobian factor
           double J[6], Zr;
-          analytic_row<1>(px, py, pz, gxi, gyi, fx, fy, cx, cyv2, cz, t1, t2, t3, t4, t5, t6, t9, t11, t14, t15, cosy, siny, J, Zr);
+          analytic_twist_row<1>(px, py, pz, gxi, gyi, fx, fy, cx, cyv2, cz, t1, t2, t3, t4, t5, t6, t9, t11, t14, J, Zr);
 
           double Jw[6];
 #pragma unroll
@@ -490,7 +490,7 @@ __device__ __forceinline__ void level_body(const GNLevelArgs &A, const LevelLds 
           for (int a = 0; a < 6; a++) {
 #pragma unroll
             for (int b = a; b < 6; b++) {
-              acc[q] = fma(Jw[a], J[b], acc[q]);                                        // J^T (W) J  :540
+              acc[q] = fma(Jw[a], J[b], acc[q]);                                        // q^T (W) q: J^T (W) J of :540 before T
               q++;
             }
           }
@@ -559,17 +559,26 @@ __device__ __forceinline__ void level_body(const GNLevelArgs &A, const LevelLds 
       asm volatile("" : "+v"(ln0));
       double h[21], g[6];
       sum_rows_broadcast<NW>(ln0, s_red, h, g, last_valid);
+      // the rotation constants of the state pass 2 ran with, before write_pass_constants below replaces them, read right
+      // behind the totals.  Scalars: as lane-uniform vector registers they are ten more beside both bases' totals, and the
+      // 1024-thread kernels with the owner map in HBM and the fp64 one-wave kernel then spilled (private segment +8 / +4 bytes,
+      // a scratch store and reload inside this section)
+      const double rot_cy = uniform_f64(s_cst[P_CY]), rot_sy = uniform_f64(s_cst[P_SY]), rot_t3 = uniform_f64(s_cst[P_T3]);
+      const double rot_t14 = uniform_f64(s_cst[P_T14]), rot_t15 = uniform_f64(s_cst[P_T15]);
 #ifdef PHOVO_PHASE_STAMPS
       asm volatile("" :: "v"(h[0]), "v"(g[5]));
       const unsigned long long solve_t0 = wall_clock64();
 #endif
+      // the totals are those of the twist basis: to the state basis, J^T J = T (sum q q^T) T^T and J^T r = T (sum q r)
+      // (gn_device.hpp, rotate_system) -- from here on everything sees what it saw when every row was rotated
+      rotate_system(h, g, rot_cy, rot_sy, rot_t3, rot_t14, rot_t15);
       double step[6];
       solve6_ldlt(h, g, step);
 #ifdef PHOVO_PHASE_STAMPS
       asm volatile("" :: "v"(step[0]), "v"(step[5]));
       const unsigned long long solve_t1 = wall_clock64();
       solve_sum[0] += solve_t0 - stamp_last;       // cross-wave sum and broadcasts
-      solve_sum[1] += solve_t1 - solve_t0;         // LDL^T
+      solve_sum[1] += solve_t1 - solve_t0;         // rotation to the state basis and LDL^T
 #endif
       double st[6];
       bool finite = true;

@@ -197,8 +197,6 @@ __global__ __launch_bounds__(T, T / 256) void gn_level_kernel_slide(const GNLeve
       const double t14 = uniform_f64(s_cst[C_T14]);
       const double t4 = uniform_f64(s_cst[C_T4]), t5 = uniform_f64(s_cst[C_T5]), t6 = uniform_f64(s_cst[C_T6]);
       const double t8 = uniform_f64(s_cst[C_T8]), t11 = uniform_f64(s_cst[C_T11]);
-      const double t15 = uniform_f64(s_cst[C_T15]);
-      const double cosy = uniform_f64(s_cst[C_CY]), siny = uniform_f64(s_cst[C_SY]);
       const double t9 = -t8;
       const double huber_delta = A.huber_delta;
       const bool huber_on = huber_delta > 0.0;
@@ -258,9 +256,9 @@ __global__ __launch_bounds__(T, T / 256) void gn_level_kernel_slide(const GNLeve
               const double rd = trunc(kd2 * inv_w), cd = fma(-rd, dW, kd2);
               const double px = fma(cd, ifx, oxv2) * pz;
               const double py = fma(rd, ify, oyv2) * pz;
-              // the analytic row, as level_body forms it (gn_device.hpp, analytic_row)
+              // the analytic row in the twist basis, as level_body forms it (gn_device.hpp, analytic_twist_row)
               double J[6], Zr;
-              analytic_row<1>(px, py, pz, gxi, gyi, fx, fy, cx, cyv2, cz, t1, t2, t3, t4, t5, t6, t9, t11, t14, t15, cosy, siny, J, Zr);
+              analytic_twist_row<1>(px, py, pz, gxi, gyi, fx, fy, cx, cyv2, cz, t1, t2, t3, t4, t5, t6, t9, t11, t14, J, Zr);
               double Jw[6];
 #pragma unroll
               for (int a = 0; a < 6; a++) Jw[a] = J[a];
@@ -275,7 +273,7 @@ __global__ __launch_bounds__(T, T / 256) void gn_level_kernel_slide(const GNLeve
               for (int a = 0; a < 6; a++) {
 #pragma unroll
                 for (int c = a; c < 6; c++) {
-                  acc[q] = fma(Jw[a], J[c], acc[q]);                    // J^T (W) J  :540
+                  acc[q] = fma(Jw[a], J[c], acc[q]);                    // q^T (W) q: J^T (W) J of :540 before T
                   q++;
                 }
               }
@@ -312,10 +310,14 @@ __global__ __launch_bounds__(T, T / 256) void gn_level_kernel_slide(const GNLeve
 
     // ---- cross-wave sum, solve, update, terminate (as gn_level_kernel) --------------------------------------------
     if (wave == 0) {
+      // the rotation constants of the state pass 2 ran with, before write_pose_constants below replaces them
+      const double rot_cy = s_cst[C_CY], rot_sy = s_cst[C_SY], rot_t3 = s_cst[C_T3], rot_t14 = s_cst[C_T14], rot_t15 = s_cst[C_T15];
       double h[21], g[6];
       int n_valid;
       sum_rows_broadcast<NW2>(lane, s_red, h, g, n_valid);
       const bool void_iteration = s_ctl[CTL_OOW] != 0;                  // wave-uniform
+      // twist basis to state basis, as level_body (gn_device.hpp, rotate_system)
+      rotate_system(h, g, rot_cy, rot_sy, rot_t3, rot_t14, rot_t15);
       double step[6];
       solve6_ldlt(h, g, step);
       double st[6];
