@@ -2,7 +2,7 @@
 // directory, writing a TUM trajectory file.
 //
 //   ./PhotoconsistencyVisualOdometry <config_file.yml> <rgbd_dataset_directory> <output_trajectory_file> [--batch [--gpus N] [--rccl]]
-//                                    [--method analytic|ceres|biobjective|affine|geometric] [--information <file>] [--system <file>]
+//                                    [--method analytic|ceres|biobjective|inverse|affine|geometric] [--information <file>] [--system <file>]
 //                                    [--geometric-system <file>] [--objective-system <file>]
 // --method picks the aligner as the reference's USE_PHOTOCONSISTENCY_ODOMETRY_METHOD does (0 = analytic, the default;
 // 1 = ceres: Levenberg-Marquardt on bilinear samples, CPhotoconsistencyOdometryCeres, which reads config_*_ceres.yml
@@ -11,6 +11,9 @@
 // which reads the analytic files.
 // geometric is not in the reference either: intensity and depth rows together on the bilinear samples,
 // CPhotoconsistencyOdometryGeometric, which reads the analytic files and their optional depth_weight / max_depth_residual keys.
+// inverse is not in the reference either: the photometric residual aligned inverse-compositionally (the Jacobian from the
+// source frame's own gradient, the step composed on SE(3)), CPhotoconsistencyOdometryInverse, which reads the analytic files;
+// it has no system call yet, so the four system flags below refuse it.
 // A configuration file of the other kind is refused with a message that says so.
 // --information <file> (not in the reference; analytic method, one device): one line per pair, stamped like its trajectory
 // line, with the Gauss-Newton system at the pair's optimal state on the finest level the configuration optimises --
@@ -72,6 +75,7 @@
 #include "rccl/shard_vote.h"
 #include "phovo/CPhotoconsistencyOdometryAnalytic.h"
 #include "phovo/CPhotoconsistencyOdometryAffine.h"
+#include "phovo/CPhotoconsistencyOdometryInverse.h"
 #include "phovo/CPhotoconsistencyOdometryGeometric.h"
 #include "phovo/CPhotoconsistencyOdometryBiObjective.h"
 #include "phovo/CPhotoconsistencyOdometryCeres.h"
@@ -190,7 +194,7 @@ static phovo_pair_system objectiveSystemOf(Odometry &, long)
 static void printHelp()
 {
   std::cout << "./PhotoconsistencyVisualOdometry <config_file.yml> <rgbd_dataset_directory> "
-               "<output_trajectory_file> [--batch [--gpus N] [--rccl]] [--method analytic|ceres|biobjective|affine|geometric] "
+               "<output_trajectory_file> [--batch [--gpus N] [--rccl]] [--method analytic|ceres|biobjective|inverse|affine|geometric] "
                "[--information <file>] [--system <file>] [--geometric-system <file>] [--objective-system <file>]" << std::endl;
 }
 
@@ -219,6 +223,7 @@ int main(int argc, char *argv[])
       else if (m == "ceres") objective = PHOVO_OBJECTIVE_TRUST_REGION;
       else if (m == "affine") objective = PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE;
       else if (m == "geometric") objective = PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC;
+      else if (m == "inverse") objective = PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL;
       else { printHelp(); return EXIT_FAILURE; }
     }
     else if (a == "--rccl") rccl = true;
@@ -386,6 +391,9 @@ int main(int argc, char *argv[])
         if (runLoop(odometry) != EXIT_SUCCESS) return EXIT_FAILURE;
       } else if (objective == PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC) {
         phovo::Analytic::CPhotoconsistencyOdometryGeometric<PixelType, CoordinateType> odometry;
+        if (runLoop(odometry) != EXIT_SUCCESS) return EXIT_FAILURE;
+      } else if (objective == PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL) {
+        phovo::Analytic::CPhotoconsistencyOdometryInverse<PixelType, CoordinateType> odometry;
         if (runLoop(odometry) != EXIT_SUCCESS) return EXIT_FAILURE;
       } else {
         phovo::Analytic::CPhotoconsistencyOdometryAnalytic<PixelType, CoordinateType> odometry;

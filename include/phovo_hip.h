@@ -254,6 +254,44 @@ typedef struct phovo_extensions {
  *                                PHOVO_PAIR_NONFINITE as under the photometric objective, gradient_norm = ||g||_2 of the
  *                                last system.  Depth rows and the two costs: phovo_geometric_report. */
 #define PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC 4
+/*   PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL  not in the reference: the photometric residual aligned inverse-compositionally
+ *                                (Baker & Matthews; 6 entries per pair, the pose; DESIGN.md §20 has the contract).  Per
+ *                                level L and pair, with the level's scaled intrinsics (line numbers: ...Analytic.h):
+ *                                  entry   (R, t) = eigenPose(state).
+ *                                  rows    the bilinear extension's: every source pixel k in raster order with
+ *                                          min_depth < D0_k < max_depth (NaN fails); p = (px, py, pz) as at :282-283,
+ *                                          P' = R p + t, (u, v) as at :295-296; in bounds iff -0.5 < u < W - 0.5 and
+ *                                          -0.5 < v < H - 0.5; I1(u, v) bilinear on four clamped taps;
+ *                                          r_k = I1(u, v) - I0_k.
+ *                                  J_k     from the SOURCE alone, twist order (nu_x, nu_y, nu_z, omega_x, omega_y, omega_z):
+ *                                          g = (GX0_k, GY0_k) from the source frame's gradient planes as stored (the
+ *                                          gradient scaling factor included),
+ *                                          a = (g_x fx / pz, g_y fy / pz, -(a_0 px + a_1 py) / pz),  J_k = (a, p x a).
+ *                                  step    H = sum J J^T, g = sum J r, xi = -lambda_L H^-1 g,
+ *                                          (R, t) <- (R E_R, R E_t + t) with (E_R, E_t) = Exp(xi) on SE(3) (Rodrigues,
+ *                                          E_t = V nu; for |omega|^2 < 1e-8 the coefficients' Taylor series through
+ *                                          |omega|^4).  R is not re-orthonormalised.
+ *                                  end     after the step when iteration + 1 >= max_num_iterations[L], else when
+ *                                          ||g||_2 < min_gradient_norm[L] (g in the TWIST basis: the shipped thresholds
+ *                                          were tuned on Euler-basis gradients, the two coincide near zero rotation only),
+ *                                          and, with PHOVO_PAIR_NONFINITE, when an entry of (R, t) is not finite.
+ *                                  exit    state = (t, yaw = atan2(R10, R00), pitch = atan2(-R20, sqrt(R00^2 + R10^2)),
+ *                                          roll = atan2(R21, R22)); a non-finite (R, t) gives a NaN state.  Levels are
+ *                                          separate launches, the n x 6 state array is all that travels between them;
+ *                                          levels with max_num_iterations 0 are not launched.
+ *                                The source's gradient planes on level L are those a TARGET upload of that frame leaves
+ *                                there: source frames need PHOVO_ROLE_BOTH, and an enqueue whose source lacks the target
+ *                                role on an active level is PHOVO_E_NOT_READY.  No new planes: switching between objectives
+ *                                0, 2, 3, 4 and 5 keeps the frame pool.  Supported: fp64 planes, the default sampling
+ *                                setting, no Huber weights, jacobian_corrected 0 -- anything else is PHOVO_E_UNSUPPORTED,
+ *                                whichever setter comes second.  All four phovo_engine_evaluate_* calls and the
+ *                                phovo_odometry_get_*_system calls are PHOVO_E_UNSUPPORTED under this objective (its
+ *                                twist-basis system is not built yet).  Fusion, sliding-window, wide, latency-form and
+ *                                batch-invariant settings are accepted and have no effect.
+ *                                phovo_pair_report keeps its meaning: iterations[L], valid_pixels[L] = rows of the level's
+ *                                last system, gradient_norm = ||g||_2 of the last system, PHOVO_PAIR_RANK_DEFICIENT
+ *                                (sticky) when a system had fewer than 6 rows. */
+#define PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL 5
 
 /* Options of the photometric-geometric objective, per level.  Both are settings to tune for the sensor and the scene, not
  * measured optima: depth_weight trades metres of depth error against intensity error (intensities are in [0, 1]), and
@@ -381,6 +419,11 @@ int phovo_extensions_read_file(const char *path, phovo_extensions *ext);
 
 /* eigenPose, CPhotoconsistencyOdometry.h:47-71: (x,y,z,yaw,pitch,roll) -> row-major 4x4. */
 int phovo_eigen_pose(const double state[6], double rt[16]);
+/* The inverse of phovo_eigen_pose (host arithmetic only): state = (rt[3], rt[7], rt[11], yaw = atan2(R10, R00),
+ * pitch = atan2(-R20, sqrt(R00^2 + R10^2)), roll = atan2(R21, R22)) of a row-major 4x4 -- the formulas by which the
+ * inverse-compositional objective leaves a level.  Exact up to rounding wherever cos(pitch) != 0 (pitch comes back in
+ * [-pi/2, pi/2]; at cos(pitch) = 0 yaw and roll are not determined by the matrix).  PHOVO_E_INVALID_ARGUMENT on NULL. */
+int phovo_state_from_pose(const double rt[16], double state[6]);
 
 /* The VisualOdometry app's pose chain and trajectory line
  * (apps/PhotoconsistencyVisualOdometry/PhotoconsistencyVisualOdometry.cpp:233-243):
@@ -856,7 +899,8 @@ enum { PHOVO_LAUNCH_PERSISTENT = 0,       /* gn_level_kernel: one level, one wor
        PHOVO_LAUNCH_BIOBJECTIVE = 6,      /* gn_level_kernel_biobjective (PHOVO_OBJECTIVE_BIOBJECTIVE) */
        PHOVO_LAUNCH_TRUST_REGION = 7,     /* gn_level_kernel_trust_region (PHOVO_OBJECTIVE_TRUST_REGION) */
        PHOVO_LAUNCH_AFFINE = 8,           /* gn_level_kernel_affine (PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE) */
-       PHOVO_LAUNCH_GEOMETRIC = 9 };      /* gn_level_kernel_geometric (PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC) */
+       PHOVO_LAUNCH_GEOMETRIC = 9,        /* gn_level_kernel_geometric (PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC) */
+       PHOVO_LAUNCH_INVERSE = 10 };       /* gn_level_kernel_inverse (PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL) */
 typedef struct phovo_launch_record {
   int level_first, level_last;            /* pyramid levels the launch covers (level_first >= level_last) */
   int kind;                               /* PHOVO_LAUNCH_* */

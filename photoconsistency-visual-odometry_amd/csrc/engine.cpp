@@ -105,8 +105,8 @@ void level_dims(int w, int h, int level, int *lw, int *lh)
 }
 
 // Every objective but the photometric one runs reference-exact only: fp64 planes, nearest / scatter sampling, no Huber
-// weights, jacobian_corrected 0 (the affine-illumination and photometric-geometric rows are fixed by the objective, not
-// chosen by the extensions).  PHOVO_OK where `objective` and `x` go together, else the refusal, in the setter's name.
+// weights, jacobian_corrected 0 (the affine-illumination, photometric-geometric and inverse-compositional rows are fixed by
+// the objective, not chosen by the extensions).  PHOVO_OK where `objective` and `x` go together, else the refusal, in the setter's name.
 int reference_exact_only(const char *setter, int objective, const phovo_extensions &x)
 {
   bool exact = x.plane_storage == PHOVO_STORAGE_F64 && x.sampling == PHOVO_SAMPLING_NEAREST_SCATTER && x.jacobian_corrected == 0;
@@ -117,6 +117,7 @@ int reference_exact_only(const char *setter, int objective, const phovo_extensio
       objective == PHOVO_OBJECTIVE_BIOBJECTIVE ? "the bi-objective runs on fp64 planes with nearest / scatter sampling and no Huber weights only"
       : objective == PHOVO_OBJECTIVE_TRUST_REGION ? "the trust-region objective runs on fp64 planes with the default sampling, no Huber weights and jacobian_corrected 0 only"
       : objective == PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE ? "the affine-illumination objective runs on fp64 planes with the default sampling setting, no Huber weights and jacobian_corrected 0 only"
+      : objective == PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL ? "the inverse-compositional objective runs on fp64 planes with the default sampling setting, no Huber weights and jacobian_corrected 0 only"
       : "the photometric-geometric objective runs on fp64 planes with the default sampling setting, no Huber weights and jacobian_corrected 0 only";
   return fail(PHOVO_E_UNSUPPORTED, std::string(setter) + ": " + only);
 }
@@ -337,6 +338,16 @@ int phovo_eigen_pose(const double s[6], double rt[16])
   return PHOVO_OK;
 }
 
+int phovo_state_from_pose(const double rt[16], double s[6])
+{
+  if (!rt || !s) return fail(PHOVO_E_INVALID_ARGUMENT, "phovo_state_from_pose: null");
+  s[0] = rt[3]; s[1] = rt[7]; s[2] = rt[11];
+  s[3] = std::atan2(rt[4], rt[0]);
+  s[4] = std::atan2(-rt[8], std::sqrt(rt[0] * rt[0] + rt[4] * rt[4]));
+  s[5] = std::atan2(rt[9], rt[10]);
+  return PHOVO_OK;
+}
+
 /* ------------------------------------------------------------------ engine ------------------ */
 
 int phovo_engine_create(int device, phovo_engine **out)
@@ -478,12 +489,12 @@ int phovo_engine_set_objective(phovo_engine *e, int objective)
   if (!e) return fail(PHOVO_E_INVALID_ARGUMENT, "set_objective: null");
   if (objective != PHOVO_OBJECTIVE_PHOTOMETRIC && objective != PHOVO_OBJECTIVE_BIOBJECTIVE &&
       objective != PHOVO_OBJECTIVE_TRUST_REGION && objective != PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE &&
-      objective != PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC)
+      objective != PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC && objective != PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL)
     return fail(PHOVO_E_INVALID_ARGUMENT, "set_objective: unknown objective");
   const int st = reference_exact_only("set_objective", objective, e->ext);
   if (st != PHOVO_OK) return st;
-  // The photometric, trust-region, affine-illumination and photometric-geometric objectives share the frame layout: a switch
-  // between them keeps the pool.
+  // The photometric, trust-region, affine-illumination, photometric-geometric and inverse-compositional objectives share the
+  // frame layout: a switch between them keeps the pool.
   auto bi = [](int o) { return o == PHOVO_OBJECTIVE_BIOBJECTIVE; };
   if (objective != e->objective && (bi(objective) || bi(e->objective))) drop_pool(e);   // the pool layout changes (the bi-objective's target planes)
   e->objective = objective;

@@ -187,6 +187,13 @@ int phovo_engine_enqueue_align(phovo_engine *e, int n_pairs, const int *source_f
                                          "frames with PHOVO_ROLE_BOTH)");
       continue;
     }
+    if (e->objective == PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL) {            // likewise; the source's gradients are a target upload's
+      for (int i = 0; i < n_pairs; i++)
+        if (!(e->frame_roles[(size_t)source_frames[i] * PHOVO_MAX_LEVELS + (size_t)l] & PHOVO_ROLE_TARGET))
+          return fail(PHOVO_E_NOT_READY, "align: the inverse-compositional objective reads the source's gradient planes (upload "
+                                         "source frames with PHOVO_ROLE_BOTH)");
+      continue;
+    }
     if (e->ext.sampling == PHOVO_SAMPLING_BILINEAR) continue;       // no owner map, no LDS limit
     const bool wide = use_wide_level(e, n_pairs, lv) && !(e->ext.huber_delta[l] > 0.0);
     if (wide) {
@@ -401,6 +408,11 @@ int phovo_engine_enqueue_align(phovo_engine *e, int n_pairs, const int *source_f
       b.geo_reports = s.geo_reports.ptr;
       PHOVO_HIP_CHECK(gn_launch_level_geometric(b, e->cu_count, s.stream));
       record(l, l, PHOVO_LAUNCH_GEOMETRIC, 256, gn_geometric_lds_bytes(), persistent_grid(gn_geometric_wgs_per_cu()));
+    } else if (e->objective == PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL) {
+      GNInverseArgs b{};
+      b.lv = a;
+      PHOVO_HIP_CHECK(gn_launch_level_inverse(b, e->cu_count, s.stream));
+      record(l, l, PHOVO_LAUNCH_INVERSE, 256, gn_inverse_lds_bytes(), persistent_grid(gn_inverse_wgs_per_cu()));
     } else if (e->ext.sampling == PHOVO_SAMPLING_BILINEAR) {
       PHOVO_HIP_CHECK(gn_launch_level_bilinear(a, e->ext.plane_storage, e->ext.jacobian_corrected != 0, e->cu_count, s.stream));
       record(l, l, PHOVO_LAUNCH_BILINEAR, 256, 0, persistent_grid(gn_bilinear_wgs_per_cu(e->ext.plane_storage)));

@@ -172,6 +172,8 @@ int phovo_engine_evaluate_sampled_pairs(phovo_engine *e, int n_pairs, const int 
                                      "system (bilinear sampling or the affine-illumination objective only)");
   if (e->objective == PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC)
     return fail(PHOVO_E_UNSUPPORTED, "evaluate_sampled_pairs: the photometric-geometric objective has no sampled system");
+  if (e->objective == PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL)
+    return fail(PHOVO_E_UNSUPPORTED, "evaluate_sampled_pairs: the inverse-compositional objective has no system call yet");
   const bool affine = e->objective == PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE;
   if (!affine && e->ext.sampling != PHOVO_SAMPLING_BILINEAR)
     return fail(PHOVO_E_UNSUPPORTED, "evaluate_sampled_pairs: nearest / scatter sampling has its system in "
@@ -258,6 +260,8 @@ int phovo_engine_evaluate_objective_pairs(phovo_engine *e, int n_pairs, const in
     case PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE:
       return fail(PHOVO_E_UNSUPPORTED, "evaluate_objective_pairs: the affine-illumination objective has its system in "
                                        "phovo_engine_evaluate_sampled_pairs");
+    case PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL:
+      return fail(PHOVO_E_UNSUPPORTED, "evaluate_objective_pairs: the inverse-compositional objective has no system call yet");
     default:
       return fail(PHOVO_E_UNSUPPORTED, "evaluate_objective_pairs: the photometric-geometric objective has its system in "
                                        "phovo_engine_evaluate_geometric_pairs");

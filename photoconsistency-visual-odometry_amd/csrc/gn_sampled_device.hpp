@@ -1,5 +1,6 @@
 // What the SAMPLED kernels share: the aligners that warp every source pixel to a real-valued target position and sample
-// there bilinearly (gn_bilinear_kernel.hip, gn_affine_kernel.hip, gn_geometric_kernel.hip) and the kernels that fill the
+// there bilinearly (gn_bilinear_kernel.hip, gn_affine_kernel.hip, gn_geometric_kernel.hip, and gn_inverse_kernel.hip, which
+// takes the pair frame, the warp, the taps and bilerp and has a source-side row of its own) and the kernels that fill the
 // same rows at a given state (k_eval_sampled, k_eval_geometric_depth, through gn_evaluate_device.hpp).  An aligner and its
 // "system at a given state" kernel promise exactly the same rows: the gates, the bounds test, the taps, the interpolation
 // and the six pose columns stand here once, and a change to them is made here.
@@ -133,6 +134,35 @@ __device__ __forceinline__ SampledPose sampled_pose(const double *s_cst)
   P.t16 = read(C_T16); P.t17 = read(C_T17); P.t24 = read(C_T24);
   P.cosy = read(C_CY); P.siny = read(C_SY);
   P.t7 = -P.t6; P.t9 = -P.t8; P.t21 = -P.t5;
+  return P;
+}
+
+// The pose as (R, t) in the same block, for a kernel that carries a rotation matrix instead of Euler angles
+// (gn_inverse_kernel.hip): write_pose_constants leaves Rt in twelve of its slots -- rows (T15, R01, R02 | X),
+// (T14, R11, R12 | Y), (-T3, T1, T2 | Z) -- and those twelve are all warp_project reads.  rt_constants_write puts a
+// row-major R and t there (one lane calls it), sampled_pose_rt reads them back; the other members are 0 and nobody may
+// hand such a pose to pose_columns.
+__device__ __forceinline__ void rt_constants_write(double *s_cst, const double (&R)[9], const double (&t)[3])
+{
+  s_cst[C_T15] = R[0]; s_cst[C_R01] = R[1]; s_cst[C_R02] = R[2]; s_cst[C_X] = t[0];
+  s_cst[C_T14] = R[3]; s_cst[C_R11] = R[4]; s_cst[C_R12] = R[5]; s_cst[C_Y] = t[1];
+  s_cst[C_T3] = -R[6]; s_cst[C_T1] = R[7]; s_cst[C_T2] = R[8]; s_cst[C_Z] = t[2];
+}
+__device__ __forceinline__ void rt_constants_read(const double *s_cst, double (&R)[9], double (&t)[3])
+{
+  R[0] = s_cst[C_T15]; R[1] = s_cst[C_R01]; R[2] = s_cst[C_R02]; t[0] = s_cst[C_X];
+  R[3] = s_cst[C_T14]; R[4] = s_cst[C_R11]; R[5] = s_cst[C_R12]; t[1] = s_cst[C_Y];
+  R[6] = -s_cst[C_T3]; R[7] = s_cst[C_T1]; R[8] = s_cst[C_T2]; t[2] = s_cst[C_Z];
+}
+__device__ __forceinline__ SampledPose sampled_pose_rt(const double *s_cst)
+{
+  SampledPose P{};
+  const auto read = [&](int c) { return uniform_f64(s_cst[c]); };
+  P.cx = read(C_X); P.cyy = read(C_Y); P.cz = read(C_Z);
+  P.r01 = read(C_R01); P.r02 = read(C_R02);
+  P.r11 = read(C_R11); P.r12 = read(C_R12);
+  P.t1 = read(C_T1); P.t2 = read(C_T2); P.t3 = read(C_T3);
+  P.t14 = read(C_T14); P.t15 = read(C_T15);
   return P;
 }
 

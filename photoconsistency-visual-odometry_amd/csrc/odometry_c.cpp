@@ -204,7 +204,9 @@ int phovo_odometry_set_source_frame(phovo_odometry *o, const uint8_t *intensity,
                                     const double *depth, size_t dstride, int width, int height)
 {
   if (!depth) return fail(PHOVO_E_INVALID_ARGUMENT, "SetSourceFrame: depth is required");
-  return odometry_set_frame(o, 0, PHOVO_ROLE_SOURCE, intensity, istride, depth, dstride, width, height);
+  // (the inverse-compositional objective reads the source's gradient planes, which are a target upload's)
+  const int role = o && o->engine->objective == PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL ? PHOVO_ROLE_BOTH : PHOVO_ROLE_SOURCE;
+  return odometry_set_frame(o, 0, role, intensity, istride, depth, dstride, width, height);
 }
 
 int phovo_odometry_set_target_frame(phovo_odometry *o, const uint8_t *intensity, size_t istride,
@@ -227,7 +229,8 @@ int phovo_odometry_set_source_frame_device(phovo_odometry *o, const phovo_device
                                            void *stream)
 {
   if (!depth) return fail(PHOVO_E_INVALID_ARGUMENT, "SetSourceFrameDevice: depth is required");
-  return odometry_set_frame_device(o, 0, PHOVO_ROLE_SOURCE, intensity, depth, depth_scale, width, height, stream);
+  const int role = o && o->engine->objective == PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL ? PHOVO_ROLE_BOTH : PHOVO_ROLE_SOURCE;
+  return odometry_set_frame_device(o, 0, role, intensity, depth, depth_scale, width, height, stream);
 }
 
 int phovo_odometry_set_target_frame_device(phovo_odometry *o, const phovo_device_image *intensity,
@@ -352,8 +355,10 @@ int phovo_odometry_optimize(phovo_odometry *o)
     return fail(PHOVO_E_NOT_READY, "Optimize: SetSourceFrame and SetTargetFrame must be called first");
   // (the affine-illumination objective carries alpha and beta inside an enqueue only: no one-iteration-per-launch form)
   // (the photometric-geometric objective's per-level record belongs to one enqueue: likewise)
+  // (the inverse-compositional objective carries (R, t) inside a level's launch only: likewise)
   if (o->engine->cfg.visualize_iterations && o->engine->objective != PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE &&
-      o->engine->objective != PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC) {
+      o->engine->objective != PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC &&
+      o->engine->objective != PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL) {
     const char *dir = std::getenv("PHOVO_VISUALIZE_DIR");
     if (dir && *dir) return optimize_visualized(o, dir);
   }
@@ -431,6 +436,8 @@ int phovo_odometry_get_trust_region_report(const phovo_odometry *o, phovo_trust_
 int phovo_odometry_get_pair_system(const phovo_odometry *o, phovo_pair_system *out)
 {
   if (!o || !out) return fail(PHOVO_E_INVALID_ARGUMENT, "get_pair_system: null");
+  if (o->engine->objective == PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL)
+    return fail(PHOVO_E_UNSUPPORTED, "get_pair_system: the inverse-compositional objective has no system call yet");
   if (!o->optimized) return fail(PHOVO_E_NOT_READY, "get_pair_system: Optimize has not run since the frames were set");
   const phovo_engine *e = o->engine;
   int finest = -1;                                        // the lowest level Optimize() iterates on
@@ -444,6 +451,8 @@ int phovo_odometry_get_pair_system(const phovo_odometry *o, phovo_pair_system *o
 int phovo_odometry_get_sampled_system(const phovo_odometry *o, phovo_sampled_system *out)
 {
   if (!o || !out) return fail(PHOVO_E_INVALID_ARGUMENT, "get_sampled_system: null");
+  if (o->engine->objective == PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL)
+    return fail(PHOVO_E_UNSUPPORTED, "get_sampled_system: the inverse-compositional objective has no system call yet");
   if (!o->optimized) return fail(PHOVO_E_NOT_READY, "get_sampled_system: Optimize has not run since the frames were set");
   const phovo_engine *e = o->engine;
   int finest = -1;                                        // the lowest level Optimize() iterates on

@@ -228,6 +228,16 @@ struct GNGeometricEvalArgs {
 hipError_t gn_eval_geometric_pairs(const GNGeometricEvalArgs &args, int n_pairs, double *g_part_sampled,
                                    phovo_sampled_system *sampled, double *g_part_depth, phovo_geometric_system *out,
                                    hipStream_t stream);
+// Inverse-compositional form (gn_inverse_kernel.hip, PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL): fp64 planes, the photometric
+// objective's frames; the bilinear extension's rows and residual, the Jacobian from the SOURCE frame's gradient planes (the
+// ones a target upload of the source frame left in the pool), the step composed on SE(3).  No owner map, any level size,
+// 256 threads.
+struct GNInverseArgs {
+  GNLevelArgs lv;                    // (huber_delta and rec_off unused)
+};
+int gn_inverse_wgs_per_cu();         // workgroups of the kernel that stay resident per CU
+int gn_inverse_lds_bytes();
+hipError_t gn_launch_level_inverse(const GNInverseArgs &args, int cu_count, hipStream_t stream);
 // Sliding-window form for levels whose owner map exceeds LDS (gn_slide_kernel.hip): owner ring in LDS; pairs whose
 // motion leaves the window are appended to args.handover_out for a follow-up gn_launch_level that takes that list.
 hipError_t gn_prepare_slide_kernels();

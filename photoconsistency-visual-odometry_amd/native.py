@@ -101,8 +101,9 @@ FUSION_AUTO, FUSION_OFF, FUSION_SPLIT = 0, -1, -2
 OBJECTIVE_PHOTOMETRIC, OBJECTIVE_BIOBJECTIVE, OBJECTIVE_TRUST_REGION = 0, 1, 2
 OBJECTIVE_PHOTOMETRIC_AFFINE = 3
 OBJECTIVE_PHOTOMETRIC_GEOMETRIC = 4
+OBJECTIVE_INVERSE_COMPOSITIONAL = 5
 LAUNCH_KINDS = ("persistent", "fused", "slide", "slide_fallback", "wide", "bilinear", "biobjective", "trust_region",
-                "affine", "geometric")
+                "affine", "geometric", "inverse")
 
 # phovo_trust_region_level.termination
 (TR_SKIPPED, TR_MAX_ITERATIONS, TR_GRADIENT, TR_FUNCTION, TR_PARAMETER, TR_MIN_RADIUS, TR_INVALID_STEP,
@@ -202,6 +203,7 @@ SYMBOLS = {
     "phovo_extensions_default": (C.c_int, [C.POINTER(Extensions)]),
     "phovo_extensions_read_file": (C.c_int, [C.c_char_p, C.POINTER(Extensions)]),
     "phovo_eigen_pose": (C.c_int, [_dp, _dp]),
+    "phovo_state_from_pose": (C.c_int, [_dp, _dp]),
     "phovo_trajectory_chain": (C.c_int, [C.c_int, _vp, _dp, _vp]),
     "phovo_trajectory_format_pose": (C.c_int, [C.c_double, _dp, C.c_char_p, C.c_size_t]),
     "phovo_pair_system_format": (C.c_int, [C.c_double, C.POINTER(PairSystem), C.c_char_p, C.c_size_t]),
@@ -416,6 +418,15 @@ def read_extensions_file(path):
     ext = Extensions()
     check(lib().phovo_extensions_read_file(os.fsencode(path), C.byref(ext)), "phovo_extensions_read_file")
     return ext
+
+
+def state_from_pose(rt):
+    """phovo_state_from_pose: (x, y, z, yaw, pitch, roll) of a 4x4 pose, the inverse of phovo_eigen_pose wherever
+    cos(pitch) != 0 (host arithmetic only)."""
+    m = np.ascontiguousarray(rt, dtype=np.float64).reshape(16)
+    s = np.zeros(6)
+    check(lib().phovo_state_from_pose(m.ctypes.data_as(_dp), s.ctypes.data_as(_dp)), "phovo_state_from_pose")
+    return s
 
 
 def read_config_file(path):

@@ -416,6 +416,17 @@ class CPhotoconsistencyOdometryGeometric(CPhotoconsistencyOdometryAnalytic):
         return gs
 
 
+class CPhotoconsistencyOdometryInverse(CPhotoconsistencyOdometryAnalytic):
+    """One frame pair at a time; not in the reference: the photometric residual aligned inverse-compositionally
+    (native.OBJECTIVE_INVERSE_COMPOSITIONAL: bilinear samples of the target, the Jacobian from the source frame's own
+    gradient, the step composed on SE(3)).  SetSourceFrame also builds the source's gradient planes.  Reads
+    the analytic yml files; extensions and every Get...System() are refused (PHOVO_E_UNSUPPORTED)."""
+
+    def __init__(self, device=0):
+        super().__init__(device)
+        check(self._lib.phovo_odometry_set_objective(self._h, native.OBJECTIVE_INVERSE_COMPOSITIONAL), "SetObjective")
+
+
 # phovo_geometric_report as a numpy record: one row of per-level fields per pair
 GEOMETRIC_REPORT_DTYPE = np.dtype([("depth_rows", "<i4", (native.MAX_LEVELS,)),
                                    ("photometric_cost", "<f8", (native.MAX_LEVELS,)),
