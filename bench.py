@@ -8,8 +8,13 @@ apps/PhotoconsistencyFrameAlignment/PhotoconsistencyFrameAlignment.cpp:99-102).
 Workload (BASELINE.json configs[1]): config_files/config_4_level_optimization_analytic.yml on synthetic
 640x480 RGB-D.  The timed region runs it in FIXED-ITERATION mode (min_gradient_norm = 0, so every pair
 executes exactly max_num_iterations = 50 + 20 iterations: deterministic work, the mode SURVEY.md section 8d
-prescribes for the roofline figure).  The shipped thresholds (data-dependent early stop) are measured too and
-reported under "reference_termination" -- that number is higher, it is not `value`.
+prescribes for the roofline figure).
+
+A plain run does what that figure needs and no more: set-up, warm-up, the timed steps, --dump-outputs, the result line
+(with the per-launch roofline rows, which come from the timed steps' own HIP events).  Every leg that takes runs of its
+own waits behind --full: the shipped thresholds (data-dependent early stop; reported under "reference_termination" --
+that number is higher, it is not `value`), the PCIe-inclusive figure, one pair at a time through the class surface, the
+CPU-oracle baselines and the parity check of the timed poses against the oracle.  Their keys are null in a plain line.
 
 N > 1: one process per GPU (torch.distributed, backend nccl = RCCL); every rank aligns its own contiguous
 shard of the pair list (weak scaling: `--pairs` per GPU) and ONE all_gather per step moves the 6-vector
@@ -61,11 +66,19 @@ def parse():
                          "repeats them, every repeat with its own copy of the planes in HBM).  The fixed-iteration headline "
                          "does not depend on it (profiles/r04_runs/distinct_pairs.txt: 32 ... 4096); with the shipped "
                          "thresholds the iteration counts are data, and 32 pairs are not a sample of them")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="bound of the CPU-oracle baseline sample")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every leg that takes runs of its own: reference_termination (shipped "
+                         "thresholds), end_to_end_pcie_inclusive, single_pair, cpu_baseline, cpu_baseline_all_cores and parity "
+                         "against the CPU oracle (a run over the parity bar exits non-zero).  Off by default: a plain run times "
+                         "the steps and prints the line, with those keys null")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: bound of the CPU-oracle baseline sample")
     ap.add_argument("--cpu-threads", type=int, default=16,
-                    help="threads of the all-cores CPU baseline (a one-GPU box's CPU share); 1 = skip it")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-reference-termination", action="store_true")
+                    help="--full: threads of the all-cores CPU baseline (a one-GPU box's CPU share); 1 = skip it")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full without the CPU-oracle legs (cpu_baseline, cpu_baseline_all_cores, parity)")
+    ap.add_argument("--no-reference-termination", action="store_true",
+                    help="--full without the legs on the shipped thresholds (reference_termination, "
+                         "end_to_end_pcie_inclusive, single_pair)")
     # extensions that are NOT in the reference; the default run (driver's BENCH/SCALE) never sets them
     ap.add_argument("--storage", choices=["f64", "f32", "f16"], default="f64",
                     help="plane storage (f64 = reference-exact; arithmetic is fp64 in every mode)")
@@ -98,6 +111,8 @@ def parse():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if not args.full:          # a plain run has no leg to leave out
+        args.no_cpu_baseline = args.no_reference_termination = True
     return args
 
 
@@ -708,6 +723,7 @@ def main():
             # arithmetic is fp64 in every mode; a narrow plane storage (an extension, never the default) is named too
             "dtype": "f64" if args.storage == "f64" else f"f64 arithmetic on {args.storage} planes",
             "data": "synthetic",
+            "full": bool(args.full),           # False: the legs behind --full did not run and their keys below are null
             "config": {
                 "workload": f"{wl['yml']} on synthetic {W}x{H} RGB-D ({args.scene} scene), "
                             + ("SHIPPED thresholds in the timed region (diagnostic: data-dependent early stop; at most "

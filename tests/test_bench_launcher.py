@@ -76,8 +76,8 @@ def test_two_gloo_ranks_share_the_gpu_and_print_one_contract_line():
     ranks on one device): the parent starts both ranks, each aligns its own shard on the shared card, one all_gather per
     step, rank 0 prints ONE JSON line with the driver's contract keys; value = pairs of both ranks / slowest rank's time."""
     import json
-    r = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--pairs", "256", "--distinct", "8", "--no-cpu-baseline"],
-             {"PHOVO_BENCH_BACKEND": "gloo"})
+    r = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--pairs", "256", "--distinct", "8", "--full",
+              "--no-cpu-baseline"], {"PHOVO_BENCH_BACKEND": "gloo"})       # --full: the shipped-threshold leg across two ranks
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -88,6 +88,7 @@ def test_two_gloo_ranks_share_the_gpu_and_print_one_contract_line():
     assert d["n_gpus"] == 2 and d["steps"] == 2 and d["warmup"] == 1 and d["scaling"] == "weak" and d["dtype"] == "f64"
     assert d["config"]["pairs_per_gpu"] == 256 and d["config"]["global_pairs_per_step"] == 512
     assert d["value"] > 0 and d["nonfinite_pairs"] == 0 and d["cpu_baseline"] is None
+    assert d["full"] is True and d["reference_termination"]["value"] > 0
     assert abs(d["value"] - 512 * 2 / (d["ms_per_step"] * 2e-3)) < 1e-6 * d["value"]
     assert "rank 0/2 joined the gloo group" in r.stderr and "rank 1/2 joined the gloo group" in r.stderr
 
@@ -160,3 +161,84 @@ def test_dump_outputs_hold_the_last_timed_step_and_repeat_exactly(tmp_path):
     assert states.shape == (256, 6) and np.all(np.isfinite(states)) and np.any(states != 0)
     its = np.load(tmp_path / "a" / "iterations.npy")
     np.testing.assert_array_equal(its.mean(axis=0), lines[0]["iterations_per_pair"])
+
+
+# what a plain run leaves null and `--full` fills: every leg that takes runs of its own after the timed steps
+LEGS_BEHIND_FULL = ("reference_termination", "end_to_end_pcie_inclusive", "single_pair", "cpu_baseline",
+                    "cpu_baseline_all_cores", "parity")
+
+
+def test_full_is_an_option_off_by_default_and_a_plain_run_has_no_leg_to_leave_out(monkeypatch):
+    """parse(): without --full every leg after the timed steps is off, whatever the --no-... options say (scripts that pass
+    them keep working); with --full they run unless one of those options takes its group out."""
+    import bench
+    for argv, full, no_cpu, no_ref in (
+            ([], False, True, True),
+            (["--gpus", "1", "--steps", "5", "--warmup", "2"], False, True, True),
+            (["--no-cpu-baseline"], False, True, True),
+            (["--full"], True, False, False),
+            (["--full", "--no-cpu-baseline"], True, True, False),
+            (["--full", "--no-reference-termination"], True, False, True)):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+        a = bench.parse()
+        assert (a.full, a.no_cpu_baseline, a.no_reference_termination) == (full, no_cpu, no_ref), argv
+    r = _run(["--help"])
+    assert r.returncode == 0 and "--full" in r.stdout
+
+
+def test_every_leg_behind_full_is_guarded_by_one_of_the_two_switches():
+    """Structure check: main() imports the oracle, and calls its optimize(), the class surface's Optimize() or an
+    enqueue_align() of its own (the timed steps enqueue inside run_steps()), only under an `if` whose test reads
+    args.no_cpu_baseline or args.no_reference_termination (directly, or through `cpu`, which is set under such an `if`)."""
+    src = open(BENCH).read()
+    main = next(n for n in ast.parse(src).body if isinstance(n, ast.FunctionDef) and n.name == "main")
+    guards = ("no_cpu_baseline", "no_reference_termination", "cpu is not None")
+
+    def guarded(node, under):
+        if isinstance(node, ast.If):
+            test = ast.get_source_segment(src, node.test)
+            inner = under or any(g in test for g in guards)
+            return [x for c in node.body for x in guarded(c, inner)] + [x for c in node.orelse for x in guarded(c, under)]
+        found = []
+        if not under:
+            for n in ast.walk(node):
+                if isinstance(n, ast.ImportFrom) and n.module == "oracle":
+                    found.append(("import oracle", n.lineno))
+                if isinstance(n, ast.Call) and getattr(n.func, "attr", "") in ("Optimize", "enqueue_align", "optimize"):
+                    found.append((n.func.attr, n.lineno))
+        if not isinstance(node, (ast.FunctionDef, ast.If)):
+            return found
+        return found + [x for c in ast.iter_child_nodes(node) for x in guarded(c, under)]
+
+    loose = [x for stmt in main.body for x in guarded(stmt, False)]
+    assert loose == [], loose
+
+
+@pytest.mark.gpu
+def test_a_plain_run_skips_every_leg_that_full_runs_and_times_the_same_steps():
+    """The same small workload plain and with --full: the plain line carries null for every leg behind --full and says
+    full = false; the --full line fills them all, its parity against the CPU oracle holds, and the contract fields both
+    lines share (metric, unit, dtype, steps, iteration counts, launches of a timed step) are equal."""
+    import json
+    args = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--pairs", "256", "--distinct", "8"]
+    lines = {}
+    for name, extra in (("plain", []), ("full", ["--full", "--cpu-seconds", "0.5", "--cpu-threads", "2"])):
+        r = _run(args + extra)
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(out) == 1, r.stdout[-2000:]
+        lines[name] = json.loads(out[0])
+    plain, full = lines["plain"], lines["full"]
+    assert plain["full"] is False and full["full"] is True
+    for key in LEGS_BEHIND_FULL:
+        assert key in plain and plain[key] is None, key
+        assert full[key] is not None, key
+    assert full["parity"]["ok"] and full["parity"]["checked"] >= 1
+    assert full["cpu_baseline"]["value"] > 0 and full["cpu_baseline_all_cores"]["cores"] == 2
+    assert full["reference_termination"]["value"] > 0 and full["end_to_end_pcie_inclusive"]["value"] > 0
+    for key in ("metric", "unit", "higher_is_better", "dtype", "n_gpus", "steps", "warmup", "scaling", "config",
+                "iterations_per_pair", "nonfinite_pairs", "launches", "pipelined"):
+        assert plain[key] == full[key], key
+    for d in (plain, full):
+        assert d["value"] > 0 and abs(d["value"] - 256 * 2 / (d["ms_per_step"] * 2e-3)) < 1e-6 * d["value"]
+        assert d["roofline"]["step_wall_ms"]["steps"] == 2

@@ -7,8 +7,8 @@ O=$1; SW=${2:?switch}; shift 2
 L=$(realpath photoconsistency-visual-odometry_amd/csrc/build_tuning/libphovo_hip_tuning.so)
 mkdir -p $O
 for rep in 1 2; do
-  timeout -k 10 300 python3 tools/bench_with.py $L --no-cpu-baseline "$@" > $O/off.$rep.json 2> $O/off.$rep.err
+  timeout -k 10 300 python3 tools/bench_with.py $L --full --no-cpu-baseline "$@" > $O/off.$rep.json 2> $O/off.$rep.err
   python3 tools/benchsum.py $O/off.$rep.json off.$rep || tail -3 $O/off.$rep.err
-  env $SW=1 timeout -k 10 300 python3 tools/bench_with.py $L --no-cpu-baseline "$@" > $O/on.$rep.json 2> $O/on.$rep.err
+  env $SW=1 timeout -k 10 300 python3 tools/bench_with.py $L --full --no-cpu-baseline "$@" > $O/on.$rep.json 2> $O/on.$rep.err
   python3 tools/benchsum.py $O/on.$rep.json on.$rep || tail -3 $O/on.$rep.err
 done

@@ -24,7 +24,7 @@ if [ "$1" = "--parse" ]; then
 fi
 O=$1
 mkdir -p $O
-bench() { name=$1; shift; timeout -k 10 300 python3 bench.py "$@" > $O/bench_$name.json 2> $O/bench_$name.err || { tail -5 $O/bench_$name.err; exit 1; }; python3 tools/benchsum.py $O/bench_$name.json $name; }
+bench() { name=$1; shift; timeout -k 10 300 python3 bench.py --full "$@" > $O/bench_$name.json 2> $O/bench_$name.err || { tail -5 $O/bench_$name.err; exit 1; }; python3 tools/benchsum.py $O/bench_$name.json $name; }
 if [ "$2" = "a" ]; then
   bench default --cpu-seconds 8
   bash tools/profile_round.sh $O/prof_full || exit 1

@@ -15,5 +15,5 @@ for rep in 1 2; do
     bench.py --gpus 1 --steps 20 --warmup 5 --distinct 32 --no-cpu-baseline --no-reference-termination > $O/bench_nccl1.$rep.json 2> $O/bench_nccl1.$rep.err
   echo "nccl1.$rep rc=$?"; python3 tools/benchsum.py $O/bench_nccl1.$rep.json nccl1.$rep || tail -5 $O/bench_nccl1.$rep.err
 done
-PHOVO_BENCH_BACKEND=gloo timeout -k 10 500 python3 bench.py --gpus 5 --steps 5 --warmup 1 --pairs 1024 --distinct 32 --no-cpu-baseline > $O/bench_gloo5.json 2> $O/bench_gloo5.err
+PHOVO_BENCH_BACKEND=gloo timeout -k 10 500 python3 bench.py --gpus 5 --steps 5 --warmup 1 --pairs 1024 --distinct 32 --full --no-cpu-baseline > $O/bench_gloo5.json 2> $O/bench_gloo5.err
 echo "gloo5 rc=$?"; python3 tools/benchsum.py $O/bench_gloo5.json gloo5 || tail -5 $O/bench_gloo5.err
