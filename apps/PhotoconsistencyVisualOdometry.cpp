@@ -3,7 +3,7 @@
 //
 //   ./PhotoconsistencyVisualOdometry <config_file.yml> <rgbd_dataset_directory> <output_trajectory_file> [--batch [--gpus N] [--rccl]]
 //                                    [--method analytic|ceres|biobjective|inverse|affine|geometric] [--information <file>] [--system <file>]
-//                                    [--geometric-system <file>] [--objective-system <file>]
+//                                    [--geometric-system <file>] [--objective-system <file>] [--inverse-system <file>]
 // --method picks the aligner as the reference's USE_PHOTOCONSISTENCY_ODOMETRY_METHOD does (0 = analytic, the default;
 // 1 = ceres: Levenberg-Marquardt on bilinear samples, CPhotoconsistencyOdometryCeres, which reads config_*_ceres.yml
 // files; 2 = bi-objective: photometric and depth error together, CPhotoconsistencyOdometryBiObjective), in every mode;
@@ -13,7 +13,7 @@
 // CPhotoconsistencyOdometryGeometric, which reads the analytic files and their optional depth_weight / max_depth_residual keys.
 // inverse is not in the reference either: the photometric residual aligned inverse-compositionally (the Jacobian from the
 // source frame's own gradient, the step composed on SE(3)), CPhotoconsistencyOdometryInverse, which reads the analytic files;
-// it has no system call yet, so the four system flags below refuse it.
+// its system is in the twist basis, so the four Euler-basis system flags below refuse it and --inverse-system writes it.
 // A configuration file of the other kind is refused with a message that says so.
 // --information <file> (not in the reference; analytic method, one device): one line per pair, stamped like its trajectory
 // line, with the Gauss-Newton system at the pair's optimal state on the finest level the configuration optimises --
@@ -37,6 +37,13 @@
 // (phovo_pair_system_format) at the pair's optimal state on the finest optimised level; under ceres cost is r^T r, twice
 // the solver's final cost.  The loop takes it from the class surface (GetObjectiveSystem), --batch from
 // phovo_engine_evaluate_objective_pairs; both write the same bytes, the trajectory file is the same with and without the
+// flag, and the printed times do not include the evaluation.
+// --inverse-system <file> (not in the reference; --method inverse, one device): the same for the inverse-compositional
+// method -- one line per pair, `timestamp rows cost` and the 21 upper-triangle entries of sum J J^T
+// (phovo_pair_system_format) at the pair's optimal state on the finest optimised level, in the TWIST basis (nu, omega) of
+// the right-hand perturbation T Exp(xi): xi lives in the source camera's frame (include/phovo_hip.h,
+// phovo_engine_evaluate_inverse_pairs).  The loop takes it from the class surface (GetInverseSystem), --batch from
+// phovo_engine_evaluate_inverse_pairs; both write the same bytes, the trajectory file is the same with and without the
 // flag, and the printed times do not include the evaluation.
 //
 // Behaviour kept from the reference's app (apps/PhotoconsistencyVisualOdometry/PhotoconsistencyVisualOdometry.cpp):
@@ -191,11 +198,24 @@ static phovo_pair_system objectiveSystemOf(Odometry &, long)
   throw std::runtime_error("--objective-system needs --method ceres or --method biobjective");
 }
 
+// GetInverseSystem() of the class that has one, in the same way.
+template <class Odometry>
+static auto inverseSystemOf(Odometry &odometry, int) -> decltype(odometry.GetInverseSystem())
+{
+  return odometry.GetInverseSystem();
+}
+template <class Odometry>
+static phovo_pair_system inverseSystemOf(Odometry &, long)
+{
+  throw std::runtime_error("--inverse-system needs --method inverse");
+}
+
 static void printHelp()
 {
   std::cout << "./PhotoconsistencyVisualOdometry <config_file.yml> <rgbd_dataset_directory> "
                "<output_trajectory_file> [--batch [--gpus N] [--rccl]] [--method analytic|ceres|biobjective|inverse|affine|geometric] "
-               "[--information <file>] [--system <file>] [--geometric-system <file>] [--objective-system <file>]" << std::endl;
+               "[--information <file>] [--system <file>] [--geometric-system <file>] [--objective-system <file>] "
+               "[--inverse-system <file>]" << std::endl;
 }
 
 #define PHOVO_OK_OR_FAIL(call)                                                              \
@@ -213,6 +233,7 @@ int main(int argc, char *argv[])
   std::string systemPath;                             // --system <file>: the same for the sampled aligners
   std::string geometricSystemPath;                    // --geometric-system <file>: the same for --method geometric
   std::string objectiveSystemPath;                    // --objective-system <file>: the same for --method ceres | biobjective
+  std::string inverseSystemPath;                      // --inverse-system <file>: the same for --method inverse (twist basis)
   for (int i = 4; i < argc; i++) {
     const std::string a(argv[i]);
     if (a == "--batch") batch = true;
@@ -232,6 +253,7 @@ int main(int argc, char *argv[])
     else if (a == "--system" && i + 1 < argc) systemPath = argv[++i];
     else if (a == "--geometric-system" && i + 1 < argc) geometricSystemPath = argv[++i];
     else if (a == "--objective-system" && i + 1 < argc) objectiveSystemPath = argv[++i];
+    else if (a == "--inverse-system" && i + 1 < argc) inverseSystemPath = argv[++i];
     else { printHelp(); return EXIT_FAILURE; }
   }
   if (nGpus < 1 || (nGpus > 1 && !batch)) { std::cerr << "--gpus N needs --batch and N >= 1" << std::endl; return EXIT_FAILURE; }
@@ -271,6 +293,15 @@ int main(int argc, char *argv[])
   }
   if (objectiveSystem && objective != PHOVO_OBJECTIVE_TRUST_REGION && objective != PHOVO_OBJECTIVE_BIOBJECTIVE) {
     std::cerr << "--objective-system needs --method ceres or --method biobjective" << std::endl;
+    return EXIT_FAILURE;
+  }
+  const bool inverseSystem = !inverseSystemPath.empty();
+  if (inverseSystem && (nGpus > 1 || rccl)) {
+    std::cerr << "--inverse-system runs on one device: it cannot be combined with --gpus N > 1 or --rccl" << std::endl;
+    return EXIT_FAILURE;
+  }
+  if (inverseSystem && objective != PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL) {
+    std::cerr << "--inverse-system needs --method inverse" << std::endl;
     return EXIT_FAILURE;
   }
   if (!fileExists(configFile)) { std::cerr << "Input config file " << configFile << " does not exist" << std::endl; return EXIT_FAILURE; }
@@ -338,6 +369,11 @@ int main(int argc, char *argv[])
     objectiveSystemFile.open(objectiveSystemPath.c_str());
     if (!objectiveSystemFile.is_open()) { std::cerr << "Cannot open output objective system file " << objectiveSystemPath << std::endl; return EXIT_FAILURE; }
   }
+  std::ofstream inverseSystemFile;
+  if (inverseSystem) {
+    inverseSystemFile.open(inverseSystemPath.c_str());
+    if (!inverseSystemFile.is_open()) { std::cerr << "Cannot open output inverse system file " << inverseSystemPath << std::endl; return EXIT_FAILURE; }
+  }
   if (nFrames < 2) return EXIT_SUCCESS;
 
   Matrix44Type pose = Matrix44Type::Identity();
@@ -373,6 +409,7 @@ int main(int argc, char *argv[])
         if (sampled && !writeSystem(systemFile, rgb[t].timestamp, odometry.GetSampledSystem())) return EXIT_FAILURE;
         if (geometricSystem && !writeSystem(geometricSystemFile, rgb[t].timestamp, geometricSystemOf(odometry, 0))) return EXIT_FAILURE;
         if (objectiveSystem && !writeSystem(objectiveSystemFile, rgb[t].timestamp, objectiveSystemOf(odometry, 0))) return EXIT_FAILURE;
+        if (inverseSystem && !writeSystem(inverseSystemFile, rgb[t].timestamp, inverseSystemOf(odometry, 0))) return EXIT_FAILURE;
         std::cout << "Rt:" << std::endl << Rt << std::endl;
         prevGray = curGray.clone();
         prevDepth = curDepth.clone();
@@ -479,6 +516,8 @@ int main(int argc, char *argv[])
       if (sampled && finestLevel < 0) { std::cerr << "--system: the configuration optimises no level" << std::endl; return EXIT_FAILURE; }
       if (geometricSystem && finestLevel < 0) { std::cerr << "--geometric-system: the configuration optimises no level" << std::endl; return EXIT_FAILURE; }
       if (objectiveSystem && finestLevel < 0) { std::cerr << "--objective-system: the configuration optimises no level" << std::endl; return EXIT_FAILURE; }
+      if (inverseSystem && finestLevel < 0) { std::cerr << "--inverse-system: the configuration optimises no level" << std::endl; return EXIT_FAILURE; }
+      std::vector<phovo_pair_system> inverseSystems(inverseSystem ? (size_t)nPairs : 0);
       std::vector<phovo_pair_system> objectiveSystems(objectiveSystem ? (size_t)nPairs : 0);
       std::vector<phovo_geometric_system> geometricSystems(geometricSystem ? (size_t)nPairs : 0);
       const int systemDim = objective == PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE ? 8 : 6;
@@ -535,7 +574,11 @@ int main(int argc, char *argv[])
           if (!rccl) {
             if (phovo_engine_align_pairs(engine, b - a, src.data(), tgt.data(), nullptr, states.data() + (size_t)a * 6, nullptr) != PHOVO_OK)
               return fail("phovo_engine_align_pairs");
-            if (information || sampled || geometricSystem || objectiveSystem) tAligned = std::chrono::steady_clock::now();      // (the evaluation is not part of the timed run)
+            if (information || sampled || geometricSystem || objectiveSystem || inverseSystem)
+              tAligned = std::chrono::steady_clock::now();                    // (the evaluation is not part of the timed run)
+            if (inverseSystem && phovo_engine_evaluate_inverse_pairs(engine, b - a, src.data(), tgt.data(), states.data() + (size_t)a * 6,
+                                                                     finestLevel, inverseSystems.data() + a) != PHOVO_OK)
+              return fail("phovo_engine_evaluate_inverse_pairs");
             if (objectiveSystem && phovo_engine_evaluate_objective_pairs(engine, b - a, src.data(), tgt.data(), states.data() + (size_t)a * 6,
                                                                          finestLevel, objectiveSystems.data() + a) != PHOVO_OK)
               return fail("phovo_engine_evaluate_objective_pairs");
@@ -591,7 +634,7 @@ int main(int argc, char *argv[])
           std::copy(group.gathered(g), group.gathered(g) + (size_t)(b - a) * 6, states.begin() + (size_t)a * 6);
         }
       }
-      const auto t1 = (information || sampled || geometricSystem || objectiveSystem) ? tAligned : std::chrono::steady_clock::now();
+      const auto t1 = (information || sampled || geometricSystem || objectiveSystem || inverseSystem) ? tAligned : std::chrono::steady_clock::now();
       std::cout << "Time = " << std::chrono::duration<double>(t1 - t0).count() << " sec. (" << nPairs << " pairs on " << nGpus
                 << " device(s), upload and pyramids included)" << std::endl;
       std::vector<double> poses((size_t)nPairs * 16);
@@ -604,6 +647,7 @@ int main(int argc, char *argv[])
         if (sampled && !writeSystem(systemFile, rgb[(size_t)p + 1].timestamp, sampledSystems[(size_t)p])) return EXIT_FAILURE;
         if (geometricSystem && !writeSystem(geometricSystemFile, rgb[(size_t)p + 1].timestamp, geometricSystems[(size_t)p])) return EXIT_FAILURE;
         if (objectiveSystem && !writeSystem(objectiveSystemFile, rgb[(size_t)p + 1].timestamp, objectiveSystems[(size_t)p])) return EXIT_FAILURE;
+        if (inverseSystem && !writeSystem(inverseSystemFile, rgb[(size_t)p + 1].timestamp, inverseSystems[(size_t)p])) return EXIT_FAILURE;
       }
     }
   } catch (const std::exception &e) {
@@ -615,5 +659,6 @@ int main(int argc, char *argv[])
   if (sampled) systemFile.close();
   if (geometricSystem) geometricSystemFile.close();
   if (objectiveSystem) objectiveSystemFile.close();
+  if (inverseSystem) inverseSystemFile.close();
   return EXIT_SUCCESS;
 }

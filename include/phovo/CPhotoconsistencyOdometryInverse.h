@@ -9,7 +9,8 @@
 // The types come from the same place as CPhotoconsistencyOdometryAnalytic.h's (PHOVO_HIP_USE_REFERENCE_TYPES or
 // phovo/compat/).  ReadConfigurationFile reads the config_*_analytic.yml keys.  SetSourceFrame also builds the source's
 // gradient planes.  Extensions are refused (std::runtime_error, PHOVO_E_UNSUPPORTED), and so are the inherited
-// GetPairSystem() and GetSampledSystem(): this objective's twist-basis system has no call yet.
+// GetPairSystem() and GetSampledSystem(), which speak the Euler basis; this objective's system is GetInverseSystem(), in
+// the twist basis.
 #ifndef PHOVO_HIP_CPHOTOCONSISTENCY_ODOMETRY_INVERSE_H
 #define PHOVO_HIP_CPHOTOCONSISTENCY_ODOMETRY_INVERSE_H
 
@@ -33,6 +34,17 @@ class CPhotoconsistencyOdometryInverse : public CPhotoconsistencyOdometryAnalyti
   explicit CPhotoconsistencyOdometryInverse(int device = 0) : Base(device)
   {
     Base::Check(phovo_odometry_set_objective(Base::Handle(), PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL), "CPhotoconsistencyOdometryInverse()");
+  }
+
+  // sum J J^T, sum J r, sum r^2 and the row count at the optimal state on the finest level the configuration optimises, in
+  // the twist basis (nu, omega) of the right-hand perturbation T Exp(xi): xi lives in the SOURCE camera's frame, and
+  // information^-1 * cost / (rows - 6) is its covariance (a caller who perturbs on the left applies Ad_T).  Evaluated on
+  // demand; std::runtime_error (PHOVO_E_NOT_READY) before Optimize() and after a Set*Frame since.
+  phovo_pair_system GetInverseSystem() const
+  {
+    phovo_pair_system s;
+    Base::Check(phovo_odometry_get_inverse_system(Base::Handle(), &s), "GetInverseSystem");
+    return s;
   }
 };
 

@@ -284,9 +284,10 @@ typedef struct phovo_extensions {
  *                                role on an active level is PHOVO_E_NOT_READY.  No new planes: switching between objectives
  *                                0, 2, 3, 4 and 5 keeps the frame pool.  Supported: fp64 planes, the default sampling
  *                                setting, no Huber weights, jacobian_corrected 0 -- anything else is PHOVO_E_UNSUPPORTED,
- *                                whichever setter comes second.  All four phovo_engine_evaluate_* calls and the
- *                                phovo_odometry_get_*_system calls are PHOVO_E_UNSUPPORTED under this objective (its
- *                                twist-basis system is not built yet).  Fusion, sliding-window, wide, latency-form and
+ *                                whichever setter comes second.  Its system, in the twist basis, is
+ *                                phovo_engine_evaluate_inverse_pairs / phovo_odometry_get_inverse_system; the four other
+ *                                phovo_engine_evaluate_* calls and phovo_odometry_get_*_system calls, which speak the
+ *                                Euler basis, stay PHOVO_E_UNSUPPORTED under this objective.  Fusion, sliding-window, wide, latency-form and
  *                                batch-invariant settings are accepted and have no effect.
  *                                phovo_pair_report keeps its meaning: iterations[L], valid_pixels[L] = rows of the level's
  *                                last system, gradient_norm = ||g||_2 of the last system, PHOVO_PAIR_RANK_DEFICIENT
@@ -532,6 +533,11 @@ int phovo_odometry_get_geometric_system(const phovo_odometry *o, phovo_geometric
  * (phovo_engine_evaluate_objective_pairs).  PHOVO_E_UNSUPPORTED under any other objective; PHOVO_E_NOT_READY before a
  * successful Optimize() and after a Set*Frame since. */
 int phovo_odometry_get_objective_system(const phovo_odometry *o, phovo_pair_system *out);
+/* not in the reference: the twist-basis system (phovo_pair_system) of the inverse-compositional objective at the optimal
+ * state on the finest level the configuration optimises, evaluated on demand (phovo_engine_evaluate_inverse_pairs has the
+ * contract: a right-hand twist in the source camera's frame).  PHOVO_E_UNSUPPORTED under any other objective;
+ * PHOVO_E_NOT_READY before a successful Optimize() and after a Set*Frame since. */
+int phovo_odometry_get_inverse_system(const phovo_odometry *o, phovo_pair_system *out);
 /* Device time of the last Optimize() in milliseconds (HIP events; the reference wraps the same
  * call in cv::TickMeter, apps/PhotoconsistencyFrameAlignment/PhotoconsistencyFrameAlignment.cpp:99-102). */
 int phovo_odometry_last_optimize_ms(const phovo_odometry *o, double *ms);
@@ -857,7 +863,39 @@ int phovo_engine_evaluate_geometric_pairs(phovo_engine *e, int n_pairs, const in
 int phovo_engine_evaluate_objective_pairs(phovo_engine *e, int n_pairs, const int *src, const int *tgt,
                                           const double *states /* [n_pairs][6] */, int level, phovo_pair_system *out);
 
-/* Pipelining.  Pairs are independent, and with data-dependent termination a batch ends with a few long pairs on an
+/* The system (phovo_pair_system) of PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL in the TWIST basis, at the states [n_pairs][6]
+ * on one level.  Synchronous; ordered behind every enqueue in flight, and it changes nothing that
+ * phovo_engine_fetch / fetch_results return.
+ *   pose      (R, t) = eigenPose(state): the state is the Euler state every other call takes and phovo_engine_fetch
+ *             returns, and (R, t) is the matrix a level of the aligner starts from.
+ *   rows      the aligner's (the objective's comment above): every source pixel in raster order with
+ *             min_depth < D0 < max_depth (NaN fails), P' = R p + t, in bounds iff -0.5 < u < W - 0.5 and
+ *             -0.5 < v < H - 0.5, I1(u, v) bilinear on four clamped taps, r = I1(u, v) - I0.
+ *   J         (a, p x a) with a = (GX0 fx / pz, GY0 fy / pz, -(a_0 px + a_1 py) / pz) from the source frame's stored
+ *             gradient planes; column order (nu_x, nu_y, nu_z, omega_x, omega_y, omega_z).
+ *   record    information = sum J J^T (exactly symmetric, filled from the upper triangle), gradient = sum J r,
+ *             cost = sum r^2 over the rows, rows = the count phovo_pair_report.valid_pixels uses; flags:
+ *             PHOVO_PAIR_RANK_DEFICIENT if rows < 6, PHOVO_PAIR_NONFINITE if any sum is inf or NaN.  No weights: the
+ *             objective has no Huber.
+ * Perturbation: the system is that of T(xi) = T Exp(xi), where T = (R, t) takes points of the source camera into the
+ * target camera: xi is a RIGHT-hand twist, expressed in the SOURCE camera's frame.  information^-1 * cost / (rows - 6)
+ * is the covariance of that right-hand twist; a caller who perturbs on the left (Exp(xi') T) applies Ad_T on their
+ * side (xi' = Ad_T xi).  No Euler-basis record of the other calls converts into this one without loss.
+ * Relation to the aligner: the system the aligner solves in the FIRST iteration of a level is this system at the state the
+ * level starts from, up to summation order; later iterations run on an (R, t) that no state holds exactly.
+ * Sums are taken in an order that depends on the level size only: a pair's record is the same bit for bit whatever the
+ * batch, its position in it, the group split, or any setting of the engine.
+ *   PHOVO_E_UNSUPPORTED       any objective but PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL
+ *   PHOVO_E_INVALID_ARGUMENT  as phovo_engine_evaluate_sampled_pairs (there is no state_dim)
+ *   PHOVO_E_NOT_READY         as phovo_engine_evaluate_sampled_pairs; also when a SOURCE frame lacks PHOVO_ROLE_TARGET on
+ *                             that level (its gradient planes are a target upload's: the enqueue's rule)
+ * n_pairs == 0 is OK.  Device memory: the evaluate workspace (shared with the other evaluate calls, kept until the engine
+ * is destroyed) -- per pair of a group 256 bytes of tile sums per 1024 pixels; large batches run in groups whose tile
+ * sums take at most 64 MB (873 pairs at 640x480). */
+int phovo_engine_evaluate_inverse_pairs(phovo_engine *e, int n_pairs, const int *src, const int *tgt,
+                                        const double *states /* [n_pairs][6] */, int level, phovo_pair_system *out);
+
+/* Pipelining. Pairs are independent, and with data-dependent termination a batch ends with a few long pairs on an
  * otherwise idle chip.  The engine therefore keeps PHOVO_ENQUEUE_DEPTH enqueues in flight, each with its own stream, pair
  * buffers and pinned mirrors: phovo_engine_enqueue_align returns at once, and the kernels of enqueue k + 1 fill the CUs
  * that the tail of enqueue k leaves free.  Every enqueue gets a ticket (1, 2, ...; phovo_engine_last_ticket right after the

@@ -1,5 +1,5 @@
 // The Gauss-Newton systems at given poses behind the C ABI (include/phovo_hip.h): phovo_engine_evaluate_pairs,
-// _evaluate_sampled_pairs, _evaluate_geometric_pairs and _evaluate_objective_pairs.  Each entry point keeps what is its own -- the objectives and
+// _evaluate_sampled_pairs, _evaluate_geometric_pairs, _evaluate_objective_pairs and _evaluate_inverse_pairs.  Each entry point keeps what is its own -- the objectives and
 // samplings it refuses, its state width, its workspace regions, the extras of its args and its launch -- and shares the
 // rest: the refusals about the call, the one workspace, and the loop over groups of pairs.
 
@@ -14,7 +14,8 @@ namespace {
 
 // Owner maps of one evaluation group take at most this much: 218 pairs at 640x480.
 constexpr size_t EVAL_OWNER_CAP_BYTES = (size_t)256 << 20;
-// Tile sums of one sampled-evaluation group take at most this much: 436 pairs of eight columns (873 of six) at 640x480.
+// Tile sums of one sampled-evaluation group take at most this much: 436 pairs of eight columns (873 of six, and of the
+// inverse-compositional call) at 640x480.
 constexpr size_t EVAL_SAMPLED_SLAB_CAP_BYTES = (size_t)64 << 20;
 // Tile sums of one geometric-evaluation group (the sampled and the depth slab together) take at most this much: 436 pairs
 // at 640x480.
@@ -39,8 +40,10 @@ struct EvalCall {                    // an entry point's name in its refusals, a
 
 // Everything the entry points refuse alike, behind their own refusals of objectives and samplings.  A call of no pairs is
 // valid once its arguments are: it returns PHOVO_OK before the pool is looked at.  `target_depth`: the launch reads the
-// target's depth plane too.  On PHOVO_OK with pairs, every enqueue in flight has finished (their slots are not touched).
-int eval_check(phovo_engine *e, const EvalCall &c, bool target_depth)
+// target's depth plane too.  `source_gradients`: it reads the source's gradient planes too (engine_align.cpp's rule for the
+// inverse-compositional objective).  On PHOVO_OK with pairs, every enqueue in flight has finished (their slots are not
+// touched).
+int eval_check(phovo_engine *e, const EvalCall &c, bool target_depth, bool source_gradients = false)
 {
   const std::string who = c.name;
   if (c.n_pairs < 0) return fail(PHOVO_E_INVALID_ARGUMENT, who + ": n_pairs < 0");
@@ -62,6 +65,9 @@ int eval_check(phovo_engine *e, const EvalCall &c, bool target_depth)
     if (target_depth && !(e->frame_roles[(size_t)c.tgt[i] * PHOVO_MAX_LEVELS + (size_t)c.level] & PHOVO_ROLE_SOURCE))
       return fail(PHOVO_E_NOT_READY, who + ": the photometric-geometric objective reads the target's depth "
                                            "(upload target frames with PHOVO_ROLE_BOTH)");
+    if (source_gradients && !(e->frame_roles[(size_t)c.src[i] * PHOVO_MAX_LEVELS + (size_t)c.level] & PHOVO_ROLE_TARGET))
+      return fail(PHOVO_E_NOT_READY, who + ": the inverse-compositional objective reads the source's gradient planes "
+                                           "(upload source frames with PHOVO_ROLE_BOTH)");
   }
   PHOVO_HIP_CHECK(hipSetDevice(e->device));
   PHOVO_HIP_CHECK(quiesce(e));                 // behind every enqueue in flight; their slots are not touched
@@ -129,7 +135,8 @@ int phovo_engine_evaluate_pairs(phovo_engine *e, int n_pairs, const int *src, co
   if (!e) return fail(PHOVO_E_INVALID_ARGUMENT, "evaluate_pairs: null engine");
   if (e->objective != PHOVO_OBJECTIVE_PHOTOMETRIC)
     return fail(PHOVO_E_UNSUPPORTED, "evaluate_pairs: the bi-objective, the trust-region and the affine-illumination objective "
-                                     "have no pair system here (photometric objective only)");
+                                     "have no pair system here (photometric objective only; the inverse-compositional "
+                                     "objective has phovo_engine_evaluate_inverse_pairs)");
   if (e->ext.sampling != PHOVO_SAMPLING_NEAREST_SCATTER)
     return fail(PHOVO_E_UNSUPPORTED, "evaluate_pairs: bilinear sampling has no pair system here (nearest / scatter only)");
   const EvalCall c{"evaluate_pairs", n_pairs, src, tgt, states, 6, level, out, sizeof(*out)};
@@ -173,7 +180,8 @@ int phovo_engine_evaluate_sampled_pairs(phovo_engine *e, int n_pairs, const int 
   if (e->objective == PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC)
     return fail(PHOVO_E_UNSUPPORTED, "evaluate_sampled_pairs: the photometric-geometric objective has no sampled system");
   if (e->objective == PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL)
-    return fail(PHOVO_E_UNSUPPORTED, "evaluate_sampled_pairs: the inverse-compositional objective has no system call yet");
+    return fail(PHOVO_E_UNSUPPORTED, "evaluate_sampled_pairs: the inverse-compositional objective has its system in "
+                                     "phovo_engine_evaluate_inverse_pairs");
   const bool affine = e->objective == PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE;
   if (!affine && e->ext.sampling != PHOVO_SAMPLING_BILINEAR)
     return fail(PHOVO_E_UNSUPPORTED, "evaluate_sampled_pairs: nearest / scatter sampling has its system in "
@@ -213,7 +221,8 @@ int phovo_engine_evaluate_geometric_pairs(phovo_engine *e, int n_pairs, const in
 {
   if (!e) return fail(PHOVO_E_INVALID_ARGUMENT, "evaluate_geometric_pairs: null engine");
   if (e->objective != PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC)
-    return fail(PHOVO_E_UNSUPPORTED, "evaluate_geometric_pairs: the photometric-geometric objective only");
+    return fail(PHOVO_E_UNSUPPORTED, "evaluate_geometric_pairs: the photometric-geometric objective only (the "
+                                     "inverse-compositional objective has phovo_engine_evaluate_inverse_pairs)");
   // (set_objective / set_extensions hold this objective to fp64 planes without Huber weights)
   const EvalCall c{"evaluate_geometric_pairs", n_pairs, src, tgt, states, 6, level, out, sizeof(*out)};
   int st = eval_check(e, c, true);
@@ -261,7 +270,8 @@ int phovo_engine_evaluate_objective_pairs(phovo_engine *e, int n_pairs, const in
       return fail(PHOVO_E_UNSUPPORTED, "evaluate_objective_pairs: the affine-illumination objective has its system in "
                                        "phovo_engine_evaluate_sampled_pairs");
     case PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL:
-      return fail(PHOVO_E_UNSUPPORTED, "evaluate_objective_pairs: the inverse-compositional objective has no system call yet");
+      return fail(PHOVO_E_UNSUPPORTED, "evaluate_objective_pairs: the inverse-compositional objective has its system in "
+                                       "phovo_engine_evaluate_inverse_pairs");
     default:
       return fail(PHOVO_E_UNSUPPORTED, "evaluate_objective_pairs: the photometric-geometric objective has its system in "
                                        "phovo_engine_evaluate_geometric_pairs");
@@ -298,6 +308,38 @@ int phovo_engine_evaluate_objective_pairs(phovo_engine *e, int n_pairs, const in
   // the trust region's pass 2 and the bi-objective's fill have put every owner map of every group back to -1
   if (st == PHOVO_OK) e->eval_owner_clean = G * n;
   return st;
+}
+
+int phovo_engine_evaluate_inverse_pairs(phovo_engine *e, int n_pairs, const int *src, const int *tgt, const double *states,
+                                        int level, phovo_pair_system *out)
+{
+  if (!e) return fail(PHOVO_E_INVALID_ARGUMENT, "evaluate_inverse_pairs: null engine");
+  if (e->objective != PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL)
+    return fail(PHOVO_E_UNSUPPORTED, "evaluate_inverse_pairs: the inverse-compositional objective only (the others have "
+                                     "phovo_engine_evaluate_pairs, _evaluate_sampled_pairs, _evaluate_geometric_pairs and "
+                                     "_evaluate_objective_pairs)");
+  // (set_objective / set_extensions hold this objective to fp64 planes without Huber weights)
+  const EvalCall c{"evaluate_inverse_pairs", n_pairs, src, tgt, states, 6, level, out, sizeof(*out)};
+  int st = eval_check(e, c, false, true);
+  if (st != PHOVO_OK || n_pairs == 0) return st;
+
+  // Workspace for a group of G pairs: tile sums, states, pair indices and the results.
+  const size_t slab_bytes = gn_eval_slab_doubles_per_pair(e->levels[level].n) * sizeof(double);
+  const int group = eval_group(n_pairs, EVAL_SAMPLED_SLAB_CAP_BYTES, slab_bytes);
+  const size_t G = (size_t)group;
+  const size_t bytes[] = {G * slab_bytes, G * 6 * sizeof(double), G * sizeof(int), G * sizeof(int),
+                          G * sizeof(phovo_pair_system)};
+  unsigned char *at[5];
+  st = eval_workspace(e, bytes, at, 0);
+  if (st != PHOVO_OK) return st;
+
+  GNInverseEvalArgs a{};
+  eval_args(a, e, level, at + 1);
+  auto *d_part = reinterpret_cast<double *>(at[0]);
+  auto *d_out = reinterpret_cast<phovo_pair_system *>(at[4]);
+  return eval_run(e, c, group, at + 1, d_out, [&](int pairs) {
+    return gn_eval_inverse_pairs(a, pairs, d_part, d_out, e->stream);
+  });
 }
 
 }  // extern "C"

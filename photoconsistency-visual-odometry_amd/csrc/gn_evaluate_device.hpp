@@ -1,6 +1,6 @@
-// The tile scaffold of the four "system at a given state" kernel files (gn_evaluate_kernels.hip,
-// gn_evaluate_sampled_kernels.hip, gn_evaluate_geometric_kernels.hip, gn_evaluate_objective_kernels.hip), included by
-// those four and by nothing else.
+// The tile scaffold of the five "system at a given state" kernel files (gn_evaluate_kernels.hip,
+// gn_evaluate_sampled_kernels.hip, gn_evaluate_geometric_kernels.hip, gn_evaluate_objective_kernels.hip,
+// gn_evaluate_inverse_kernels.hip), included by those five and by nothing else.
 //
 // The form (the wide form's shape, gn_wide_kernels.hip): a pair is cut into tiles of 16 64-pixel chunks, one 256-thread
 // workgroup per tile, grid (tiles, pairs of the group), and the kernel boundary is the only synchronisation (no grid
@@ -13,12 +13,13 @@
 //                    sums are added in subset order, and one wave writes the record
 // The tile count and every summation order depend on the level size only: a pair's record is the same bit for bit
 // whatever the batch, its position in it, the group split, or any setting of the engine.  That promise rests on every
-// kernel of the four files having this geometry and these orders, which is why they stand here once.
+// kernel of the five files having this geometry and these orders, which is why they stand here once.
 //
 // Everything is __forceinline__ in an anonymous namespace, as in gn_device.hpp.  The first half (geometry, pose preamble,
 // row sums, tile sums, finish) holds explicit fma() and plain adds only, so it means the same under
 // `#pragma clang fp contract(off)` (gn_evaluate_objective_kernels.hip) and without; the bilinear warp at the end (and
-// gn_sampled_device.hpp behind it) has products feeding adds and is for the two files compiled with default contraction only.
+// gn_sampled_device.hpp behind it) has products feeding adds and is for the files compiled with default contraction only
+// (k_eval_inverse calls that warp's parts itself, as its aligner does).
 #pragma once
 
 #include <hip/hip_runtime.h>

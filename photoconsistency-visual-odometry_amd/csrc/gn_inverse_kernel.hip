@@ -196,14 +196,8 @@ __global__ __launch_bounds__(T, WPS) void gn_level_kernel_inverse(const GNInvers
       n_rows += __builtin_popcountll(w.m);
       if (__builtin_amdgcn_inverse_ballot_w64(w.m)) {
         const double res = bilerp(w.ax, w.ay, w.tap[0], w.tap[1], w.tap[2], w.tap[3]) - w.i0;
-        const double ipz = fast_rcp(w.pz);
         double J[6];
-        J[0] = (w.gx * F.fx) * ipz;
-        J[1] = (w.gy * F.fy) * ipz;
-        J[2] = -(J[0] * w.px + J[1] * w.py) * ipz;
-        J[3] = w.py * J[2] - w.pz * J[1];                                 // p x a
-        J[4] = w.pz * J[0] - w.px * J[2];
-        J[5] = w.px * J[1] - w.py * J[0];
+        inverse_row(J, w.gx, w.gy, w.px, w.py, w.pz, F.fx, F.fy);
         add_row(acc, J, res);
       }
     };

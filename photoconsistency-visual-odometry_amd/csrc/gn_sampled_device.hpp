@@ -1,7 +1,7 @@
 // What the SAMPLED kernels share: the aligners that warp every source pixel to a real-valued target position and sample
 // there bilinearly (gn_bilinear_kernel.hip, gn_affine_kernel.hip, gn_geometric_kernel.hip, and gn_inverse_kernel.hip, which
 // takes the pair frame, the warp, the taps and bilerp and has a source-side row of its own) and the kernels that fill the
-// same rows at a given state (k_eval_sampled, k_eval_geometric_depth, through gn_evaluate_device.hpp).  An aligner and its
+// same rows at a given state (k_eval_sampled, k_eval_geometric_depth, k_eval_inverse, through gn_evaluate_device.hpp).  An aligner and its
 // "system at a given state" kernel promise exactly the same rows: the gates, the bounds test, the taps, the interpolation
 // and the six pose columns stand here once, and a change to them is made here.
 // TWIN, by measurement (comments at the places): gn_level_kernel_geometric has its own lines for pose_columns (both rows);
@@ -164,6 +164,22 @@ __device__ __forceinline__ SampledPose sampled_pose_rt(const double *s_cst)
   P.t1 = read(C_T1); P.t2 = read(C_T2); P.t3 = read(C_T3);
   P.t14 = read(C_T14); P.t15 = read(C_T15);
   return P;
+}
+
+// The source-side row of the inverse-compositional objective (gn_inverse_kernel.hip and k_eval_inverse), twist order
+// (nu, omega): with p = (px, py, pz) the unprojected source pixel and (gx, gy) the SOURCE frame's stored gradients,
+//   a = (gx fx / pz, gy fy / pz, -(a_0 px + a_1 py) / pz),   J = (a, p x a).
+// It depends on no pose: the aligner and its "system at a given state" kernel fill the same row from these six lines.
+__device__ __forceinline__ void inverse_row(double (&J)[6], double gx, double gy, double px, double py, double pz, double fx,
+                                            double fy)
+{
+  const double ipz = fast_rcp(pz);
+  J[0] = (gx * fx) * ipz;
+  J[1] = (gy * fy) * ipz;
+  J[2] = -(J[0] * px + J[1] * py) * ipz;
+  J[3] = py * J[2] - pz * J[1];                                           // p x a
+  J[4] = pz * J[0] - px * J[2];
+  J[5] = px * J[1] - py * J[0];
 }
 
 // ---- the warp --------------------------------------------------------------------------------------------------------

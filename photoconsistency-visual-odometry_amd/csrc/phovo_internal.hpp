@@ -238,6 +238,22 @@ struct GNInverseArgs {
 int gn_inverse_wgs_per_cu();         // workgroups of the kernel that stay resident per CU
 int gn_inverse_lds_bytes();
 hipError_t gn_launch_level_inverse(const GNInverseArgs &args, int cu_count, hipStream_t stream);
+// Evaluation of that objective's system at given states, in the twist basis (gn_evaluate_inverse_kernels.hip,
+// phovo_engine_evaluate_inverse_pairs): fp64 planes, the tile form of gn_eval_sampled_pairs, gn_eval_tiles(n) tiles per
+// pair, no owner map, no ballots.  The source frame's gradient planes are read (a target upload's).
+struct GNInverseEvalArgs {
+  int w, h, n, n_chunks;
+  double fx, fy, ox, oy, ifx, ify;   // level-scaled intrinsics, as GNLevelArgs
+  double min_depth, max_depth;       // the depth range in force at the call
+  const unsigned char *planes;       // pool of the level (GNLevelArgs)
+  size_t frame_bytes;
+  size_t plane_off[PLANES_PER_FRAME];
+  const int *src, *tgt;              // [pairs of the group]
+  const double *states;              // [pairs of the group][6]
+};
+// g_part: [n_pairs][gn_eval_slab_doubles_per_pair(n)]; out: [n_pairs] on the device.
+hipError_t gn_eval_inverse_pairs(const GNInverseEvalArgs &a, int n_pairs, double *g_part, phovo_pair_system *out,
+                                 hipStream_t stream);
 // Sliding-window form for levels whose owner map exceeds LDS (gn_slide_kernel.hip): owner ring in LDS; pairs whose
 // motion leaves the window are appended to args.handover_out for a follow-up gn_launch_level that takes that list.
 hipError_t gn_prepare_slide_kernels();

@@ -233,6 +233,7 @@ SYMBOLS = {
     "phovo_odometry_get_sampled_system": (C.c_int, [_vp, C.POINTER(SampledSystem)]),
     "phovo_odometry_get_geometric_system": (C.c_int, [_vp, C.POINTER(GeometricSystem)]),
     "phovo_odometry_get_objective_system": (C.c_int, [_vp, C.POINTER(PairSystem)]),
+    "phovo_odometry_get_inverse_system": (C.c_int, [_vp, C.POINTER(PairSystem)]),
     "phovo_engine_create": (C.c_int, [C.c_int, C.POINTER(_vp)]),
     "phovo_engine_destroy": (C.c_int, [_vp]),
     "phovo_engine_set_config": (C.c_int, [_vp, C.POINTER(Config)]),
@@ -305,6 +306,7 @@ SYMBOLS = {
     "phovo_engine_evaluate_sampled_pairs": (C.c_int, [_vp, C.c_int, _ip, _ip, _vp, C.c_int, C.c_int, _vp]),
     "phovo_engine_evaluate_geometric_pairs": (C.c_int, [_vp, C.c_int, _ip, _ip, _vp, C.c_int, _vp]),
     "phovo_engine_evaluate_objective_pairs": (C.c_int, [_vp, C.c_int, _ip, _ip, _vp, C.c_int, _vp]),
+    "phovo_engine_evaluate_inverse_pairs": (C.c_int, [_vp, C.c_int, _ip, _ip, _vp, C.c_int, _vp]),
 }
 
 

@@ -420,11 +420,20 @@ class CPhotoconsistencyOdometryInverse(CPhotoconsistencyOdometryAnalytic):
     """One frame pair at a time; not in the reference: the photometric residual aligned inverse-compositionally
     (native.OBJECTIVE_INVERSE_COMPOSITIONAL: bilinear samples of the target, the Jacobian from the source frame's own
     gradient, the step composed on SE(3)).  SetSourceFrame also builds the source's gradient planes.  Reads
-    the analytic yml files; extensions and every Get...System() are refused (PHOVO_E_UNSUPPORTED)."""
+    the analytic yml files; extensions and the Euler-basis Get...System() calls are refused (PHOVO_E_UNSUPPORTED);
+    GetInverseSystem() returns this objective's system in the twist basis."""
 
     def __init__(self, device=0):
         super().__init__(device)
         check(self._lib.phovo_odometry_set_objective(self._h, native.OBJECTIVE_INVERSE_COMPOSITIONAL), "SetObjective")
+
+    def GetInverseSystem(self):
+        """native.PairSystem at the optimal state on the finest level the configuration optimises, in the twist basis
+        (nu, omega) of a right-hand perturbation T Exp(xi) in the source camera's frame: sum J J^T, sum J r, rows and
+        cost = sum r^2; evaluated on demand after Optimize()."""
+        ps = native.PairSystem()
+        check(self._lib.phovo_odometry_get_inverse_system(self._h, C.byref(ps)), "GetInverseSystem")
+        return ps
 
 
 # phovo_geometric_report as a numpy record: one row of per-level fields per pair
@@ -788,6 +797,26 @@ class AlignmentEngine:
         check(self._lib.phovo_engine_evaluate_objective_pairs(self._h, n, s.ctypes.data_as(ip), t.ctypes.data_as(ip),
                                                               st.ctypes.data, int(level), out.ctypes.data),
               "phovo_engine_evaluate_objective_pairs")
+        out = out[:n]
+        res = dict(information=out["information"].reshape(n, 6, 6).copy(), gradient=out["gradient"].copy(),
+                   cost=out["cost"].copy(), rows=out["rows"].astype(np.int64), flags=out["flags"].astype(np.int64))
+        if want_structs:
+            res["structs"] = list((native.PairSystem * n).from_buffer_copy(out.tobytes()))
+        return res
+
+    def evaluate_inverse_pairs(self, src, tgt, states, level, want_structs=False):
+        """The twist-basis system of each (source, target) pair under the inverse-compositional objective at states [n, 6]
+        on `level` (phovo_engine_evaluate_inverse_pairs: columns nu, omega of a right-hand twist in the source camera's
+        frame).  Returns what evaluate_pairs returns: information [n, 6, 6], gradient [n, 6], cost [n], rows [n], flags [n]
+        (with want_structs, also the native.PairSystem records under "structs")."""
+        s, t = self._pairs(src, tgt)
+        n = s.size
+        st = np.ascontiguousarray(states, dtype=np.float64).reshape(n, 6)
+        out = np.zeros(max(n, 1), dtype=PAIR_SYSTEM_DTYPE)         # the C records, written in place
+        ip = C.POINTER(C.c_int)
+        check(self._lib.phovo_engine_evaluate_inverse_pairs(self._h, n, s.ctypes.data_as(ip), t.ctypes.data_as(ip),
+                                                            st.ctypes.data, int(level), out.ctypes.data),
+              "phovo_engine_evaluate_inverse_pairs")
         out = out[:n]
         res = dict(information=out["information"].reshape(n, 6, 6).copy(), gradient=out["gradient"].copy(),
                    cost=out["cost"].copy(), rows=out["rows"].astype(np.int64), flags=out["flags"].astype(np.int64))
