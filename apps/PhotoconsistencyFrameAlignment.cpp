@@ -3,7 +3,7 @@
 // Same command line, hard-coded intrinsics, depth scale and console output as the reference's app
 // (apps/PhotoconsistencyFrameAlignment/PhotoconsistencyFrameAlignment.cpp:49-115):
 //   ./PhotoconsistencyFrameAlignment <config_file.yml> <imgRGB0.png> <imgDepth0.png> <imgRGB1.png> <imgDepth1.png> [diff.png]
-//                                    [--method analytic|ceres|biobjective|inverse|affine|geometric]
+//                                    [--method analytic|ceres|biobjective|inverse|robust|affine|geometric]
 // --method picks the aligner as the reference's USE_PHOTOCONSISTENCY_ODOMETRY_METHOD does: analytic (0, the default),
 // ceres (1, CPhotoconsistencyOdometryCeres: Levenberg-Marquardt on bilinear samples; reads config_*_ceres.yml files) or
 // biobjective (2, CPhotoconsistencyOdometryBiObjective: photometric and depth error together).  A configuration file of
@@ -22,6 +22,7 @@
 #include "phovo/CPhotoconsistencyOdometryAffine.h"
 #include "phovo/CPhotoconsistencyOdometryGeometric.h"
 #include "phovo/CPhotoconsistencyOdometryInverse.h"
+#include "phovo/CPhotoconsistencyOdometryRobust.h"
 #include "phovo/CPhotoconsistencyOdometryBiObjective.h"
 #include "phovo/CPhotoconsistencyOdometryCeres.h"
 
@@ -36,7 +37,7 @@ typedef phovo::compat::Mat_<CoordinateType> DepthImageType;
 static void printHelp()
 {
   std::cout << "./PhotoconsistencyFrameAlignment <config_file.yml> <imgRGB0.png> <imgDepth0.png> "
-               "<imgRGB1.png> <imgDepth1.png> [imgDiff.png] [--method analytic|ceres|biobjective|inverse|affine|geometric]" << std::endl;
+               "<imgRGB1.png> <imgDepth1.png> [imgDiff.png] [--method analytic|ceres|biobjective|inverse|robust|affine|geometric]" << std::endl;
 }
 
 static bool loadGray(const char *path, IntensityImageType &img)
@@ -59,7 +60,7 @@ static bool loadDepthMetres(const char *path, DepthImageType &img)
   return true;
 }
 
-enum Method { METHOD_ANALYTIC, METHOD_CERES, METHOD_BIOBJECTIVE, METHOD_AFFINE, METHOD_GEOMETRIC, METHOD_INVERSE };      // (affine, geometric, inverse: not in the reference, read the analytic files)
+enum Method { METHOD_ANALYTIC, METHOD_CERES, METHOD_BIOBJECTIVE, METHOD_AFFINE, METHOD_GEOMETRIC, METHOD_INVERSE, METHOD_ROBUST };      // (affine, geometric, inverse, robust: not in the reference, read the analytic files)
 static int alignPair(int argc, char **argv, Method method);
 
 // The Ceres method reads the config_*_ceres.yml keys, the other two the config_*_analytic.yml keys.
@@ -90,6 +91,7 @@ int main(int argc, char **argv)
       else if (m == "affine") method = METHOD_AFFINE;
       else if (m == "geometric") method = METHOD_GEOMETRIC;
       else if (m == "inverse") method = METHOD_INVERSE;
+      else if (m == "robust") method = METHOD_ROBUST;
       else if (m != "analytic") { printHelp(); return -1; }
       continue;
     }
@@ -109,6 +111,7 @@ static int alignPair(int argc, char **argv, Method method)
   if (method == METHOD_AFFINE) return alignWith<phovo::Analytic::CPhotoconsistencyOdometryAffine<PixelType, CoordinateType>>(argc, argv);
   if (method == METHOD_GEOMETRIC) return alignWith<phovo::Analytic::CPhotoconsistencyOdometryGeometric<PixelType, CoordinateType>>(argc, argv);
   if (method == METHOD_INVERSE) return alignWith<phovo::Analytic::CPhotoconsistencyOdometryInverse<PixelType, CoordinateType>>(argc, argv);
+  if (method == METHOD_ROBUST) return alignWith<phovo::Analytic::CPhotoconsistencyOdometryRobust<PixelType, CoordinateType>>(argc, argv);
   return alignWith<phovo::Analytic::CPhotoconsistencyOdometryAnalytic<PixelType, CoordinateType>>(argc, argv);
 }
 

@@ -2,7 +2,7 @@
 // directory, writing a TUM trajectory file.
 //
 //   ./PhotoconsistencyVisualOdometry <config_file.yml> <rgbd_dataset_directory> <output_trajectory_file> [--batch [--gpus N] [--rccl]]
-//                                    [--method analytic|ceres|biobjective|inverse|affine|geometric] [--information <file>] [--system <file>]
+//                                    [--method analytic|ceres|biobjective|inverse|robust|affine|geometric] [--information <file>] [--system <file>]
 //                                    [--geometric-system <file>] [--objective-system <file>] [--inverse-system <file>]
 // --method picks the aligner as the reference's USE_PHOTOCONSISTENCY_ODOMETRY_METHOD does (0 = analytic, the default;
 // 1 = ceres: Levenberg-Marquardt on bilinear samples, CPhotoconsistencyOdometryCeres, which reads config_*_ceres.yml
@@ -14,6 +14,9 @@
 // inverse is not in the reference either: the photometric residual aligned inverse-compositionally (the Jacobian from the
 // source frame's own gradient, the step composed on SE(3)), CPhotoconsistencyOdometryInverse, which reads the analytic files;
 // its system is in the twist basis, so the four Euler-basis system flags below refuse it and --inverse-system writes it.
+// robust is not in the reference either: the inverse-compositional aligner under a Huber weight whose threshold follows the
+// median of the pair's own residuals, CPhotoconsistencyOdometryRobust, which reads the analytic files; it has no system
+// call yet, so all five system flags below refuse it.
 // A configuration file of the other kind is refused with a message that says so.
 // --information <file> (not in the reference; analytic method, one device): one line per pair, stamped like its trajectory
 // line, with the Gauss-Newton system at the pair's optimal state on the finest level the configuration optimises --
@@ -83,6 +86,7 @@
 #include "phovo/CPhotoconsistencyOdometryAnalytic.h"
 #include "phovo/CPhotoconsistencyOdometryAffine.h"
 #include "phovo/CPhotoconsistencyOdometryInverse.h"
+#include "phovo/CPhotoconsistencyOdometryRobust.h"
 #include "phovo/CPhotoconsistencyOdometryGeometric.h"
 #include "phovo/CPhotoconsistencyOdometryBiObjective.h"
 #include "phovo/CPhotoconsistencyOdometryCeres.h"
@@ -213,7 +217,7 @@ static phovo_pair_system inverseSystemOf(Odometry &, long)
 static void printHelp()
 {
   std::cout << "./PhotoconsistencyVisualOdometry <config_file.yml> <rgbd_dataset_directory> "
-               "<output_trajectory_file> [--batch [--gpus N] [--rccl]] [--method analytic|ceres|biobjective|inverse|affine|geometric] "
+               "<output_trajectory_file> [--batch [--gpus N] [--rccl]] [--method analytic|ceres|biobjective|inverse|robust|affine|geometric] "
                "[--information <file>] [--system <file>] [--geometric-system <file>] [--objective-system <file>] "
                "[--inverse-system <file>]" << std::endl;
 }
@@ -245,6 +249,7 @@ int main(int argc, char *argv[])
       else if (m == "affine") objective = PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE;
       else if (m == "geometric") objective = PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC;
       else if (m == "inverse") objective = PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL;
+      else if (m == "robust") objective = PHOVO_OBJECTIVE_INVERSE_ROBUST;
       else { printHelp(); return EXIT_FAILURE; }
     }
     else if (a == "--rccl") rccl = true;
@@ -431,6 +436,9 @@ int main(int argc, char *argv[])
         if (runLoop(odometry) != EXIT_SUCCESS) return EXIT_FAILURE;
       } else if (objective == PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL) {
         phovo::Analytic::CPhotoconsistencyOdometryInverse<PixelType, CoordinateType> odometry;
+        if (runLoop(odometry) != EXIT_SUCCESS) return EXIT_FAILURE;
+      } else if (objective == PHOVO_OBJECTIVE_INVERSE_ROBUST) {
+        phovo::Analytic::CPhotoconsistencyOdometryRobust<PixelType, CoordinateType> odometry;
         if (runLoop(odometry) != EXIT_SUCCESS) return EXIT_FAILURE;
       } else {
         phovo::Analytic::CPhotoconsistencyOdometryAnalytic<PixelType, CoordinateType> odometry;

@@ -1,0 +1,60 @@
+// Not in the reference: the inverse-compositional aligner of CPhotoconsistencyOdometryInverse under a Huber weight whose
+// threshold follows the pair's own residuals, with the class shape of CPhotoconsistencyOdometryAnalytic, forwarding to the
+// MI355X library through the C ABI of phovo_hip.h (PHOVO_OBJECTIVE_INVERSE_ROBUST: delta = scale_factor * median |r| from a
+// histogram of the rows' residuals, lagging one iteration; gn_inverse_robust_kernel.hip).
+//
+//   #include "phovo/CPhotoconsistencyOdometryRobust.h"
+//   phovo::Analytic::CPhotoconsistencyOdometryRobust<unsigned char, double> odometry;
+//
+// The types come from the same place as CPhotoconsistencyOdometryAnalytic.h's (PHOVO_HIP_USE_REFERENCE_TYPES or
+// phovo/compat/).  ReadConfigurationFile reads the config_*_analytic.yml keys.  SetSourceFrame also builds the source's
+// gradient planes.  Extensions are refused (std::runtime_error, PHOVO_E_UNSUPPORTED), and so are the inherited
+// GetPairSystem() and GetSampledSystem(): this objective's weighted system has no call yet.
+#ifndef PHOVO_HIP_CPHOTOCONSISTENCY_ODOMETRY_ROBUST_H
+#define PHOVO_HIP_CPHOTOCONSISTENCY_ODOMETRY_ROBUST_H
+
+#include "phovo/CPhotoconsistencyOdometryAnalytic.h"
+
+namespace phovo {
+namespace Analytic {
+
+template <class TPixel, class TCoordinate>
+class CPhotoconsistencyOdometryRobust : public CPhotoconsistencyOdometryAnalytic<TPixel, TCoordinate> {
+ public:
+  typedef CPhotoconsistencyOdometryAnalytic<TPixel, TCoordinate> Base;
+  typedef typename Base::CoordinateType CoordinateType;
+  typedef typename Base::IntensityImageType IntensityImageType;
+  typedef typename Base::DepthImageType DepthImageType;
+  typedef typename Base::Matrix33Type Matrix33Type;
+  typedef typename Base::Matrix44Type Matrix44Type;
+  typedef typename Base::Vector6Type Vector6Type;
+  typedef typename Base::Vector4Type Vector4Type;
+
+  explicit CPhotoconsistencyOdometryRobust(int device = 0) : Base(device)
+  {
+    Base::Check(phovo_odometry_set_objective(Base::Handle(), PHOVO_OBJECTIVE_INVERSE_ROBUST), "CPhotoconsistencyOdometryRobust()");
+  }
+
+  // delta = scale_factor * median |r| (phovo_robust_options; the default is 1.345 * 1.4826).
+  void SetRobustOptions(const phovo_robust_options &opt)
+  {
+    Base::Check(phovo_odometry_set_robust_options(Base::Handle(), &opt), "SetRobustOptions");
+  }
+  phovo_robust_options GetRobustOptions() const
+  {
+    phovo_robust_options opt;
+    Base::Check(phovo_odometry_get_robust_options(Base::Handle(), &opt), "GetRobustOptions");
+    return opt;
+  }
+  // Per level, the threshold and the outlier rows of the last system of the last Optimize().
+  phovo_robust_report GetRobustReport() const
+  {
+    phovo_robust_report r;
+    Base::Check(phovo_odometry_get_robust_report(Base::Handle(), &r), "GetRobustReport");
+    return r;
+  }
+};
+
+}  // namespace Analytic
+}  // namespace phovo
+#endif

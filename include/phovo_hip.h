@@ -293,6 +293,44 @@ typedef struct phovo_extensions {
  *                                last system, gradient_norm = ||g||_2 of the last system, PHOVO_PAIR_RANK_DEFICIENT
  *                                (sticky) when a system had fewer than 6 rows. */
 #define PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL 5
+/*   PHOVO_OBJECTIVE_INVERSE_ROBUST  not in the reference: the inverse-compositional aligner under a Huber weight whose
+ *                                threshold follows the pair's own residuals (DESIGN.md §22 has the contract).  Per level L
+ *                                and pair:
+ *                                  rows    entry, rows, r_k and J_k exactly as under PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL.
+ *                                  hist    4096 bins of width 2^-12 over |r| of the rows: with q = fabs(r) * 4096.0 the bin
+ *                                          is q < 4096.0 ? (int)q : 4095 (|r| >= 1 and a NaN residual: the last bin).
+ *                                  median  n rows, half = (n + 1) / 2 in integers, k the first bin whose cumulative count
+ *                                          reaches half, before the count below bin k, h[k] the count in it:
+ *                                          m = ((double)k + (double)(half - before) / (double)h[k]) * 0x1p-12 in fp64, in
+ *                                          that order; n = 0 gives m = 0.  delta = scale_factor * m (phovo_robust_options).
+ *                                  lag     delta_0 from a histogram-only pass at the level's entry pose; iteration i builds
+ *                                          its system with delta_i, and delta_{i+1} is the median rule on iteration i's
+ *                                          residuals (so delta_1 = delta_0).
+ *                                  system  w = fabs(r) <= delta_i ? 1.0 : delta_i / fabs(r); H = sum w J J^T, g = sum w J r;
+ *                                          outliers = rows with fabs(r) > delta_i.
+ *                                  step    xi = -lambda_L H^-1 g, composition, termination (||g||_2 of the WEIGHTED g), the
+ *                                          finite test, the flags and the level's exit as under objective 5.
+ *                                phovo_robust_report has the delta and the outliers of every level's last system.  Source
+ *                                frames need PHOVO_ROLE_BOTH (else PHOVO_E_NOT_READY), as under objective 5; switching between
+ *                                objectives 0, 2, 3, 4, 5 and 6 keeps the frame pool.  Supported: fp64 planes, the default
+ *                                sampling setting, no huber_delta extension, jacobian_corrected 0 -- anything else is
+ *                                PHOVO_E_UNSUPPORTED, whichever setter comes second.  All five phovo_engine_evaluate_* calls
+ *                                and the phovo_odometry_get_*_system calls are PHOVO_E_UNSUPPORTED under this objective (its
+ *                                weighted system is not built yet).  phovo_pair_report keeps its meaning. */
+#define PHOVO_OBJECTIVE_INVERSE_ROBUST 6
+
+/* Option of the robust inverse-compositional objective: delta = scale_factor * (median of |r|).  The default,
+ * 1.345 * 1.4826, is Huber's 95 %-efficiency constant times the factor that makes the median absolute deviation a
+ * consistent estimate of a normal sigma. */
+typedef struct phovo_robust_options {
+  double scale_factor;                          /* finite and > 0 */
+} phovo_robust_options;
+
+/* Per pair and level, from the level's LAST system (levels with max_num_iterations 0 stay 0). */
+typedef struct phovo_robust_report {
+  double  delta[PHOVO_MAX_LEVELS];              /* the Huber threshold that system was built with */
+  int32_t outliers[PHOVO_MAX_LEVELS];           /* its rows with fabs(r) > delta */
+} phovo_robust_report;
 
 /* Options of the photometric-geometric objective, per level.  Both are settings to tune for the sensor and the scene, not
  * measured optima: depth_weight trades metres of depth error against intensity error (intensities are in [0, 1]), and
@@ -411,6 +449,9 @@ int phovo_geometric_options_default(phovo_geometric_options *opt);
  * or a weight that is not finite and > 0 is PHOVO_E_CONFIG.  The rest of the file is not read: phovo_config_read_file. */
 int phovo_geometric_read_file(const char *path, phovo_geometric_options *opt);
 
+/* Robust inverse-compositional objective: scale_factor 1.345 * 1.4826. */
+int phovo_robust_options_default(phovo_robust_options *opt);
+
 int phovo_extensions_default(phovo_extensions *ext);
 /* Optional keys in the same yml file (the reference's cv::FileStorage lookups ignore keys they do not ask for,
  * so such a file still loads there): "huber_delta (at each level): [..]", "plane_storage_bits: 64|32|16",
@@ -496,6 +537,13 @@ int phovo_odometry_get_illumination(const phovo_odometry *o, double alpha_beta[2
 int phovo_odometry_set_geometric_options(phovo_odometry *o, const phovo_geometric_options *opt);
 int phovo_odometry_get_geometric_options(const phovo_odometry *o, phovo_geometric_options *opt);
 int phovo_odometry_get_geometric_report(const phovo_odometry *o, phovo_geometric_report *report);
+/* Robust inverse-compositional objective: its options (default: phovo_robust_options_default; kept under every objective,
+ * used by this one; a scale_factor that is not finite and > 0 is PHOVO_E_INVALID_ARGUMENT) and the record of the last
+ * Optimize() (PHOVO_E_NOT_READY before a successful one; PHOVO_E_UNSUPPORTED under another objective).  Under this
+ * objective phovo_odometry_set_source_frame uploads the source with both roles, as under objective 5. */
+int phovo_odometry_set_robust_options(phovo_odometry *o, const phovo_robust_options *opt);
+int phovo_odometry_get_robust_options(const phovo_odometry *o, phovo_robust_options *opt);
+int phovo_odometry_get_robust_report(const phovo_odometry *o, phovo_robust_report *report);
 int phovo_odometry_set_min_depth(phovo_odometry *o, double min_depth);     /* :448 */
 int phovo_odometry_set_max_depth(phovo_odometry *o, double max_depth);     /* :454 */
 int phovo_odometry_set_intrinsic_matrix(phovo_odometry *o, const double k[9]);     /* :460, row-major 3x3 */
@@ -633,6 +681,12 @@ int phovo_engine_fetch_illumination(phovo_engine *e, int n_pairs, double *alpha_
 int phovo_engine_set_geometric_options(phovo_engine *e, const phovo_geometric_options *opt);
 int phovo_engine_get_geometric_options(const phovo_engine *e, phovo_geometric_options *opt);
 int phovo_engine_fetch_geometric_reports(phovo_engine *e, int n_pairs, phovo_geometric_report *reports);
+/* Robust inverse-compositional objective: its option (kept under every objective, used by this one; scale_factor must be
+ * finite and > 0, else PHOVO_E_INVALID_ARGUMENT) and the per-pair records of the LAST enqueue, with the call-order rules of
+ * phovo_engine_fetch_geometric_reports. */
+int phovo_engine_set_robust_options(phovo_engine *e, const phovo_robust_options *opt);
+int phovo_engine_get_robust_options(const phovo_engine *e, phovo_robust_options *opt);
+int phovo_engine_fetch_robust_reports(phovo_engine *e, int n_pairs, phovo_robust_report *reports);
 
 /* Page-locks (and releases) a host buffer the caller will hand to the upload entry points repeatedly: uploads from
  * registered memory are direct DMA at the link rate instead of going through the runtime's bounce buffers.  Optional;
@@ -938,7 +992,8 @@ enum { PHOVO_LAUNCH_PERSISTENT = 0,       /* gn_level_kernel: one level, one wor
        PHOVO_LAUNCH_TRUST_REGION = 7,     /* gn_level_kernel_trust_region (PHOVO_OBJECTIVE_TRUST_REGION) */
        PHOVO_LAUNCH_AFFINE = 8,           /* gn_level_kernel_affine (PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE) */
        PHOVO_LAUNCH_GEOMETRIC = 9,        /* gn_level_kernel_geometric (PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC) */
-       PHOVO_LAUNCH_INVERSE = 10 };       /* gn_level_kernel_inverse (PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL) */
+       PHOVO_LAUNCH_INVERSE = 10,         /* gn_level_kernel_inverse (PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL) */
+       PHOVO_LAUNCH_INVERSE_ROBUST = 11 };  /* gn_level_kernel_inverse_robust (PHOVO_OBJECTIVE_INVERSE_ROBUST) */
 typedef struct phovo_launch_record {
   int level_first, level_last;            /* pyramid levels the launch covers (level_first >= level_last) */
   int kind;                               /* PHOVO_LAUNCH_* */

@@ -105,8 +105,8 @@ void level_dims(int w, int h, int level, int *lw, int *lh)
 }
 
 // Every objective but the photometric one runs reference-exact only: fp64 planes, nearest / scatter sampling, no Huber
-// weights, jacobian_corrected 0 (the affine-illumination, photometric-geometric and inverse-compositional rows are fixed by
-// the objective, not chosen by the extensions).  PHOVO_OK where `objective` and `x` go together, else the refusal, in the setter's name.
+// weights, jacobian_corrected 0 (the affine-illumination, photometric-geometric and inverse-compositional rows, and the robust
+// inverse-compositional objective's own weights, are fixed by the objective, not chosen by the extensions).  PHOVO_OK where `objective` and `x` go together, else the refusal, in the setter's name.
 int reference_exact_only(const char *setter, int objective, const phovo_extensions &x)
 {
   bool exact = x.plane_storage == PHOVO_STORAGE_F64 && x.sampling == PHOVO_SAMPLING_NEAREST_SCATTER && x.jacobian_corrected == 0;
@@ -118,6 +118,7 @@ int reference_exact_only(const char *setter, int objective, const phovo_extensio
       : objective == PHOVO_OBJECTIVE_TRUST_REGION ? "the trust-region objective runs on fp64 planes with the default sampling, no Huber weights and jacobian_corrected 0 only"
       : objective == PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE ? "the affine-illumination objective runs on fp64 planes with the default sampling setting, no Huber weights and jacobian_corrected 0 only"
       : objective == PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL ? "the inverse-compositional objective runs on fp64 planes with the default sampling setting, no Huber weights and jacobian_corrected 0 only"
+      : objective == PHOVO_OBJECTIVE_INVERSE_ROBUST ? "the robust inverse-compositional objective runs on fp64 planes with the default sampling setting, no huber_delta extension and jacobian_corrected 0 only"
       : "the photometric-geometric objective runs on fp64 planes with the default sampling setting, no Huber weights and jacobian_corrected 0 only";
   return fail(PHOVO_E_UNSUPPORTED, std::string(setter) + ": " + only);
 }
@@ -367,6 +368,7 @@ int phovo_engine_create(int device, phovo_engine **out)
   phovo_extensions_default(&e->ext);
   phovo_trust_region_options_default(&e->tr_opt);
   phovo_geometric_options_default(&e->geo_opt);
+  phovo_robust_options_default(&e->rob_opt);
   hipError_t he = hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking);
   if (he == hipSuccess) he = hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking);
   for (int i = 0; i < 2 && he == hipSuccess; i++) {
@@ -489,12 +491,13 @@ int phovo_engine_set_objective(phovo_engine *e, int objective)
   if (!e) return fail(PHOVO_E_INVALID_ARGUMENT, "set_objective: null");
   if (objective != PHOVO_OBJECTIVE_PHOTOMETRIC && objective != PHOVO_OBJECTIVE_BIOBJECTIVE &&
       objective != PHOVO_OBJECTIVE_TRUST_REGION && objective != PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE &&
-      objective != PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC && objective != PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL)
+      objective != PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC && objective != PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL &&
+      objective != PHOVO_OBJECTIVE_INVERSE_ROBUST)
     return fail(PHOVO_E_INVALID_ARGUMENT, "set_objective: unknown objective");
   const int st = reference_exact_only("set_objective", objective, e->ext);
   if (st != PHOVO_OK) return st;
-  // The photometric, trust-region, affine-illumination, photometric-geometric and inverse-compositional objectives share the
-  // frame layout: a switch between them keeps the pool.
+  // The photometric, trust-region, affine-illumination, photometric-geometric and both inverse-compositional objectives share
+  // the frame layout: a switch between them keeps the pool.
   auto bi = [](int o) { return o == PHOVO_OBJECTIVE_BIOBJECTIVE; };
   if (objective != e->objective && (bi(objective) || bi(e->objective))) drop_pool(e);   // the pool layout changes (the bi-objective's target planes)
   e->objective = objective;
@@ -552,6 +555,29 @@ int phovo_engine_get_geometric_options(const phovo_engine *e, phovo_geometric_op
 {
   if (!e || !opt) return fail(PHOVO_E_INVALID_ARGUMENT, "get_geometric_options: null");
   *opt = e->geo_opt;
+  return PHOVO_OK;
+}
+
+int phovo_robust_options_default(phovo_robust_options *opt)
+{
+  if (!opt) return fail(PHOVO_E_INVALID_ARGUMENT, "robust_options_default: null");
+  opt->scale_factor = 1.345 * 1.4826;
+  return PHOVO_OK;
+}
+
+int phovo_engine_set_robust_options(phovo_engine *e, const phovo_robust_options *opt)
+{
+  if (!e || !opt) return fail(PHOVO_E_INVALID_ARGUMENT, "set_robust_options: null");
+  if (!(opt->scale_factor > 0.0 && std::isfinite(opt->scale_factor)))
+    return fail(PHOVO_E_INVALID_ARGUMENT, "set_robust_options: scale_factor must be finite and > 0");
+  e->rob_opt = *opt;
+  return PHOVO_OK;
+}
+
+int phovo_engine_get_robust_options(const phovo_engine *e, phovo_robust_options *opt)
+{
+  if (!e || !opt) return fail(PHOVO_E_INVALID_ARGUMENT, "get_robust_options: null");
+  *opt = e->rob_opt;
   return PHOVO_OK;
 }
 

@@ -135,6 +135,7 @@ void phovo_hip::free_slot(AlignSlot &s)
   s.tr_reports.release();
   s.illum.release();
   s.geo_reports.release();
+  s.rob_reports.release();
 }
 
 extern "C" {
@@ -187,7 +188,7 @@ int phovo_engine_enqueue_align(phovo_engine *e, int n_pairs, const int *source_f
                                          "frames with PHOVO_ROLE_BOTH)");
       continue;
     }
-    if (e->objective == PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL) {            // likewise; the source's gradients are a target upload's
+    if (e->objective == PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL || e->objective == PHOVO_OBJECTIVE_INVERSE_ROBUST) {   // likewise; the source's gradients are a target upload's
       for (int i = 0; i < n_pairs; i++)
         if (!(e->frame_roles[(size_t)source_frames[i] * PHOVO_MAX_LEVELS + (size_t)l] & PHOVO_ROLE_TARGET))
           return fail(PHOVO_E_NOT_READY, "align: the inverse-compositional objective reads the source's gradient planes (upload "
@@ -230,6 +231,7 @@ int phovo_engine_enqueue_align(phovo_engine *e, int n_pairs, const int *source_f
   s.tr_ran = e->objective == PHOVO_OBJECTIVE_TRUST_REGION;
   s.affine_ran = e->objective == PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE;
   s.geometric_ran = e->objective == PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC;
+  s.robust_ran = e->objective == PHOVO_OBJECTIVE_INVERSE_ROBUST;
   s.num_levels = e->cfg.num_levels;
   for (int l = 0; l < PHOVO_MAX_LEVELS; l++) s.level_skipped[l] = l < e->cfg.num_levels && e->cfg.max_num_iterations[l] <= 0;
   if (n_pairs == 0) {                    // nothing to run: a valid, empty enqueue (fetch of 0 pairs succeeds, no device buffer)
@@ -260,6 +262,7 @@ int phovo_engine_enqueue_align(phovo_engine *e, int n_pairs, const int *source_f
   if (s.tr_ran) PHOVO_HIP_CHECK(s.tr_reports.reserve((size_t)n_pairs));
   if (s.affine_ran) PHOVO_HIP_CHECK(s.illum.reserve(2 * (size_t)n_pairs));
   if (s.geometric_ran) PHOVO_HIP_CHECK(s.geo_reports.reserve((size_t)n_pairs));
+  if (s.robust_ran) PHOVO_HIP_CHECK(s.rob_reports.reserve((size_t)n_pairs));
   // The caller may reuse its arrays as soon as this returns and the copies below are asynchronous: the slot's pinned
   // mirror keeps them alive until the slot is used again (synchronised above).
   const PairLayout lay = pair_layout(n_pairs);
@@ -283,6 +286,8 @@ int phovo_engine_enqueue_align(phovo_engine *e, int n_pairs, const int *source_f
     PHOVO_HIP_CHECK(hipMemsetAsync(s.illum.ptr, 0, sizeof(double) * 2 * (size_t)n_pairs, s.stream));
   if (s.geometric_ran)   // (every level the configuration skips stays 0)
     PHOVO_HIP_CHECK(hipMemsetAsync(s.geo_reports.ptr, 0, sizeof(phovo_geometric_report) * (size_t)n_pairs, s.stream));
+  if (s.robust_ran)      // (likewise)
+    PHOVO_HIP_CHECK(hipMemsetAsync(s.rob_reports.ptr, 0, sizeof(phovo_robust_report) * (size_t)n_pairs, s.stream));
   PHOVO_HIP_CHECK(hipEventRecord(s.ev_total_start, s.stream));
 
   auto record = [&](int first, int last, int kind, int threads, int lds, int wgs) {
@@ -413,6 +418,13 @@ int phovo_engine_enqueue_align(phovo_engine *e, int n_pairs, const int *source_f
       b.lv = a;
       PHOVO_HIP_CHECK(gn_launch_level_inverse(b, e->cu_count, s.stream));
       record(l, l, PHOVO_LAUNCH_INVERSE, 256, gn_inverse_lds_bytes(), persistent_grid(gn_inverse_wgs_per_cu()));
+    } else if (e->objective == PHOVO_OBJECTIVE_INVERSE_ROBUST) {
+      GNInverseRobustArgs b{};
+      b.lv = a;
+      b.scale_factor = e->rob_opt.scale_factor;
+      b.rob_reports = s.rob_reports.ptr;
+      PHOVO_HIP_CHECK(gn_launch_level_inverse_robust(b, e->cu_count, s.stream));
+      record(l, l, PHOVO_LAUNCH_INVERSE_ROBUST, 256, gn_inverse_robust_lds_bytes(), persistent_grid(gn_inverse_robust_wgs_per_cu()));
     } else if (e->ext.sampling == PHOVO_SAMPLING_BILINEAR) {
       PHOVO_HIP_CHECK(gn_launch_level_bilinear(a, e->ext.plane_storage, e->ext.jacobian_corrected != 0, e->cu_count, s.stream));
       record(l, l, PHOVO_LAUNCH_BILINEAR, 256, 0, persistent_grid(gn_bilinear_wgs_per_cu(e->ext.plane_storage)));
@@ -535,6 +547,12 @@ int phovo_engine_fetch_geometric_reports(phovo_engine *e, int n_pairs, phovo_geo
 {
   return fetch_records(e, "fetch_geometric_reports", PHOVO_E_NOT_READY, &AlignSlot::geometric_ran, &AlignSlot::geo_reports, 1,
                        n_pairs, reports);
+}
+
+int phovo_engine_fetch_robust_reports(phovo_engine *e, int n_pairs, phovo_robust_report *reports)
+{
+  return fetch_records(e, "fetch_robust_reports", PHOVO_E_NOT_READY, &AlignSlot::robust_ran, &AlignSlot::rob_reports, 1, n_pairs,
+                       reports);
 }
 
 int phovo_engine_fetch_results(phovo_engine *e, int n_pairs, double *out_states, phovo_pair_report *reports)

@@ -1,6 +1,7 @@
 // What the SAMPLED kernels share: the aligners that warp every source pixel to a real-valued target position and sample
-// there bilinearly (gn_bilinear_kernel.hip, gn_affine_kernel.hip, gn_geometric_kernel.hip, and gn_inverse_kernel.hip, which
-// takes the pair frame, the warp, the taps and bilerp and has a source-side row of its own) and the kernels that fill the
+// there bilinearly (gn_bilinear_kernel.hip, gn_affine_kernel.hip, gn_geometric_kernel.hip, and gn_inverse_kernel.hip and
+// gn_inverse_robust_kernel.hip, which take the pair frame, the warp, the taps and bilerp and have a source-side row of
+// their own) and the kernels that fill the
 // same rows at a given state (k_eval_sampled, k_eval_geometric_depth, k_eval_inverse, through gn_evaluate_device.hpp).  An aligner and its
 // "system at a given state" kernel promise exactly the same rows: the gates, the bounds test, the taps, the interpolation
 // and the six pose columns stand here once, and a change to them is made here.

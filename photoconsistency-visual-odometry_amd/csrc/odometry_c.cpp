@@ -26,9 +26,19 @@ struct phovo_odometry {
   bool have_illumination = false;
   phovo_geometric_report geo_report{};           // photometric-geometric objective: the record of the last Optimize()
   bool have_geo_report = false;
+  phovo_robust_report rob_report{};              // robust inverse-compositional objective: the record of the last Optimize()
+  bool have_rob_report = false;
 };
 
 namespace {
+
+// Both inverse-compositional objectives read the source's gradient planes, which are a target upload's.
+int source_role(const phovo_odometry *o)
+{
+  const bool inverse = o && (o->engine->objective == PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL ||
+                             o->engine->objective == PHOVO_OBJECTIVE_INVERSE_ROBUST);
+  return inverse ? PHOVO_ROLE_BOTH : PHOVO_ROLE_SOURCE;
+}
 
 int odometry_set_frame(phovo_odometry *o, int slot, int role, const uint8_t *intensity, size_t istride,
                        const double *depth, size_t dstride, int width, int height)
@@ -145,6 +155,18 @@ int phovo_odometry_get_geometric_options(const phovo_odometry *o, phovo_geometri
   return phovo_engine_get_geometric_options(o->engine, opt);
 }
 
+int phovo_odometry_set_robust_options(phovo_odometry *o, const phovo_robust_options *opt)
+{
+  if (!o) return fail(PHOVO_E_INVALID_ARGUMENT, "set_robust_options: null");
+  return phovo_engine_set_robust_options(o->engine, opt);
+}
+
+int phovo_odometry_get_robust_options(const phovo_odometry *o, phovo_robust_options *opt)
+{
+  if (!o) return fail(PHOVO_E_INVALID_ARGUMENT, "get_robust_options: null");
+  return phovo_engine_get_robust_options(o->engine, opt);
+}
+
 int phovo_odometry_set_latency_forms(phovo_odometry *o, int on)
 {
   if (!o) return fail(PHOVO_E_INVALID_ARGUMENT, "set_latency_forms: null");
@@ -204,9 +226,7 @@ int phovo_odometry_set_source_frame(phovo_odometry *o, const uint8_t *intensity,
                                     const double *depth, size_t dstride, int width, int height)
 {
   if (!depth) return fail(PHOVO_E_INVALID_ARGUMENT, "SetSourceFrame: depth is required");
-  // (the inverse-compositional objective reads the source's gradient planes, which are a target upload's)
-  const int role = o && o->engine->objective == PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL ? PHOVO_ROLE_BOTH : PHOVO_ROLE_SOURCE;
-  return odometry_set_frame(o, 0, role, intensity, istride, depth, dstride, width, height);
+  return odometry_set_frame(o, 0, source_role(o), intensity, istride, depth, dstride, width, height);
 }
 
 int phovo_odometry_set_target_frame(phovo_odometry *o, const uint8_t *intensity, size_t istride,
@@ -229,8 +249,7 @@ int phovo_odometry_set_source_frame_device(phovo_odometry *o, const phovo_device
                                            void *stream)
 {
   if (!depth) return fail(PHOVO_E_INVALID_ARGUMENT, "SetSourceFrameDevice: depth is required");
-  const int role = o && o->engine->objective == PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL ? PHOVO_ROLE_BOTH : PHOVO_ROLE_SOURCE;
-  return odometry_set_frame_device(o, 0, role, intensity, depth, depth_scale, width, height, stream);
+  return odometry_set_frame_device(o, 0, source_role(o), intensity, depth, depth_scale, width, height, stream);
 }
 
 int phovo_odometry_set_target_frame_device(phovo_odometry *o, const phovo_device_image *intensity,
@@ -344,6 +363,7 @@ static int optimize_visualized(phovo_odometry *o, const char *dir)
   o->report = total;
   o->have_illumination = false;
   o->have_geo_report = false;
+  o->have_rob_report = false;
   o->optimized = true;
   return PHOVO_OK;
 }
@@ -355,10 +375,11 @@ int phovo_odometry_optimize(phovo_odometry *o)
     return fail(PHOVO_E_NOT_READY, "Optimize: SetSourceFrame and SetTargetFrame must be called first");
   // (the affine-illumination objective carries alpha and beta inside an enqueue only: no one-iteration-per-launch form)
   // (the photometric-geometric objective's per-level record belongs to one enqueue: likewise)
-  // (the inverse-compositional objective carries (R, t) inside a level's launch only: likewise)
+  // (the inverse-compositional objectives carry (R, t) inside a level's launch only: likewise)
   if (o->engine->cfg.visualize_iterations && o->engine->objective != PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE &&
       o->engine->objective != PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC &&
-      o->engine->objective != PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL) {
+      o->engine->objective != PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL &&
+      o->engine->objective != PHOVO_OBJECTIVE_INVERSE_ROBUST) {
     const char *dir = std::getenv("PHOVO_VISUALIZE_DIR");
     if (dir && *dir) return optimize_visualized(o, dir);
   }
@@ -381,7 +402,21 @@ int phovo_odometry_optimize(phovo_odometry *o)
     st = phovo_engine_fetch_geometric_reports(o->engine, 1, &o->geo_report);
     if (st != PHOVO_OK) return st;
   }
+  o->have_rob_report = o->engine->objective == PHOVO_OBJECTIVE_INVERSE_ROBUST;
+  if (o->have_rob_report) {
+    st = phovo_engine_fetch_robust_reports(o->engine, 1, &o->rob_report);
+    if (st != PHOVO_OK) return st;
+  }
   o->optimized = true;
+  return PHOVO_OK;
+}
+
+int phovo_odometry_get_robust_report(const phovo_odometry *o, phovo_robust_report *report)
+{
+  if (!o || !report) return fail(PHOVO_E_INVALID_ARGUMENT, "get_robust_report: null");
+  if (!o->optimized) return fail(PHOVO_E_NOT_READY, "get_robust_report: Optimize has not run");
+  if (!o->have_rob_report) return fail(PHOVO_E_UNSUPPORTED, "get_robust_report: the last Optimize ran under another objective");
+  *report = o->rob_report;
   return PHOVO_OK;
 }
 
@@ -439,6 +474,8 @@ int phovo_odometry_get_pair_system(const phovo_odometry *o, phovo_pair_system *o
   if (o->engine->objective == PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL)
     return fail(PHOVO_E_UNSUPPORTED, "get_pair_system: the inverse-compositional objective has its system in "
                                      "phovo_odometry_get_inverse_system");
+  if (o->engine->objective == PHOVO_OBJECTIVE_INVERSE_ROBUST)
+    return fail(PHOVO_E_UNSUPPORTED, "get_pair_system: the robust inverse-compositional objective has no system call yet");
   if (!o->optimized) return fail(PHOVO_E_NOT_READY, "get_pair_system: Optimize has not run since the frames were set");
   const phovo_engine *e = o->engine;
   int finest = -1;                                        // the lowest level Optimize() iterates on
@@ -455,6 +492,8 @@ int phovo_odometry_get_sampled_system(const phovo_odometry *o, phovo_sampled_sys
   if (o->engine->objective == PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL)
     return fail(PHOVO_E_UNSUPPORTED, "get_sampled_system: the inverse-compositional objective has its system in "
                                      "phovo_odometry_get_inverse_system");
+  if (o->engine->objective == PHOVO_OBJECTIVE_INVERSE_ROBUST)
+    return fail(PHOVO_E_UNSUPPORTED, "get_sampled_system: the robust inverse-compositional objective has no system call yet");
   if (!o->optimized) return fail(PHOVO_E_NOT_READY, "get_sampled_system: Optimize has not run since the frames were set");
   const phovo_engine *e = o->engine;
   int finest = -1;                                        // the lowest level Optimize() iterates on

@@ -238,6 +238,17 @@ struct GNInverseArgs {
 int gn_inverse_wgs_per_cu();         // workgroups of the kernel that stay resident per CU
 int gn_inverse_lds_bytes();
 hipError_t gn_launch_level_inverse(const GNInverseArgs &args, int cu_count, hipStream_t stream);
+// Robust inverse-compositional form (gn_inverse_robust_kernel.hip, PHOVO_OBJECTIVE_INVERSE_ROBUST): the same rows, residual,
+// Jacobian and step, every row under a Huber weight whose threshold is scale_factor times the median of |r| over the pair's
+// rows, taken from a 4096-bin histogram in LDS and lagging one iteration.  256 threads.
+struct GNInverseRobustArgs {
+  GNLevelArgs lv;                    // (huber_delta and rec_off unused)
+  double scale_factor;               // phovo_robust_options: finite, > 0
+  phovo_robust_report *rob_reports;  // [pairs], zeroed before the first level
+};
+int gn_inverse_robust_wgs_per_cu();
+int gn_inverse_robust_lds_bytes();
+hipError_t gn_launch_level_inverse_robust(const GNInverseRobustArgs &args, int cu_count, hipStream_t stream);
 // Evaluation of that objective's system at given states, in the twist basis (gn_evaluate_inverse_kernels.hip,
 // phovo_engine_evaluate_inverse_pairs): fp64 planes, the tile form of gn_eval_sampled_pairs, gn_eval_tiles(n) tiles per
 // pair, no owner map, no ballots.  The source frame's gradient planes are read (a target upload's).

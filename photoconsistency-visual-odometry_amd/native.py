@@ -102,8 +102,9 @@ OBJECTIVE_PHOTOMETRIC, OBJECTIVE_BIOBJECTIVE, OBJECTIVE_TRUST_REGION = 0, 1, 2
 OBJECTIVE_PHOTOMETRIC_AFFINE = 3
 OBJECTIVE_PHOTOMETRIC_GEOMETRIC = 4
 OBJECTIVE_INVERSE_COMPOSITIONAL = 5
+OBJECTIVE_INVERSE_ROBUST = 6
 LAUNCH_KINDS = ("persistent", "fused", "slide", "slide_fallback", "wide", "bilinear", "biobjective", "trust_region",
-                "affine", "geometric", "inverse")
+                "affine", "geometric", "inverse", "inverse_robust")
 
 # phovo_trust_region_level.termination
 (TR_SKIPPED, TR_MAX_ITERATIONS, TR_GRADIENT, TR_FUNCTION, TR_PARAMETER, TR_MIN_RADIUS, TR_INVALID_STEP,
@@ -138,6 +139,16 @@ class GeometricReport(C.Structure):
     """phovo_geometric_report: depth rows and the two costs of every level's last system."""
     _fields_ = [("depth_rows", C.c_int32 * MAX_LEVELS), ("photometric_cost", C.c_double * MAX_LEVELS),
                 ("depth_cost", C.c_double * MAX_LEVELS)]
+
+
+class RobustOptions(C.Structure):
+    """phovo_robust_options: the robust inverse-compositional objective's delta = scale_factor * median |r|."""
+    _fields_ = [("scale_factor", C.c_double)]
+
+
+class RobustReport(C.Structure):
+    """phovo_robust_report: the Huber threshold and the outlier rows of every level's last system."""
+    _fields_ = [("delta", C.c_double * MAX_LEVELS), ("outliers", C.c_int32 * MAX_LEVELS)]
 
 
 GEOMETRIC_SYSTEM_LINE_CAPACITY = 1280
@@ -269,6 +280,13 @@ SYMBOLS = {
     "phovo_odometry_set_geometric_options": (C.c_int, [_vp, C.POINTER(GeometricOptions)]),
     "phovo_odometry_get_geometric_options": (C.c_int, [_vp, C.POINTER(GeometricOptions)]),
     "phovo_odometry_get_geometric_report": (C.c_int, [_vp, C.POINTER(GeometricReport)]),
+    "phovo_robust_options_default": (C.c_int, [C.POINTER(RobustOptions)]),
+    "phovo_engine_set_robust_options": (C.c_int, [_vp, C.POINTER(RobustOptions)]),
+    "phovo_engine_get_robust_options": (C.c_int, [_vp, C.POINTER(RobustOptions)]),
+    "phovo_engine_fetch_robust_reports": (C.c_int, [_vp, C.c_int, _vp]),
+    "phovo_odometry_set_robust_options": (C.c_int, [_vp, C.POINTER(RobustOptions)]),
+    "phovo_odometry_get_robust_options": (C.c_int, [_vp, C.POINTER(RobustOptions)]),
+    "phovo_odometry_get_robust_report": (C.c_int, [_vp, C.POINTER(RobustReport)]),
     "phovo_host_register": (C.c_int, [_vp, C.c_size_t]),
     "phovo_host_unregister": (C.c_int, [_vp]),
     "phovo_engine_reserve_frames": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int]),
@@ -498,6 +516,15 @@ def make_geometric_options(depth_weight=None, max_depth_residual=None):
         vals = [vals] * MAX_LEVELS if np.isscalar(vals) else list(vals)
         for i, v in enumerate(vals[:MAX_LEVELS]):
             arr[i] = float(v)
+    return opt
+
+
+def make_robust_options(scale_factor=None):
+    """phovo_robust_options_default, or with the given scale_factor."""
+    opt = RobustOptions()
+    check(lib().phovo_robust_options_default(C.byref(opt)), "phovo_robust_options_default")
+    if scale_factor is not None:
+        opt.scale_factor = float(scale_factor)
     return opt
 
 

@@ -436,6 +436,37 @@ class CPhotoconsistencyOdometryInverse(CPhotoconsistencyOdometryAnalytic):
         return ps
 
 
+class CPhotoconsistencyOdometryRobust(CPhotoconsistencyOdometryAnalytic):
+    """One frame pair at a time; not in the reference: the inverse-compositional aligner under a Huber weight whose
+    threshold is scale_factor times the median of |r| over the pair's own rows (native.OBJECTIVE_INVERSE_ROBUST, DESIGN.md
+    §22).  SetSourceFrame also builds the source's gradient planes.  Reads the analytic yml files; extensions and every
+    Get...System() call are refused (PHOVO_E_UNSUPPORTED)."""
+
+    def __init__(self, device=0):
+        super().__init__(device)
+        check(self._lib.phovo_odometry_set_objective(self._h, native.OBJECTIVE_INVERSE_ROBUST), "SetObjective")
+
+    def SetRobustOptions(self, opt):
+        """native.RobustOptions (native.make_robust_options)."""
+        check(self._lib.phovo_odometry_set_robust_options(self._h, C.byref(opt)), "SetRobustOptions")
+
+    def GetRobustOptions(self):
+        opt = native.RobustOptions()
+        check(self._lib.phovo_odometry_get_robust_options(self._h, C.byref(opt)), "GetRobustOptions")
+        return opt
+
+    def GetRobustReport(self):
+        """native.RobustReport of the last Optimize(): per level the delta and the outliers of the last system."""
+        rep = native.RobustReport()
+        check(self._lib.phovo_odometry_get_robust_report(self._h, C.byref(rep)), "GetRobustReport")
+        return rep
+
+
+# phovo_robust_report as a numpy record: one row of per-level fields per pair
+ROBUST_REPORT_DTYPE = np.dtype({"names": ["delta", "outliers"], "formats": [("<f8", (native.MAX_LEVELS,)), ("<i4", (native.MAX_LEVELS,))],
+                                "offsets": [native.RobustReport.delta.offset, native.RobustReport.outliers.offset],
+                                "itemsize": C.sizeof(native.RobustReport)})
+
 # phovo_geometric_report as a numpy record: one row of per-level fields per pair
 GEOMETRIC_REPORT_DTYPE = np.dtype([("depth_rows", "<i4", (native.MAX_LEVELS,)),
                                    ("photometric_cost", "<f8", (native.MAX_LEVELS,)),
@@ -697,6 +728,23 @@ class AlignmentEngine:
         out = np.zeros(int(n_pairs), dtype=GEOMETRIC_REPORT_DTYPE)
         check(self._lib.phovo_engine_fetch_geometric_reports(self._h, int(n_pairs), out.ctypes.data),
               "phovo_engine_fetch_geometric_reports")
+        return out
+
+    def set_robust_options(self, opt):
+        """native.RobustOptions (native.make_robust_options)."""
+        check(self._lib.phovo_engine_set_robust_options(self._h, C.byref(opt)), "phovo_engine_set_robust_options")
+
+    def get_robust_options(self):
+        opt = native.RobustOptions()
+        check(self._lib.phovo_engine_get_robust_options(self._h, C.byref(opt)), "phovo_engine_get_robust_options")
+        return opt
+
+    def fetch_robust_reports(self, n_pairs):
+        """The records of the last enqueue's pairs, which ran under native.OBJECTIVE_INVERSE_ROBUST, as one structured
+        numpy array of ROBUST_REPORT_DTYPE: out["delta"][p, L], out["outliers"][p, L]."""
+        out = np.zeros(int(n_pairs), dtype=ROBUST_REPORT_DTYPE)
+        check(self._lib.phovo_engine_fetch_robust_reports(self._h, int(n_pairs), out.ctypes.data),
+              "phovo_engine_fetch_robust_reports")
         return out
 
     def trust_region_reports(self, n):
