@@ -415,24 +415,33 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t frame_rsrc(const unsigned char
 // element of the plane that lies there (behind the frame it is 0 again, so nothing outside the frame is ever read).
 // Every read of that kind is a chunk-ahead prefetch or the tail of the last, partial chunk, whose lanes the in-image
 // mask drops; an owner of -1 is an offset of 4 GiB less 8 bytes and reads 0 with either descriptor.
+// plane_load_at takes the BYTE offset of the element instead of its index, for a caller that carries the offset itself: bit
+// 31 of an offset survives (an index loses it to the shift), and an offset with bit 31 set -- 2 GiB and more, past any
+// descriptor; the byte offset -1 of an owner map that holds offsets among them -- reads 0 like the index -1 does.  The
+// level kernels' residual of a pixel without an owner rests on that (gn_kernels.hip, pass 2).
 template <typename T>
-__device__ __forceinline__ double plane_load(__amdgpu_buffer_rsrc_t r, int idx, int soff = 0);
+__device__ __forceinline__ double plane_load_at(__amdgpu_buffer_rsrc_t r, int byte_off, int soff = 0);
 template <>
-__device__ __forceinline__ double plane_load<double>(__amdgpu_buffer_rsrc_t r, int idx, int soff)
+__device__ __forceinline__ double plane_load_at<double>(__amdgpu_buffer_rsrc_t r, int byte_off, int soff)
 {
-  const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(r, idx * 8, soff, 0);
+  const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(r, byte_off, soff, 0);
   return __hiloint2double((int)v.y, (int)v.x);
 }
 template <>
-__device__ __forceinline__ double plane_load<float>(__amdgpu_buffer_rsrc_t r, int idx, int soff)
+__device__ __forceinline__ double plane_load_at<float>(__amdgpu_buffer_rsrc_t r, int byte_off, int soff)
 {
-  return (double)__uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, idx * 4, soff, 0));
+  return (double)__uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, byte_off, soff, 0));
 }
 template <>
-__device__ __forceinline__ double plane_load<__half>(__amdgpu_buffer_rsrc_t r, int idx, int soff)
+__device__ __forceinline__ double plane_load_at<__half>(__amdgpu_buffer_rsrc_t r, int byte_off, int soff)
 {
-  const unsigned short bits = __builtin_amdgcn_raw_buffer_load_b16(r, idx * 2, soff, 0);
+  const unsigned short bits = __builtin_amdgcn_raw_buffer_load_b16(r, byte_off, soff, 0);
   return (double)__half2float(__ushort_as_half(bits));
+}
+template <typename T>
+__device__ __forceinline__ double plane_load(__amdgpu_buffer_rsrc_t r, int idx, int soff = 0)
+{
+  return plane_load_at<T>(r, idx * (int)sizeof(T), soff);
 }
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));

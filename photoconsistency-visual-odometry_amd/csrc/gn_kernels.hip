@@ -63,7 +63,8 @@ struct LevelLds {
   double *red;                 // [NW][NRED] one row of wave sums per wave
   int *ctl;                    // [CTL_COUNT]
   unsigned long long *mask;    // [n_chunks] in-bounds ballots (!MASK_REG)
-  int *owner;                  // owner map (OWNER_LDS) or its leading n_lds entries (owner map in HBM)
+  int *owner;                  // owner map (OWNER_LDS; without SRC_LDS its entries are byte offsets of the intensity plane:
+                               // level_body, KS) or its leading n_lds entries (owner map in HBM)
   double *i0;                  // [n] source intensity (SRC_LDS)
 };
 
@@ -111,6 +112,27 @@ __device__ __forceinline__ void level_body(const GNLevelArgs &A, const LevelLds 
   const __amdgpu_buffer_rsrc_t rS = frame_rsrc(src_frame, A.frame_bytes), rT = frame_rsrc(tgt_frame, A.frame_bytes);
   const int oI = (int)A.plane_off[PLANE_I], oD = (int)A.plane_off[PLANE_D];
   const int oGX = (int)A.plane_off[PLANE_GX], oGY = (int)A.plane_off[PLANE_GY];
+  // What a lane's running pixel counter counts in both passes.  With the owner map in LDS (and the source intensity in
+  // memory) it is the pixel's BYTE offset in an intensity plane, k * sizeof(TI), and that is also what the owner map holds:
+  // ds_max_i32 picks the same winner among offsets as among indices, -1 stays "nobody", the plane loads take the counter as
+  // their offset, the gather of I0 takes the owner entry as it is, and the owner slot and the parked depth of a pixel are a
+  // shift of it away -- one add per chunk where an index, its byte offset and the slot's address each had an instruction
+  // of their own.  Otherwise (SRC_LDS gathers from an array of doubles; the tagged entries of the map in HBM) it is the index.
+  constexpr bool BYTE_OWNER = OWNER_LDS && !SRC_LDS;
+  constexpr int KS = BYTE_OWNER ? (int)sizeof(TI) : 1;
+  auto depth_at = [&](const int kq) { return plane_load_at<TD>(rS, kq * (int)(sizeof(TD) / KS), oD); };
+  auto target_at = [&](const int kq, const int plane) { return plane_load_at<TI>(rT, kq * (int)(sizeof(TI) / KS), plane); };
+  auto park_slot = [&](const int kq) -> double & {
+    return *reinterpret_cast<double *>(reinterpret_cast<unsigned char *>(s_i0) + kq * (int)(sizeof(double) / KS));
+  };
+  // (the slot of the pixel `ahead` counts further on, `ahead` a constant: each term is scaled on its own, so that the constant
+  // one goes into the LDS instruction's offset field -- the NW rows of wave sums in front of s_owner take as many bytes as
+  // one round of the workgroup's chunks has slots, so the slot a round in front of a wave walking backwards is still a
+  // non-negative offset, 336)
+  auto owner_slot = [&](const int kq, const int ahead = 0) -> int & {
+    auto at = [](const int v) { return !BYTE_OWNER ? v * 4 : sizeof(TI) == 8 ? v >> 1 : sizeof(TI) == 4 ? v : v * 2; };
+    return *reinterpret_cast<int *>(reinterpret_cast<unsigned char *>(s_owner) + at(kq) + at(ahead));
+  };
 
   // ---- level prologue -------------------------------------------------------------------
   // (a level that follows another one in the same workgroup: every wave must have read the previous level's last
@@ -218,14 +240,14 @@ __device__ __forceinline__ void level_body(const GNLevelArgs &A, const LevelLds 
     int inb_lo = 0, inb_hi = 0;
     int n_rows = 0;                 // Jacobian rows this wave fills in this iteration (!MASK_REG: popcount of the ballots as they come)
     {
-      int k = k0, j = 0;
+      int k = k0 * KS, j = 0;                 // (k: the running pixel counter, in units of KS)
       PHOVO_ROWCOL_BEGIN
       // software prefetch: the depth of the NEXT chunk is requested before this chunk is processed, so
       // every wave keeps a load in flight while it computes (the passes are bound by bytes in flight per CU)
       // (PARK, after the first trip: a wave whose first chunk is parked finds that depth in the park block)
       double pz_next;
-      if (PARK && OWNER_LDS && !first_trip && wv < depth_chunks) pz_next = s_i0[k];      // wave-uniform
-      else pz_next = plane_load<TD>(rS, k, oD);
+      if (PARK && OWNER_LDS && !first_trip && wv < depth_chunks) pz_next = park_slot(k);      // wave-uniform
+      else pz_next = depth_at(k);
       // warp of one 64-pixel chunk: ballot of "valid and landed in bounds" and the target index of every lane
       auto warp_chunk = [&](const double pz, const int chunk, unsigned long long &m_out, int &t_out) {
         // No branch around the arithmetic: a lane that fails the depth gate computes on whatever it loaded and is
@@ -276,20 +298,20 @@ __device__ __forceinline__ void level_body(const GNLevelArgs &A, const LevelLds 
         // depth is stored there (both compile-time: the loops below exist in one copy per combination that occurs)
         auto chunk_body = [&](const int chunk, auto next_parked_tag, auto park_tag) {
           const double pz = pz_next;                                      // :279
-          if constexpr (decltype(next_parked_tag)::value) pz_next = s_i0[k + NW * WAVE];
-          else pz_next = plane_load<TD>(rS, k + NW * WAVE, oD);              // (past the plane: masked out)
+          if constexpr (decltype(next_parked_tag)::value) pz_next = park_slot(k + NW * WAVE * KS);
+          else pz_next = depth_at(k + NW * WAVE * KS);                       // (past the plane: masked out)
           // The depth plane is the one plane both passes read.  Whatever LDS this geometry leaves unused keeps the depth of
           // the image's LEADING chunks for pass 2 (the same lane reads back what it wrote); pass 2 walks backwards, so the
           // trailing chunks -- read last here -- still come from the XCD's L2.  The kernel is bound by bytes at the fabric.
           if constexpr (decltype(park_tag)::value) {
-            if (chunk < depth_chunks) s_i0[k] = pz;                       // (wave-uniform; s_i0: the block behind the owner map)
+            if (chunk < depth_chunks) park_slot(k) = pz;                  // (wave-uniform; s_i0: the block behind the owner map)
           }
           unsigned long long m;
           int t;
           warp_chunk(pz, chunk, m, t);
-          if (__builtin_amdgcn_inverse_ballot_w64(m)) atomicMax(&s_owner[t], k);     // last raster writer wins  :358
+          if (__builtin_amdgcn_inverse_ballot_w64(m)) atomicMax(&s_owner[t], k);     // last raster writer wins  :358 (k: BYTE_OWNER)
           keep_mask(m, chunk);
-          k += NW * WAVE;
+          k += NW * WAVE * KS;
           j++;
           PHOVO_ROWCOL_NEXT
         };
@@ -400,8 +422,8 @@ __device__ __forceinline__ void level_body(const GNLevelArgs &A, const LevelLds 
       constexpr bool REV = OWNER_LDS;
       const int my_chunks = wv < A.n_chunks ? (A.n_chunks - 1 - wv) / NW + 1 : 0;       // wave-uniform
       const int first = REV ? my_chunks - 1 : 0;                                            // position of the first chunk taken
-      const int k_step = REV ? -NW * WAVE : NW * WAVE;
-      int k = k0 + first * (NW * WAVE), j = first;
+      const int k_step = (REV ? -NW * WAVE : NW * WAVE) * KS;
+      int k = (k0 + first * (NW * WAVE)) * KS, j = first;            // (in units of KS, as in pass 1)
       double kd = kd0 + (double)first * kd_step, cd, rd;
       // software prefetch, as in pass 1: owner + four planes of the NEXT chunk are requested (and the
       // gathered source intensity right behind them) before this chunk's arithmetic starts.
@@ -429,9 +451,8 @@ __device__ __forceinline__ void level_body(const GNLevelArgs &A, const LevelLds 
           o_n = o_ahead;
           o_ahead = -1;
           if (another_behind) {                     // (walking backwards: not the chunk in front of the first)
-            const int k2 = kk + k_step;
-            o_ahead = s_owner[k2];                  // (past the image: the padding, -1)
-            s_owner[k2] = -1;                       // ready for the next iteration
+            o_ahead = owner_slot(kk, k_step);       // (past the image: the padding, -1)
+            owner_slot(kk, k_step) = -1;            // ready for the next iteration
           }
         } else {
           if (kk < n_lds) {                         // n_lds is a multiple of 64: the whole chunk is on one side
@@ -442,17 +463,22 @@ __device__ __forceinline__ void level_body(const GNLevelArgs &A, const LevelLds 
           }
           owner_request(kk + NW * WAVE);
         }
-        if constexpr (decltype(parked_tag)::value) pz_n = s_i0[max(kk, 0)];      // (kk < 0: the chunk in front of the first, unused)
-        else pz_n = plane_load<TD>(rS, kk, oD);
-        gx_n = plane_load<TI>(rT, kk, oGX);             // gradient at the SOURCE index  :346-347
-        gy_n = plane_load<TI>(rT, kk, oGY);
-        i1_n = plane_load<TI>(rT, kk, oI);             // :309
+        if constexpr (decltype(parked_tag)::value) pz_n = park_slot(max(kk, 0)); // (kk < 0: the chunk in front of the first, unused)
+        else pz_n = depth_at(kk);
+        gx_n = target_at(kk, oGX);                      // gradient at the SOURCE index  :346-347
+        gy_n = target_at(kk, oGY);
+        // :309.  A pixel nobody landed on has the residual 0 (:358): its lane asks for I1 at an offset with bit 31 set -- the
+        // sign of its owner entry, -1 -- which the descriptor's range check answers with 0, as it answers the gather of
+        // I0[-1] below, and the residual is the plain difference, 0 - 0 = +0: no compare and no select in the pixel loop,
+        // and no I1 bytes for those rows.  (SRC_LDS keeps the i0_n of the chunk before for such a lane, and the select.)
+        if (SRC_LDS) i1_n = target_at(kk, oI);
+        else i1_n = plane_load_at<TI>(rT, (kk * (int)(sizeof(TI) / KS)) | (o_n & (int)0x80000000), oI);
         if (SRC_LDS) { if (o_n >= 0) i0_n = s_i0[o_n]; }
-        else i0_n = plane_load<TI>(rS, o_n, oI);       // :308 of the owning source pixel (o = -1: offset past the plane -> 0)
+        else i0_n = plane_load_at<TI>(rS, o_n * (int)(sizeof(TI) / KS), oI);      // :308 of the owning source pixel (o = -1: an offset past the frame -> 0)
       };
       if (OWNER_LDS && my_chunks > 0) {
-        o_ahead = s_owner[k];
-        s_owner[k] = -1;
+        o_ahead = owner_slot(k);
+        owner_slot(k) = -1;
       }
       if (PARK && wv + first * NW < depth_chunks) fetch(k, std::true_type{}, my_chunks >= 2);
       else fetch(k, std::false_type{}, my_chunks >= 2);
@@ -466,7 +492,7 @@ __device__ __forceinline__ void level_body(const GNLevelArgs &A, const LevelLds 
                         (unsigned long long)(unsigned)__builtin_amdgcn_readlane(inb_lo, j))
                      : s_mask[chunk];
         if (__builtin_amdgcn_inverse_ballot_w64(mbits)) {                 // the ballot becomes the exec mask
-          const double res = (o >= 0) ? (pixel2 - pixel1) : 0.0;          // :358
+          const double res = SRC_LDS ? ((o >= 0) ? (pixel2 - pixel1) : 0.0) : pixel2 - pixel1;   // :358 (ownerless: 0 - 0, fetch)
           PHOVO_ROWCOL_HERE
           const double px = fma(cd, ifx, oxv2) * pz;
           const double py = fma(rd, ify, oyv2) * pz;
