@@ -4,6 +4,7 @@
 //   ./PhotoconsistencyVisualOdometry <config_file.yml> <rgbd_dataset_directory> <output_trajectory_file> [--batch [--gpus N] [--rccl]]
 //                                    [--method analytic|ceres|biobjective|inverse|robust|affine|geometric] [--information <file>] [--system <file>]
 //                                    [--geometric-system <file>] [--objective-system <file>] [--inverse-system <file>]
+//                                    [--robust-system <file>]
 // --method picks the aligner as the reference's USE_PHOTOCONSISTENCY_ODOMETRY_METHOD does (0 = analytic, the default;
 // 1 = ceres: Levenberg-Marquardt on bilinear samples, CPhotoconsistencyOdometryCeres, which reads config_*_ceres.yml
 // files; 2 = bi-objective: photometric and depth error together, CPhotoconsistencyOdometryBiObjective), in every mode;
@@ -15,8 +16,8 @@
 // source frame's own gradient, the step composed on SE(3)), CPhotoconsistencyOdometryInverse, which reads the analytic files;
 // its system is in the twist basis, so the four Euler-basis system flags below refuse it and --inverse-system writes it.
 // robust is not in the reference either: the inverse-compositional aligner under a Huber weight whose threshold follows the
-// median of the pair's own residuals, CPhotoconsistencyOdometryRobust, which reads the analytic files; it has no system
-// call yet, so all five system flags below refuse it.
+// median of the pair's own residuals, CPhotoconsistencyOdometryRobust, which reads the analytic files; its system carries
+// the weights, so the five older system flags below refuse it and --robust-system writes it.
 // A configuration file of the other kind is refused with a message that says so.
 // --information <file> (not in the reference; analytic method, one device): one line per pair, stamped like its trajectory
 // line, with the Gauss-Newton system at the pair's optimal state on the finest level the configuration optimises --
@@ -48,6 +49,13 @@
 // phovo_engine_evaluate_inverse_pairs).  The loop takes it from the class surface (GetInverseSystem), --batch from
 // phovo_engine_evaluate_inverse_pairs; both write the same bytes, the trajectory file is the same with and without the
 // flag, and the printed times do not include the evaluation.
+// --robust-system <file> (not in the reference; --method robust, one device): the same for the robust method -- one line per
+// pair, `timestamp rows outliers delta median cost huber_cost squared_cost`, the 6 entries of sum w J r and the 21
+// upper-triangle entries of sum w J J^T (phovo_robust_system_format) at the pair's optimal state on the finest optimised
+// level, with the Huber threshold taken from the median of the residuals at that state, in the twist basis of
+// --inverse-system (include/phovo_hip.h, phovo_engine_evaluate_robust_pairs).  The loop takes it from the class surface
+// (GetRobustSystem), --batch from phovo_engine_evaluate_robust_pairs; both write the same bytes, the trajectory file is the
+// same with and without the flag, and the printed times do not include the evaluation.
 //
 // Behaviour kept from the reference's app (apps/PhotoconsistencyVisualOdometry/PhotoconsistencyVisualOdometry.cpp):
 //   * <dir>/rgb.txt and <dir>/depth.txt are read in lock step -- line n of one is paired with line n of the
@@ -161,6 +169,14 @@ static bool writeSystem(std::ofstream &f, double timestamp, const phovo_pair_sys
   return true;
 }
 
+static bool writeSystem(std::ofstream &f, double timestamp, const phovo_robust_system &s)
+{
+  char line[1024];
+  if (phovo_robust_system_format(timestamp, &s, line, sizeof(line)) != PHOVO_OK) return false;
+  f << line << std::endl;
+  return true;
+}
+
 static bool writeSystem(std::ofstream &f, double timestamp, const phovo_sampled_system &s)
 {
   char line[1024];
@@ -214,12 +230,24 @@ static phovo_pair_system inverseSystemOf(Odometry &, long)
   throw std::runtime_error("--inverse-system needs --method inverse");
 }
 
+// GetRobustSystem() of the class that has one, in the same way.
+template <class Odometry>
+static auto robustSystemOf(Odometry &odometry, int) -> decltype(odometry.GetRobustSystem())
+{
+  return odometry.GetRobustSystem();
+}
+template <class Odometry>
+static phovo_robust_system robustSystemOf(Odometry &, long)
+{
+  throw std::runtime_error("--robust-system needs --method robust");
+}
+
 static void printHelp()
 {
   std::cout << "./PhotoconsistencyVisualOdometry <config_file.yml> <rgbd_dataset_directory> "
                "<output_trajectory_file> [--batch [--gpus N] [--rccl]] [--method analytic|ceres|biobjective|inverse|robust|affine|geometric] "
                "[--information <file>] [--system <file>] [--geometric-system <file>] [--objective-system <file>] "
-               "[--inverse-system <file>]" << std::endl;
+               "[--inverse-system <file>] [--robust-system <file>]" << std::endl;
 }
 
 #define PHOVO_OK_OR_FAIL(call)                                                              \
@@ -238,6 +266,7 @@ int main(int argc, char *argv[])
   std::string geometricSystemPath;                    // --geometric-system <file>: the same for --method geometric
   std::string objectiveSystemPath;                    // --objective-system <file>: the same for --method ceres | biobjective
   std::string inverseSystemPath;                      // --inverse-system <file>: the same for --method inverse (twist basis)
+  std::string robustSystemPath;                       // --robust-system <file>: the same for --method robust (weighted, twist basis)
   for (int i = 4; i < argc; i++) {
     const std::string a(argv[i]);
     if (a == "--batch") batch = true;
@@ -259,6 +288,7 @@ int main(int argc, char *argv[])
     else if (a == "--geometric-system" && i + 1 < argc) geometricSystemPath = argv[++i];
     else if (a == "--objective-system" && i + 1 < argc) objectiveSystemPath = argv[++i];
     else if (a == "--inverse-system" && i + 1 < argc) inverseSystemPath = argv[++i];
+    else if (a == "--robust-system" && i + 1 < argc) robustSystemPath = argv[++i];
     else { printHelp(); return EXIT_FAILURE; }
   }
   if (nGpus < 1 || (nGpus > 1 && !batch)) { std::cerr << "--gpus N needs --batch and N >= 1" << std::endl; return EXIT_FAILURE; }
@@ -307,6 +337,15 @@ int main(int argc, char *argv[])
   }
   if (inverseSystem && objective != PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL) {
     std::cerr << "--inverse-system needs --method inverse" << std::endl;
+    return EXIT_FAILURE;
+  }
+  const bool robustSystem = !robustSystemPath.empty();
+  if (robustSystem && (nGpus > 1 || rccl)) {
+    std::cerr << "--robust-system runs on one device: it cannot be combined with --gpus N > 1 or --rccl" << std::endl;
+    return EXIT_FAILURE;
+  }
+  if (robustSystem && objective != PHOVO_OBJECTIVE_INVERSE_ROBUST) {
+    std::cerr << "--robust-system needs --method robust" << std::endl;
     return EXIT_FAILURE;
   }
   if (!fileExists(configFile)) { std::cerr << "Input config file " << configFile << " does not exist" << std::endl; return EXIT_FAILURE; }
@@ -379,6 +418,11 @@ int main(int argc, char *argv[])
     inverseSystemFile.open(inverseSystemPath.c_str());
     if (!inverseSystemFile.is_open()) { std::cerr << "Cannot open output inverse system file " << inverseSystemPath << std::endl; return EXIT_FAILURE; }
   }
+  std::ofstream robustSystemFile;
+  if (robustSystem) {
+    robustSystemFile.open(robustSystemPath.c_str());
+    if (!robustSystemFile.is_open()) { std::cerr << "Cannot open output robust system file " << robustSystemPath << std::endl; return EXIT_FAILURE; }
+  }
   if (nFrames < 2) return EXIT_SUCCESS;
 
   Matrix44Type pose = Matrix44Type::Identity();
@@ -415,6 +459,7 @@ int main(int argc, char *argv[])
         if (geometricSystem && !writeSystem(geometricSystemFile, rgb[t].timestamp, geometricSystemOf(odometry, 0))) return EXIT_FAILURE;
         if (objectiveSystem && !writeSystem(objectiveSystemFile, rgb[t].timestamp, objectiveSystemOf(odometry, 0))) return EXIT_FAILURE;
         if (inverseSystem && !writeSystem(inverseSystemFile, rgb[t].timestamp, inverseSystemOf(odometry, 0))) return EXIT_FAILURE;
+        if (robustSystem && !writeSystem(robustSystemFile, rgb[t].timestamp, robustSystemOf(odometry, 0))) return EXIT_FAILURE;
         std::cout << "Rt:" << std::endl << Rt << std::endl;
         prevGray = curGray.clone();
         prevDepth = curDepth.clone();
@@ -526,6 +571,8 @@ int main(int argc, char *argv[])
       if (objectiveSystem && finestLevel < 0) { std::cerr << "--objective-system: the configuration optimises no level" << std::endl; return EXIT_FAILURE; }
       if (inverseSystem && finestLevel < 0) { std::cerr << "--inverse-system: the configuration optimises no level" << std::endl; return EXIT_FAILURE; }
       std::vector<phovo_pair_system> inverseSystems(inverseSystem ? (size_t)nPairs : 0);
+      if (robustSystem && finestLevel < 0) { std::cerr << "--robust-system: the configuration optimises no level" << std::endl; return EXIT_FAILURE; }
+      std::vector<phovo_robust_system> robustSystems(robustSystem ? (size_t)nPairs : 0);
       std::vector<phovo_pair_system> objectiveSystems(objectiveSystem ? (size_t)nPairs : 0);
       std::vector<phovo_geometric_system> geometricSystems(geometricSystem ? (size_t)nPairs : 0);
       const int systemDim = objective == PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE ? 8 : 6;
@@ -582,8 +629,11 @@ int main(int argc, char *argv[])
           if (!rccl) {
             if (phovo_engine_align_pairs(engine, b - a, src.data(), tgt.data(), nullptr, states.data() + (size_t)a * 6, nullptr) != PHOVO_OK)
               return fail("phovo_engine_align_pairs");
-            if (information || sampled || geometricSystem || objectiveSystem || inverseSystem)
+            if (information || sampled || geometricSystem || objectiveSystem || inverseSystem || robustSystem)
               tAligned = std::chrono::steady_clock::now();                    // (the evaluation is not part of the timed run)
+            if (robustSystem && phovo_engine_evaluate_robust_pairs(engine, b - a, src.data(), tgt.data(), states.data() + (size_t)a * 6,
+                                                                   nullptr, finestLevel, robustSystems.data() + a) != PHOVO_OK)
+              return fail("phovo_engine_evaluate_robust_pairs");
             if (inverseSystem && phovo_engine_evaluate_inverse_pairs(engine, b - a, src.data(), tgt.data(), states.data() + (size_t)a * 6,
                                                                      finestLevel, inverseSystems.data() + a) != PHOVO_OK)
               return fail("phovo_engine_evaluate_inverse_pairs");
@@ -642,7 +692,7 @@ int main(int argc, char *argv[])
           std::copy(group.gathered(g), group.gathered(g) + (size_t)(b - a) * 6, states.begin() + (size_t)a * 6);
         }
       }
-      const auto t1 = (information || sampled || geometricSystem || objectiveSystem || inverseSystem) ? tAligned : std::chrono::steady_clock::now();
+      const auto t1 = (information || sampled || geometricSystem || objectiveSystem || inverseSystem || robustSystem) ? tAligned : std::chrono::steady_clock::now();
       std::cout << "Time = " << std::chrono::duration<double>(t1 - t0).count() << " sec. (" << nPairs << " pairs on " << nGpus
                 << " device(s), upload and pyramids included)" << std::endl;
       std::vector<double> poses((size_t)nPairs * 16);
@@ -656,6 +706,7 @@ int main(int argc, char *argv[])
         if (geometricSystem && !writeSystem(geometricSystemFile, rgb[(size_t)p + 1].timestamp, geometricSystems[(size_t)p])) return EXIT_FAILURE;
         if (objectiveSystem && !writeSystem(objectiveSystemFile, rgb[(size_t)p + 1].timestamp, objectiveSystems[(size_t)p])) return EXIT_FAILURE;
         if (inverseSystem && !writeSystem(inverseSystemFile, rgb[(size_t)p + 1].timestamp, inverseSystems[(size_t)p])) return EXIT_FAILURE;
+        if (robustSystem && !writeSystem(robustSystemFile, rgb[(size_t)p + 1].timestamp, robustSystems[(size_t)p])) return EXIT_FAILURE;
       }
     }
   } catch (const std::exception &e) {
@@ -668,5 +719,6 @@ int main(int argc, char *argv[])
   if (geometricSystem) geometricSystemFile.close();
   if (objectiveSystem) objectiveSystemFile.close();
   if (inverseSystem) inverseSystemFile.close();
+  if (robustSystem) robustSystemFile.close();
   return EXIT_SUCCESS;
 }

@@ -9,7 +9,8 @@
 // The types come from the same place as CPhotoconsistencyOdometryAnalytic.h's (PHOVO_HIP_USE_REFERENCE_TYPES or
 // phovo/compat/).  ReadConfigurationFile reads the config_*_analytic.yml keys.  SetSourceFrame also builds the source's
 // gradient planes.  Extensions are refused (std::runtime_error, PHOVO_E_UNSUPPORTED), and so are the inherited
-// GetPairSystem() and GetSampledSystem(): this objective's weighted system has no call yet.
+// GetPairSystem() and GetSampledSystem(), which speak the Euler basis; this objective's weighted system is
+// GetRobustSystem(), in the twist basis.
 #ifndef PHOVO_HIP_CPHOTOCONSISTENCY_ODOMETRY_ROBUST_H
 #define PHOVO_HIP_CPHOTOCONSISTENCY_ODOMETRY_ROBUST_H
 
@@ -52,6 +53,17 @@ class CPhotoconsistencyOdometryRobust : public CPhotoconsistencyOdometryAnalytic
     phovo_robust_report r;
     Base::Check(phovo_odometry_get_robust_report(Base::Handle(), &r), "GetRobustReport");
     return r;
+  }
+  // The weighted system at the optimal state on the finest level the configuration optimises, with the median rule taken
+  // at that state: sum w J J^T and sum w J r in the twist basis (nu, omega) of the right-hand perturbation T Exp(xi) (xi in
+  // the SOURCE camera's frame), sum w r^2, the Huber and the squared cost, delta, the median, rows and outliers
+  // (phovo_engine_evaluate_robust_pairs has the contract).  Evaluated on demand; std::runtime_error
+  // (PHOVO_E_NOT_READY) before Optimize() and after a Set*Frame since.
+  phovo_robust_system GetRobustSystem() const
+  {
+    phovo_robust_system s;
+    Base::Check(phovo_odometry_get_robust_system(Base::Handle(), &s), "GetRobustSystem");
+    return s;
   }
 };
 

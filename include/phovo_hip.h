@@ -314,9 +314,10 @@ typedef struct phovo_extensions {
  *                                frames need PHOVO_ROLE_BOTH (else PHOVO_E_NOT_READY), as under objective 5; switching between
  *                                objectives 0, 2, 3, 4, 5 and 6 keeps the frame pool.  Supported: fp64 planes, the default
  *                                sampling setting, no huber_delta extension, jacobian_corrected 0 -- anything else is
- *                                PHOVO_E_UNSUPPORTED, whichever setter comes second.  All five phovo_engine_evaluate_* calls
- *                                and the phovo_odometry_get_*_system calls are PHOVO_E_UNSUPPORTED under this objective (its
- *                                weighted system is not built yet).  phovo_pair_report keeps its meaning. */
+ *                                PHOVO_E_UNSUPPORTED, whichever setter comes second.  Its weighted system, in the twist basis, is
+ *                                phovo_engine_evaluate_robust_pairs / phovo_odometry_get_robust_system; the five other
+ *                                phovo_engine_evaluate_* calls and their phovo_odometry_get_*_system calls stay
+ *                                PHOVO_E_UNSUPPORTED under this objective.  phovo_pair_report keeps its meaning. */
 #define PHOVO_OBJECTIVE_INVERSE_ROBUST 6
 
 /* Option of the robust inverse-compositional objective: delta = scale_factor * (median of |r|).  The default,
@@ -331,6 +332,21 @@ typedef struct phovo_robust_report {
   double  delta[PHOVO_MAX_LEVELS];              /* the Huber threshold that system was built with */
   int32_t outliers[PHOVO_MAX_LEVELS];           /* its rows with fabs(r) > delta */
 } phovo_robust_report;
+
+/* The weighted Gauss-Newton system of one frame pair under the robust inverse-compositional objective at a given state on
+ * one level (phovo_engine_evaluate_robust_pairs, which has the contract; phovo_odometry_get_robust_system). */
+typedef struct phovo_robust_system {
+  double   information[36];  /* sum w J J^T, twist basis (nu, omega) of T Exp(xi), row-major, exactly symmetric */
+  double   gradient[6];      /* sum w J r */
+  double   cost;             /* sum w r^2            (r^T W r, as phovo_pair_system.cost under a Huber weight) */
+  double   huber_cost;       /* sum (|r| <= delta ? r^2 : 2 delta |r| - delta^2)   = 2 sum rho_delta(r) */
+  double   squared_cost;     /* sum r^2 */
+  double   delta;            /* the threshold the weights were built with */
+  double   median;           /* m of the median rule at this state; 0 when deltas were given */
+  int32_t  rows, outliers;   /* rows as valid_pixels counts them; rows with fabs(r) > delta */
+  uint32_t flags;            /* PHOVO_PAIR_RANK_DEFICIENT if rows < 6; PHOVO_PAIR_NONFINITE if any sum is inf/NaN */
+  int32_t  reserved;         /* 0 */
+} phovo_robust_system;
 
 /* Options of the photometric-geometric objective, per level.  Both are settings to tune for the sensor and the scene, not
  * measured optima: depth_weight trades metres of depth error against intensity error (intensities are in [0, 1]), and
@@ -483,6 +499,11 @@ int phovo_trajectory_format_pose(double timestamp, const double pose[16], char *
  * s->information in row-major order (H00 H01 .. H05 H11 .. H55), every double as "%.17g" (round-trips exactly), no
  * newline.  Host only.  PHOVO_E_INVALID_ARGUMENT for NULL pointers or if `capacity` is too small (640 always suffices). */
 int phovo_pair_system_format(double timestamp, const phovo_pair_system *s, char *line, size_t capacity);
+/* One line of the VisualOdometry app's --robust-system file: `timestamp rows outliers delta median cost huber_cost
+ * squared_cost`, the 6 entries of s->gradient and the 21 upper-triangle entries of s->information in row-major order, every
+ * double as "%.17g" (round-trips exactly), no newline.  Host only.  PHOVO_E_INVALID_ARGUMENT for NULL pointers or if
+ * `capacity` is too small (1024 always suffices: 33 doubles of at most 24 characters, two integers, 34 blanks). */
+int phovo_robust_system_format(double timestamp, const phovo_robust_system *s, char *line, size_t capacity);
 
 /* One line of the VisualOdometry app's --system file: `timestamp rows cost dim` and the dim (dim + 1) / 2 upper-triangle
  * entries of s->information in row-major order, every double as "%.17g" (round-trips exactly), no newline.  Host only.
@@ -586,6 +607,11 @@ int phovo_odometry_get_objective_system(const phovo_odometry *o, phovo_pair_syst
  * contract: a right-hand twist in the source camera's frame).  PHOVO_E_UNSUPPORTED under any other objective;
  * PHOVO_E_NOT_READY before a successful Optimize() and after a Set*Frame since. */
 int phovo_odometry_get_inverse_system(const phovo_odometry *o, phovo_pair_system *out);
+/* not in the reference: the weighted twist-basis system (phovo_robust_system) of the robust inverse-compositional
+ * objective at the optimal state on the finest level the configuration optimises, with the median rule taken at that state
+ * (phovo_engine_evaluate_robust_pairs with deltas == NULL has the contract), evaluated on demand.  PHOVO_E_UNSUPPORTED under
+ * any other objective; PHOVO_E_NOT_READY before a successful Optimize() and after a Set*Frame since. */
+int phovo_odometry_get_robust_system(const phovo_odometry *o, phovo_robust_system *out);
 /* Device time of the last Optimize() in milliseconds (HIP events; the reference wraps the same
  * call in cv::TickMeter, apps/PhotoconsistencyFrameAlignment/PhotoconsistencyFrameAlignment.cpp:99-102). */
 int phovo_odometry_last_optimize_ms(const phovo_odometry *o, double *ms);
@@ -948,6 +974,38 @@ int phovo_engine_evaluate_objective_pairs(phovo_engine *e, int n_pairs, const in
  * sums take at most 64 MB (873 pairs at 640x480). */
 int phovo_engine_evaluate_inverse_pairs(phovo_engine *e, int n_pairs, const int *src, const int *tgt,
                                         const double *states /* [n_pairs][6] */, int level, phovo_pair_system *out);
+
+/* The WEIGHTED system of PHOVO_OBJECTIVE_INVERSE_ROBUST in the TWIST basis, at the states [n_pairs][6] on one level
+ * (DESIGN.md §23).  Synchronous; ordered behind every enqueue in flight, and it changes nothing that phovo_engine_fetch /
+ * fetch_results / fetch_robust_reports return.
+ *   pose, rows, r, J   exactly phovo_engine_evaluate_inverse_pairs': (R, t) = eigenPose(state), the aligner's rows,
+ *             r = I1(u, v) - I0, J = (a, p x a), columns (nu_x, nu_y, nu_z, omega_x, omega_y, omega_z) of the right-hand
+ *             perturbation T Exp(xi) in the source camera's frame.
+ *   delta     deltas == NULL: delta = scale_factor * m, with m the objective's median rule (4096 bins,
+ *             q = fabs(r) * 4096.0, bin q < 4096.0 ? (int)q : 4095, half = (n + 1) / 2, the same fp64 expression in the
+ *             same order) on the residuals of THIS state and scale_factor from phovo_engine_set_robust_options; n = 0
+ *             gives m = 0, delta = 0 and all sums zero.
+ *             deltas != NULL: every entry finite and > 0 (else PHOVO_E_INVALID_ARGUMENT, before any launch); the weights
+ *             use deltas[k], `delta` echoes it bit for bit, `median` is 0, and no histogram pass runs.  That is H(delta)
+ *             for a caller's own threshold, and the system of any later iteration of the aligner at a state and the delta
+ *             that phovo_robust_report names.
+ *   sums      w = fabs(r) <= delta ? 1.0 : delta / fabs(r) (a true fp64 division); the record's fields below.  A NaN
+ *             residual lands in the last bin and is counted in n; it is no outlier; it poisons the sums
+ *             (PHOVO_PAIR_NONFINITE).
+ * Relation to the aligner: its threshold lags one iteration and delta_1 = delta_0, the median at the entry pose, so the
+ * system the aligner solves in the FIRST iteration of a level started at `state` is this record at `state` with
+ * deltas == NULL, up to summation order.
+ * Counts are integers and sums are taken in an order that depends on the level size only: a pair's record is the same bit
+ * for bit whatever the batch, its position in it, the group split, or any setting of the engine.
+ *   PHOVO_E_UNSUPPORTED       any objective but PHOVO_OBJECTIVE_INVERSE_ROBUST
+ *   PHOVO_E_INVALID_ARGUMENT  as phovo_engine_evaluate_inverse_pairs; a deltas entry that is not finite and > 0
+ *   PHOVO_E_NOT_READY         as phovo_engine_evaluate_inverse_pairs (source frames need PHOVO_ROLE_BOTH)
+ * n_pairs == 0 is OK.  Device memory: the evaluate workspace -- per pair of a group 256 bytes of tile sums per 1024 pixels,
+ * 16 KiB of histogram and 16 bytes for (m, delta); large batches run in groups that take at most 64 MB of these (720 pairs
+ * at 640x480). */
+int phovo_engine_evaluate_robust_pairs(phovo_engine *e, int n_pairs, const int *src, const int *tgt,
+                                       const double *states /* [n_pairs][6] */, const double *deltas /* [n_pairs] or NULL */,
+                                       int level, phovo_robust_system *out);
 
 /* Pipelining. Pairs are independent, and with data-dependent termination a batch ends with a few long pairs on an
  * otherwise idle chip.  The engine therefore keeps PHOVO_ENQUEUE_DEPTH enqueues in flight, each with its own stream, pair

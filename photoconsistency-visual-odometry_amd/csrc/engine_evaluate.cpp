@@ -1,10 +1,13 @@
 // The Gauss-Newton systems at given poses behind the C ABI (include/phovo_hip.h): phovo_engine_evaluate_pairs,
-// _evaluate_sampled_pairs, _evaluate_geometric_pairs, _evaluate_objective_pairs and _evaluate_inverse_pairs.  Each entry point keeps what is its own -- the objectives and
+// _evaluate_sampled_pairs, _evaluate_geometric_pairs, _evaluate_objective_pairs, _evaluate_inverse_pairs and
+// _evaluate_robust_pairs.  Each entry point keeps what is its own -- the objectives and
 // samplings it refuses, its state width, its workspace regions, the extras of its args and its launch -- and shares the
 // rest: the refusals about the call, the one workspace, and the loop over groups of pairs.
 
 #include <algorithm>
+#include <cmath>
 #include <string>
+#include <vector>
 
 #include "engine_internal.hpp"
 
@@ -183,7 +186,8 @@ int phovo_engine_evaluate_sampled_pairs(phovo_engine *e, int n_pairs, const int 
     return fail(PHOVO_E_UNSUPPORTED, "evaluate_sampled_pairs: the inverse-compositional objective has its system in "
                                      "phovo_engine_evaluate_inverse_pairs");
   if (e->objective == PHOVO_OBJECTIVE_INVERSE_ROBUST)
-    return fail(PHOVO_E_UNSUPPORTED, "evaluate_sampled_pairs: the robust inverse-compositional objective has no system call yet");
+    return fail(PHOVO_E_UNSUPPORTED, "evaluate_sampled_pairs: the robust inverse-compositional objective has its system in "
+                                     "phovo_engine_evaluate_robust_pairs");
   const bool affine = e->objective == PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE;
   if (!affine && e->ext.sampling != PHOVO_SAMPLING_BILINEAR)
     return fail(PHOVO_E_UNSUPPORTED, "evaluate_sampled_pairs: nearest / scatter sampling has its system in "
@@ -275,7 +279,8 @@ int phovo_engine_evaluate_objective_pairs(phovo_engine *e, int n_pairs, const in
       return fail(PHOVO_E_UNSUPPORTED, "evaluate_objective_pairs: the inverse-compositional objective has its system in "
                                        "phovo_engine_evaluate_inverse_pairs");
     case PHOVO_OBJECTIVE_INVERSE_ROBUST:
-      return fail(PHOVO_E_UNSUPPORTED, "evaluate_objective_pairs: the robust inverse-compositional objective has no system call yet");
+      return fail(PHOVO_E_UNSUPPORTED, "evaluate_objective_pairs: the robust inverse-compositional objective has its system in "
+                                       "phovo_engine_evaluate_robust_pairs");
     default:
       return fail(PHOVO_E_UNSUPPORTED, "evaluate_objective_pairs: the photometric-geometric objective has its system in "
                                        "phovo_engine_evaluate_geometric_pairs");
@@ -343,6 +348,55 @@ int phovo_engine_evaluate_inverse_pairs(phovo_engine *e, int n_pairs, const int 
   auto *d_out = reinterpret_cast<phovo_pair_system *>(at[4]);
   return eval_run(e, c, group, at + 1, d_out, [&](int pairs) {
     return gn_eval_inverse_pairs(a, pairs, d_part, d_out, e->stream);
+  });
+}
+
+int phovo_engine_evaluate_robust_pairs(phovo_engine *e, int n_pairs, const int *src, const int *tgt, const double *states,
+                                       const double *deltas, int level, phovo_robust_system *out)
+{
+  if (!e) return fail(PHOVO_E_INVALID_ARGUMENT, "evaluate_robust_pairs: null engine");
+  if (e->objective != PHOVO_OBJECTIVE_INVERSE_ROBUST)
+    return fail(PHOVO_E_UNSUPPORTED, "evaluate_robust_pairs: the robust inverse-compositional objective only (the others have "
+                                     "phovo_engine_evaluate_pairs, _evaluate_sampled_pairs, _evaluate_geometric_pairs, "
+                                     "_evaluate_objective_pairs and _evaluate_inverse_pairs)");
+  // (set_objective / set_extensions hold this objective to fp64 planes without the huber_delta extension)
+  const EvalCall c{"evaluate_robust_pairs", n_pairs, src, tgt, states, 6, level, out, sizeof(*out)};
+  if (deltas && c.n_pairs >= 0 && src && tgt && states && out) {          // (eval_check refuses the rest below, in its order)
+    for (int i = 0; i < n_pairs; i++)
+      if (!(deltas[i] > 0.0) || !std::isfinite(deltas[i]))
+        return fail(PHOVO_E_INVALID_ARGUMENT, "evaluate_robust_pairs: a delta is not finite and > 0");
+  }
+  int st = eval_check(e, c, false, true);
+  if (st != PHOVO_OK || n_pairs == 0) return st;
+
+  // Workspace for a group of G pairs: tile sums, states, pair indices, the histograms, (m, delta) and the results.
+  const size_t slab_bytes = gn_eval_slab_doubles_per_pair(e->levels[level].n) * sizeof(double);
+  const size_t hist_bytes = 4096 * sizeof(unsigned), md_bytes = 2 * sizeof(double);
+  const int group = eval_group(n_pairs, EVAL_SAMPLED_SLAB_CAP_BYTES, slab_bytes + hist_bytes + md_bytes);
+  const size_t G = (size_t)group;
+  const size_t bytes[] = {G * slab_bytes, G * 6 * sizeof(double), G * sizeof(int), G * sizeof(int), G * hist_bytes,
+                          G * md_bytes, G * sizeof(phovo_robust_system)};
+  unsigned char *at[7];
+  st = eval_workspace(e, bytes, at, 0);
+  if (st != PHOVO_OK) return st;
+
+  GNInverseEvalArgs a{};
+  eval_args(a, e, level, at + 1);
+  auto *d_part = reinterpret_cast<double *>(at[0]);
+  auto *d_hist = reinterpret_cast<unsigned *>(at[4]);
+  auto *d_md = reinterpret_cast<double *>(at[5]);
+  auto *d_out = reinterpret_cast<phovo_robust_system *>(at[6]);
+  // The caller's deltas travel with the states, as (0, delta) per pair: the place the median kernel would have written.
+  std::vector<double> md(deltas ? 2 * (size_t)n_pairs : 0);
+  for (size_t i = 0; i < md.size() / 2; i++) { md[2 * i] = 0.0; md[2 * i + 1] = deltas[i]; }
+  int g0 = 0;                                                             // eval_run's groups come in order
+  return eval_run(e, c, group, at + 1, d_out, [&](int pairs) {
+    if (deltas) {
+      const hipError_t up = hipMemcpyAsync(d_md, md.data() + 2 * (size_t)g0, md_bytes * (size_t)pairs, hipMemcpyHostToDevice, e->stream);
+      if (up != hipSuccess) return up;
+    }
+    g0 += pairs;
+    return gn_eval_robust_pairs(a, pairs, e->rob_opt.scale_factor, deltas != nullptr, d_hist, d_md, d_part, d_out, e->stream);
   });
 }
 

@@ -1,6 +1,6 @@
-// The tile scaffold of the five "system at a given state" kernel files (gn_evaluate_kernels.hip,
+// The tile scaffold of the six "system at a given state" kernel files (gn_evaluate_kernels.hip,
 // gn_evaluate_sampled_kernels.hip, gn_evaluate_geometric_kernels.hip, gn_evaluate_objective_kernels.hip,
-// gn_evaluate_inverse_kernels.hip), included by those five and by nothing else.
+// gn_evaluate_inverse_kernels.hip, gn_evaluate_robust_kernels.hip), included by those six and by nothing else.
 //
 // The form (the wide form's shape, gn_wide_kernels.hip): a pair is cut into tiles of 16 64-pixel chunks, one 256-thread
 // workgroup per tile, grid (tiles, pairs of the group), and the kernel boundary is the only synchronisation (no grid
@@ -13,7 +13,7 @@
 //                    sums are added in subset order, and one wave writes the record
 // The tile count and every summation order depend on the level size only: a pair's record is the same bit for bit
 // whatever the batch, its position in it, the group split, or any setting of the engine.  That promise rests on every
-// kernel of the five files having this geometry and these orders, which is why they stand here once.
+// kernel of the six files having this geometry and these orders, which is why they stand here once.
 //
 // Everything is __forceinline__ in an anonymous namespace, as in gn_device.hpp.  The first half (geometry, pose preamble,
 // row sums, tile sums, finish) holds explicit fma() and plain adds only, so it means the same under

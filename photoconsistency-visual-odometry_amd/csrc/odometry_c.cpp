@@ -475,7 +475,8 @@ int phovo_odometry_get_pair_system(const phovo_odometry *o, phovo_pair_system *o
     return fail(PHOVO_E_UNSUPPORTED, "get_pair_system: the inverse-compositional objective has its system in "
                                      "phovo_odometry_get_inverse_system");
   if (o->engine->objective == PHOVO_OBJECTIVE_INVERSE_ROBUST)
-    return fail(PHOVO_E_UNSUPPORTED, "get_pair_system: the robust inverse-compositional objective has no system call yet");
+    return fail(PHOVO_E_UNSUPPORTED, "get_pair_system: the robust inverse-compositional objective has its system in "
+                                     "phovo_odometry_get_robust_system");
   if (!o->optimized) return fail(PHOVO_E_NOT_READY, "get_pair_system: Optimize has not run since the frames were set");
   const phovo_engine *e = o->engine;
   int finest = -1;                                        // the lowest level Optimize() iterates on
@@ -493,7 +494,8 @@ int phovo_odometry_get_sampled_system(const phovo_odometry *o, phovo_sampled_sys
     return fail(PHOVO_E_UNSUPPORTED, "get_sampled_system: the inverse-compositional objective has its system in "
                                      "phovo_odometry_get_inverse_system");
   if (o->engine->objective == PHOVO_OBJECTIVE_INVERSE_ROBUST)
-    return fail(PHOVO_E_UNSUPPORTED, "get_sampled_system: the robust inverse-compositional objective has no system call yet");
+    return fail(PHOVO_E_UNSUPPORTED, "get_sampled_system: the robust inverse-compositional objective has its system in "
+                                     "phovo_odometry_get_robust_system");
   if (!o->optimized) return fail(PHOVO_E_NOT_READY, "get_sampled_system: Optimize has not run since the frames were set");
   const phovo_engine *e = o->engine;
   int finest = -1;                                        // the lowest level Optimize() iterates on
@@ -556,6 +558,23 @@ int phovo_odometry_get_inverse_system(const phovo_odometry *o, phovo_pair_system
   if (finest < 0) return fail(PHOVO_E_NOT_READY, "get_inverse_system: the configuration optimises no level");
   const int src = 0, tgt = 1;
   return phovo_engine_evaluate_inverse_pairs(o->engine, 1, &src, &tgt, o->state, finest, out);
+}
+
+int phovo_odometry_get_robust_system(const phovo_odometry *o, phovo_robust_system *out)
+{
+  if (!o || !out) return fail(PHOVO_E_INVALID_ARGUMENT, "get_robust_system: null");
+  const phovo_engine *e = o->engine;
+  if (e->objective != PHOVO_OBJECTIVE_INVERSE_ROBUST)
+    return fail(PHOVO_E_UNSUPPORTED, "get_robust_system: the robust inverse-compositional objective only (the others have "
+                                     "phovo_odometry_get_pair_system, _get_sampled_system, _get_geometric_system, "
+                                     "_get_objective_system and _get_inverse_system)");
+  if (!o->optimized) return fail(PHOVO_E_NOT_READY, "get_robust_system: Optimize has not run since the frames were set");
+  int finest = -1;                                        // the lowest level Optimize() iterates on
+  for (int l = e->cfg.num_levels - 1; l >= 0; l--)
+    if (e->cfg.max_num_iterations[l] > 0) finest = l;
+  if (finest < 0) return fail(PHOVO_E_NOT_READY, "get_robust_system: the configuration optimises no level");
+  const int src = 0, tgt = 1;
+  return phovo_engine_evaluate_robust_pairs(o->engine, 1, &src, &tgt, o->state, nullptr, finest, out);
 }
 
 int phovo_odometry_last_optimize_ms(const phovo_odometry *o, double *ms)

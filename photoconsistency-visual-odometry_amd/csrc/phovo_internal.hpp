@@ -265,6 +265,12 @@ struct GNInverseEvalArgs {
 // g_part: [n_pairs][gn_eval_slab_doubles_per_pair(n)]; out: [n_pairs] on the device.
 hipError_t gn_eval_inverse_pairs(const GNInverseEvalArgs &a, int n_pairs, double *g_part, phovo_pair_system *out,
                                  hipStream_t stream);
+// The weighted system of the robust inverse-compositional objective at given states (gn_evaluate_robust_kernels.hip,
+// phovo_engine_evaluate_robust_pairs): the same args and tile form.  g_hist: [n_pairs][4096] words, cleared here on the
+// stream in front of the histogram launch; g_md: [n_pairs][2] doubles (m, delta) -- written by the median kernel, or, with
+// deltas_given, filled by the caller with (0, delta) before the call, and then neither g_hist nor scale_factor is used.
+hipError_t gn_eval_robust_pairs(const GNInverseEvalArgs &a, int n_pairs, double scale_factor, bool deltas_given,
+                                unsigned *g_hist, double *g_md, double *g_part, phovo_robust_system *out, hipStream_t stream);
 // Sliding-window form for levels whose owner map exceeds LDS (gn_slide_kernel.hip): owner ring in LDS; pairs whose
 // motion leaves the window are appended to args.handover_out for a follow-up gn_launch_level that takes that list.
 hipError_t gn_prepare_slide_kernels();

@@ -72,6 +72,30 @@ int phovo_pair_system_format(double timestamp, const phovo_pair_system *s, char 
   return PHOVO_OK;
 }
 
+// One line of the app's --robust-system file (include/phovo_hip.h): every double as %.17g, which round-trips.
+int phovo_robust_system_format(double timestamp, const phovo_robust_system *s, char *line, size_t capacity)
+{
+  if (!s || !line) return fail(PHOVO_E_INVALID_ARGUMENT, "robust_system_format: null");
+  std::string out;
+  char buf[192];
+  std::snprintf(buf, sizeof(buf), "%.17g %d %d %.17g %.17g %.17g %.17g %.17g", timestamp, (int)s->rows, (int)s->outliers,
+                s->delta, s->median, s->cost, s->huber_cost, s->squared_cost);
+  out += buf;
+  for (int a = 0; a < 6; a++) {
+    std::snprintf(buf, sizeof(buf), " %.17g", s->gradient[a]);
+    out += buf;
+  }
+  for (int a = 0; a < 6; a++)
+    for (int b = a; b < 6; b++) {
+      std::snprintf(buf, sizeof(buf), " %.17g", s->information[6 * a + b]);
+      out += buf;
+    }
+  if (out.size() + 1 > capacity) return fail(PHOVO_E_INVALID_ARGUMENT, "robust_system_format: buffer too small");
+  out.copy(line, out.size());
+  line[out.size()] = '\0';
+  return PHOVO_OK;
+}
+
 // One line of the app's --system file (include/phovo_hip.h): every double as %.17g, which round-trips.
 int phovo_sampled_system_format(double timestamp, const phovo_sampled_system *s, char *line, size_t capacity)
 {

@@ -151,6 +151,24 @@ class RobustReport(C.Structure):
     _fields_ = [("delta", C.c_double * MAX_LEVELS), ("outliers", C.c_int32 * MAX_LEVELS)]
 
 
+class RobustSystem(C.Structure):
+    """phovo_robust_system: the weighted twist-basis system of one pair under the robust inverse-compositional objective at a
+    given state on one level, with the threshold it was built with, the three costs and the outlier count."""
+    _fields_ = [
+        ("information", C.c_double * 36),
+        ("gradient", C.c_double * 6),
+        ("cost", C.c_double),
+        ("huber_cost", C.c_double),
+        ("squared_cost", C.c_double),
+        ("delta", C.c_double),
+        ("median", C.c_double),
+        ("rows", C.c_int32),
+        ("outliers", C.c_int32),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_int32),
+    ]
+
+
 GEOMETRIC_SYSTEM_LINE_CAPACITY = 1280
 
 
@@ -218,6 +236,7 @@ SYMBOLS = {
     "phovo_trajectory_chain": (C.c_int, [C.c_int, _vp, _dp, _vp]),
     "phovo_trajectory_format_pose": (C.c_int, [C.c_double, _dp, C.c_char_p, C.c_size_t]),
     "phovo_pair_system_format": (C.c_int, [C.c_double, C.POINTER(PairSystem), C.c_char_p, C.c_size_t]),
+    "phovo_robust_system_format": (C.c_int, [C.c_double, C.POINTER(RobustSystem), C.c_char_p, C.c_size_t]),
     "phovo_sampled_system_format": (C.c_int, [C.c_double, C.POINTER(SampledSystem), C.c_char_p, C.c_size_t]),
     "phovo_geometric_system_format": (C.c_int, [C.c_double, C.POINTER(GeometricSystem), C.c_char_p, C.c_size_t]),
     "phovo_warp_image": (C.c_int, [C.c_int, _vp, C.c_size_t, _vp, C.c_size_t, C.c_int, C.c_int, _dp, _dp, C.c_int,
@@ -245,6 +264,7 @@ SYMBOLS = {
     "phovo_odometry_get_geometric_system": (C.c_int, [_vp, C.POINTER(GeometricSystem)]),
     "phovo_odometry_get_objective_system": (C.c_int, [_vp, C.POINTER(PairSystem)]),
     "phovo_odometry_get_inverse_system": (C.c_int, [_vp, C.POINTER(PairSystem)]),
+    "phovo_odometry_get_robust_system": (C.c_int, [_vp, C.POINTER(RobustSystem)]),
     "phovo_engine_create": (C.c_int, [C.c_int, C.POINTER(_vp)]),
     "phovo_engine_destroy": (C.c_int, [_vp]),
     "phovo_engine_set_config": (C.c_int, [_vp, C.POINTER(Config)]),
@@ -325,6 +345,7 @@ SYMBOLS = {
     "phovo_engine_evaluate_geometric_pairs": (C.c_int, [_vp, C.c_int, _ip, _ip, _vp, C.c_int, _vp]),
     "phovo_engine_evaluate_objective_pairs": (C.c_int, [_vp, C.c_int, _ip, _ip, _vp, C.c_int, _vp]),
     "phovo_engine_evaluate_inverse_pairs": (C.c_int, [_vp, C.c_int, _ip, _ip, _vp, C.c_int, _vp]),
+    "phovo_engine_evaluate_robust_pairs": (C.c_int, [_vp, C.c_int, _ip, _ip, _vp, _vp, C.c_int, _vp]),
 }
 
 
@@ -459,6 +480,13 @@ def format_pair_system(timestamp, system):
     """phovo_pair_system_format: the line the VisualOdometry app writes per pair with --information."""
     buf = C.create_string_buffer(1024)
     check(lib().phovo_pair_system_format(float(timestamp), C.byref(system), buf, len(buf)), "phovo_pair_system_format")
+    return buf.value.decode()
+
+
+def format_robust_system(timestamp, system):
+    """phovo_robust_system_format: the line the VisualOdometry app writes per pair with --robust-system."""
+    buf = C.create_string_buffer(1024)
+    check(lib().phovo_robust_system_format(float(timestamp), C.byref(system), buf, len(buf)), "phovo_robust_system_format")
     return buf.value.decode()
 
 

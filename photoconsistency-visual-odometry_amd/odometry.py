@@ -455,6 +455,14 @@ class CPhotoconsistencyOdometryRobust(CPhotoconsistencyOdometryAnalytic):
         check(self._lib.phovo_odometry_get_robust_options(self._h, C.byref(opt)), "GetRobustOptions")
         return opt
 
+    def GetRobustSystem(self):
+        """native.RobustSystem at the optimal state on the finest level the configuration optimises, with the median rule
+        taken at that state: sum w J J^T, sum w J r in the twist basis of GetInverseSystem(), the three costs, delta, the
+        median, rows and outliers; evaluated on demand after Optimize()."""
+        rs = native.RobustSystem()
+        check(self._lib.phovo_odometry_get_robust_system(self._h, C.byref(rs)), "GetRobustSystem")
+        return rs
+
     def GetRobustReport(self):
         """native.RobustReport of the last Optimize(): per level the delta and the outliers of the last system."""
         rep = native.RobustReport()
@@ -508,6 +516,13 @@ GEOMETRIC_SYSTEM_DTYPE = np.dtype([("information", "<f8", (36,)), ("gradient", "
                                    ("photometric_cost", "<f8"), ("depth_cost", "<f8"), ("rows", "<i4"),
                                    ("depth_rows", "<i4"), ("flags", "<u4"), ("reserved", "<i4")])
 assert GEOMETRIC_SYSTEM_DTYPE.itemsize == C.sizeof(native.GeometricSystem)
+
+
+# phovo_robust_system as a numpy record (the layout of native.RobustSystem): evaluate_robust_pairs fills an array of these
+ROBUST_SYSTEM_DTYPE = np.dtype([("information", "<f8", (36,)), ("gradient", "<f8", (6,)), ("cost", "<f8"),
+                                ("huber_cost", "<f8"), ("squared_cost", "<f8"), ("delta", "<f8"), ("median", "<f8"),
+                                ("rows", "<i4"), ("outliers", "<i4"), ("flags", "<u4"), ("reserved", "<i4")])
+assert ROBUST_SYSTEM_DTYPE.itemsize == C.sizeof(native.RobustSystem)
 
 
 class AlignmentEngine:
@@ -870,6 +885,38 @@ class AlignmentEngine:
                    cost=out["cost"].copy(), rows=out["rows"].astype(np.int64), flags=out["flags"].astype(np.int64))
         if want_structs:
             res["structs"] = list((native.PairSystem * n).from_buffer_copy(out.tobytes()))
+        return res
+
+    def evaluate_robust_pairs(self, src, tgt, states, level, deltas=None, want_structs=False):
+        """The weighted twist-basis system of each (source, target) pair under the robust inverse-compositional objective
+        at states [n, 6] on `level` (phovo_engine_evaluate_robust_pairs).  deltas None: the threshold is scale_factor times
+        the median of |r| at that state; deltas [n], every entry finite and > 0: the caller's own (then median is 0).
+        Returns what evaluate_inverse_pairs returns -- information [n, 6, 6], gradient [n, 6], cost [n], rows [n],
+        flags [n] -- plus huber_cost, squared_cost, delta, median [n] and outliers [n] (with want_structs, also the
+        native.RobustSystem records under "structs")."""
+        s, t = self._pairs(src, tgt)
+        n = s.size
+        st = np.ascontiguousarray(states, dtype=np.float64).reshape(n, 6)
+        dl = None
+        if deltas is not None:
+            dl = np.ascontiguousarray(deltas, dtype=np.float64).reshape(-1)
+            if dl.size != n:
+                raise ValueError("evaluate_robust_pairs: deltas must have one entry per pair")
+            if not (np.all(np.isfinite(dl)) and np.all(dl > 0.0)):
+                raise ValueError("evaluate_robust_pairs: every delta must be finite and > 0")
+        out = np.zeros(max(n, 1), dtype=ROBUST_SYSTEM_DTYPE)       # the C records, written in place
+        ip = C.POINTER(C.c_int)
+        check(self._lib.phovo_engine_evaluate_robust_pairs(self._h, n, s.ctypes.data_as(ip), t.ctypes.data_as(ip),
+                                                           st.ctypes.data, None if dl is None else dl.ctypes.data,
+                                                           int(level), out.ctypes.data),
+              "phovo_engine_evaluate_robust_pairs")
+        out = out[:n]
+        res = dict(information=out["information"].reshape(n, 6, 6).copy(), gradient=out["gradient"].copy(),
+                   cost=out["cost"].copy(), rows=out["rows"].astype(np.int64), flags=out["flags"].astype(np.int64),
+                   huber_cost=out["huber_cost"].copy(), squared_cost=out["squared_cost"].copy(),
+                   delta=out["delta"].copy(), median=out["median"].copy(), outliers=out["outliers"].astype(np.int64))
+        if want_structs:
+            res["structs"] = list((native.RobustSystem * n).from_buffer_copy(out.tobytes()))
         return res
 
     def evaluate_sampled_pairs(self, src, tgt, states, level, want_structs=False):
