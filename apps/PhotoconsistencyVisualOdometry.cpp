@@ -4,7 +4,7 @@
 //   ./PhotoconsistencyVisualOdometry <config_file.yml> <rgbd_dataset_directory> <output_trajectory_file> [--batch [--gpus N] [--rccl]]
 //                                    [--method analytic|ceres|biobjective|inverse|robust|affine|geometric] [--information <file>] [--system <file>]
 //                                    [--geometric-system <file>] [--objective-system <file>] [--inverse-system <file>]
-//                                    [--robust-system <file>]
+//                                    [--robust-system <file>] [--prior-weight <wt>,<wr>]
 // --method picks the aligner as the reference's USE_PHOTOCONSISTENCY_ODOMETRY_METHOD does (0 = analytic, the default;
 // 1 = ceres: Levenberg-Marquardt on bilinear samples, CPhotoconsistencyOdometryCeres, which reads config_*_ceres.yml
 // files; 2 = bi-objective: photometric and depth error together, CPhotoconsistencyOdometryBiObjective), in every mode;
@@ -49,6 +49,11 @@
 // phovo_engine_evaluate_inverse_pairs).  The loop takes it from the class surface (GetInverseSystem), --batch from
 // phovo_engine_evaluate_inverse_pairs; both write the same bytes, the trajectory file is the same with and without the
 // flag, and the printed times do not include the evaluation.
+// --prior-weight <wt>,<wr> (not in the reference; --method inverse | robust, the pair-by-pair loop): a constant-velocity
+// Gaussian prior on every pair's pose (include/phovo_hip.h, phovo_prior_options) -- the prior pose is the
+// previous pair's result, zero for the first pair, and Lambda = diag(wt, wt, wt, wr, wr, wr) in the twist order (nu, omega);
+// every pair's record (phovo_prior_report_format) goes to the standard output.  Refused with --batch, where no pair knows the
+// one before it, and under the other methods.  With 0,0 the trajectory file is the one without the flag, byte for byte.
 // --robust-system <file> (not in the reference; --method robust, one device): the same for the robust method -- one line per
 // pair, `timestamp rows outliers delta median cost huber_cost squared_cost`, the 6 entries of sum w J r and the 21
 // upper-triangle entries of sum w J J^T (phovo_robust_system_format) at the pair's optimal state on the finest optimised
@@ -77,6 +82,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <cstdlib>
 #include <fstream>
 #include <iomanip>
@@ -242,12 +248,35 @@ static phovo_robust_system robustSystemOf(Odometry &, long)
   throw std::runtime_error("--robust-system needs --method robust");
 }
 
+// SetPosePrior() / GetPriorReport() of the classes that have them, in the same way.
+template <class Odometry>
+static auto setPosePriorOf(Odometry &odometry, const double *state, const double *information, int)
+    -> decltype(odometry.SetPosePrior(state, information), void())
+{
+  odometry.SetPosePrior(state, information);
+}
+template <class Odometry>
+static void setPosePriorOf(Odometry &, const double *, const double *, long)
+{
+  throw std::runtime_error("--prior-weight needs --method inverse or --method robust");
+}
+template <class Odometry>
+static auto priorReportOf(Odometry &odometry, int) -> decltype(odometry.GetPriorReport())
+{
+  return odometry.GetPriorReport();
+}
+template <class Odometry>
+static phovo_prior_report priorReportOf(Odometry &, long)
+{
+  throw std::runtime_error("--prior-weight needs --method inverse or --method robust");
+}
+
 static void printHelp()
 {
   std::cout << "./PhotoconsistencyVisualOdometry <config_file.yml> <rgbd_dataset_directory> "
                "<output_trajectory_file> [--batch [--gpus N] [--rccl]] [--method analytic|ceres|biobjective|inverse|robust|affine|geometric] "
                "[--information <file>] [--system <file>] [--geometric-system <file>] [--objective-system <file>] "
-               "[--inverse-system <file>] [--robust-system <file>]" << std::endl;
+               "[--inverse-system <file>] [--robust-system <file>] [--prior-weight <wt>,<wr>]" << std::endl;
 }
 
 #define PHOVO_OK_OR_FAIL(call)                                                              \
@@ -267,9 +296,24 @@ int main(int argc, char *argv[])
   std::string objectiveSystemPath;                    // --objective-system <file>: the same for --method ceres | biobjective
   std::string inverseSystemPath;                      // --inverse-system <file>: the same for --method inverse (twist basis)
   std::string robustSystemPath;                       // --robust-system <file>: the same for --method robust (weighted, twist basis)
+  bool priorWeight = false;                           // --prior-weight <wt>,<wr>: a constant-velocity pose prior (loop mode)
+  double priorWt = 0.0, priorWr = 0.0;
   for (int i = 4; i < argc; i++) {
     const std::string a(argv[i]);
     if (a == "--batch") batch = true;
+    else if (a == "--prior-weight" && i + 1 < argc) {
+      const char *text = argv[++i];
+      char *end = nullptr;
+      priorWt = std::strtod(text, &end);
+      const bool comma = end != text && *end == ',';
+      const char *second = comma ? end + 1 : end;
+      priorWr = comma ? std::strtod(second, &end) : 0.0;
+      if (!comma || end == second || *end != '\0' || !std::isfinite(priorWt) || !std::isfinite(priorWr) || priorWt < 0.0 || priorWr < 0.0) {
+        std::cerr << "--prior-weight needs <wt>,<wr>: two finite numbers >= 0" << std::endl;
+        return EXIT_FAILURE;
+      }
+      priorWeight = true;
+    }
     else if (a == "--method" && i + 1 < argc) {
       const std::string m(argv[++i]);
       if (m == "analytic") objective = PHOVO_OBJECTIVE_PHOTOMETRIC;
@@ -346,6 +390,14 @@ int main(int argc, char *argv[])
   }
   if (robustSystem && objective != PHOVO_OBJECTIVE_INVERSE_ROBUST) {
     std::cerr << "--robust-system needs --method robust" << std::endl;
+    return EXIT_FAILURE;
+  }
+  if (priorWeight && batch) {
+    std::cerr << "--prior-weight runs pair by pair (the prior is the previous pair's result): it cannot be combined with --batch" << std::endl;
+    return EXIT_FAILURE;
+  }
+  if (priorWeight && objective != PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL && objective != PHOVO_OBJECTIVE_INVERSE_ROBUST) {
+    std::cerr << "--prior-weight needs --method inverse or --method robust" << std::endl;
     return EXIT_FAILURE;
   }
   if (!fileExists(configFile)) { std::cerr << "Input config file " << configFile << " does not exist" << std::endl; return EXIT_FAILURE; }
@@ -437,6 +489,9 @@ int main(int argc, char *argv[])
       if (!loadGray(rgb[0].path, prevGray) || !loadDepth16(depth[0].path, d16)) return EXIT_FAILURE;
       prevDepth.create(d16.height, d16.width);
       for (size_t i = 0; i < d16.pixels.size(); i++) prevDepth.data[i] = (double)d16.pixels[i] * depthScalingFactor;
+      Vector6Type priorState = Vector6Type::Zero();                          // --prior-weight: the previous pair's result
+      double priorInformation[36] = {};
+      for (int d = 0; d < 6; d++) priorInformation[7 * d] = d < 3 ? priorWt : priorWr;
       for (size_t t = 1; t < nFrames; t++) {
         if (!loadGray(rgb[t].path, curGray) || !loadDepth16(depth[t].path, d16)) return EXIT_FAILURE;
         curDepth.create(d16.height, d16.width);
@@ -445,6 +500,7 @@ int main(int argc, char *argv[])
         odometry.SetSourceFrame(prevGray, prevDepth);                        // :222-224
         odometry.SetTargetFrame(curGray, curDepth);
         odometry.SetInitialStateVector(Vector6Type::Zero());
+        if (priorWeight) setPosePriorOf(odometry, priorState.data(), priorInformation, 0);
         const auto t0 = std::chrono::steady_clock::now();
         odometry.Optimize();
         const auto t1 = std::chrono::steady_clock::now();
@@ -452,6 +508,13 @@ int main(int argc, char *argv[])
 
         const Matrix44Type Rt = odometry.GetOptimalRigidTransformationMatrix();
         const Vector6Type state = odometry.GetOptimalStateVector();
+        if (priorWeight) {
+          const phovo_prior_report report = priorReportOf(odometry, 0);
+          char line[256];
+          PHOVO_OK_OR_FAIL(phovo_prior_report_format(rgb[t].timestamp, &report, line, sizeof(line)));
+          std::cout << "Prior: " << line << std::endl;
+          priorState = state;
+        }
         PHOVO_OK_OR_FAIL(phovo_trajectory_chain(1, state.data(), pose.data(), nullptr));   // pose *= Rt^-1  :233-234
         if (!writePose(trajectoryFile, rgb[t].timestamp, pose)) return EXIT_FAILURE;
         if (information && !writeSystem(informationFile, rgb[t].timestamp, odometry.GetPairSystem())) return EXIT_FAILURE;

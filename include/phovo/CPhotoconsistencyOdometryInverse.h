@@ -46,6 +46,34 @@ class CPhotoconsistencyOdometryInverse : public CPhotoconsistencyOdometryAnalyti
     Base::Check(phovo_odometry_get_inverse_system(Base::Handle(), &s), "GetInverseSystem");
     return s;
   }
+
+  // A Gaussian pose prior for every later Optimize() until ClearPosePrior() (phovo_hip.h, phovo_prior_options; DESIGN.md
+  // §24): state = (x, y, z, yaw, pitch, roll) of the prior pose, information row-major 6 x 6 in the twist order (nu, omega)
+  // of GetInverseSystem(), its upper triangle read.  std::runtime_error (PHOVO_E_INVALID_ARGUMENT) for a non-finite entry
+  // or a negative diagonal.
+  void SetPosePrior(const double state[6], const double information[36])
+  {
+    Base::Check(phovo_odometry_set_pose_prior(Base::Handle(), state, information), "SetPosePrior");
+  }
+  void ClearPosePrior() { Base::Check(phovo_odometry_clear_pose_prior(Base::Handle()), "ClearPosePrior"); }
+  // The per-level scale s_L of the prior (default 1 on every level).
+  void SetPriorOptions(const phovo_prior_options &opt)
+  {
+    Base::Check(phovo_odometry_set_prior_options(Base::Handle(), &opt), "SetPriorOptions");
+  }
+  phovo_prior_options GetPriorOptions() const
+  {
+    phovo_prior_options opt;
+    Base::Check(phovo_odometry_get_prior_options(Base::Handle(), &opt), "GetPriorOptions");
+    return opt;
+  }
+  // e = Log(T_p^-1 T) and e^T Lambda e at the optimal state of the last Optimize(), which carried a prior.
+  phovo_prior_report GetPriorReport() const
+  {
+    phovo_prior_report r;
+    Base::Check(phovo_odometry_get_prior_report(Base::Handle(), &r), "GetPriorReport");
+    return r;
+  }
 };
 
 }  // namespace Analytic

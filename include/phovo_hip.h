@@ -348,6 +348,34 @@ typedef struct phovo_robust_system {
   int32_t  reserved;         /* 0 */
 } phovo_robust_system;
 
+/* A Gaussian pose prior for objectives 5 and 6 (phovo_engine_enqueue_align_prior, phovo_odometry_set_pose_prior; not in the
+ * reference; DESIGN.md §24 has the contract).  Each pair gets a prior pose, a state (x, y, z, yaw, pitch, roll) with
+ * T_p = eigenPose(state) = (R_p, t_p), and a symmetric 6 x 6 information matrix Lambda in the twist order (nu, omega) of the
+ * right-hand perturbation T Exp(xi) -- the basis phovo_engine_evaluate_inverse_pairs returns.  Each level L has a scale s_L
+ * (phovo_prior_options.level_scale).  In every iteration, before the solve, with the level's current (R, t):
+ *     e   = Log(T_p^-1 T) = Log(R_p^T R, R_p^T (t - t_p)), a twist;
+ *     H'  = H + s_L Lambda,   g' = g + s_L Lambda e;
+ *     xi  = -lambda_L H'^-1 g', composed as without a prior.
+ * The prior's Jacobian is taken as the identity (first order in e, as in Kerl et al.'s dense RGB-D odometry): the fixed
+ * point satisfies g + s_L Lambda e = 0, not the exact stationarity condition with the right Jacobian of Log.  Termination and
+ * the reported gradient_norm use ||g'||_2.  PHOVO_PAIR_RANK_DEFICIENT keeps its meaning (a system with fewer than 6 data
+ * rows, sticky); the pose may now be finite beside it.  Under objective 6, H and g are the weighted sums; the median, delta
+ * and the outlier count do not see the prior.
+ *   Log(R, t):  w = vee(R - R^T) / 2, s = |w|, c = (tr R - 1) / 2, th = atan2(s, c), omega = (th / s) w,
+ *               nu = (I - W / 2 + D W^2) t with W = [omega]x and D = (1 - (th / 2) cot(th / 2)) / th^2; below th^2 = 1e-8
+ *               th / s = 1 + th^2 / 6 + 7 th^4 / 360 and D = 1 / 12 + th^2 / 720 + th^4 / 30240.  Relative rotations beyond
+ *               3.0 rad between prior and pose are outside the accuracy contract; the result is finite wherever s != 0.
+ * With Lambda = 0, or s_L = 0, the two additions are skipped and every output bit equals the call without a prior. */
+typedef struct phovo_prior_options {
+  double level_scale[PHOVO_MAX_LEVELS];         /* s_L: finite and >= 0; default 1 on every level */
+} phovo_prior_options;
+
+/* Per pair, at the pose the finest executed level ended on (all 0 when no level ran). */
+typedef struct phovo_prior_report {
+  double error[6];                              /* e = Log(T_p^-1 T), twist order (nu, omega) */
+  double prior_cost;                            /* e^T Lambda e (without s_L); 0 where Lambda = 0 */
+} phovo_prior_report;
+
 /* Options of the photometric-geometric objective, per level.  Both are settings to tune for the sensor and the scene, not
  * measured optima: depth_weight trades metres of depth error against intensity error (intensities are in [0, 1]), and
  * max_depth_residual is the occlusion gate -- without one, depth rows across a depth discontinuity pull the pose away
@@ -504,6 +532,10 @@ int phovo_pair_system_format(double timestamp, const phovo_pair_system *s, char 
  * double as "%.17g" (round-trips exactly), no newline.  Host only.  PHOVO_E_INVALID_ARGUMENT for NULL pointers or if
  * `capacity` is too small (1024 always suffices: 33 doubles of at most 24 characters, two integers, 34 blanks). */
 int phovo_robust_system_format(double timestamp, const phovo_robust_system *s, char *line, size_t capacity);
+/* One line for a phovo_prior_report: `timestamp prior_cost` and the 6 entries of r->error, every double as "%.17g"
+ * (round-trips exactly), no newline.  Host only.  PHOVO_E_INVALID_ARGUMENT for NULL pointers or if `capacity` is too small
+ * (256 always suffices). */
+int phovo_prior_report_format(double timestamp, const phovo_prior_report *r, char *line, size_t capacity);
 
 /* One line of the VisualOdometry app's --system file: `timestamp rows cost dim` and the dim (dim + 1) / 2 upper-triangle
  * entries of s->information in row-major order, every double as "%.17g" (round-trips exactly), no newline.  Host only.
@@ -565,6 +597,16 @@ int phovo_odometry_get_geometric_report(const phovo_odometry *o, phovo_geometric
 int phovo_odometry_set_robust_options(phovo_odometry *o, const phovo_robust_options *opt);
 int phovo_odometry_get_robust_options(const phovo_odometry *o, phovo_robust_options *opt);
 int phovo_odometry_get_robust_report(const phovo_odometry *o, phovo_robust_report *report);
+/* Gaussian pose prior (phovo_prior_options above has the rule): the prior of every later Optimize() until it is cleared or
+ * set again -- state[6] the prior pose, information[36] row-major with its upper triangle read; a non-finite entry or a
+ * negative diagonal is PHOVO_E_INVALID_ARGUMENT.  It may be set under any objective; Optimize() with a prior set is
+ * PHOVO_E_UNSUPPORTED under any objective but 5 and 6.  The level scales (default 1; kept under every objective) and the
+ * record of the last Optimize() (PHOVO_E_NOT_READY before a successful one; PHOVO_E_UNSUPPORTED if it ran without a prior). */
+int phovo_odometry_set_pose_prior(phovo_odometry *o, const double state[6], const double information[36]);
+int phovo_odometry_clear_pose_prior(phovo_odometry *o);
+int phovo_odometry_set_prior_options(phovo_odometry *o, const phovo_prior_options *opt);
+int phovo_odometry_get_prior_options(const phovo_odometry *o, phovo_prior_options *opt);
+int phovo_odometry_get_prior_report(const phovo_odometry *o, phovo_prior_report *report);
 int phovo_odometry_set_min_depth(phovo_odometry *o, double min_depth);     /* :448 */
 int phovo_odometry_set_max_depth(phovo_odometry *o, double max_depth);     /* :454 */
 int phovo_odometry_set_intrinsic_matrix(phovo_odometry *o, const double k[9]);     /* :460, row-major 3x3 */
@@ -713,6 +755,14 @@ int phovo_engine_fetch_geometric_reports(phovo_engine *e, int n_pairs, phovo_geo
 int phovo_engine_set_robust_options(phovo_engine *e, const phovo_robust_options *opt);
 int phovo_engine_get_robust_options(const phovo_engine *e, phovo_robust_options *opt);
 int phovo_engine_fetch_robust_reports(phovo_engine *e, int n_pairs, phovo_robust_report *reports);
+/* Gaussian pose prior: the level scales (kept under every objective, used by phovo_engine_enqueue_align_prior; every
+ * level_scale must be finite and >= 0, else PHOVO_E_INVALID_ARGUMENT; phovo_prior_options_default: 1 everywhere) and the
+ * per-pair records of the LAST enqueue, with the call-order rules of phovo_engine_fetch_robust_reports
+ * (PHOVO_E_UNSUPPORTED if the last enqueue carried no prior). */
+int phovo_prior_options_default(phovo_prior_options *opt);
+int phovo_engine_set_prior_options(phovo_engine *e, const phovo_prior_options *opt);
+int phovo_engine_get_prior_options(const phovo_engine *e, phovo_prior_options *opt);
+int phovo_engine_fetch_prior_reports(phovo_engine *e, int n_pairs, phovo_prior_report *reports);
 
 /* Page-locks (and releases) a host buffer the caller will hand to the upload entry points repeatedly: uploads from
  * registered memory are direct DMA at the link rate instead of going through the runtime's bounce buffers.  Optional;
@@ -860,6 +910,22 @@ int phovo_engine_align_pairs(phovo_engine *e, int n_pairs,
 int phovo_engine_enqueue_align(phovo_engine *e, int n_pairs,
                                const int *source_frames, const int *target_frames,
                                const double *init_states);
+/* phovo_engine_enqueue_align under a Gaussian pose prior per pair (phovo_prior_options above has the rule): the same
+ * ticket, slot and ordering rules, and the prior travels with the enqueue -- two enqueues in flight keep their own.
+ *   prior_states  n_pairs x 6: the prior poses, T_p = eigenPose(state)
+ *   information   n_pairs x 36: Lambda row-major, twist order (nu, omega); the UPPER triangle is read
+ * The level launches are PHOVO_LAUNCH_INVERSE_PRIOR / PHOVO_LAUNCH_INVERSE_ROBUST_PRIOR; phovo_engine_fetch_prior_reports
+ * has e and e^T Lambda e of every pair.  The posterior information of a pair is the H that phovo_engine_evaluate_inverse_pairs
+ * (or _robust_pairs) returns at its pose plus s_L Lambda.
+ *   PHOVO_E_UNSUPPORTED       any objective but PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL and PHOVO_OBJECTIVE_INVERSE_ROBUST
+ *   PHOVO_E_INVALID_ARGUMENT  NULL prior_states or information (with n_pairs > 0), a non-finite entry of either, a negative
+ *                             diagonal entry of an information matrix; everything phovo_engine_enqueue_align refuses
+ * A refused enqueue leaves the engine as it was. */
+int phovo_engine_enqueue_align_prior(phovo_engine *e, int n_pairs,
+                                     const int *source_frames, const int *target_frames,
+                                     const double *init_states,
+                                     const double *prior_states /* [n_pairs][6] */,
+                                     const double *information /* [n_pairs][36] */);
 int phovo_engine_synchronize(phovo_engine *e);
 int phovo_engine_fetch_results(phovo_engine *e, int n_pairs, double *out_states,
                                phovo_pair_report *reports);
@@ -1051,7 +1117,9 @@ enum { PHOVO_LAUNCH_PERSISTENT = 0,       /* gn_level_kernel: one level, one wor
        PHOVO_LAUNCH_AFFINE = 8,           /* gn_level_kernel_affine (PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE) */
        PHOVO_LAUNCH_GEOMETRIC = 9,        /* gn_level_kernel_geometric (PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC) */
        PHOVO_LAUNCH_INVERSE = 10,         /* gn_level_kernel_inverse (PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL) */
-       PHOVO_LAUNCH_INVERSE_ROBUST = 11 };  /* gn_level_kernel_inverse_robust (PHOVO_OBJECTIVE_INVERSE_ROBUST) */
+       PHOVO_LAUNCH_INVERSE_ROBUST = 11,  /* gn_level_kernel_inverse_robust (PHOVO_OBJECTIVE_INVERSE_ROBUST) */
+       PHOVO_LAUNCH_INVERSE_PRIOR = 12,   /* gn_level_kernel_inverse_prior (objective 5, phovo_engine_enqueue_align_prior) */
+       PHOVO_LAUNCH_INVERSE_ROBUST_PRIOR = 13 };  /* gn_level_kernel_inverse_prior, robust (objective 6, likewise) */
 typedef struct phovo_launch_record {
   int level_first, level_last;            /* pyramid levels the launch covers (level_first >= level_last) */
   int kind;                               /* PHOVO_LAUNCH_* */

@@ -369,6 +369,7 @@ int phovo_engine_create(int device, phovo_engine **out)
   phovo_trust_region_options_default(&e->tr_opt);
   phovo_geometric_options_default(&e->geo_opt);
   phovo_robust_options_default(&e->rob_opt);
+  phovo_prior_options_default(&e->prior_opt);
   hipError_t he = hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking);
   if (he == hipSuccess) he = hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking);
   for (int i = 0; i < 2 && he == hipSuccess; i++) {
@@ -578,6 +579,30 @@ int phovo_engine_get_robust_options(const phovo_engine *e, phovo_robust_options 
 {
   if (!e || !opt) return fail(PHOVO_E_INVALID_ARGUMENT, "get_robust_options: null");
   *opt = e->rob_opt;
+  return PHOVO_OK;
+}
+
+int phovo_prior_options_default(phovo_prior_options *opt)
+{
+  if (!opt) return fail(PHOVO_E_INVALID_ARGUMENT, "prior_options_default: null");
+  for (double &s : opt->level_scale) s = 1.0;
+  return PHOVO_OK;
+}
+
+int phovo_engine_set_prior_options(phovo_engine *e, const phovo_prior_options *opt)
+{
+  if (!e || !opt) return fail(PHOVO_E_INVALID_ARGUMENT, "set_prior_options: null");
+  for (double s : opt->level_scale)
+    if (!(s >= 0.0 && std::isfinite(s)))
+      return fail(PHOVO_E_INVALID_ARGUMENT, "set_prior_options: every level_scale must be finite and >= 0");
+  e->prior_opt = *opt;
+  return PHOVO_OK;
+}
+
+int phovo_engine_get_prior_options(const phovo_engine *e, phovo_prior_options *opt)
+{
+  if (!e || !opt) return fail(PHOVO_E_INVALID_ARGUMENT, "get_prior_options: null");
+  *opt = e->prior_opt;
   return PHOVO_OK;
 }
 

@@ -136,6 +136,10 @@ void phovo_hip::free_slot(AlignSlot &s)
   s.illum.release();
   s.geo_reports.release();
   s.rob_reports.release();
+  s.prior.release();
+  s.prior_reports.release();
+  if (s.h_prior) (void)hipHostFree(s.h_prior);
+  s.h_prior = nullptr; s.h_prior_capacity = 0;
 }
 
 extern "C" {
@@ -147,11 +151,26 @@ int phovo_engine_level_uses_wide(const phovo_engine *e, int level, int n_pairs)
   return use_wide_level(e, n_pairs, e->levels[level]) && !(e->ext.huber_delta[level] > 0.0) ? 1 : 0;
 }
 
-int phovo_engine_enqueue_align(phovo_engine *e, int n_pairs, const int *source_frames,
-                               const int *target_frames, const double *init_states)
+// phovo_engine_enqueue_align and, with `with_prior`, phovo_engine_enqueue_align_prior.
+static int enqueue(phovo_engine *e, int n_pairs, const int *source_frames, const int *target_frames,
+                   const double *init_states, bool with_prior, const double *prior_states, const double *information)
 {
   if (!e || !source_frames || !target_frames) return fail(PHOVO_E_INVALID_ARGUMENT, "align: null");
   if (n_pairs < 0) return fail(PHOVO_E_INVALID_ARGUMENT, "align: n_pairs < 0");
+  if (with_prior) {
+    if (e->objective != PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL && e->objective != PHOVO_OBJECTIVE_INVERSE_ROBUST)
+      return fail(PHOVO_E_UNSUPPORTED, "align_prior: the pose prior belongs to the two inverse-compositional objectives "
+                                       "(PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL, PHOVO_OBJECTIVE_INVERSE_ROBUST)");
+    if (n_pairs > 0 && (!prior_states || !information)) return fail(PHOVO_E_INVALID_ARGUMENT, "align_prior: null");
+    for (size_t i = 0; i < (size_t)n_pairs * 6; i++)
+      if (!std::isfinite(prior_states[i])) return fail(PHOVO_E_INVALID_ARGUMENT, "align_prior: a prior state is not finite");
+    for (size_t i = 0; i < (size_t)n_pairs * 36; i++)
+      if (!std::isfinite(information[i])) return fail(PHOVO_E_INVALID_ARGUMENT, "align_prior: an information entry is not finite");
+    for (size_t i = 0; i < (size_t)n_pairs; i++)
+      for (int d = 0; d < 6; d++)
+        if (information[i * 36 + (size_t)d * 7] < 0.0)
+          return fail(PHOVO_E_INVALID_ARGUMENT, "align_prior: an information matrix has a negative diagonal entry");
+  }
   if (e->n_frames == 0) return fail(PHOVO_E_NOT_READY, "align: no frames resident (reserve_frames and upload first; set_config, set_extensions and set_objective drop the pool when its layout changes)");
   if (!e->have_K) return fail(PHOVO_E_NOT_READY, "align: SetIntrinsicMatrix has not been called");
   for (int i = 0; i < n_pairs; i++) {
@@ -232,6 +251,7 @@ int phovo_engine_enqueue_align(phovo_engine *e, int n_pairs, const int *source_f
   s.affine_ran = e->objective == PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE;
   s.geometric_ran = e->objective == PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC;
   s.robust_ran = e->objective == PHOVO_OBJECTIVE_INVERSE_ROBUST;
+  s.prior_ran = with_prior;
   s.num_levels = e->cfg.num_levels;
   for (int l = 0; l < PHOVO_MAX_LEVELS; l++) s.level_skipped[l] = l < e->cfg.num_levels && e->cfg.max_num_iterations[l] <= 0;
   if (n_pairs == 0) {                    // nothing to run: a valid, empty enqueue (fetch of 0 pairs succeeds, no device buffer)
@@ -263,6 +283,36 @@ int phovo_engine_enqueue_align(phovo_engine *e, int n_pairs, const int *source_f
   if (s.affine_ran) PHOVO_HIP_CHECK(s.illum.reserve(2 * (size_t)n_pairs));
   if (s.geometric_ran) PHOVO_HIP_CHECK(s.geo_reports.reserve((size_t)n_pairs));
   if (s.robust_ran) PHOVO_HIP_CHECK(s.rob_reports.reserve((size_t)n_pairs));
+  if (s.prior_ran) {
+    const size_t doubles = (size_t)GN_PRIOR_DOUBLES * (size_t)n_pairs;
+    PHOVO_HIP_CHECK(s.prior.reserve(doubles));
+    PHOVO_HIP_CHECK(s.prior_reports.reserve((size_t)n_pairs));
+    if (doubles > s.h_prior_capacity) {
+      if (s.h_prior) (void)hipHostFree(s.h_prior);
+      s.h_prior = nullptr; s.h_prior_capacity = 0;
+      PHOVO_HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&s.h_prior), sizeof(double) * doubles, hipHostMallocDefault));
+      s.h_prior_capacity = doubles;
+    }
+    // a pair's block: eigenPose(prior state) as (R_p, t_p), Lambda's upper triangle, and whether Lambda has an entry at all
+    for (int i = 0; i < n_pairs; i++) {
+      const double *ps = prior_states + (size_t)i * 6, *li = information + (size_t)i * 36;
+      double *b = s.h_prior + (size_t)i * GN_PRIOR_DOUBLES;
+      const double sy = std::sin(ps[3]), cy = std::cos(ps[3]), sp = std::sin(ps[4]), cp = std::cos(ps[4]);
+      const double sr = std::sin(ps[5]), cr = std::cos(ps[5]);
+      b[0] = cy * cp; b[1] = cy * sp * sr - sy * cr; b[2] = cy * sp * cr + sy * sr;
+      b[3] = sy * cp; b[4] = sy * sp * sr + cy * cr; b[5] = sy * sp * cr - cy * sr;
+      b[6] = -sp;     b[7] = cp * sr;                b[8] = cp * cr;
+      b[9] = ps[0]; b[10] = ps[1]; b[11] = ps[2];
+      bool any = false;
+      int k = 12;
+      for (int r = 0; r < 6; r++)
+        for (int c = r; c < 6; c++) {
+          b[k++] = li[r * 6 + c];
+          any = any || li[r * 6 + c] != 0.0;
+        }
+      b[k] = any ? 1.0 : 0.0;
+    }
+  }
   // The caller may reuse its arrays as soon as this returns and the copies below are asynchronous: the slot's pinned
   // mirror keeps them alive until the slot is used again (synchronised above).
   const PairLayout lay = pair_layout(n_pairs);
@@ -288,6 +338,11 @@ int phovo_engine_enqueue_align(phovo_engine *e, int n_pairs, const int *source_f
     PHOVO_HIP_CHECK(hipMemsetAsync(s.geo_reports.ptr, 0, sizeof(phovo_geometric_report) * (size_t)n_pairs, s.stream));
   if (s.robust_ran)      // (likewise)
     PHOVO_HIP_CHECK(hipMemsetAsync(s.rob_reports.ptr, 0, sizeof(phovo_robust_report) * (size_t)n_pairs, s.stream));
+  if (s.prior_ran) {
+    PHOVO_HIP_CHECK(hipMemcpyAsync(s.prior.ptr, s.h_prior, sizeof(double) * GN_PRIOR_DOUBLES * (size_t)n_pairs,
+                                   hipMemcpyHostToDevice, s.stream));
+    PHOVO_HIP_CHECK(hipMemsetAsync(s.prior_reports.ptr, 0, sizeof(phovo_prior_report) * (size_t)n_pairs, s.stream));
+  }
   PHOVO_HIP_CHECK(hipEventRecord(s.ev_total_start, s.stream));
 
   auto record = [&](int first, int last, int kind, int threads, int lds, int wgs) {
@@ -413,6 +468,18 @@ int phovo_engine_enqueue_align(phovo_engine *e, int n_pairs, const int *source_f
       b.geo_reports = s.geo_reports.ptr;
       PHOVO_HIP_CHECK(gn_launch_level_geometric(b, e->cu_count, s.stream));
       record(l, l, PHOVO_LAUNCH_GEOMETRIC, 256, gn_geometric_lds_bytes(), persistent_grid(gn_geometric_wgs_per_cu()));
+    } else if (s.prior_ran) {                        // objective 5 or 6 (checked at the top)
+      const bool robust = e->objective == PHOVO_OBJECTIVE_INVERSE_ROBUST;
+      GNInversePriorArgs b{};
+      b.lv = a;
+      b.scale_factor = e->rob_opt.scale_factor;
+      b.rob_reports = robust ? s.rob_reports.ptr : nullptr;
+      b.prior = s.prior.ptr;
+      b.prior_reports = s.prior_reports.ptr;
+      b.level_scale = e->prior_opt.level_scale[l];
+      PHOVO_HIP_CHECK(gn_launch_level_inverse_prior(b, robust, e->cu_count, s.stream));
+      record(l, l, robust ? PHOVO_LAUNCH_INVERSE_ROBUST_PRIOR : PHOVO_LAUNCH_INVERSE_PRIOR, 256,
+             gn_inverse_prior_lds_bytes(robust), persistent_grid(gn_inverse_prior_wgs_per_cu()));
     } else if (e->objective == PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL) {
       GNInverseArgs b{};
       b.lv = a;
@@ -472,6 +539,18 @@ int phovo_engine_enqueue_align(phovo_engine *e, int n_pairs, const int *source_f
   e->ticket = ticket;                  // issued completely: the enqueue exists
   s.ticket = ticket;
   return PHOVO_OK;
+}
+
+int phovo_engine_enqueue_align(phovo_engine *e, int n_pairs, const int *source_frames,
+                               const int *target_frames, const double *init_states)
+{
+  return enqueue(e, n_pairs, source_frames, target_frames, init_states, false, nullptr, nullptr);
+}
+
+int phovo_engine_enqueue_align_prior(phovo_engine *e, int n_pairs, const int *source_frames, const int *target_frames,
+                                     const double *init_states, const double *prior_states, const double *information)
+{
+  return enqueue(e, n_pairs, source_frames, target_frames, init_states, true, prior_states, information);
 }
 
 int phovo_engine_last_ticket(const phovo_engine *e) { return e ? e->ticket : 0; }
@@ -552,6 +631,12 @@ int phovo_engine_fetch_geometric_reports(phovo_engine *e, int n_pairs, phovo_geo
 int phovo_engine_fetch_robust_reports(phovo_engine *e, int n_pairs, phovo_robust_report *reports)
 {
   return fetch_records(e, "fetch_robust_reports", PHOVO_E_NOT_READY, &AlignSlot::robust_ran, &AlignSlot::rob_reports, 1, n_pairs,
+                       reports);
+}
+
+int phovo_engine_fetch_prior_reports(phovo_engine *e, int n_pairs, phovo_prior_report *reports)
+{
+  return fetch_records(e, "fetch_prior_reports", PHOVO_E_NOT_READY, &AlignSlot::prior_ran, &AlignSlot::prior_reports, 1, n_pairs,
                        reports);
 }
 

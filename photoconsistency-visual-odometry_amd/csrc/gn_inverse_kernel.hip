@@ -14,6 +14,8 @@
 // The form is gn_level_kernel_affine's: persistent, one 256-thread workgroup runs all iterations of a level for a pair, one
 // pass per iteration, no scatter and no owner map, any level size.  A chunk's taps are 8 registers (not 24) and the sums
 // are the 27 + 1 of the pose block alone, so TWO chunks' taps are in flight (see the pixel loop).
+// TWIN: the pixel loop (Warped, warp_issue, the two-chunk pipeline around consume) stands in gn_inverse_robust_kernel.hip and
+// in gn_inverse_prior_kernel.hip (the form with a pose prior) too; a change to it goes into all three.
 #include <hip/hip_runtime.h>
 
 #include "gn_inverse_device.hpp"          // se3_exp, euler_from_rotation_lane0, inverse_solve_compose

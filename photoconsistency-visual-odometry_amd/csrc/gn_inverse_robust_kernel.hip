@@ -3,8 +3,10 @@
 //   delta = scale_factor * median |r|,     w = |r| <= delta ? 1 : delta / |r|,     H = sum w J J^T,   g = sum w J r.
 // Rows, residual, Jacobian row, solve, composition, termination and the level's exit are that kernel's, through the same
 // helpers (gn_sampled_device.hpp, gn_inverse_device.hpp).
-// TWIN: the pixel loop (Warped, warp_issue, the two-chunk pipeline around consume) stands in gn_level_kernel_inverse too; a
-// change to it goes into both.  It is restated, not shared, so that objective 5's code stays what it was.
+// TWIN: the pixel loop (Warped, warp_issue, the two-chunk pipeline around consume) stands in gn_level_kernel_inverse too, and
+// this whole kernel -- that loop, the histogram and the median scan -- a second time in gn_inverse_prior_kernel.hip (the form
+// with a pose prior); a change goes into all three.  It is restated, not shared, so that objective 5's code
+// stays what it was.
 // The median is the grouped-data median of a histogram in LDS: 4096 bins of width 2^-12 over |r|, filled with LDS integer
 // atomic adds while the rows are consumed, so the counts -- and with them every bit of the result -- do not depend on the
 // order in which the lanes arrive.  The threshold lags one iteration: a histogram-only pass at the level's entry pose gives

@@ -28,6 +28,11 @@ struct phovo_odometry {
   bool have_geo_report = false;
   phovo_robust_report rob_report{};              // robust inverse-compositional objective: the record of the last Optimize()
   bool have_rob_report = false;
+  bool have_prior = false;                       // phovo_odometry_set_pose_prior: every Optimize() carries it until it is cleared
+  double prior_state[6] = {0, 0, 0, 0, 0, 0};
+  double prior_information[36] = {};
+  phovo_prior_report prior_report{};             // the record of the last Optimize(), if it carried a prior
+  bool have_prior_report = false;
 };
 
 namespace {
@@ -373,6 +378,10 @@ int phovo_odometry_optimize(phovo_odometry *o)
   if (!o) return fail(PHOVO_E_INVALID_ARGUMENT, "Optimize: null");
   if (!o->have_source || !o->have_target)
     return fail(PHOVO_E_NOT_READY, "Optimize: SetSourceFrame and SetTargetFrame must be called first");
+  if (o->have_prior && o->engine->objective != PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL &&
+      o->engine->objective != PHOVO_OBJECTIVE_INVERSE_ROBUST)
+    return fail(PHOVO_E_UNSUPPORTED, "Optimize: a pose prior is set, which only the two inverse-compositional objectives take "
+                                     "(phovo_odometry_clear_pose_prior)");
   // (the affine-illumination objective carries alpha and beta inside an enqueue only: no one-iteration-per-launch form)
   // (the photometric-geometric objective's per-level record belongs to one enqueue: likewise)
   // (the inverse-compositional objectives carry (R, t) inside a level's launch only: likewise)
@@ -385,8 +394,19 @@ int phovo_odometry_optimize(phovo_odometry *o)
   }
   const int src = 0, tgt = 1;
   // Like the reference, Optimize() starts from the CURRENT state vector (:539 updates m_StateVector in place).
-  int st = phovo_engine_align_pairs(o->engine, 1, &src, &tgt, o->state, o->state, &o->report);
+  int st;
+  if (o->have_prior) {
+    st = phovo_engine_enqueue_align_prior(o->engine, 1, &src, &tgt, o->state, o->prior_state, o->prior_information);
+    if (st == PHOVO_OK) st = phovo_engine_fetch_results(o->engine, 1, o->state, &o->report);
+  } else {
+    st = phovo_engine_align_pairs(o->engine, 1, &src, &tgt, o->state, o->state, &o->report);
+  }
   if (st != PHOVO_OK) return st;
+  o->have_prior_report = o->have_prior;
+  if (o->have_prior_report) {
+    st = phovo_engine_fetch_prior_reports(o->engine, 1, &o->prior_report);
+    if (st != PHOVO_OK) return st;
+  }
   o->have_tr_report = o->engine->objective == PHOVO_OBJECTIVE_TRUST_REGION;
   if (o->have_tr_report) {
     st = phovo_engine_fetch_trust_region_reports(o->engine, 1, &o->tr_report);
@@ -417,6 +437,49 @@ int phovo_odometry_get_robust_report(const phovo_odometry *o, phovo_robust_repor
   if (!o->optimized) return fail(PHOVO_E_NOT_READY, "get_robust_report: Optimize has not run");
   if (!o->have_rob_report) return fail(PHOVO_E_UNSUPPORTED, "get_robust_report: the last Optimize ran under another objective");
   *report = o->rob_report;
+  return PHOVO_OK;
+}
+
+int phovo_odometry_set_pose_prior(phovo_odometry *o, const double state[6], const double information[36])
+{
+  if (!o || !state || !information) return fail(PHOVO_E_INVALID_ARGUMENT, "set_pose_prior: null");
+  for (int i = 0; i < 6; i++)
+    if (!std::isfinite(state[i])) return fail(PHOVO_E_INVALID_ARGUMENT, "set_pose_prior: the prior state is not finite");
+  for (int i = 0; i < 36; i++)
+    if (!std::isfinite(information[i])) return fail(PHOVO_E_INVALID_ARGUMENT, "set_pose_prior: an information entry is not finite");
+  for (int d = 0; d < 6; d++)
+    if (information[7 * d] < 0.0) return fail(PHOVO_E_INVALID_ARGUMENT, "set_pose_prior: a negative diagonal entry");
+  std::memcpy(o->prior_state, state, sizeof(o->prior_state));
+  std::memcpy(o->prior_information, information, sizeof(o->prior_information));
+  o->have_prior = true;
+  return PHOVO_OK;
+}
+
+int phovo_odometry_clear_pose_prior(phovo_odometry *o)
+{
+  if (!o) return fail(PHOVO_E_INVALID_ARGUMENT, "clear_pose_prior: null");
+  o->have_prior = false;
+  return PHOVO_OK;
+}
+
+int phovo_odometry_set_prior_options(phovo_odometry *o, const phovo_prior_options *opt)
+{
+  if (!o) return fail(PHOVO_E_INVALID_ARGUMENT, "set_prior_options: null");
+  return phovo_engine_set_prior_options(o->engine, opt);
+}
+
+int phovo_odometry_get_prior_options(const phovo_odometry *o, phovo_prior_options *opt)
+{
+  if (!o) return fail(PHOVO_E_INVALID_ARGUMENT, "get_prior_options: null");
+  return phovo_engine_get_prior_options(o->engine, opt);
+}
+
+int phovo_odometry_get_prior_report(const phovo_odometry *o, phovo_prior_report *report)
+{
+  if (!o || !report) return fail(PHOVO_E_INVALID_ARGUMENT, "get_prior_report: null");
+  if (!o->optimized) return fail(PHOVO_E_NOT_READY, "get_prior_report: Optimize has not run");
+  if (!o->have_prior_report) return fail(PHOVO_E_UNSUPPORTED, "get_prior_report: the last Optimize ran without a pose prior");
+  *report = o->prior_report;
   return PHOVO_OK;
 }
 

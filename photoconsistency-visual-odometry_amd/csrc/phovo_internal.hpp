@@ -249,6 +249,21 @@ struct GNInverseRobustArgs {
 int gn_inverse_robust_wgs_per_cu();
 int gn_inverse_robust_lds_bytes();
 hipError_t gn_launch_level_inverse_robust(const GNInverseRobustArgs &args, int cu_count, hipStream_t stream);
+// The two forms above under a Gaussian pose prior (gn_inverse_prior_kernel.hip, phovo_engine_enqueue_align_prior, DESIGN.md
+// §24): one template over `robust`.  prior: [pairs][GN_PRIOR_DOUBLES] -- R_p row-major (9), t_p (3), the upper triangle of
+// Lambda row-major (21), and 1.0 where Lambda has a non-zero entry, else 0.0.
+constexpr int GN_PRIOR_DOUBLES = 34;
+struct GNInversePriorArgs {
+  GNLevelArgs lv;                    // (huber_delta and rec_off unused)
+  double scale_factor;               // robust only, as GNInverseRobustArgs
+  phovo_robust_report *rob_reports;  // robust only
+  const double *prior;               // [pairs][GN_PRIOR_DOUBLES]
+  phovo_prior_report *prior_reports; // [pairs], zeroed before the first level
+  double level_scale;                // phovo_prior_options.level_scale[level]: finite, >= 0
+};
+int gn_inverse_prior_wgs_per_cu();
+int gn_inverse_prior_lds_bytes(bool robust);
+hipError_t gn_launch_level_inverse_prior(const GNInversePriorArgs &args, bool robust, int cu_count, hipStream_t stream);
 // Evaluation of that objective's system at given states, in the twist basis (gn_evaluate_inverse_kernels.hip,
 // phovo_engine_evaluate_inverse_pairs): fp64 planes, the tile form of gn_eval_sampled_pairs, gn_eval_tiles(n) tiles per
 // pair, no owner map, no ballots.  The source frame's gradient planes are read (a target upload's).

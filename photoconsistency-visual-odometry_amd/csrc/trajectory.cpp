@@ -96,6 +96,24 @@ int phovo_robust_system_format(double timestamp, const phovo_robust_system *s, c
   return PHOVO_OK;
 }
 
+// One line for a pose prior's record (include/phovo_hip.h): every double as %.17g, which round-trips.
+int phovo_prior_report_format(double timestamp, const phovo_prior_report *r, char *line, size_t capacity)
+{
+  if (!r || !line) return fail(PHOVO_E_INVALID_ARGUMENT, "prior_report_format: null");
+  std::string out;
+  char buf[64];
+  std::snprintf(buf, sizeof(buf), "%.17g %.17g", timestamp, r->prior_cost);
+  out += buf;
+  for (int a = 0; a < 6; a++) {
+    std::snprintf(buf, sizeof(buf), " %.17g", r->error[a]);
+    out += buf;
+  }
+  if (out.size() + 1 > capacity) return fail(PHOVO_E_INVALID_ARGUMENT, "prior_report_format: buffer too small");
+  out.copy(line, out.size());
+  line[out.size()] = '\0';
+  return PHOVO_OK;
+}
+
 // One line of the app's --system file (include/phovo_hip.h): every double as %.17g, which round-trips.
 int phovo_sampled_system_format(double timestamp, const phovo_sampled_system *s, char *line, size_t capacity)
 {

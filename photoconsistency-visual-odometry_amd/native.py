@@ -104,7 +104,7 @@ OBJECTIVE_PHOTOMETRIC_GEOMETRIC = 4
 OBJECTIVE_INVERSE_COMPOSITIONAL = 5
 OBJECTIVE_INVERSE_ROBUST = 6
 LAUNCH_KINDS = ("persistent", "fused", "slide", "slide_fallback", "wide", "bilinear", "biobjective", "trust_region",
-                "affine", "geometric", "inverse", "inverse_robust")
+                "affine", "geometric", "inverse", "inverse_robust", "inverse_prior", "inverse_robust_prior")
 
 # phovo_trust_region_level.termination
 (TR_SKIPPED, TR_MAX_ITERATIONS, TR_GRADIENT, TR_FUNCTION, TR_PARAMETER, TR_MIN_RADIUS, TR_INVALID_STEP,
@@ -149,6 +149,16 @@ class RobustOptions(C.Structure):
 class RobustReport(C.Structure):
     """phovo_robust_report: the Huber threshold and the outlier rows of every level's last system."""
     _fields_ = [("delta", C.c_double * MAX_LEVELS), ("outliers", C.c_int32 * MAX_LEVELS)]
+
+
+class PriorOptions(C.Structure):
+    """phovo_prior_options: the pose prior's per-level scale s_L (H' = H + s_L Lambda)."""
+    _fields_ = [("level_scale", C.c_double * MAX_LEVELS)]
+
+
+class PriorReport(C.Structure):
+    """phovo_prior_report: e = Log(T_p^-1 T) and e^T Lambda e at the pose the finest executed level ended on."""
+    _fields_ = [("error", C.c_double * 6), ("prior_cost", C.c_double)]
 
 
 class RobustSystem(C.Structure):
@@ -307,6 +317,17 @@ SYMBOLS = {
     "phovo_odometry_set_robust_options": (C.c_int, [_vp, C.POINTER(RobustOptions)]),
     "phovo_odometry_get_robust_options": (C.c_int, [_vp, C.POINTER(RobustOptions)]),
     "phovo_odometry_get_robust_report": (C.c_int, [_vp, C.POINTER(RobustReport)]),
+    "phovo_prior_options_default": (C.c_int, [C.POINTER(PriorOptions)]),
+    "phovo_engine_set_prior_options": (C.c_int, [_vp, C.POINTER(PriorOptions)]),
+    "phovo_engine_get_prior_options": (C.c_int, [_vp, C.POINTER(PriorOptions)]),
+    "phovo_engine_fetch_prior_reports": (C.c_int, [_vp, C.c_int, _vp]),
+    "phovo_engine_enqueue_align_prior": (C.c_int, [_vp, C.c_int, _ip, _ip, _vp, _vp, _vp]),
+    "phovo_odometry_set_pose_prior": (C.c_int, [_vp, _dp, _dp]),
+    "phovo_odometry_clear_pose_prior": (C.c_int, [_vp]),
+    "phovo_odometry_set_prior_options": (C.c_int, [_vp, C.POINTER(PriorOptions)]),
+    "phovo_odometry_get_prior_options": (C.c_int, [_vp, C.POINTER(PriorOptions)]),
+    "phovo_odometry_get_prior_report": (C.c_int, [_vp, C.POINTER(PriorReport)]),
+    "phovo_prior_report_format": (C.c_int, [C.c_double, C.POINTER(PriorReport), C.c_char_p, C.c_size_t]),
     "phovo_host_register": (C.c_int, [_vp, C.c_size_t]),
     "phovo_host_unregister": (C.c_int, [_vp]),
     "phovo_engine_reserve_frames": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int]),
@@ -490,6 +511,13 @@ def format_robust_system(timestamp, system):
     return buf.value.decode()
 
 
+def format_prior_report(timestamp, report):
+    """phovo_prior_report_format: `timestamp prior_cost e0 .. e5`."""
+    buf = C.create_string_buffer(256)
+    check(lib().phovo_prior_report_format(float(timestamp), C.byref(report), buf, len(buf)), "phovo_prior_report_format")
+    return buf.value.decode()
+
+
 def format_sampled_system(timestamp, system):
     """phovo_sampled_system_format: the line the VisualOdometry app writes per pair with --system."""
     buf = C.create_string_buffer(1024)
@@ -553,6 +581,17 @@ def make_robust_options(scale_factor=None):
     check(lib().phovo_robust_options_default(C.byref(opt)), "phovo_robust_options_default")
     if scale_factor is not None:
         opt.scale_factor = float(scale_factor)
+    return opt
+
+
+def make_prior_options(level_scale=None):
+    """phovo_prior_options_default (1 on every level), or with level_scale as a per-level list (or one value for every level)."""
+    opt = PriorOptions()
+    check(lib().phovo_prior_options_default(C.byref(opt)), "phovo_prior_options_default")
+    if level_scale is not None:
+        vals = [level_scale] * MAX_LEVELS if np.isscalar(level_scale) else list(level_scale)
+        for i, v in enumerate(vals[:MAX_LEVELS]):
+            opt.level_scale[i] = float(v)
     return opt
 
 

@@ -416,7 +416,39 @@ class CPhotoconsistencyOdometryGeometric(CPhotoconsistencyOdometryAnalytic):
         return gs
 
 
-class CPhotoconsistencyOdometryInverse(CPhotoconsistencyOdometryAnalytic):
+class _PosePrior:
+    """The Gaussian pose prior of the two inverse-compositional classes (phovo_hip.h, phovo_prior_options)."""
+
+    def SetPosePrior(self, state, information):
+        """The prior of every later Optimize() until ClearPosePrior(): state[6] the prior pose (x, y, z, yaw, pitch, roll),
+        information[6, 6] symmetric, in the twist order (nu, omega) of GetInverseSystem(); its upper triangle is read."""
+        st = np.ascontiguousarray(state, dtype=np.float64).reshape(-1)
+        info = np.ascontiguousarray(information, dtype=np.float64).reshape(-1)
+        if st.size != 6 or info.size != 36:
+            raise ValueError("SetPosePrior: state must have 6 entries and information 6 x 6")
+        dp = C.POINTER(C.c_double)
+        check(self._lib.phovo_odometry_set_pose_prior(self._h, st.ctypes.data_as(dp), info.ctypes.data_as(dp)), "SetPosePrior")
+
+    def ClearPosePrior(self):
+        check(self._lib.phovo_odometry_clear_pose_prior(self._h), "ClearPosePrior")
+
+    def SetPriorOptions(self, opt):
+        """native.PriorOptions (native.make_prior_options)."""
+        check(self._lib.phovo_odometry_set_prior_options(self._h, C.byref(opt)), "SetPriorOptions")
+
+    def GetPriorOptions(self):
+        opt = native.PriorOptions()
+        check(self._lib.phovo_odometry_get_prior_options(self._h, C.byref(opt)), "GetPriorOptions")
+        return opt
+
+    def GetPriorReport(self):
+        """native.PriorReport of the last Optimize(), which carried a prior: e = Log(T_p^-1 T) and e^T Lambda e."""
+        rep = native.PriorReport()
+        check(self._lib.phovo_odometry_get_prior_report(self._h, C.byref(rep)), "GetPriorReport")
+        return rep
+
+
+class CPhotoconsistencyOdometryInverse(_PosePrior, CPhotoconsistencyOdometryAnalytic):
     """One frame pair at a time; not in the reference: the photometric residual aligned inverse-compositionally
     (native.OBJECTIVE_INVERSE_COMPOSITIONAL: bilinear samples of the target, the Jacobian from the source frame's own
     gradient, the step composed on SE(3)).  SetSourceFrame also builds the source's gradient planes.  Reads
@@ -436,7 +468,7 @@ class CPhotoconsistencyOdometryInverse(CPhotoconsistencyOdometryAnalytic):
         return ps
 
 
-class CPhotoconsistencyOdometryRobust(CPhotoconsistencyOdometryAnalytic):
+class CPhotoconsistencyOdometryRobust(_PosePrior, CPhotoconsistencyOdometryAnalytic):
     """One frame pair at a time; not in the reference: the inverse-compositional aligner under a Huber weight whose
     threshold is scale_factor times the median of |r| over the pair's own rows (native.OBJECTIVE_INVERSE_ROBUST, DESIGN.md
     §22).  SetSourceFrame also builds the source's gradient planes.  Reads the analytic yml files; extensions and every
@@ -474,6 +506,10 @@ class CPhotoconsistencyOdometryRobust(CPhotoconsistencyOdometryAnalytic):
 ROBUST_REPORT_DTYPE = np.dtype({"names": ["delta", "outliers"], "formats": [("<f8", (native.MAX_LEVELS,)), ("<i4", (native.MAX_LEVELS,))],
                                 "offsets": [native.RobustReport.delta.offset, native.RobustReport.outliers.offset],
                                 "itemsize": C.sizeof(native.RobustReport)})
+
+# phovo_prior_report as a numpy record
+PRIOR_REPORT_DTYPE = np.dtype([("error", "<f8", (6,)), ("prior_cost", "<f8")])
+assert PRIOR_REPORT_DTYPE.itemsize == C.sizeof(native.PriorReport)
 
 # phovo_geometric_report as a numpy record: one row of per-level fields per pair
 GEOMETRIC_REPORT_DTYPE = np.dtype([("depth_rows", "<i4", (native.MAX_LEVELS,)),
@@ -754,6 +790,23 @@ class AlignmentEngine:
         check(self._lib.phovo_engine_get_robust_options(self._h, C.byref(opt)), "phovo_engine_get_robust_options")
         return opt
 
+    def set_prior_options(self, opt):
+        """native.PriorOptions (native.make_prior_options)."""
+        check(self._lib.phovo_engine_set_prior_options(self._h, C.byref(opt)), "phovo_engine_set_prior_options")
+
+    def get_prior_options(self):
+        opt = native.PriorOptions()
+        check(self._lib.phovo_engine_get_prior_options(self._h, C.byref(opt)), "phovo_engine_get_prior_options")
+        return opt
+
+    def fetch_prior_reports(self, n_pairs):
+        """The records of the last enqueue's pairs, which carried a pose prior, as one structured numpy array of
+        PRIOR_REPORT_DTYPE: out["error"][p] = Log(T_p^-1 T), out["prior_cost"][p] = e^T Lambda e."""
+        out = np.zeros(int(n_pairs), dtype=PRIOR_REPORT_DTYPE)
+        check(self._lib.phovo_engine_fetch_prior_reports(self._h, int(n_pairs), out.ctypes.data),
+              "phovo_engine_fetch_prior_reports")
+        return out
+
     def fetch_robust_reports(self, n_pairs):
         """The records of the last enqueue's pairs, which ran under native.OBJECTIVE_INVERSE_ROBUST, as one structured
         numpy array of ROBUST_REPORT_DTYPE: out["delta"][p, L], out["outliers"][p, L]."""
@@ -958,11 +1011,23 @@ class AlignmentEngine:
               "phovo_engine_evaluate_geometric_pairs")
         return out[:n].copy()
 
-    def enqueue_align(self, src, tgt, init_states=None):
+    def enqueue_align(self, src, tgt, init_states=None, prior_states=None, information=None):
+        """phovo_engine_enqueue_align, or, with prior_states [n, 6] and information [n, 6, 6] (both or neither),
+        phovo_engine_enqueue_align_prior: a Gaussian pose prior per pair (objectives 5 and 6)."""
         s, t = self._pairs(src, tgt)
         n = s.size
         init = None if init_states is None else np.ascontiguousarray(init_states, dtype=np.float64).reshape(n, 6)
         ip = C.POINTER(C.c_int)
+        if (prior_states is None) != (information is None):
+            raise ValueError("enqueue_align: prior_states and information go together")
+        if prior_states is not None:
+            ps = np.ascontiguousarray(prior_states, dtype=np.float64).reshape(n, 6)
+            info = np.ascontiguousarray(information, dtype=np.float64).reshape(n, 36)
+            check(self._lib.phovo_engine_enqueue_align_prior(
+                self._h, n, s.ctypes.data_as(ip), t.ctypes.data_as(ip),
+                init.ctypes.data if init is not None else None, ps.ctypes.data, info.ctypes.data),
+                "phovo_engine_enqueue_align_prior")
+            return n
         check(self._lib.phovo_engine_enqueue_align(
             self._h, n, s.ctypes.data_as(ip), t.ctypes.data_as(ip),
             init.ctypes.data if init is not None else None), "phovo_engine_enqueue_align")
