@@ -10,7 +10,7 @@ termination and gradient_norm on ||g'||; with Lambda = 0 or s_L = 0 the two addi
 inverse_ref.optimize's (inverse_robust_ref.optimize's) bit for bit.  The record adds `error` (e at the final pose of the
 finest executed level), `prior_cost` (e^T Lambda e there) and `max_angle` (the largest |omega| of any e that was formed).
 `mutant` builds a deliberately wrong rule, for the tests that show the fixtures can tell: "left" takes e = Log(T T_p^-1),
-"minus" subtracts s_L Lambda e."""
+"minus" subtracts s_L Lambda e, "data_norm" terminates and reports on ||g|| instead of ||g'||."""
 import numpy as np
 
 import inverse_ref as ir
@@ -107,6 +107,7 @@ def optimize(pyr, K, cfg, prior_state, information, level_scale=None, robust=Fal
             valid[L] = n_rows
             if n_rows < 6:
                 flags |= PAIR_RANK_DEFICIENT
+            g_data = g
             if has_lambda and scales[L] != 0.0:
                 e = prior_error(Rp, tp, R, t, mutant)
                 max_angle = max(max_angle, float(np.linalg.norm(e[3:]))) if np.all(np.isfinite(e)) else np.inf
@@ -123,7 +124,7 @@ def optimize(pyr, K, cfg, prior_state, information, level_scale=None, robust=Fal
             with np.errstate(all="ignore"):
                 ER, Et = ir.se3_exp(-cfg["lam"][L] * step)
                 R, t = R @ ER, R @ Et + t
-            gnorm = float(np.linalg.norm(g))
+            gnorm = float(np.linalg.norm(g_data if mutant == "data_norm" else g))
             h_norm = float(np.linalg.norm(Hm, 2)) if np.all(np.isfinite(Hm)) else np.inf
             thr = cfg["min_grad"][L]
             if thr > 0:
