@@ -3,11 +3,16 @@
 // Same command line, hard-coded intrinsics, depth scale and console output as the reference's app
 // (apps/PhotoconsistencyFrameAlignment/PhotoconsistencyFrameAlignment.cpp:49-115):
 //   ./PhotoconsistencyFrameAlignment <config_file.yml> <imgRGB0.png> <imgDepth0.png> <imgRGB1.png> <imgDepth1.png> [diff.png]
-//                                    [--method analytic|ceres|biobjective|inverse|robust|affine|geometric]
+//                                    [--method analytic|ceres|biobjective|inverse|robust|semidense|affine|geometric]
+//                                    [--min-pixel-gradient <g>[,<g>...]]
 // --method picks the aligner as the reference's USE_PHOTOCONSISTENCY_ODOMETRY_METHOD does: analytic (0, the default),
 // ceres (1, CPhotoconsistencyOdometryCeres: Levenberg-Marquardt on bilinear samples; reads config_*_ceres.yml files) or
 // biobjective (2, CPhotoconsistencyOdometryBiObjective: photometric and depth error together).  A configuration file of
 // the other kind is refused with a message that says so.
+// semidense is not in the reference: the inverse-compositional aligner on the source pixels whose gradient magnitude reaches
+// a per-level threshold (CPhotoconsistencyOdometrySemiDense; reads the analytic files and their optional key
+// `min_pixel_gradient (at each level)`).  --min-pixel-gradient sets that threshold from the command line: one value for all
+// levels or one per level, each finite and >= 0; it needs --method semidense.
 // Differences: the reference tests `argc<5` but reads argv[5] (:56,79) -- five arguments are required
 // here; the final |I1 - warp(I0)| image goes to the optional sixth argument as a PNG instead of an
 // imshow window (:107-112), because the target machines are headless.
@@ -23,6 +28,8 @@
 #include "phovo/CPhotoconsistencyOdometryGeometric.h"
 #include "phovo/CPhotoconsistencyOdometryInverse.h"
 #include "phovo/CPhotoconsistencyOdometryRobust.h"
+#include "phovo/CPhotoconsistencyOdometrySemiDense.h"
+#include "min_pixel_gradient.h"
 #include "phovo/CPhotoconsistencyOdometryBiObjective.h"
 #include "phovo/CPhotoconsistencyOdometryCeres.h"
 
@@ -37,7 +44,8 @@ typedef phovo::compat::Mat_<CoordinateType> DepthImageType;
 static void printHelp()
 {
   std::cout << "./PhotoconsistencyFrameAlignment <config_file.yml> <imgRGB0.png> <imgDepth0.png> "
-               "<imgRGB1.png> <imgDepth1.png> [imgDiff.png] [--method analytic|ceres|biobjective|inverse|robust|affine|geometric]" << std::endl;
+               "<imgRGB1.png> <imgDepth1.png> [imgDiff.png] [--method analytic|ceres|biobjective|inverse|robust|semidense|affine|geometric] "
+               "[--min-pixel-gradient <g>[,<g>...]]" << std::endl;
 }
 
 static bool loadGray(const char *path, IntensityImageType &img)
@@ -60,7 +68,8 @@ static bool loadDepthMetres(const char *path, DepthImageType &img)
   return true;
 }
 
-enum Method { METHOD_ANALYTIC, METHOD_CERES, METHOD_BIOBJECTIVE, METHOD_AFFINE, METHOD_GEOMETRIC, METHOD_INVERSE, METHOD_ROBUST };      // (affine, geometric, inverse, robust: not in the reference, read the analytic files)
+enum Method { METHOD_ANALYTIC, METHOD_CERES, METHOD_BIOBJECTIVE, METHOD_AFFINE, METHOD_GEOMETRIC, METHOD_INVERSE, METHOD_ROBUST, METHOD_SEMIDENSE };      // (affine, geometric, inverse, robust, semidense: not in the reference, read the analytic files)
+static std::vector<double> minPixelGradient;          // --min-pixel-gradient: empty, one value for all levels, or one per level
 static int alignPair(int argc, char **argv, Method method);
 
 // The Ceres method reads the config_*_ceres.yml keys, the other two the config_*_analytic.yml keys.
@@ -92,10 +101,22 @@ int main(int argc, char **argv)
       else if (m == "geometric") method = METHOD_GEOMETRIC;
       else if (m == "inverse") method = METHOD_INVERSE;
       else if (m == "robust") method = METHOD_ROBUST;
+      else if (m == "semidense") method = METHOD_SEMIDENSE;
       else if (m != "analytic") { printHelp(); return -1; }
       continue;
     }
+    if (i > 0 && std::string(argv[i]) == "--min-pixel-gradient") {
+      if (i + 1 >= argc || !phovo_apps::parseMinPixelGradient(argv[++i], minPixelGradient)) {
+        std::cerr << "--min-pixel-gradient takes <g>[,<g>...]: one value for all levels or one per level, each finite and >= 0" << std::endl;
+        return EXIT_FAILURE;
+      }
+      continue;
+    }
     args.push_back(argv[i]);
+  }
+  if (!minPixelGradient.empty() && method != METHOD_SEMIDENSE) {
+    std::cerr << "--min-pixel-gradient needs --method semidense" << std::endl;
+    return EXIT_FAILURE;
   }
   if (args.size() >= 6 && !configFitsMethod(args[1], method)) return EXIT_FAILURE;
   return alignPair((int)args.size(), args.data(), method);
@@ -112,6 +133,7 @@ static int alignPair(int argc, char **argv, Method method)
   if (method == METHOD_GEOMETRIC) return alignWith<phovo::Analytic::CPhotoconsistencyOdometryGeometric<PixelType, CoordinateType>>(argc, argv);
   if (method == METHOD_INVERSE) return alignWith<phovo::Analytic::CPhotoconsistencyOdometryInverse<PixelType, CoordinateType>>(argc, argv);
   if (method == METHOD_ROBUST) return alignWith<phovo::Analytic::CPhotoconsistencyOdometryRobust<PixelType, CoordinateType>>(argc, argv);
+  if (method == METHOD_SEMIDENSE) return alignWith<phovo::Analytic::CPhotoconsistencyOdometrySemiDense<PixelType, CoordinateType>>(argc, argv);
   return alignWith<phovo::Analytic::CPhotoconsistencyOdometryAnalytic<PixelType, CoordinateType>>(argc, argv);
 }
 
@@ -135,6 +157,7 @@ static int alignWith(int argc, char **argv)
     Odometry photoconsistencyOdometry;
     Vector6Type stateVector;                          // x,y,z,yaw,pitch,roll = 0
     photoconsistencyOdometry.ReadConfigurationFile(std::string(argv[1]));       // :92
+    phovo_apps::applyMinPixelGradient(photoconsistencyOdometry, minPixelGradient, 0);
     photoconsistencyOdometry.SetIntrinsicMatrix(intrinsicMatrix);
     photoconsistencyOdometry.SetSourceFrame(imgGray0, imgDepth0);
     photoconsistencyOdometry.SetTargetFrame(imgGray1, imgDepth1);

@@ -2,9 +2,9 @@
 // directory, writing a TUM trajectory file.
 //
 //   ./PhotoconsistencyVisualOdometry <config_file.yml> <rgbd_dataset_directory> <output_trajectory_file> [--batch [--gpus N] [--rccl]]
-//                                    [--method analytic|ceres|biobjective|inverse|robust|affine|geometric] [--information <file>] [--system <file>]
+//                                    [--method analytic|ceres|biobjective|inverse|robust|semidense|affine|geometric] [--information <file>] [--system <file>]
 //                                    [--geometric-system <file>] [--objective-system <file>] [--inverse-system <file>]
-//                                    [--robust-system <file>] [--prior-weight <wt>,<wr>]
+//                                    [--robust-system <file>] [--prior-weight <wt>,<wr>] [--min-pixel-gradient <g>[,<g>...]]
 // --method picks the aligner as the reference's USE_PHOTOCONSISTENCY_ODOMETRY_METHOD does (0 = analytic, the default;
 // 1 = ceres: Levenberg-Marquardt on bilinear samples, CPhotoconsistencyOdometryCeres, which reads config_*_ceres.yml
 // files; 2 = bi-objective: photometric and depth error together, CPhotoconsistencyOdometryBiObjective), in every mode;
@@ -49,6 +49,11 @@
 // phovo_engine_evaluate_inverse_pairs).  The loop takes it from the class surface (GetInverseSystem), --batch from
 // phovo_engine_evaluate_inverse_pairs; both write the same bytes, the trajectory file is the same with and without the
 // flag, and the printed times do not include the evaluation.
+// semidense is not in the reference either: the inverse-compositional aligner on the source pixels whose gradient magnitude
+// reaches a per-level threshold, CPhotoconsistencyOdometrySemiDense, which reads the analytic files and their optional key
+// `min_pixel_gradient (at each level)`; it has no system yet, so every system flag below refuses it.
+// --min-pixel-gradient <g>[,<g>...] (--method semidense, the loop and --batch): that threshold from the command line, one
+// value for all levels or one per level, each finite and >= 0, in place of the file's.
 // --prior-weight <wt>,<wr> (not in the reference; --method inverse | robust, the pair-by-pair loop): a constant-velocity
 // Gaussian prior on every pair's pose (include/phovo_hip.h, phovo_prior_options) -- the prior pose is the
 // previous pair's result, zero for the first pair, and Lambda = diag(wt, wt, wt, wr, wr, wr) in the twist order (nu, omega);
@@ -101,6 +106,8 @@
 #include "phovo/CPhotoconsistencyOdometryAffine.h"
 #include "phovo/CPhotoconsistencyOdometryInverse.h"
 #include "phovo/CPhotoconsistencyOdometryRobust.h"
+#include "phovo/CPhotoconsistencyOdometrySemiDense.h"
+#include "min_pixel_gradient.h"
 #include "phovo/CPhotoconsistencyOdometryGeometric.h"
 #include "phovo/CPhotoconsistencyOdometryBiObjective.h"
 #include "phovo/CPhotoconsistencyOdometryCeres.h"
@@ -274,9 +281,10 @@ static phovo_prior_report priorReportOf(Odometry &, long)
 static void printHelp()
 {
   std::cout << "./PhotoconsistencyVisualOdometry <config_file.yml> <rgbd_dataset_directory> "
-               "<output_trajectory_file> [--batch [--gpus N] [--rccl]] [--method analytic|ceres|biobjective|inverse|robust|affine|geometric] "
+               "<output_trajectory_file> [--batch [--gpus N] [--rccl]] [--method analytic|ceres|biobjective|inverse|robust|semidense|affine|geometric] "
                "[--information <file>] [--system <file>] [--geometric-system <file>] [--objective-system <file>] "
-               "[--inverse-system <file>] [--robust-system <file>] [--prior-weight <wt>,<wr>]" << std::endl;
+               "[--inverse-system <file>] [--robust-system <file>] [--min-pixel-gradient <g>[,<g>...]] "
+               "[--prior-weight <wt>,<wr>]" << std::endl;
 }
 
 #define PHOVO_OK_OR_FAIL(call)                                                              \
@@ -298,6 +306,7 @@ int main(int argc, char *argv[])
   std::string robustSystemPath;                       // --robust-system <file>: the same for --method robust (weighted, twist basis)
   bool priorWeight = false;                           // --prior-weight <wt>,<wr>: a constant-velocity pose prior (loop mode)
   double priorWt = 0.0, priorWr = 0.0;
+  std::vector<double> minPixelGradient;               // --min-pixel-gradient <g>[,<g>...]: --method semidense's thresholds
   for (int i = 4; i < argc; i++) {
     const std::string a(argv[i]);
     if (a == "--batch") batch = true;
@@ -323,7 +332,14 @@ int main(int argc, char *argv[])
       else if (m == "geometric") objective = PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC;
       else if (m == "inverse") objective = PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL;
       else if (m == "robust") objective = PHOVO_OBJECTIVE_INVERSE_ROBUST;
+      else if (m == "semidense") objective = PHOVO_OBJECTIVE_INVERSE_SEMIDENSE;
       else { printHelp(); return EXIT_FAILURE; }
+    }
+    else if (a == "--min-pixel-gradient" && i + 1 < argc) {
+      if (!phovo_apps::parseMinPixelGradient(argv[++i], minPixelGradient)) {
+        std::cerr << "--min-pixel-gradient needs <g>[,<g>...]: one value for all levels or one per level, each finite and >= 0" << std::endl;
+        return EXIT_FAILURE;
+      }
     }
     else if (a == "--rccl") rccl = true;
     else if (a == "--gpus" && i + 1 < argc) nGpus = std::atoi(argv[++i]);
@@ -390,6 +406,10 @@ int main(int argc, char *argv[])
   }
   if (robustSystem && objective != PHOVO_OBJECTIVE_INVERSE_ROBUST) {
     std::cerr << "--robust-system needs --method robust" << std::endl;
+    return EXIT_FAILURE;
+  }
+  if (!minPixelGradient.empty() && objective != PHOVO_OBJECTIVE_INVERSE_SEMIDENSE) {
+    std::cerr << "--min-pixel-gradient needs --method semidense" << std::endl;
     return EXIT_FAILURE;
   }
   if (priorWeight && batch) {
@@ -482,6 +502,7 @@ int main(int argc, char *argv[])
     // the pair-by-pair loop through the class surface, with the class --method names
     auto runLoop = [&](auto &odometry) -> int {
       odometry.ReadConfigurationFile(configFile);
+      phovo_apps::applyMinPixelGradient(odometry, minPixelGradient, 0);
       odometry.SetIntrinsicMatrix(intrinsicMatrix);
       IntensityImageType prevGray, curGray;
       DepthImageType prevDepth, curDepth;
@@ -548,6 +569,9 @@ int main(int argc, char *argv[])
       } else if (objective == PHOVO_OBJECTIVE_INVERSE_ROBUST) {
         phovo::Analytic::CPhotoconsistencyOdometryRobust<PixelType, CoordinateType> odometry;
         if (runLoop(odometry) != EXIT_SUCCESS) return EXIT_FAILURE;
+      } else if (objective == PHOVO_OBJECTIVE_INVERSE_SEMIDENSE) {
+        phovo::Analytic::CPhotoconsistencyOdometrySemiDense<PixelType, CoordinateType> odometry;
+        if (runLoop(odometry) != EXIT_SUCCESS) return EXIT_FAILURE;
       } else {
         phovo::Analytic::CPhotoconsistencyOdometryAnalytic<PixelType, CoordinateType> odometry;
         if (runLoop(odometry) != EXIT_SUCCESS) return EXIT_FAILURE;
@@ -563,6 +587,12 @@ int main(int argc, char *argv[])
       PHOVO_OK_OR_FAIL(phovo_geometric_options_default(&geoOptions));
       if (objective == PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC)
         PHOVO_OK_OR_FAIL(phovo_geometric_read_file(configFile.c_str(), &geoOptions));
+      phovo_semidense_options sdOptions;              // --method semidense: the optional key of the file, then the command line
+      PHOVO_OK_OR_FAIL(phovo_semidense_options_default(&sdOptions));
+      if (objective == PHOVO_OBJECTIVE_INVERSE_SEMIDENSE) {
+        PHOVO_OK_OR_FAIL(phovo_semidense_read_file(configFile.c_str(), &sdOptions));
+        phovo_apps::overrideMinPixelGradient(minPixelGradient, sdOptions);
+      }
       const int nDevices = phovo_device_count();
       if (nDevices < 1) { std::cerr << "phovo_engine_create: no HIP device available: this library has no CPU path" << std::endl; return EXIT_FAILURE; }
       // PHOVO_VO_SHARE_DEVICES=1 lets more shards than devices run (a rehearsal of --gpus N on a smaller machine)
@@ -675,6 +705,8 @@ int main(int argc, char *argv[])
           if (phovo_engine_set_objective(engine, objective) != PHOVO_OK) return fail("phovo_engine_set_objective");
           if (objective == PHOVO_OBJECTIVE_PHOTOMETRIC && phovo_engine_set_extensions(engine, &extensions) != PHOVO_OK)
             return fail("phovo_engine_set_extensions");
+          if (objective == PHOVO_OBJECTIVE_INVERSE_SEMIDENSE && phovo_engine_set_semidense_options(engine, &sdOptions) != PHOVO_OK)
+            return fail("phovo_engine_set_semidense_options");
           if (objective == PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC && phovo_engine_set_geometric_options(engine, &geoOptions) != PHOVO_OK)
             return fail("phovo_engine_set_geometric_options");
           if (objective == PHOVO_OBJECTIVE_TRUST_REGION && phovo_engine_set_trust_region_options(engine, &trOptions) != PHOVO_OK)

@@ -319,6 +319,46 @@ typedef struct phovo_extensions {
  *                                phovo_engine_evaluate_* calls and their phovo_odometry_get_*_system calls stay
  *                                PHOVO_E_UNSUPPORTED under this objective.  phovo_pair_report keeps its meaning. */
 #define PHOVO_OBJECTIVE_INVERSE_ROBUST 6
+/*   PHOVO_OBJECTIVE_INVERSE_SEMIDENSE  not in the reference: the inverse-compositional aligner on the source pixels worth a
+ *                                row (DESIGN.md §25 has the contract).  Per level L and pair:
+ *                                  select  once, before the first iteration: source pixel k is SELECTED iff
+ *                                          min_depth < D0_k < max_depth and GX0_k*GX0_k + GY0_k*GY0_k >= tau_L*tau_L, in fp64
+ *                                          on the gradient planes as stored (the gradient scaling factor included; the
+ *                                          sum may or may not be contracted); NaN fails either comparison.  tau_L =
+ *                                          phovo_semidense_options.min_pixel_gradient[L].  The selection depends on the
+ *                                          source frame, the level and tau_L only.
+ *                                  rows    the selected pixels whose warp lands in bounds; for a selected pixel the warp, the
+ *                                          bounds test, the taps, r_k and J_k are objective 5's.
+ *                                  step    step, end and exit exactly as under PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL.
+ *                                So this is objective 5 on a source whose depth is NaN wherever the pixel is not selected;
+ *                                the order of summation is the kernel's own, results agree with that within rounding, and a
+ *                                pair's bits depend on nothing but the pair.  phovo_semidense_report has the number of
+ *                                selected pixels per level; phovo_pair_report keeps its meaning (valid_pixels[L] = rows of
+ *                                the level's last system).  Source frames need PHOVO_ROLE_BOTH (else PHOVO_E_NOT_READY);
+ *                                switching between objectives 0, 2, 3, 4, 5, 6 and 7 keeps the frame pool.  Supported: fp64
+ *                                planes, the default sampling setting, no Huber weights, jacobian_corrected 0 -- anything
+ *                                else is PHOVO_E_UNSUPPORTED, whichever setter comes second.  A level wider or taller than
+ *                                65535 pixels is PHOVO_E_SHAPE at the enqueue (a list record is col | row << 16).  Each
+ *                                enqueue slot keeps a device workspace of (resident workgroups) x (level size padded to 256)
+ *                                x 4 bytes for the largest active level: 0.63 GB for 640x480 on 512 workgroups; it is
+ *                                kept until the engine is destroyed, also under another objective.
+ *                                phovo_engine_enqueue_align_prior, the six phovo_engine_evaluate_* calls and their
+ *                                phovo_odometry_get_*_system calls are PHOVO_E_UNSUPPORTED under this objective.  Fusion,
+ *                                sliding-window, wide, latency-form and batch-invariant settings are accepted and have no
+ *                                effect. */
+#define PHOVO_OBJECTIVE_INVERSE_SEMIDENSE 7
+
+/* Option of the semi-dense inverse-compositional objective: tau_L, the smallest gradient magnitude (of the stored gradient
+ * planes) a selected pixel has on level L.  The default, 0 everywhere, selects every depth-valid pixel with finite
+ * gradients. */
+typedef struct phovo_semidense_options {
+  double min_pixel_gradient[PHOVO_MAX_LEVELS];  /* finite and >= 0 */
+} phovo_semidense_options;
+
+/* Per pair and level: the selected pixels (levels with max_num_iterations 0 stay 0). */
+typedef struct phovo_semidense_report {
+  int32_t selected[PHOVO_MAX_LEVELS];
+} phovo_semidense_report;
 
 /* Option of the robust inverse-compositional objective: delta = scale_factor * (median of |r|).  The default,
  * 1.345 * 1.4826, is Huber's 95 %-efficiency constant times the factor that makes the median absolute deviation a
@@ -496,6 +536,13 @@ int phovo_geometric_read_file(const char *path, phovo_geometric_options *opt);
 /* Robust inverse-compositional objective: scale_factor 1.345 * 1.4826. */
 int phovo_robust_options_default(phovo_robust_options *opt);
 
+/* Semi-dense inverse-compositional objective: min_pixel_gradient 0 on every level (every depth-valid pixel). */
+int phovo_semidense_options_default(phovo_semidense_options *opt);
+/* The optional key of an ANALYTIC yml file, "min_pixel_gradient (at each level): [..]", read the way
+ * phovo_geometric_read_file reads depth_weight: an absent key leaves the defaults; a list shorter than the file's
+ * numOptimizationLevels, a malformed one or a value that is not finite and >= 0 is PHOVO_E_CONFIG. */
+int phovo_semidense_read_file(const char *path, phovo_semidense_options *opt);
+
 int phovo_extensions_default(phovo_extensions *ext);
 /* Optional keys in the same yml file (the reference's cv::FileStorage lookups ignore keys they do not ask for,
  * so such a file still loads there): "huber_delta (at each level): [..]", "plane_storage_bits: 64|32|16",
@@ -597,6 +644,14 @@ int phovo_odometry_get_geometric_report(const phovo_odometry *o, phovo_geometric
 int phovo_odometry_set_robust_options(phovo_odometry *o, const phovo_robust_options *opt);
 int phovo_odometry_get_robust_options(const phovo_odometry *o, phovo_robust_options *opt);
 int phovo_odometry_get_robust_report(const phovo_odometry *o, phovo_robust_report *report);
+/* Semi-dense inverse-compositional objective: its options (default: phovo_semidense_options_default; kept under every
+ * objective, used by this one; a min_pixel_gradient that is not finite and >= 0 is PHOVO_E_INVALID_ARGUMENT) and the record
+ * of the last Optimize() (PHOVO_E_NOT_READY before a successful one; PHOVO_E_UNSUPPORTED under another objective).  Under
+ * this objective phovo_odometry_set_source_frame uploads the source with both roles, as under objective 5, and
+ * phovo_odometry_read_configuration_file reads the optional key as well (phovo_semidense_read_file). */
+int phovo_odometry_set_semidense_options(phovo_odometry *o, const phovo_semidense_options *opt);
+int phovo_odometry_get_semidense_options(const phovo_odometry *o, phovo_semidense_options *opt);
+int phovo_odometry_get_semidense_report(const phovo_odometry *o, phovo_semidense_report *report);
 /* Gaussian pose prior (phovo_prior_options above has the rule): the prior of every later Optimize() until it is cleared or
  * set again -- state[6] the prior pose, information[36] row-major with its upper triangle read; a non-finite entry or a
  * negative diagonal is PHOVO_E_INVALID_ARGUMENT.  It may be set under any objective; Optimize() with a prior set is
@@ -755,6 +810,12 @@ int phovo_engine_fetch_geometric_reports(phovo_engine *e, int n_pairs, phovo_geo
 int phovo_engine_set_robust_options(phovo_engine *e, const phovo_robust_options *opt);
 int phovo_engine_get_robust_options(const phovo_engine *e, phovo_robust_options *opt);
 int phovo_engine_fetch_robust_reports(phovo_engine *e, int n_pairs, phovo_robust_report *reports);
+/* Semi-dense inverse-compositional objective: its option (kept under every objective, used by this one; every
+ * min_pixel_gradient must be finite and >= 0, else PHOVO_E_INVALID_ARGUMENT) and the per-pair records of the LAST enqueue,
+ * with the call-order rules of phovo_engine_fetch_robust_reports. */
+int phovo_engine_set_semidense_options(phovo_engine *e, const phovo_semidense_options *opt);
+int phovo_engine_get_semidense_options(const phovo_engine *e, phovo_semidense_options *opt);
+int phovo_engine_fetch_semidense_reports(phovo_engine *e, int n_pairs, phovo_semidense_report *reports);
 /* Gaussian pose prior: the level scales (kept under every objective, used by phovo_engine_enqueue_align_prior; every
  * level_scale must be finite and >= 0, else PHOVO_E_INVALID_ARGUMENT; phovo_prior_options_default: 1 everywhere) and the
  * per-pair records of the LAST enqueue, with the call-order rules of phovo_engine_fetch_robust_reports
@@ -1119,7 +1180,8 @@ enum { PHOVO_LAUNCH_PERSISTENT = 0,       /* gn_level_kernel: one level, one wor
        PHOVO_LAUNCH_INVERSE = 10,         /* gn_level_kernel_inverse (PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL) */
        PHOVO_LAUNCH_INVERSE_ROBUST = 11,  /* gn_level_kernel_inverse_robust (PHOVO_OBJECTIVE_INVERSE_ROBUST) */
        PHOVO_LAUNCH_INVERSE_PRIOR = 12,   /* gn_level_kernel_inverse_prior (objective 5, phovo_engine_enqueue_align_prior) */
-       PHOVO_LAUNCH_INVERSE_ROBUST_PRIOR = 13 };  /* gn_level_kernel_inverse_prior, robust (objective 6, likewise) */
+       PHOVO_LAUNCH_INVERSE_ROBUST_PRIOR = 13,    /* gn_level_kernel_inverse_prior, robust (objective 6, likewise) */
+       PHOVO_LAUNCH_INVERSE_SEMIDENSE = 14 };     /* gn_level_kernel_inverse_semidense (PHOVO_OBJECTIVE_INVERSE_SEMIDENSE) */
 typedef struct phovo_launch_record {
   int level_first, level_last;            /* pyramid levels the launch covers (level_first >= level_last) */
   int kind;                               /* PHOVO_LAUNCH_* */

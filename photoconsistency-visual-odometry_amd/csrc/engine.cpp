@@ -118,6 +118,7 @@ int reference_exact_only(const char *setter, int objective, const phovo_extensio
       : objective == PHOVO_OBJECTIVE_TRUST_REGION ? "the trust-region objective runs on fp64 planes with the default sampling, no Huber weights and jacobian_corrected 0 only"
       : objective == PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE ? "the affine-illumination objective runs on fp64 planes with the default sampling setting, no Huber weights and jacobian_corrected 0 only"
       : objective == PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL ? "the inverse-compositional objective runs on fp64 planes with the default sampling setting, no Huber weights and jacobian_corrected 0 only"
+      : objective == PHOVO_OBJECTIVE_INVERSE_SEMIDENSE ? "the semi-dense inverse-compositional objective runs on fp64 planes with the default sampling setting, no Huber weights and jacobian_corrected 0 only"
       : objective == PHOVO_OBJECTIVE_INVERSE_ROBUST ? "the robust inverse-compositional objective runs on fp64 planes with the default sampling setting, no huber_delta extension and jacobian_corrected 0 only"
       : "the photometric-geometric objective runs on fp64 planes with the default sampling setting, no Huber weights and jacobian_corrected 0 only";
   return fail(PHOVO_E_UNSUPPORTED, std::string(setter) + ": " + only);
@@ -369,6 +370,7 @@ int phovo_engine_create(int device, phovo_engine **out)
   phovo_trust_region_options_default(&e->tr_opt);
   phovo_geometric_options_default(&e->geo_opt);
   phovo_robust_options_default(&e->rob_opt);
+  phovo_semidense_options_default(&e->sd_opt);
   phovo_prior_options_default(&e->prior_opt);
   hipError_t he = hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking);
   if (he == hipSuccess) he = hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking);
@@ -493,11 +495,11 @@ int phovo_engine_set_objective(phovo_engine *e, int objective)
   if (objective != PHOVO_OBJECTIVE_PHOTOMETRIC && objective != PHOVO_OBJECTIVE_BIOBJECTIVE &&
       objective != PHOVO_OBJECTIVE_TRUST_REGION && objective != PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE &&
       objective != PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC && objective != PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL &&
-      objective != PHOVO_OBJECTIVE_INVERSE_ROBUST)
+      objective != PHOVO_OBJECTIVE_INVERSE_ROBUST && objective != PHOVO_OBJECTIVE_INVERSE_SEMIDENSE)
     return fail(PHOVO_E_INVALID_ARGUMENT, "set_objective: unknown objective");
   const int st = reference_exact_only("set_objective", objective, e->ext);
   if (st != PHOVO_OK) return st;
-  // The photometric, trust-region, affine-illumination, photometric-geometric and both inverse-compositional objectives share
+  // The photometric, trust-region, affine-illumination, photometric-geometric and the three inverse-compositional objectives share
   // the frame layout: a switch between them keeps the pool.
   auto bi = [](int o) { return o == PHOVO_OBJECTIVE_BIOBJECTIVE; };
   if (objective != e->objective && (bi(objective) || bi(e->objective))) drop_pool(e);   // the pool layout changes (the bi-objective's target planes)
@@ -579,6 +581,25 @@ int phovo_engine_get_robust_options(const phovo_engine *e, phovo_robust_options 
 {
   if (!e || !opt) return fail(PHOVO_E_INVALID_ARGUMENT, "get_robust_options: null");
   *opt = e->rob_opt;
+  return PHOVO_OK;
+}
+
+int phovo_semidense_read_file(const char *path, phovo_semidense_options *opt) { return read_semidense_file(path, opt); }
+
+int phovo_engine_set_semidense_options(phovo_engine *e, const phovo_semidense_options *opt)
+{
+  if (!e || !opt) return fail(PHOVO_E_INVALID_ARGUMENT, "set_semidense_options: null");
+  for (double t : opt->min_pixel_gradient)
+    if (!(t >= 0.0 && std::isfinite(t)))
+      return fail(PHOVO_E_INVALID_ARGUMENT, "set_semidense_options: every min_pixel_gradient must be finite and >= 0");
+  e->sd_opt = *opt;
+  return PHOVO_OK;
+}
+
+int phovo_engine_get_semidense_options(const phovo_engine *e, phovo_semidense_options *opt)
+{
+  if (!e || !opt) return fail(PHOVO_E_INVALID_ARGUMENT, "get_semidense_options: null");
+  *opt = e->sd_opt;
   return PHOVO_OK;
 }
 

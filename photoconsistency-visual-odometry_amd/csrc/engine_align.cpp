@@ -136,6 +136,8 @@ void phovo_hip::free_slot(AlignSlot &s)
   s.illum.release();
   s.geo_reports.release();
   s.rob_reports.release();
+  s.sd_reports.release();
+  s.sd_records.release();
   s.prior.release();
   s.prior_reports.release();
   if (s.h_prior) (void)hipHostFree(s.h_prior);
@@ -158,7 +160,7 @@ static int enqueue(phovo_engine *e, int n_pairs, const int *source_frames, const
   if (!e || !source_frames || !target_frames) return fail(PHOVO_E_INVALID_ARGUMENT, "align: null");
   if (n_pairs < 0) return fail(PHOVO_E_INVALID_ARGUMENT, "align: n_pairs < 0");
   if (with_prior) {
-    if (e->objective != PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL && e->objective != PHOVO_OBJECTIVE_INVERSE_ROBUST)
+    if (e->objective != PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL && e->objective != PHOVO_OBJECTIVE_INVERSE_ROBUST)   // (7: a follow-up)
       return fail(PHOVO_E_UNSUPPORTED, "align_prior: the pose prior belongs to the two inverse-compositional objectives "
                                        "(PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL, PHOVO_OBJECTIVE_INVERSE_ROBUST)");
     if (n_pairs > 0 && (!prior_states || !information)) return fail(PHOVO_E_INVALID_ARGUMENT, "align_prior: null");
@@ -180,7 +182,7 @@ static int enqueue(phovo_engine *e, int n_pairs, const int *source_frames, const
   PHOVO_HIP_CHECK(hipSetDevice(e->device));
   // Every active level must be launchable BEFORE the enqueue takes a ticket and a slot: a refused enqueue leaves the
   // engine as it was -- in particular the results of the enqueue before the last stay fetchable.
-  size_t owner_need = 0, wide_need = 0, mask_need = 0;
+  size_t owner_need = 0, wide_need = 0, mask_need = 0, sd_slab = 0;
   for (int l = 0; l < e->cfg.num_levels && n_pairs > 0; l++) {
     if (e->cfg.max_num_iterations[l] <= 0) continue;
     const LevelPool &lv = e->levels[l];
@@ -207,11 +209,18 @@ static int enqueue(phovo_engine *e, int n_pairs, const int *source_frames, const
                                          "frames with PHOVO_ROLE_BOTH)");
       continue;
     }
-    if (e->objective == PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL || e->objective == PHOVO_OBJECTIVE_INVERSE_ROBUST) {   // likewise; the source's gradients are a target upload's
+    if (e->objective == PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL || e->objective == PHOVO_OBJECTIVE_INVERSE_ROBUST ||
+        e->objective == PHOVO_OBJECTIVE_INVERSE_SEMIDENSE) {                // likewise; the source's gradients are a target upload's
       for (int i = 0; i < n_pairs; i++)
         if (!(e->frame_roles[(size_t)source_frames[i] * PHOVO_MAX_LEVELS + (size_t)l] & PHOVO_ROLE_TARGET))
           return fail(PHOVO_E_NOT_READY, "align: the inverse-compositional objective reads the source's gradient planes (upload "
                                          "source frames with PHOVO_ROLE_BOTH)");
+      if (e->objective == PHOVO_OBJECTIVE_INVERSE_SEMIDENSE) {
+        if (lv.w > 65535 || lv.h > 65535)
+          return fail(PHOVO_E_SHAPE, "align: the semi-dense objective's pixel records hold 16-bit columns and rows (a level wider "
+                                     "or taller than 65535 pixels)");
+        sd_slab = std::max(sd_slab, gn_inverse_semidense_slab_records((lv.n + 63) / 64));
+      }
       continue;
     }
     if (e->ext.sampling == PHOVO_SAMPLING_BILINEAR) continue;       // no owner map, no LDS limit
@@ -251,6 +260,7 @@ static int enqueue(phovo_engine *e, int n_pairs, const int *source_frames, const
   s.affine_ran = e->objective == PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE;
   s.geometric_ran = e->objective == PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC;
   s.robust_ran = e->objective == PHOVO_OBJECTIVE_INVERSE_ROBUST;
+  s.semidense_ran = e->objective == PHOVO_OBJECTIVE_INVERSE_SEMIDENSE;
   s.prior_ran = with_prior;
   s.num_levels = e->cfg.num_levels;
   for (int l = 0; l < PHOVO_MAX_LEVELS; l++) s.level_skipped[l] = l < e->cfg.num_levels && e->cfg.max_num_iterations[l] <= 0;
@@ -283,6 +293,12 @@ static int enqueue(phovo_engine *e, int n_pairs, const int *source_frames, const
   if (s.affine_ran) PHOVO_HIP_CHECK(s.illum.reserve(2 * (size_t)n_pairs));
   if (s.geometric_ran) PHOVO_HIP_CHECK(s.geo_reports.reserve((size_t)n_pairs));
   if (s.robust_ran) PHOVO_HIP_CHECK(s.rob_reports.reserve((size_t)n_pairs));
+  if (s.semidense_ran) {
+    PHOVO_HIP_CHECK(s.sd_reports.reserve((size_t)n_pairs));
+    // one slab per workgroup of the persistent grid (the same grid on every level)
+    const size_t grid = (size_t)std::min(n_pairs, e->cu_count * gn_inverse_semidense_wgs_per_cu());
+    PHOVO_HIP_CHECK(take_or_grow(s.sd_records, other_idle ? &other.sd_records : nullptr, grid * sd_slab));
+  }
   if (s.prior_ran) {
     const size_t doubles = (size_t)GN_PRIOR_DOUBLES * (size_t)n_pairs;
     PHOVO_HIP_CHECK(s.prior.reserve(doubles));
@@ -338,6 +354,8 @@ static int enqueue(phovo_engine *e, int n_pairs, const int *source_frames, const
     PHOVO_HIP_CHECK(hipMemsetAsync(s.geo_reports.ptr, 0, sizeof(phovo_geometric_report) * (size_t)n_pairs, s.stream));
   if (s.robust_ran)      // (likewise)
     PHOVO_HIP_CHECK(hipMemsetAsync(s.rob_reports.ptr, 0, sizeof(phovo_robust_report) * (size_t)n_pairs, s.stream));
+  if (s.semidense_ran)   // (likewise)
+    PHOVO_HIP_CHECK(hipMemsetAsync(s.sd_reports.ptr, 0, sizeof(phovo_semidense_report) * (size_t)n_pairs, s.stream));
   if (s.prior_ran) {
     PHOVO_HIP_CHECK(hipMemcpyAsync(s.prior.ptr, s.h_prior, sizeof(double) * GN_PRIOR_DOUBLES * (size_t)n_pairs,
                                    hipMemcpyHostToDevice, s.stream));
@@ -492,6 +510,17 @@ static int enqueue(phovo_engine *e, int n_pairs, const int *source_frames, const
       b.rob_reports = s.rob_reports.ptr;
       PHOVO_HIP_CHECK(gn_launch_level_inverse_robust(b, e->cu_count, s.stream));
       record(l, l, PHOVO_LAUNCH_INVERSE_ROBUST, 256, gn_inverse_robust_lds_bytes(), persistent_grid(gn_inverse_robust_wgs_per_cu()));
+    } else if (e->objective == PHOVO_OBJECTIVE_INVERSE_SEMIDENSE) {
+      GNInverseSemiDenseArgs b{};
+      b.lv = a;
+      b.tau2 = e->sd_opt.min_pixel_gradient[l] * e->sd_opt.min_pixel_gradient[l];
+      b.records = s.sd_records.ptr;
+      b.slab_records = sd_slab;
+      b.seg_records = gn_inverse_semidense_segment_records(a.n_chunks);
+      b.sd_reports = s.sd_reports.ptr;
+      PHOVO_HIP_CHECK(gn_launch_level_inverse_semidense(b, e->cu_count, s.stream));
+      record(l, l, PHOVO_LAUNCH_INVERSE_SEMIDENSE, 256, gn_inverse_semidense_lds_bytes(),
+             persistent_grid(gn_inverse_semidense_wgs_per_cu()));
     } else if (e->ext.sampling == PHOVO_SAMPLING_BILINEAR) {
       PHOVO_HIP_CHECK(gn_launch_level_bilinear(a, e->ext.plane_storage, e->ext.jacobian_corrected != 0, e->cu_count, s.stream));
       record(l, l, PHOVO_LAUNCH_BILINEAR, 256, 0, persistent_grid(gn_bilinear_wgs_per_cu(e->ext.plane_storage)));
@@ -632,6 +661,12 @@ int phovo_engine_fetch_robust_reports(phovo_engine *e, int n_pairs, phovo_robust
 {
   return fetch_records(e, "fetch_robust_reports", PHOVO_E_NOT_READY, &AlignSlot::robust_ran, &AlignSlot::rob_reports, 1, n_pairs,
                        reports);
+}
+
+int phovo_engine_fetch_semidense_reports(phovo_engine *e, int n_pairs, phovo_semidense_report *reports)
+{
+  return fetch_records(e, "fetch_semidense_reports", PHOVO_E_NOT_READY, &AlignSlot::semidense_ran, &AlignSlot::sd_reports, 1,
+                       n_pairs, reports);
 }
 
 int phovo_engine_fetch_prior_reports(phovo_engine *e, int n_pairs, phovo_prior_report *reports)

@@ -188,6 +188,8 @@ int phovo_engine_evaluate_sampled_pairs(phovo_engine *e, int n_pairs, const int 
   if (e->objective == PHOVO_OBJECTIVE_INVERSE_ROBUST)
     return fail(PHOVO_E_UNSUPPORTED, "evaluate_sampled_pairs: the robust inverse-compositional objective has its system in "
                                      "phovo_engine_evaluate_robust_pairs");
+  if (e->objective == PHOVO_OBJECTIVE_INVERSE_SEMIDENSE)
+    return fail(PHOVO_E_UNSUPPORTED, "evaluate_sampled_pairs: the semi-dense inverse-compositional objective has no system yet");
   const bool affine = e->objective == PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE;
   if (!affine && e->ext.sampling != PHOVO_SAMPLING_BILINEAR)
     return fail(PHOVO_E_UNSUPPORTED, "evaluate_sampled_pairs: nearest / scatter sampling has its system in "
@@ -281,6 +283,8 @@ int phovo_engine_evaluate_objective_pairs(phovo_engine *e, int n_pairs, const in
     case PHOVO_OBJECTIVE_INVERSE_ROBUST:
       return fail(PHOVO_E_UNSUPPORTED, "evaluate_objective_pairs: the robust inverse-compositional objective has its system in "
                                        "phovo_engine_evaluate_robust_pairs");
+    case PHOVO_OBJECTIVE_INVERSE_SEMIDENSE:
+      return fail(PHOVO_E_UNSUPPORTED, "evaluate_objective_pairs: the semi-dense inverse-compositional objective has no system yet");
     default:
       return fail(PHOVO_E_UNSUPPORTED, "evaluate_objective_pairs: the photometric-geometric objective has its system in "
                                        "phovo_engine_evaluate_geometric_pairs");

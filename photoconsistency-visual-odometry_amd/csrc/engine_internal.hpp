@@ -100,6 +100,11 @@ struct AlignSlot {
   bool geometric_ran = false;                  // the enqueue ran under PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC
   phovo_hip::DeviceBuffer<phovo_robust_report> rob_reports;        // robust inverse-compositional objective: the records of the enqueue's pairs
   bool robust_ran = false;                     // the enqueue ran under PHOVO_OBJECTIVE_INVERSE_ROBUST
+  phovo_hip::DeviceBuffer<phovo_semidense_report> sd_reports;      // semi-dense inverse-compositional objective: the records of the enqueue's pairs
+  bool semidense_ran = false;                  // the enqueue ran under PHOVO_OBJECTIVE_INVERSE_SEMIDENSE
+  // that objective's pixel lists: [grid][slab] 4-byte records, grid = the persistent grid of the enqueue, slab = the padded
+  // size of its largest active level (GNInverseSemiDenseArgs); the slot's own, so two enqueues in flight never share one
+  phovo_hip::DeviceBuffer<unsigned> sd_records;
   // phovo_engine_enqueue_align_prior: the enqueue's own prior blocks ([pairs][GN_PRIOR_DOUBLES], copied from the pinned
   // h_prior, which stays untouched until the slot is used again) and the records of its pairs
   phovo_hip::DeviceBuffer<double> prior;
@@ -154,6 +159,7 @@ struct phovo_engine {
   phovo_trust_region_options tr_opt{};         // phovo_engine_set_trust_region_options (Ceres's defaults at creation)
   phovo_geometric_options geo_opt{};           // phovo_engine_set_geometric_options (phovo_geometric_options_default at creation)
   phovo_robust_options rob_opt{};              // phovo_engine_set_robust_options (phovo_robust_options_default at creation)
+  phovo_semidense_options sd_opt{};            // phovo_engine_set_semidense_options (phovo_semidense_options_default at creation)
   phovo_prior_options prior_opt{};             // phovo_engine_set_prior_options (phovo_prior_options_default at creation)
   bool latency_forms = false;                  // a handful of pairs may take the forms that finish soonest also where a level has a one-workgroup form with its owner map in LDS (phovo_engine_set_latency_forms)
   std::vector<unsigned char> frame_roles;      // [frame][PHOVO_MAX_LEVELS]: PHOVO_ROLE_* each level of each frame has been given since the

@@ -28,6 +28,8 @@ struct phovo_odometry {
   bool have_geo_report = false;
   phovo_robust_report rob_report{};              // robust inverse-compositional objective: the record of the last Optimize()
   bool have_rob_report = false;
+  phovo_semidense_report sd_report{};            // semi-dense inverse-compositional objective: the record of the last Optimize()
+  bool have_sd_report = false;
   bool have_prior = false;                       // phovo_odometry_set_pose_prior: every Optimize() carries it until it is cleared
   double prior_state[6] = {0, 0, 0, 0, 0, 0};
   double prior_information[36] = {};
@@ -37,11 +39,12 @@ struct phovo_odometry {
 
 namespace {
 
-// Both inverse-compositional objectives read the source's gradient planes, which are a target upload's.
+// The inverse-compositional objectives read the source's gradient planes, which are a target upload's.
 int source_role(const phovo_odometry *o)
 {
   const bool inverse = o && (o->engine->objective == PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL ||
-                             o->engine->objective == PHOVO_OBJECTIVE_INVERSE_ROBUST);
+                             o->engine->objective == PHOVO_OBJECTIVE_INVERSE_ROBUST ||
+                             o->engine->objective == PHOVO_OBJECTIVE_INVERSE_SEMIDENSE);
   return inverse ? PHOVO_ROLE_BOTH : PHOVO_ROLE_SOURCE;
 }
 
@@ -172,6 +175,18 @@ int phovo_odometry_get_robust_options(const phovo_odometry *o, phovo_robust_opti
   return phovo_engine_get_robust_options(o->engine, opt);
 }
 
+int phovo_odometry_set_semidense_options(phovo_odometry *o, const phovo_semidense_options *opt)
+{
+  if (!o) return fail(PHOVO_E_INVALID_ARGUMENT, "set_semidense_options: null");
+  return phovo_engine_set_semidense_options(o->engine, opt);
+}
+
+int phovo_odometry_get_semidense_options(const phovo_odometry *o, phovo_semidense_options *opt)
+{
+  if (!o) return fail(PHOVO_E_INVALID_ARGUMENT, "get_semidense_options: null");
+  return phovo_engine_get_semidense_options(o->engine, opt);
+}
+
 int phovo_odometry_set_latency_forms(phovo_odometry *o, int on)
 {
   if (!o) return fail(PHOVO_E_INVALID_ARGUMENT, "set_latency_forms: null");
@@ -197,6 +212,13 @@ int phovo_odometry_read_configuration_file(phovo_odometry *o, const char *path)
     st = read_geometric_file(path, &g);
     if (st != PHOVO_OK) return st;
     st = phovo_engine_set_geometric_options(o->engine, &g);
+    if (st != PHOVO_OK) return st;
+  }
+  if (o->engine->objective == PHOVO_OBJECTIVE_INVERSE_SEMIDENSE) {          // its optional key; absent: the defaults
+    phovo_semidense_options sd;
+    st = read_semidense_file(path, &sd);
+    if (st != PHOVO_OK) return st;
+    st = phovo_engine_set_semidense_options(o->engine, &sd);
     if (st != PHOVO_OK) return st;
   }
   phovo_extensions x;                        // optional keys; a reference yml has none -> everything stays off
@@ -369,6 +391,7 @@ static int optimize_visualized(phovo_odometry *o, const char *dir)
   o->have_illumination = false;
   o->have_geo_report = false;
   o->have_rob_report = false;
+  o->have_sd_report = false;
   o->optimized = true;
   return PHOVO_OK;
 }
@@ -388,7 +411,8 @@ int phovo_odometry_optimize(phovo_odometry *o)
   if (o->engine->cfg.visualize_iterations && o->engine->objective != PHOVO_OBJECTIVE_PHOTOMETRIC_AFFINE &&
       o->engine->objective != PHOVO_OBJECTIVE_PHOTOMETRIC_GEOMETRIC &&
       o->engine->objective != PHOVO_OBJECTIVE_INVERSE_COMPOSITIONAL &&
-      o->engine->objective != PHOVO_OBJECTIVE_INVERSE_ROBUST) {
+      o->engine->objective != PHOVO_OBJECTIVE_INVERSE_ROBUST &&
+      o->engine->objective != PHOVO_OBJECTIVE_INVERSE_SEMIDENSE) {
     const char *dir = std::getenv("PHOVO_VISUALIZE_DIR");
     if (dir && *dir) return optimize_visualized(o, dir);
   }
@@ -427,7 +451,21 @@ int phovo_odometry_optimize(phovo_odometry *o)
     st = phovo_engine_fetch_robust_reports(o->engine, 1, &o->rob_report);
     if (st != PHOVO_OK) return st;
   }
+  o->have_sd_report = o->engine->objective == PHOVO_OBJECTIVE_INVERSE_SEMIDENSE;
+  if (o->have_sd_report) {
+    st = phovo_engine_fetch_semidense_reports(o->engine, 1, &o->sd_report);
+    if (st != PHOVO_OK) return st;
+  }
   o->optimized = true;
+  return PHOVO_OK;
+}
+
+int phovo_odometry_get_semidense_report(const phovo_odometry *o, phovo_semidense_report *report)
+{
+  if (!o || !report) return fail(PHOVO_E_INVALID_ARGUMENT, "get_semidense_report: null");
+  if (!o->optimized) return fail(PHOVO_E_NOT_READY, "get_semidense_report: Optimize has not run");
+  if (!o->have_sd_report) return fail(PHOVO_E_UNSUPPORTED, "get_semidense_report: the last Optimize ran under another objective");
+  *report = o->sd_report;
   return PHOVO_OK;
 }
 
@@ -540,6 +578,8 @@ int phovo_odometry_get_pair_system(const phovo_odometry *o, phovo_pair_system *o
   if (o->engine->objective == PHOVO_OBJECTIVE_INVERSE_ROBUST)
     return fail(PHOVO_E_UNSUPPORTED, "get_pair_system: the robust inverse-compositional objective has its system in "
                                      "phovo_odometry_get_robust_system");
+  if (o->engine->objective == PHOVO_OBJECTIVE_INVERSE_SEMIDENSE)
+    return fail(PHOVO_E_UNSUPPORTED, "get_pair_system: the semi-dense inverse-compositional objective has no system yet");
   if (!o->optimized) return fail(PHOVO_E_NOT_READY, "get_pair_system: Optimize has not run since the frames were set");
   const phovo_engine *e = o->engine;
   int finest = -1;                                        // the lowest level Optimize() iterates on
@@ -559,6 +599,8 @@ int phovo_odometry_get_sampled_system(const phovo_odometry *o, phovo_sampled_sys
   if (o->engine->objective == PHOVO_OBJECTIVE_INVERSE_ROBUST)
     return fail(PHOVO_E_UNSUPPORTED, "get_sampled_system: the robust inverse-compositional objective has its system in "
                                      "phovo_odometry_get_robust_system");
+  if (o->engine->objective == PHOVO_OBJECTIVE_INVERSE_SEMIDENSE)
+    return fail(PHOVO_E_UNSUPPORTED, "get_sampled_system: the semi-dense inverse-compositional objective has no system yet");
   if (!o->optimized) return fail(PHOVO_E_NOT_READY, "get_sampled_system: Optimize has not run since the frames were set");
   const phovo_engine *e = o->engine;
   int finest = -1;                                        // the lowest level Optimize() iterates on

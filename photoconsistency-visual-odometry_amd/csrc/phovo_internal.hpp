@@ -249,7 +249,25 @@ struct GNInverseRobustArgs {
 int gn_inverse_robust_wgs_per_cu();
 int gn_inverse_robust_lds_bytes();
 hipError_t gn_launch_level_inverse_robust(const GNInverseRobustArgs &args, int cu_count, hipStream_t stream);
-// The two forms above under a Gaussian pose prior (gn_inverse_prior_kernel.hip, phovo_engine_enqueue_align_prior, DESIGN.md
+// Semi-dense inverse-compositional form (gn_inverse_semidense_kernel.hip, PHOVO_OBJECTIVE_INVERSE_SEMIDENSE):
+// objective 5's rows on the source pixels selected once per pair and level by depth and gradient magnitude.  256 threads.
+// records: [grid][slab_records] 4-byte records, grid = min(pairs, CUs x gn_inverse_semidense_wgs_per_cu()); a workgroup
+// touches the slab at blockIdx.x alone.  seg_records = gn_inverse_semidense_segment_records(lv.n_chunks) is one wave's
+// segment of THIS level; slab_records >= gn_inverse_semidense_slab_records(lv.n_chunks) (the enqueue's largest level's).
+struct GNInverseSemiDenseArgs {
+  GNLevelArgs lv;                    // (huber_delta and rec_off unused)
+  double tau2;                       // min_pixel_gradient[level] squared in fp64
+  unsigned *records;
+  size_t slab_records;
+  int seg_records;
+  phovo_semidense_report *sd_reports;   // [pairs], zeroed before the first level
+};
+int gn_inverse_semidense_wgs_per_cu();
+int gn_inverse_semidense_lds_bytes();
+int gn_inverse_semidense_segment_records(int n_chunks);
+size_t gn_inverse_semidense_slab_records(int n_chunks);
+hipError_t gn_launch_level_inverse_semidense(const GNInverseSemiDenseArgs &args, int cu_count, hipStream_t stream);
+// The two forms above (5 and 6) under a Gaussian pose prior (gn_inverse_prior_kernel.hip, phovo_engine_enqueue_align_prior, DESIGN.md
 // §24): one template over `robust`.  prior: [pairs][GN_PRIOR_DOUBLES] -- R_p row-major (9), t_p (3), the upper triangle of
 // Lambda row-major (21), and 1.0 where Lambda has a non-zero entry, else 0.0.
 constexpr int GN_PRIOR_DOUBLES = 34;
@@ -351,5 +369,6 @@ int read_config_file(const char *path, phovo_config *cfg);
 int read_extensions_file(const char *path, phovo_extensions *ext);
 int read_trust_region_file(const char *path, phovo_config *cfg, phovo_trust_region_options *opt);
 int read_geometric_file(const char *path, phovo_geometric_options *opt);
+int read_semidense_file(const char *path, phovo_semidense_options *opt);
 
 }  // namespace phovo_hip

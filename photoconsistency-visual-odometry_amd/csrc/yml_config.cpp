@@ -237,6 +237,36 @@ int read_geometric_file(const char *path, phovo_geometric_options *opt)
   return PHOVO_OK;
 }
 
+// The semi-dense inverse-compositional objective's optional key in an analytic file, read the way read_geometric_file reads
+// depth_weight.
+int read_semidense_file(const char *path, phovo_semidense_options *opt)
+{
+  if (!path || !opt) return fail(PHOVO_E_INVALID_ARGUMENT, "read_semidense_file: null argument");
+  std::map<std::string, std::string> kv;
+  const int rst = read_key_values(path, kv);
+  if (rst != PHOVO_OK) return rst;
+  phovo_semidense_options o;
+  phovo_semidense_options_default(&o);
+  int levels = 0;
+  std::vector<double> v;
+  auto nl = kv.find("numOptimizationLevels");
+  if (nl != kv.end() && parse_values(nl->second, &v) && v.size() == 1 && v[0] >= 1 && v[0] <= PHOVO_MAX_LEVELS) levels = to_int(v[0]);
+  const char *key = "min_pixel_gradient (at each level)";
+  auto it = kv.find(key);
+  if (it != kv.end()) {
+    if (!parse_values(it->second, &v)) return fail(PHOVO_E_CONFIG, std::string("configuration key malformed: '") + key + "'");
+    if ((int)v.size() < levels)
+      return fail(PHOVO_E_CONFIG, std::string("'") + key + "' has fewer entries than numOptimizationLevels");
+    for (int i = 0; i < PHOVO_MAX_LEVELS && i < (int)v.size(); i++) {
+      if (!(v[i] >= 0.0 && std::isfinite(v[i])))
+        return fail(PHOVO_E_CONFIG, std::string("'") + key + "': every entry must be finite and >= 0");
+      o.min_pixel_gradient[i] = v[i];
+    }
+  }
+  *opt = o;
+  return PHOVO_OK;
+}
+
 }  // namespace phovo_hip
 
 extern "C" int phovo_geometric_options_default(phovo_geometric_options *opt)
@@ -331,3 +361,10 @@ int read_trust_region_file(const char *path, phovo_config *cfg, phovo_trust_regi
 }
 
 }  // namespace phovo_hip
+
+extern "C" int phovo_semidense_options_default(phovo_semidense_options *opt)
+{
+  if (!opt) return phovo_hip::fail(PHOVO_E_INVALID_ARGUMENT, "semidense_options_default: null");
+  for (int l = 0; l < PHOVO_MAX_LEVELS; l++) opt->min_pixel_gradient[l] = 0.0;     // every depth-valid pixel
+  return PHOVO_OK;
+}

@@ -103,8 +103,10 @@ OBJECTIVE_PHOTOMETRIC_AFFINE = 3
 OBJECTIVE_PHOTOMETRIC_GEOMETRIC = 4
 OBJECTIVE_INVERSE_COMPOSITIONAL = 5
 OBJECTIVE_INVERSE_ROBUST = 6
+OBJECTIVE_INVERSE_SEMIDENSE = 7
 LAUNCH_KINDS = ("persistent", "fused", "slide", "slide_fallback", "wide", "bilinear", "biobjective", "trust_region",
-                "affine", "geometric", "inverse", "inverse_robust", "inverse_prior", "inverse_robust_prior")
+                "affine", "geometric", "inverse", "inverse_robust", "inverse_prior", "inverse_robust_prior",
+                "inverse_semidense")
 
 # phovo_trust_region_level.termination
 (TR_SKIPPED, TR_MAX_ITERATIONS, TR_GRADIENT, TR_FUNCTION, TR_PARAMETER, TR_MIN_RADIUS, TR_INVALID_STEP,
@@ -149,6 +151,16 @@ class RobustOptions(C.Structure):
 class RobustReport(C.Structure):
     """phovo_robust_report: the Huber threshold and the outlier rows of every level's last system."""
     _fields_ = [("delta", C.c_double * MAX_LEVELS), ("outliers", C.c_int32 * MAX_LEVELS)]
+
+
+class SemiDenseOptions(C.Structure):
+    """phovo_semidense_options: the semi-dense inverse-compositional objective's per-level gradient threshold tau_L."""
+    _fields_ = [("min_pixel_gradient", C.c_double * MAX_LEVELS)]
+
+
+class SemiDenseReport(C.Structure):
+    """phovo_semidense_report: the selected pixels of every level."""
+    _fields_ = [("selected", C.c_int32 * MAX_LEVELS)]
 
 
 class PriorOptions(C.Structure):
@@ -317,6 +329,14 @@ SYMBOLS = {
     "phovo_odometry_set_robust_options": (C.c_int, [_vp, C.POINTER(RobustOptions)]),
     "phovo_odometry_get_robust_options": (C.c_int, [_vp, C.POINTER(RobustOptions)]),
     "phovo_odometry_get_robust_report": (C.c_int, [_vp, C.POINTER(RobustReport)]),
+    "phovo_semidense_options_default": (C.c_int, [C.POINTER(SemiDenseOptions)]),
+    "phovo_semidense_read_file": (C.c_int, [C.c_char_p, C.POINTER(SemiDenseOptions)]),
+    "phovo_engine_set_semidense_options": (C.c_int, [_vp, C.POINTER(SemiDenseOptions)]),
+    "phovo_engine_get_semidense_options": (C.c_int, [_vp, C.POINTER(SemiDenseOptions)]),
+    "phovo_engine_fetch_semidense_reports": (C.c_int, [_vp, C.c_int, _vp]),
+    "phovo_odometry_set_semidense_options": (C.c_int, [_vp, C.POINTER(SemiDenseOptions)]),
+    "phovo_odometry_get_semidense_options": (C.c_int, [_vp, C.POINTER(SemiDenseOptions)]),
+    "phovo_odometry_get_semidense_report": (C.c_int, [_vp, C.POINTER(SemiDenseReport)]),
     "phovo_prior_options_default": (C.c_int, [C.POINTER(PriorOptions)]),
     "phovo_engine_set_prior_options": (C.c_int, [_vp, C.POINTER(PriorOptions)]),
     "phovo_engine_get_prior_options": (C.c_int, [_vp, C.POINTER(PriorOptions)]),
@@ -581,6 +601,27 @@ def make_robust_options(scale_factor=None):
     check(lib().phovo_robust_options_default(C.byref(opt)), "phovo_robust_options_default")
     if scale_factor is not None:
         opt.scale_factor = float(scale_factor)
+    return opt
+
+
+def make_semidense_options(min_pixel_gradient=None):
+    """phovo_semidense_options_default (0 on every level), or with min_pixel_gradient as a per-level list (or one value for
+    every level).  A value that is not finite and >= 0 is a ValueError here, before the library sees it."""
+    opt = SemiDenseOptions()
+    check(lib().phovo_semidense_options_default(C.byref(opt)), "phovo_semidense_options_default")
+    if min_pixel_gradient is not None:
+        vals = [min_pixel_gradient] * MAX_LEVELS if np.isscalar(min_pixel_gradient) else list(min_pixel_gradient)
+        for i, v in enumerate(vals[:MAX_LEVELS]):
+            if not (np.isfinite(v) and v >= 0):
+                raise ValueError(f"min_pixel_gradient[{i}] = {v!r}: must be finite and >= 0")
+            opt.min_pixel_gradient[i] = float(v)
+    return opt
+
+
+def read_semidense_file(path):
+    """phovo_semidense_read_file: SemiDenseOptions from the optional key of an analytic yml."""
+    opt = SemiDenseOptions()
+    check(lib().phovo_semidense_read_file(os.fsencode(path), C.byref(opt)), "phovo_semidense_read_file")
     return opt
 
 

@@ -502,6 +502,72 @@ class CPhotoconsistencyOdometryRobust(_PosePrior, CPhotoconsistencyOdometryAnaly
         return rep
 
 
+class CPhotoconsistencyOdometrySemiDense(CPhotoconsistencyOdometryAnalytic):
+    """One frame pair at a time; not in the reference: the inverse-compositional aligner on the source pixels selected
+    once per level by depth and gradient magnitude (native.OBJECTIVE_INVERSE_SEMIDENSE).  SetSourceFrame
+    also builds the source's gradient planes.  Reads the analytic yml files and their optional key
+    `min_pixel_gradient (at each level)`; extensions and every Get...System() call are refused (PHOVO_E_UNSUPPORTED)."""
+
+    def __init__(self, device=0):
+        super().__init__(device)
+        check(self._lib.phovo_odometry_set_objective(self._h, native.OBJECTIVE_INVERSE_SEMIDENSE), "SetObjective")
+
+    def SetSemiDenseOptions(self, opt):
+        """native.SemiDenseOptions (native.make_semidense_options)."""
+        check(self._lib.phovo_odometry_set_semidense_options(self._h, C.byref(opt)), "SetSemiDenseOptions")
+
+    def GetSemiDenseOptions(self):
+        opt = native.SemiDenseOptions()
+        check(self._lib.phovo_odometry_get_semidense_options(self._h, C.byref(opt)), "GetSemiDenseOptions")
+        return opt
+
+    def GetSemiDenseReport(self):
+        """native.SemiDenseReport of the last Optimize(): per level the number of selected pixels."""
+        rep = native.SemiDenseReport()
+        check(self._lib.phovo_odometry_get_semidense_report(self._h, C.byref(rep)), "GetSemiDenseReport")
+        return rep
+
+
+# phovo_semidense_report as a numpy record
+SEMIDENSE_REPORT_DTYPE = np.dtype([("selected", "<i4", (native.MAX_LEVELS,))])
+assert SEMIDENSE_REPORT_DTYPE.itemsize == C.sizeof(native.SemiDenseReport)
+
+
+def semidense_thresholds(engine, frame, fraction, min_depth=None, max_depth=None):
+    """Per level the tau_L that keeps about `fraction` of the depth-valid pixels of `frame` (0 < fraction <= 1) under
+    native.OBJECTIVE_INVERSE_SEMIDENSE: the (1 - fraction) quantile of the gradient magnitude over the pixels with
+    min_depth < D < max_depth, on the planes read back from the pool, moved to the middle of the gap between the two
+    samples around it.  The depth range is the one the engine was given through set_depth_range (0.3 ... 5.0 without such a
+    call), unless passed here.  Host-side only; a list of native.MAX_LEVELS values
+    (0 for levels the pool does not hold, and where no pixel is depth-valid) for native.make_semidense_options."""
+    if not 0.0 < fraction <= 1.0:
+        raise ValueError("semidense_thresholds: fraction must lie in (0, 1]")
+    # the depth gate of the selection is the engine's: what set_depth_range was given, else the library's default
+    lo, hi = getattr(engine, "depth_range", (0.3, 5.0))
+    min_depth = lo if min_depth is None else min_depth
+    max_depth = hi if max_depth is None else max_depth
+    taus = [0.0] * native.MAX_LEVELS
+    for level in range(engine.get_config().num_levels):
+        if not engine._lib.phovo_engine_level_is_stored(engine._h, level):
+            continue
+        _, d, gx, gy = engine.get_level_planes(frame, level)
+        with np.errstate(invalid="ignore"):
+            ok = (d > min_depth) & (d < max_depth)
+        g = np.sqrt(gx[ok] * gx[ok] + gy[ok] * gy[ok])
+        g = g[np.isfinite(g)]
+        if g.size and fraction < 1.0:
+            taus[level] = _between_samples(g, float(np.quantile(g, 1.0 - fraction)))
+    return taus
+
+
+def _between_samples(g, q):
+    """q moved to the middle of the gap between the samples next to it (the largest <= q, the smallest > q), so that no
+    pixel sits on the threshold and rounding cannot decide a pixel's selection; q itself where no sample lies above it."""
+    above = g[g > q * (1.0 + 1e-9)]                  # (samples within rounding of q count as q)
+    below = g[g <= q * (1.0 + 1e-9)]
+    return 0.5 * (float(below.max()) + float(above.min())) if above.size and below.size else q
+
+
 # phovo_robust_report as a numpy record: one row of per-level fields per pair
 ROBUST_REPORT_DTYPE = np.dtype({"names": ["delta", "outliers"], "formats": [("<f8", (native.MAX_LEVELS,)), ("<i4", (native.MAX_LEVELS,))],
                                 "offsets": [native.RobustReport.delta.offset, native.RobustReport.outliers.offset],
@@ -619,6 +685,7 @@ class AlignmentEngine:
     def set_depth_range(self, min_depth, max_depth):
         check(self._lib.phovo_engine_set_depth_range(self._h, float(min_depth), float(max_depth)),
               "phovo_engine_set_depth_range")
+        self.depth_range = (float(min_depth), float(max_depth))      # (the library has no getter; semidense_thresholds reads it)
 
     def set_build_all_levels(self, on):
         check(self._lib.phovo_engine_set_build_all_levels(self._h, int(bool(on))), "phovo_engine_set_build_all_levels")
@@ -789,6 +856,23 @@ class AlignmentEngine:
         opt = native.RobustOptions()
         check(self._lib.phovo_engine_get_robust_options(self._h, C.byref(opt)), "phovo_engine_get_robust_options")
         return opt
+
+    def set_semidense_options(self, opt):
+        """native.SemiDenseOptions (native.make_semidense_options)."""
+        check(self._lib.phovo_engine_set_semidense_options(self._h, C.byref(opt)), "phovo_engine_set_semidense_options")
+
+    def get_semidense_options(self):
+        opt = native.SemiDenseOptions()
+        check(self._lib.phovo_engine_get_semidense_options(self._h, C.byref(opt)), "phovo_engine_get_semidense_options")
+        return opt
+
+    def fetch_semidense_reports(self, n_pairs):
+        """The records of the last enqueue's pairs, which ran under native.OBJECTIVE_INVERSE_SEMIDENSE, as one structured
+        numpy array of SEMIDENSE_REPORT_DTYPE: out["selected"][p, L]."""
+        out = np.zeros(int(n_pairs), dtype=SEMIDENSE_REPORT_DTYPE)
+        check(self._lib.phovo_engine_fetch_semidense_reports(self._h, int(n_pairs), out.ctypes.data),
+              "phovo_engine_fetch_semidense_reports")
+        return out
 
     def set_prior_options(self, opt):
         """native.PriorOptions (native.make_prior_options)."""
